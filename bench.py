@@ -51,6 +51,36 @@ def _compact(o, top=True):
     return o
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, params=None):
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step, one DIR/<name>.npy per array (float32, or
+    float64 where the path computed float64), so that two builds can be compared output for output on identical inputs.  `params`
+    (training modes): the parameters the step left behind, flattened in named_parameters() order as `params.npy`.  An array larger
+    than its share of the 64 MB budget is replaced by a fixed sample of its elements (default_rng(0), sorted indices: the same
+    elements on every run of the same configuration); DIR/manifest.json records shapes and which arrays were sampled."""
+    if params is not None:
+        arrays = dict(arrays, params=torch.cat([p.detach().reshape(-1).float() for p in params]))
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // max(len(arrays), 1)         # elements per array (float64 arrays count double below)
+    manifest = {}
+    for name, a in arrays.items():
+        t = a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        shape, n = list(t.shape), t.numel()
+        limit = cap // (2 if t.dtype == torch.float64 else 1)
+        rec = dict(shape=shape, dtype=str(t.dtype).replace("torch.", ""), sampled=n > limit)
+        if n > limit:
+            idx = np.sort(np.random.default_rng(0).choice(n, limit, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            rec.update(sample_elements=limit, sample="np.random.default_rng(0).choice(numel, sample_elements, replace=False), sorted, of the flattened array")
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+        manifest[name] = rec
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+
+
 def tvsum_lens(n_videos=50):
     return [int(np.ceil(v)) for v in np.random.default_rng(0).uniform(150, 320, n_videos)]
 
@@ -266,6 +296,9 @@ def bench_sumgan(args, dev, rank, world, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert all(bool(torch.isfinite(v).all()) for v in vals)
+    if args.dump_outputs and rank == 0:
+        names = ("loss_s_e", "loss_d", "loss_c", "d_real", "d_fake", "d_uniform", "scores")
+        dump_outputs(args.dump_outputs, dict(zip(names, vals)), tr.model.parameters())
     if rank == 0:
         n_params = sum(p.numel() for p in tr.model.parameters())
         print(json.dumps(dict(metric="frames scored/sec (T x 1024)", value=round(T * world * args.steps / elapsed, 1), unit="frames/s",
@@ -659,6 +692,9 @@ def main():
                     help="GEMM arithmetic: fp32 = exact fp32 MFMA (headline); bf16x6 / bf16x3 = fp32 operands split into 3 / 2 bf16 "
                          "planes, 6 / 3 bf16 MFMAs per product, fp32 accumulate (fp32-grade / ~1e-5 on scores); bf16 = plain bf16 "
                          "operands, 1 MFMA per product: the mixed-precision TRAINING mode of BASELINE config 2 (use with --mode train)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32/float64, "
+                         "64 MB at most: larger outputs as a fixed seeded sample) plus DIR/manifest.json; inputs are identical for identical arguments.  bench_outputs/ is git-ignored")
     args = ap.parse_args()
     if args.fold_vo:
         args.headline_only = True          # (the side legs toggle fold_vo themselves)
@@ -753,14 +789,15 @@ def main():
         off = np.concatenate([[0], np.cumsum(lens)])
         vids = [(i, xh[off[i]:off[i + 1]]) for i in range(len(lens))]
         scorer = StreamingScorer(model, max_frames=frames, depth=3, stage_dtype=args.stage_dtype)
-        last = [None]
+        last = {}
         def run_steps(n):
             def feed():
                 for _ in range(n):
                     yield from vids
-            for _, sc in scorer.score(feed()):
-                last[0] = sc
-            return torch.from_numpy(last[0])
+            for i, sc in scorer.score(feed()):
+                last[i] = sc                    # the last step's scores of every video
+        def stream_scores():                    # (outside the timed region) in batch order
+            return torch.from_numpy(np.concatenate([last[i] for i in range(len(vids))]))
         run_step = None
     else:
         def run_step():
@@ -794,7 +831,7 @@ def main():
             return graph_out
 
     if run_step is None:
-        s = run_steps(args.warmup)
+        run_steps(args.warmup)
     else:
         for _ in range(args.warmup):
             s = run_step()
@@ -804,7 +841,7 @@ def main():
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if run_step is not None else []
     t0 = time.perf_counter()
     if run_step is None:
-        s = run_steps(args.steps)
+        run_steps(args.steps)
     else:
         marks[0].record()
         for i in range(args.steps):
@@ -812,6 +849,8 @@ def main():
             marks[i + 1].record()          # per-step device time (median and p10 / p90), no host sync inside the loop
     barrier()
     t1 = time.perf_counter()
+    if run_step is None:
+        s = stream_scores()
     step_ms = None
     if marks:
         per = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)])
@@ -824,6 +863,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert bool(torch.isfinite(s).all())
+    if args.dump_outputs and rank == 0:
+        # before any side leg touches the model or the library's buffers: scores (score / stream) or the loss and the updated
+        # parameters (train / reinforce) of the last timed step
+        if args.mode in ("train", "reinforce"):
+            dump_outputs(args.dump_outputs, {"loss": s}, model.parameters())
+        else:
+            dump_outputs(args.dump_outputs, {"scores": s})
 
     ms = C.c_double(0); n = C.c_int64(0)
     lib.sumk_prof_read(_lib.PROF_GEMM_QKV, C.byref(ms), C.byref(n), 1)
