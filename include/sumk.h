@@ -546,6 +546,60 @@ int sumk_prof_gemm_stamps(uint64_t* out, int32_t n_blocks);
  * (may be null) = the timed launch. */
 int sumk_probe_mfma_rate(int32_t kind, int32_t iters, double* tflops, double* seconds, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ Transformer stacks (SumGAN-Att)
+ * The encoder and decoder stacks of the reference's SumGAN-Att (summarizer/models/sumgan_att.py:20-80) on the exact-fp32 path:
+ * stock post-norm nn.TransformerEncoderLayer / nn.TransformerDecoderLayer (ReLU, dim_feedforward F, no masks), weights as torch
+ * stores them.  Dropout: opts->layer_dropout_p at every site torch has one, deterministic hash masks of (opts->seed, site,
+ * element); opts->layer_eps is the eps of the layers' norms, opts->final_eps that of the encoder's optional final norm;
+ * opts->precision must be SUMK_PRECISION_FP32 and opts->wplanes NULL.  Gradients are ACCUMULATED into the grad structs. */
+size_t sumk_tf_encoder_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                       const int32_t* seq_off_host, int32_t training);
+/* x (n_rows,D) packed -> hidden (n_rows,D): n_layers encoder layers, then LayerNorm(norm_w, norm_b) when norm_w is non-NULL */
+int sumk_tf_encoder_forward(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                            const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_tf_layer_weights* layers,
+                            const float* norm_w, const float* norm_b, const sumk_tf_opts* opts, float* hidden, void* workspace,
+                            size_t workspace_bytes, int32_t training, void* stream);
+/* Backward of sum(dhidden * hidden) after a training-mode forward on the same workspace: dx (if non-NULL) is written; the
+ * final norm's gradients go to dnorm_w / dnorm_b (both non-NULL when the forward had the norm). */
+int sumk_tf_encoder_backward(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                             const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_tf_layer_weights* layers,
+                             const float* norm_w, const float* norm_b, const sumk_tf_opts* opts, const float* dhidden,
+                             const sumk_tf_layer_grads* layer_grads, float* dnorm_w, float* dnorm_b, float* dx, void* workspace,
+                             size_t workspace_bytes, void* stream);
+typedef struct sumk_tf_dec_layer_weights {
+  const float* sa_in_w; const float* sa_in_b; const float* sa_out_w; const float* sa_out_b;   /* self_attn      (3D,D),(3D),(D,D),(D) */
+  const float* ca_in_w; const float* ca_in_b; const float* ca_out_w; const float* ca_out_b;   /* multihead_attn (3D,D),(3D),(D,D),(D) */
+  const float* lin1_w; const float* lin1_b; const float* lin2_w; const float* lin2_b;         /* (F,D),(F),(D,F),(D)                  */
+  const float* norm1_w; const float* norm1_b; const float* norm2_w; const float* norm2_b;
+  const float* norm3_w; const float* norm3_b;                                                 /* (D)                                  */
+} sumk_tf_dec_layer_weights;
+typedef struct sumk_tf_dec_layer_grads {   /* same fields, same shapes */
+  float* sa_in_w; float* sa_in_b; float* sa_out_w; float* sa_out_b; float* ca_in_w; float* ca_in_b; float* ca_out_w; float* ca_out_b;
+  float* lin1_w; float* lin1_b; float* lin2_w; float* lin2_b; float* norm1_w; float* norm1_b; float* norm2_w; float* norm2_b;
+  float* norm3_w; float* norm3_b;
+} sumk_tf_dec_layer_grads;
+size_t sumk_tf_decoder_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                       const int32_t* seq_off_host);
+/* tgt, memory (n_rows,D), packed with the SAME segment table (video v attends over its own memory rows) -> out (n_rows,D):
+ * per layer norm1(t + SA(t)), norm2(. + CA(., memory)), norm3(. + FF(.)).  The memory's K / V projections of every layer are
+ * computed up front.  training != 0 allows dropout. */
+int sumk_tf_decoder_forward(const float* tgt, const float* memory, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
+                            int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                            const sumk_tf_dec_layer_weights* layers, const sumk_tf_opts* opts, float* out, void* workspace,
+                            size_t workspace_bytes, int32_t training, void* stream);
+/* Backward of sum(dout * out) after sumk_tf_decoder_forward on the same workspace: dtgt and dmemory (each if non-NULL) are
+ * WRITTEN, dmemory summed over every layer's cross-attention. */
+int sumk_tf_decoder_backward(const float* tgt, const float* memory, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
+                             int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                             const sumk_tf_dec_layer_weights* layers, const sumk_tf_opts* opts, const float* dout,
+                             const sumk_tf_dec_layer_grads* layer_grads, float* dtgt, float* dmemory, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* Row scaling y[r,:] = x[r,:] * s[r] (sumgan_att.py:117) and its backward: dx[r,:] = s[r] g[r,:] (written if dx non-NULL),
+ * ds[r] = <x[r,:], g[r,:]> (written if ds non-NULL).  D % 4 == 0. */
+int sumk_row_scale_forward(const float* x, const float* s, int64_t n_rows, int32_t D, float* y, void* stream);
+int sumk_row_scale_backward(const float* x, const float* s, const float* g, int64_t n_rows, int32_t D, float* dx, float* ds,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

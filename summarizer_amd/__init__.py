@@ -7,7 +7,8 @@ PyTorch is used for device memory, streams, autograd plumbing and torch.distribu
 __version__ = "0.1.0"
 
 # Reference dotted path -> module of this package that replaces it.  Only the hot-path modules are
-# aliased: `summarizer.models.rand / logistic / sumgan_att`, `summarizer.utils.config / io` and `main.py` stay the reference's.
+# aliased: `summarizer.models.rand / logistic`, `summarizer.utils.config / io` and `main.py` stay the reference's.  SumGAN-Att is
+# opt-in (OPT_IN_ALIASES, `install_as_reference(opt_in=("sumgan_att",))`): by default the reference's own module runs.
 REFERENCE_ALIASES = {
     "summarizer.models.vasnet": "summarizer_amd.models.vasnet",            # VASNet, VASNetTrainer
     "summarizer.models.dsn": "summarizer_amd.models.dsn",                  # DSN, DSNTrainer
@@ -16,18 +17,25 @@ REFERENCE_ALIASES = {
     "summarizer.utils.eval": "summarizer_amd.utils.eval",                  # upsample, generate_summary, evaluate_*
     "summarizer.utils.knapsack": "summarizer_amd.utils.knapsack",          # knapsack_ortools (native DP, no OR-tools)
 }
+OPT_IN_ALIASES = {
+    "sumgan_att": ("summarizer.models.sumgan_att", "summarizer_amd.models.sumgan_att"),   # SumGANAtt, SumGANAttTrainer
+}
 
 
-def install_as_reference():
+def install_as_reference(opt_in=()):
     """Make the reference's OWN files run on the HIP path without editing them: after this call
     `from summarizer.models.vasnet import VASNetTrainer` (summarizer/utils/config.py:12-18) -- and the same for dsn, sumgan,
     transformer, utils.eval, utils.knapsack -- resolve to this package, so `summarizer/utils/config.py` (HParameters, the
     `-m vasnet|dsn|sumgan|transformer` registry, config.py:68-77), `summarizer/main.py` and `benchmark.py` work unchanged.
-    Call it before anything imports `summarizer.utils.config`; idempotent.  Returns the list of installed aliases."""
+    Call it before anything imports `summarizer.utils.config`; idempotent.  `opt_in` names further aliases of OPT_IN_ALIASES
+    (e.g. ("sumgan_att",)).  Returns the list of installed aliases."""
     import importlib
     import sys
+    unknown = [k for k in opt_in if k not in OPT_IN_ALIASES]
+    if unknown:
+        raise ValueError(f"unknown opt-in alias {unknown}; known: {sorted(OPT_IN_ALIASES)}")
     done = []
-    for ref_name, own_name in REFERENCE_ALIASES.items():
+    for ref_name, own_name in list(REFERENCE_ALIASES.items()) + [OPT_IN_ALIASES[k] for k in opt_in]:
         mod = importlib.import_module(own_name)
         have = sys.modules.get(ref_name)
         if have is not None and have is not mod:

@@ -58,6 +58,14 @@ class TfOpts(C.Structure):
                 ("wplanes", C.c_void_p)]
 
 
+TF_DEC_LAYER_FIELDS = ("sa_in_w", "sa_in_b", "sa_out_w", "sa_out_b", "ca_in_w", "ca_in_b", "ca_out_w", "ca_out_b", "lin1_w", "lin1_b",
+                       "lin2_w", "lin2_b", "norm1_w", "norm1_b", "norm2_w", "norm2_b", "norm3_w", "norm3_b")
+
+
+class TfDecLayerWeights(C.Structure):      # sumk_tf_dec_layer_weights; sumk_tf_dec_layer_grads has the same layout
+    _fields_ = [(n, C.c_void_p) for n in TF_DEC_LAYER_FIELDS]
+
+
 class EvalVideo(C.Structure):
     _fields_ = [("scores", C.c_void_p), ("n_steps", C.c_int32), ("picks", C.c_void_p), ("n_picks", C.c_int32),
                 ("n_frames", C.c_int32), ("cps", C.c_void_p), ("nfps", C.c_void_p), ("n_segs", C.c_int32),
@@ -146,6 +154,20 @@ _SIGS = {
     "sumk_transformer_backward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p, c_f32p,
                                             C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_tf_encoder_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, C.c_int32]),
+    "sumk_tf_encoder_forward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p, C.c_void_p,
+                                          c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    "sumk_tf_encoder_backward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p, C.c_void_p,
+                                           c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_void_p,
+                                           C.c_size_t, C.c_void_p]),
+    "sumk_tf_decoder_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P]),
+    "sumk_tf_decoder_forward": (C.c_int, [c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
+                                          C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    "sumk_tf_decoder_backward": (C.c_int, [c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
+                                           C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]),
+    "sumk_row_scale_forward": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_void_p]),
+    "sumk_row_scale_backward": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_f32p, C.c_void_p]),
     "sumk_dsn_reward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, HOST_I32P, C.c_int32]),
     "sumk_dsn_reward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, HOST_I32P, c_i32p, c_f32p, C.c_int32, C.c_int32,
                                   C.c_int32, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),

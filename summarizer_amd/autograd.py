@@ -130,6 +130,67 @@ class TransformerFunction(torch.autograd.Function):
         return (dx if ctx.needs_input_grad[0] else None, None, None, None, None, None, None) + tuple(ret)
 
 
+class TfEncoderFunction(torch.autograd.Function):
+    """hidden = encoder stack(x) [+ final LayerNorm] for a packed batch (sumgan_att.py:20-80).  cfg: n_layers, n_heads, dff."""
+
+    @staticmethod
+    def forward(ctx, xp, sb, cfg, opts, names, *params):
+        hidden, ws = kernels.tf_encoder_forward(xp, sb, list(params), cfg["n_layers"], cfg["n_heads"], cfg["dff"], opts, training=True)
+        ctx.meta = (sb, cfg, opts, names)
+        ctx.ws, ctx.params = ws, params
+        ctx.save_for_backward(xp)
+        return hidden
+
+    @staticmethod
+    def backward(ctx, dhidden):
+        (xp,) = ctx.saved_tensors
+        sb, cfg, opts, names = ctx.meta
+        grads, ret = _grad_targets(names, ctx.params)
+        dx = kernels.tf_encoder_backward(xp, sb, list(ctx.params), [grads[n] for n in names], cfg["n_layers"], cfg["n_heads"],
+                                         cfg["dff"], opts, dhidden, ctx.ws, want_dx=ctx.needs_input_grad[0])
+        ctx.ws = ctx.params = None
+        return (dx, None, None, None, None) + tuple(ret)
+
+
+class TfDecoderFunction(torch.autograd.Function):
+    """out = decoder stack(tgt, memory) for a packed batch (nn.TransformerDecoder, sumgan_att.py:66-80).  cfg: n_layers, n_heads, dff."""
+
+    @staticmethod
+    def forward(ctx, tgt, memory, sb, cfg, opts, names, *params):
+        out, ws = kernels.tf_decoder_forward(tgt, memory, sb, list(params), cfg["n_layers"], cfg["n_heads"], cfg["dff"], opts,
+                                             training=True)
+        ctx.meta = (sb, cfg, opts, names)
+        ctx.ws, ctx.params = ws, params
+        ctx.save_for_backward(tgt, memory)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        tgt, memory = ctx.saved_tensors
+        sb, cfg, opts, names = ctx.meta
+        grads, ret = _grad_targets(names, ctx.params)
+        dtgt, dmem = kernels.tf_decoder_backward(tgt, memory, sb, list(ctx.params), [grads[n] for n in names], cfg["n_layers"],
+                                                 cfg["n_heads"], cfg["dff"], opts, dout, ctx.ws, want_dtgt=ctx.needs_input_grad[0],
+                                                 want_dmemory=ctx.needs_input_grad[1])
+        ctx.ws = ctx.params = None
+        return (dtgt, dmem, None, None, None, None) + tuple(ret)
+
+
+class RowScaleFunction(torch.autograd.Function):
+    """y = x * s[:, None] for x (n_rows, D), s (n_rows,): the score weighting of sumgan_att.py:117."""
+
+    @staticmethod
+    def forward(ctx, x, s):
+        x, s = x.contiguous(), s.contiguous()
+        ctx.save_for_backward(x, s)
+        return kernels.row_scale_forward(x, s)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, s = ctx.saved_tensors
+        return kernels.row_scale_backward(x, s, g, want_dx=ctx.needs_input_grad[0], want_ds=ctx.needs_input_grad[1])
+
+
 class LinearFunction(torch.autograd.Function):
     """y = x W^T + b on the MFMA GEMM (the small Linear layers around SumGAN's LSTM stacks, sumgan.py:58-59,84)."""
 

@@ -9,23 +9,11 @@
 // (frames, D) layout; softmax is one wave per (query row, head) with shuffle reductions.
 // Inference in bf16x6 / bf16x3 with the weights' planes given (round 5): every projection on the plane GEMM (gemm_pw.hip), and -- heads of 128
 // columns, videos of at most 320 frames -- the per-head attention on the multi-head form of attn_pw.hip; see "plane path" below.
-#include "sumk_internal.h"
+#include "tf_internal.h"
 #include <math.h>
 #include <algorithm>
 
 namespace sumk {
-
-struct TfSeq { int64_t eoff; int32_t row0, T, ldE, pad_; };   // eoff: offset of this video's [heads][T][ldE] logits block
-
-struct TfWs {
-  size_t qkv, e, ctx, h0, h1, h2, t1, ff, seq, prob_row, prob_tabs, total;
-  // training: per-layer saves (offset of layer 0 + l * lay_stride) and backward scratch
-  size_t lay0, lay_stride, l_qkv, l_p, l_pd, l_ctx, l_t1a, l_hmid, l_ff, l_t1b, l_hout, l_stats;
-  size_t hfin, z, stats_fin, scores, g0, g1, g2, dqkv, dff, lnpart, colpart, slab, prob_sk;
-  size_t slab_elems;
-  int64_t e_elems; int32_t n_rows;
-};
-enum { TT_S = 0, TT_PV = 1, TT_DV = 2, TT_DP = 3, TT_DQ = 4, TT_DK = 5, TT_COUNT = 6 };
 
 // Plane path (inference in bf16x6 / bf16x3; gemm_pw.hip): every projection of the stack reads bf16 planes of both operands.  The
 // weights' planes are built once per weight change (sumk_transformer_wplanes_build: per layer [Win | Wo | W1 | W2], then k1), the
@@ -76,9 +64,7 @@ static int tf_np(int precision) { return precision == SUMK_PRECISION_BF16X6 ? 3 
 static bool tf_pw_rows_ok(int D, int F, int64_t R, int np) {
   return R >= 128 && pw_ok(R, 3 * (int64_t)D, D, R, 3 * (int64_t)D, np) && pw_ok(R, F, D, R, F, np) && pw_ok(R, D, F, R, D, np);
 }
-constexpr int TF_SPLITK_PROBS = 64, TF_COLSUM_CHUNKS = 128;
-
-static int tf_carve(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, TfWs* w) {
+int tf_carve(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, TfWs* w) {
   SUMK_ARG(D > 0 && D % 4 == 0 && F > 0 && F % 4 == 0, "transformer: D=%d / F=%d must be positive multiples of 4", D, F);
   SUMK_ARG(heads > 0 && D % heads == 0 && (D / heads) % 4 == 0, "transformer: head dim must be a multiple of 4 (D=%d heads=%d)", D, heads);
   SUMK_ARG(n_seq > 0 && off && off[0] == 0, "transformer: empty batch / seq_off[0] != 0");
@@ -260,10 +246,7 @@ __global__ void relu_drop_bwd_kernel(float* __restrict__ g, const float* __restr
   if (i < n) g[i] = act[i] > 0.f ? g[i] * scale : 0.f;
 }
 
-struct TfGeom { TfWs L; int R, dh, tiles_s, tiles_pv, c_qkv, c_dd, c_df; };
-enum { P_QKV = 0, P_DD = 1, P_DF = 2, P_FD = 3, P_DQKV = 4, P_NN_DF = 5, P_NN_FD = 6 };
-
-static int tf_geometry(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, TfGeom* G) {
+int tf_geometry(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, TfGeom* G) {
   SUMK_TRY(tf_carve(D, F, heads, n_layers, n_seq, off, training, &G->L));
   G->R = G->L.n_rows; G->dh = D / heads; G->tiles_s = G->tiles_pv = 0;
   for (int s = 0; s < n_seq; ++s) {
@@ -275,7 +258,7 @@ static int tf_geometry(int D, int F, int heads, int n_layers, int n_seq, const i
   return SUMK_OK;
 }
 
-static int tf_tables(const TfGeom& G, int D, int F, int heads, int n_seq, const int32_t* off_dev, char* ws, hipStream_t stream) {
+int tf_tables(const TfGeom& G, int D, int F, int heads, int n_seq, const int32_t* off_dev, char* ws, hipStream_t stream) {
   const int R = G.R;
   GemmProb* prow = (GemmProb*)(ws + G.L.prob_row);
   hipLaunchKernelGGL(tf_setup_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, stream, off_dev, n_seq, D, heads,
@@ -288,6 +271,152 @@ static int tf_tables(const TfGeom& G, int D, int F, int heads, int n_seq, const 
   SUMK_TRY(fill_single_prob(prow + P_NN_DF, R, F, D, D, F, F, 0, G.c_df, stream));          // (R,F)  <- (R,D) x (D,F)    (NN)
   SUMK_TRY(fill_single_prob(prow + P_NN_FD, R, D, F, F, D, D, D, G.c_dd, stream));          // (R,D)  <- (R,F) x (F,D)    (NN)
   return SUMK_OK;
+}
+
+
+// ---- exact-fp32 blocks of one post-norm layer (tf_internal.h), shared with the encoder / decoder stack entries (tf_decoder.hip)
+int tf_in_proj(const TfRun& r, const float* hin, const float* in_w, const float* in_b, float* QKV) {
+  const TfGeom& G = *r.G; const int R = G.R, D = r.D;
+  GemmLaunch g; g.precision = r.precision;
+  g.A = hin; g.B[0] = in_w; g.bias0[0] = in_b; g.C = QKV; g.probs = (const GemmProb*)(r.ws + G.L.prob_row) + P_QKV; g.small_tile = G.c_qkv;
+  g.total_tiles = gemm_tiles(R, 3 * D, G.c_qkv); g.xcd_M = R; g.xcd_N = 3 * D; g.lean = gemm_lean_ok(R, 3 * D, D, D, D);
+  return launch_gemm(GEMM_NT, EPI_BIAS2, g, r.stream);
+}
+
+int tf_out_proj(const TfRun& r, const float* CTX, const float* out_w, const float* out_b, const float* hres, float* T, Drop dl,
+                uint32_t site) {
+  const TfGeom& G = *r.G; const int R = G.R, D = r.D;
+  GemmLaunch g; g.precision = r.precision;
+  g.A = CTX; g.B[0] = out_w; g.bias0[0] = out_b; g.R = hres; g.C = T; g.probs = (const GemmProb*)(r.ws + G.L.prob_row) + P_DD;
+  g.small_tile = G.c_dd; g.total_tiles = gemm_tiles(R, D, G.c_dd); g.xcd_M = R; g.xcd_N = D; g.lean = gemm_lean_ok(R, D, D, D, D);
+  g.drop_seed = dl.seed; g.drop_thr = dl.thr; g.drop_scale = dl.scale; g.drop_site = site;
+  return launch_gemm(GEMM_NT, EPI_BIAS_RESIDUAL, g, r.stream);
+}
+
+int tf_attn_core_fwd(const TfRun& r, const GemmProb* tabs, const float* qbase, const float* kvbase, float* E, float* E2, float* CTX,
+                     Drop dl, uint32_t site) {
+  const TfGeom& G = *r.G; const int R = G.R, np = r.n_seq * r.heads;
+  {  // logits per (video, head)
+    GemmLaunch g; g.precision = r.precision;
+    g.A = qbase; g.B[0] = kvbase; g.C = E; g.probs = tabs + (size_t)TT_S * np; g.nprob = np; g.small_tile = 1; g.total_tiles = G.tiles_s;
+    SUMK_TRY(launch_gemm(GEMM_NT, EPI_NONE, g, r.stream));
+  }
+  hipLaunchKernelGGL(tf_softmax_kernel, dim3((unsigned)(((int64_t)R * r.heads + 3) / 4)), dim3(256), 0, r.stream, E,
+                     dl.thr ? E2 : nullptr, (const TfSeq*)(r.ws + G.L.seq), r.off_dev, r.n_seq, R, r.heads,
+                     1.0f / sqrtf((float)G.dh), dl, site);
+  {  // context, heads written side by side
+    GemmLaunch g; g.precision = r.precision;
+    g.A = dl.thr ? E2 : E; g.B[0] = kvbase; g.C = CTX; g.probs = tabs + (size_t)TT_PV * np; g.nprob = np; g.small_tile = 1;
+    g.total_tiles = G.tiles_pv;
+    SUMK_TRY(launch_gemm(GEMM_NN, EPI_NONE, g, r.stream));
+  }
+  return SUMK_OK;
+}
+
+int tf_attn_core_bwd(const TfRun& r, const GemmProb* tabs, const float* qbase, const float* kvbase, const float* P, float* E2,
+                     const float* dCTX, float* dq_base, float* dkv_base, Drop dl, uint32_t site) {
+  const TfGeom& G = *r.G; const int R = G.R, np = r.n_seq * r.heads;
+  const float* Pd = dl.thr ? (const float*)E2 : P;
+  {
+    GemmLaunch g; g.precision = r.precision;
+    g.A = Pd; g.B[0] = dCTX; g.C = dkv_base; g.probs = tabs + (size_t)TT_DV * np; g.nprob = np; g.small_tile = 1; g.total_tiles = G.tiles_pv;
+    SUMK_TRY(launch_gemm(GEMM_TN, EPI_NONE, g, r.stream));
+  }
+  {
+    GemmLaunch g; g.precision = r.precision;
+    g.A = dCTX; g.B[0] = kvbase; g.C = E2; g.probs = tabs + (size_t)TT_DP * np; g.nprob = np; g.small_tile = 1; g.total_tiles = G.tiles_s;
+    SUMK_TRY(launch_gemm(GEMM_NT, EPI_NONE, g, r.stream));
+  }
+  hipLaunchKernelGGL(tf_softmax_bwd_kernel, dim3((unsigned)(((int64_t)R * r.heads + 3) / 4)), dim3(256), 0, r.stream, P, E2,
+                     (const TfSeq*)(r.ws + G.L.seq), r.off_dev, r.n_seq, R, r.heads, 1.0f / sqrtf((float)G.dh), dl, site);
+  {
+    GemmLaunch g; g.precision = r.precision;
+    g.A = E2; g.B[0] = kvbase; g.C = dq_base; g.probs = tabs + (size_t)TT_DQ * np; g.nprob = np; g.small_tile = 1; g.total_tiles = G.tiles_pv;
+    SUMK_TRY(launch_gemm(GEMM_NN, EPI_NONE, g, r.stream));
+  }
+  {
+    GemmLaunch g; g.precision = r.precision;
+    g.A = E2; g.B[0] = qbase; g.C = dkv_base; g.probs = tabs + (size_t)TT_DK * np; g.nprob = np; g.small_tile = 1; g.total_tiles = G.tiles_pv;
+    SUMK_TRY(launch_gemm(GEMM_TN, EPI_NONE, g, r.stream));
+  }
+  return SUMK_OK;
+}
+
+int tf_sa_fwd(const TfRun& r, const TfAttnW& W, const float* hin, float* QKV, float* E, float* E2, float* CTX, float* T1a, Drop dl,
+              uint32_t site) {
+  SUMK_TRY(tf_in_proj(r, hin, W.in_w, W.in_b, QKV));
+  SUMK_TRY(tf_attn_core_fwd(r, (const GemmProb*)(r.ws + r.G->L.prob_tabs), QKV, QKV, E, E2, CTX, dl, site + 0));
+  return tf_out_proj(r, CTX, W.out_w, W.out_b, hin, T1a, dl, site + 1);
+}
+
+int tf_wgrad(const TfRun& r, const float* dY, int ldy, int M, const float* Xin, int ldx, int N, float* out) {
+  const TfWs& L = r.G->L;
+  float* outs[4] = {out, nullptr, nullptr, nullptr};
+  return gemm_tn_splitk_accum(dY, ldy, Xin, ldx, M, N, r.G->R, (float*)(r.ws + L.slab), L.slab_elems, (GemmProb*)(r.ws + L.prob_sk),
+                              TF_SPLITK_PROBS, outs, M, N, 1.f, r.stream, r.precision);
+}
+
+int tf_nn(const TfRun& r, const float* A, const float* B, float* C, int prob, GemmEpi epi, int N) {
+  const TfGeom& G = *r.G;
+  GemmLaunch g; g.precision = r.precision;
+  g.A = A; g.B[0] = B; g.C = C; g.probs = (const GemmProb*)(r.ws + G.L.prob_row) + prob; g.small_tile = (N == r.F ? G.c_df : G.c_dd);
+  g.total_tiles = gemm_tiles(G.R, N, g.small_tile);
+  return launch_gemm(GEMM_NN, epi, g, r.stream);
+}
+
+static dim3 tf_blocks(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+int tf_sa_bwd(const TfRun& r, const TfAttnW& W, const TfAttnG& Gd, const float* hin, const float* QKV, const float* P, float* E2,
+              const float* CTX, float* dT, float* s1, float* s2, float* dQKV, Drop dl, uint32_t site) {
+  const int R = r.G->R, D = r.D; const int64_t nRD = (int64_t)R * D;
+  float* colpart = (float*)(r.ws + r.G->L.colpart);
+  const float* dAO = dT;
+  if (dl.thr) { hipLaunchKernelGGL(mask_scale_kernel, tf_blocks(nRD), dim3(256), 0, r.stream, s2, dT, nRD, dl, site + 1); dAO = s2; }
+  SUMK_TRY(colsum_accum(dAO, D, R, D, colpart, TF_COLSUM_CHUNKS, Gd.out_b, r.stream));
+  SUMK_TRY(tf_wgrad(r, dAO, D, D, CTX, D, D, Gd.out_w));
+  SUMK_TRY(tf_nn(r, dAO, W.out_w, s1, P_DD, EPI_NONE, D));                  // s1 = dCTX
+  // multi-head attention backward, per (video, head)
+  SUMK_TRY(tf_attn_core_bwd(r, (const GemmProb*)(r.ws + r.G->L.prob_tabs), QKV, QKV, P, E2, s1, dQKV, dQKV, dl, site + 0));
+  SUMK_TRY(colsum_accum(dQKV, 3 * D, R, 3 * D, colpart, TF_COLSUM_CHUNKS, Gd.in_b, r.stream));
+  SUMK_TRY(tf_wgrad(r, dQKV, 3 * D, 3 * D, hin, D, D, Gd.in_w));
+  return tf_nn(r, dQKV, W.in_w, dT, P_DQKV, EPI_ACCUM, D);                  // dHin = dT1a + dQKV . Win   (Win stored (3D,D) = (K,N))
+}
+
+int tf_ff_fwd(const TfRun& r, const TfFfW& W, const float* h, float* FF, float* T, Drop dl, uint32_t site_a, uint32_t site_b) {
+  const TfGeom& G = *r.G; const int R = G.R, D = r.D, F = r.F;
+  const GemmProb* prow = (const GemmProb*)(r.ws + G.L.prob_row);
+  {  // feed-forward 1: bias + ReLU (+dropout)
+    GemmLaunch g; g.precision = r.precision;
+    g.A = h; g.B[0] = W.w1; g.bias0[0] = W.b1; g.C = FF; g.probs = prow + P_DF; g.small_tile = G.c_df;
+    g.total_tiles = gemm_tiles(R, F, G.c_df); g.xcd_M = R; g.xcd_N = F; g.lean = gemm_lean_ok(R, F, D, D, D);
+    g.drop_seed = dl.seed; g.drop_thr = dl.thr; g.drop_scale = dl.scale; g.drop_site = site_a;
+    SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS_RELU, g, r.stream));
+  }
+  {  // feed-forward 2: bias (+dropout) + residual
+    GemmLaunch g; g.precision = r.precision;
+    g.A = FF; g.B[0] = W.w2; g.bias0[0] = W.b2; g.R = h; g.C = T; g.probs = prow + P_FD; g.small_tile = G.c_dd;
+    g.total_tiles = gemm_tiles(R, D, G.c_dd); g.xcd_M = R; g.xcd_N = D; g.lean = gemm_lean_ok(R, D, F, F, F);
+    g.drop_seed = dl.seed; g.drop_thr = dl.thr; g.drop_scale = dl.scale; g.drop_site = site_b;
+    SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS_RESIDUAL, g, r.stream));
+  }
+  return SUMK_OK;
+}
+
+int tf_ff_bwd(const TfRun& r, const TfFfW& W, const TfFfG& Gd, const float* h, const float* FFa, float* dT, float* s1, float* dFF,
+              Drop dl, uint32_t site_a, uint32_t site_b) {
+  (void)site_a;   // the ReLU / dropout mask of lin1 is read back from the stored post-dropout activation
+  const int R = r.G->R, D = r.D, F = r.F; const int64_t nRD = (int64_t)R * D, nRF = (int64_t)R * F;
+  float* colpart = (float*)(r.ws + r.G->L.colpart);
+  // dT is also the residual gradient into h.  dropout mask -> s1 = d(linear2 output)
+  const float* dL2 = dT;
+  if (dl.thr) { hipLaunchKernelGGL(mask_scale_kernel, tf_blocks(nRD), dim3(256), 0, r.stream, s1, dT, nRD, dl, site_b); dL2 = s1; }
+  SUMK_TRY(colsum_accum(dL2, D, R, D, colpart, TF_COLSUM_CHUNKS, Gd.b2, r.stream));
+  SUMK_TRY(tf_wgrad(r, dL2, D, D, FFa, F, F, Gd.w2));
+  SUMK_TRY(tf_nn(r, dL2, W.w2, dFF, P_NN_DF, EPI_NONE, F));                 // dFF = dL2 . W2   (W2 stored (D,F) = (K,N))
+  hipLaunchKernelGGL(relu_drop_bwd_kernel, tf_blocks(nRF), dim3(256), 0, r.stream, dFF, FFa, nRF, dl.scale);
+  SUMK_TRY(colsum_accum(dFF, F, R, F, colpart, TF_COLSUM_CHUNKS, Gd.b1, r.stream));
+  SUMK_TRY(tf_wgrad(r, dFF, F, F, h, D, D, Gd.w1));
+  return tf_nn(r, dFF, W.w1, dT, P_NN_FD, EPI_ACCUM, D);                    // dH = dT + dFF . W1   (W1 stored (F,D) = (K,N))
 }
 
 }  // namespace sumk
@@ -356,7 +485,7 @@ extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t 
   const TfWs& L = G.L;
   if (workspace_bytes < L.total) { set_error("transformer_forward: workspace %zu < required %zu", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
   char* ws = (char*)workspace;
-  const int R = G.R, dh = G.dh, np = n_seq * n_heads;
+  const int R = G.R, dh = G.dh;
   // the plane path: inference in a split-bf16 arithmetic with the weights' planes at hand
   const int npl = tf_np(opts->precision);
   const bool pw = !training && npl && opts->wplanes && tf_wplanes_ok(D, F, npl) && tf_pw_rows_ok(D, F, R, npl);
@@ -382,12 +511,12 @@ extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t 
     g.bias = bias; g.R = Rs; g.ldr = N; g.relu = relu; g.C = C_; g.ldc = N; g.O = O_; g.o_rows = R;
     return launch_gemm_pw(O_ ? PW_PLANES : Rs ? PW_RES_F32 : PW_F32, g, stream);
   };
-  TfSeq* seq = (TfSeq*)(ws + L.seq);
   GemmProb* prow = (GemmProb*)(ws + L.prob_row);
   GemmProb* tabs = (GemmProb*)(ws + L.prob_tabs);
   float* T1 = (float*)(ws + L.t1);
   const Drop dl = make_drop(opts->layer_dropout_p, opts->seed), dhd = make_drop(opts->head_dropout_p, opts->seed);
   const float att_scale = 1.0f / sqrtf((float)dh);
+  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream};
 
   if (pos_table) SUMK_TRY(launch_add_pos(x, pos_table, pos_rows, R, D, stream));
   SUMK_TRY(tf_tables(G, D, F, n_heads, n_seq, seq_off_dev, ws, stream));
@@ -425,33 +554,14 @@ extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t 
         SUMK_TRY(split_planes(hin, R, D, D, npl, PA, stream));
         SUMK_TRY(pw_linear(PA, wl + WL.win, 3 * D, D, W.in_proj_b, nullptr, 0, QKV, nullptr));
       } else {  // packed in-projection  [Q|K|V] = h Win^T + bin
-        GemmLaunch g; g.precision = opts->precision;
-        g.A = hin; g.B[0] = W.in_proj_w; g.bias0[0] = W.in_proj_b; g.C = QKV; g.probs = prow + P_QKV; g.small_tile = G.c_qkv;
-        g.total_tiles = gemm_tiles(R, 3 * D, G.c_qkv); g.xcd_M = R; g.xcd_N = 3 * D; g.lean = gemm_lean_ok(R, 3 * D, D, D, D);
-        SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS2, g, stream));
+        SUMK_TRY(tf_in_proj(run, hin, W.in_proj_w, W.in_proj_b, QKV));
       }
-      {  // logits per (video, head)
-        GemmLaunch g; g.precision = opts->precision;
-        g.A = QKV; g.B[0] = QKV; g.C = E; g.probs = tabs + (size_t)TT_S * np; g.nprob = np; g.small_tile = 1; g.total_tiles = G.tiles_s;
-        SUMK_TRY(launch_gemm(GEMM_NT, EPI_NONE, g, stream));
-      }
-      hipLaunchKernelGGL(tf_softmax_kernel, dim3((unsigned)(((int64_t)R * n_heads + 3) / 4)), dim3(256), 0, stream, E, E2, seq,
-                         seq_off_dev, n_seq, R, n_heads, att_scale, dl, site + 0);
-      {  // context, heads written side by side
-        GemmLaunch g; g.precision = opts->precision;
-        g.A = E2 ? E2 : E; g.B[0] = QKV; g.C = CTX; g.probs = tabs + (size_t)TT_PV * np; g.nprob = np; g.small_tile = 1;
-        g.total_tiles = G.tiles_pv;
-        SUMK_TRY(launch_gemm(GEMM_NN, EPI_NONE, g, stream));
-      }
+      SUMK_TRY(tf_attn_core_fwd(run, tabs, QKV, QKV, E, E2, CTX, dl, site + 0));   // logits, softmax, context per (video, head)
       if (pw) {
         SUMK_TRY(split_planes(CTX, R, D, D, npl, PA, stream));
         SUMK_TRY(pw_linear(PA, wl + WL.wo, D, D, W.out_proj_b, hin, 0, T1a, nullptr));
       } else {  // out-projection + bias (+dropout1) + residual
-        GemmLaunch g; g.precision = opts->precision;
-        g.A = CTX; g.B[0] = W.out_proj_w; g.bias0[0] = W.out_proj_b; g.R = hin; g.C = T1a; g.probs = prow + P_DD; g.small_tile = G.c_dd;
-        g.total_tiles = gemm_tiles(R, D, G.c_dd); g.xcd_M = R; g.xcd_N = D; g.lean = gemm_lean_ok(R, D, D, D, D);
-        g.drop_seed = dl.seed; g.drop_thr = dl.thr; g.drop_scale = dl.scale; g.drop_site = site + 1;
-        SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS_RESIDUAL, g, stream));
+        SUMK_TRY(tf_out_proj(run, CTX, W.out_proj_w, W.out_proj_b, hin, T1a, dl, site + 1));
       }
     }
     SUMK_TRY(launch_layernorm(T1a, hmid, W.norm1_w, W.norm1_b, R, D, opts->layer_eps, stats, stream));
@@ -459,21 +569,8 @@ extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t 
       SUMK_TRY(split_planes(hmid, R, D, D, npl, PA, stream));
       SUMK_TRY(pw_linear(PA, wl + WL.w1, F, D, W.lin1_b, nullptr, 1, nullptr, PB));
       SUMK_TRY(pw_linear(PB, wl + WL.w2, D, F, W.lin2_b, hmid, 0, T1b, nullptr));
-    } else {
-      {  // feed-forward 1: bias + ReLU (+dropout)
-        GemmLaunch g; g.precision = opts->precision;
-        g.A = hmid; g.B[0] = W.lin1_w; g.bias0[0] = W.lin1_b; g.C = FF; g.probs = prow + P_DF; g.small_tile = G.c_df;
-        g.total_tiles = gemm_tiles(R, F, G.c_df); g.xcd_M = R; g.xcd_N = F; g.lean = gemm_lean_ok(R, F, D, D, D);
-        g.drop_seed = dl.seed; g.drop_thr = dl.thr; g.drop_scale = dl.scale; g.drop_site = site + 2;
-        SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS_RELU, g, stream));
-      }
-      {  // feed-forward 2: bias (+dropout2) + residual
-        GemmLaunch g; g.precision = opts->precision;
-        g.A = FF; g.B[0] = W.lin2_w; g.bias0[0] = W.lin2_b; g.R = hmid; g.C = T1b; g.probs = prow + P_FD; g.small_tile = G.c_dd;
-        g.total_tiles = gemm_tiles(R, D, G.c_dd); g.xcd_M = R; g.xcd_N = D; g.lean = gemm_lean_ok(R, D, F, F, F);
-        g.drop_seed = dl.seed; g.drop_thr = dl.thr; g.drop_scale = dl.scale; g.drop_site = site + 3;
-        SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS_RESIDUAL, g, stream));
-      }
+    } else {   // feed-forward 1: bias + ReLU (+dropout); feed-forward 2: bias (+dropout2) + residual
+      SUMK_TRY(tf_ff_fwd(run, TfFfW{W.lin1_w, W.lin1_b, W.lin2_w, W.lin2_b}, hmid, FF, T1b, dl, site + 2, site + 3));
     }
     SUMK_TRY(launch_layernorm(T1b, hout, W.norm2_w, W.norm2_b, R, D, opts->layer_eps, stats ? stats + 2 * (size_t)R : nullptr, stream));
     hin = hout;
@@ -516,21 +613,19 @@ extern "C" int sumk_transformer_backward(const float* x, int32_t D, int32_t F, i
   const TfWs& L = G.L;
   if (workspace_bytes < L.total) { set_error("transformer_backward: workspace %zu < required %zu (needs the training-mode forward's workspace)", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
   char* ws = (char*)workspace;
-  const int R = G.R, dh = G.dh, np = n_seq * n_heads;
-  const int64_t nRD = (int64_t)R * D, nRF = (int64_t)R * F;
-  TfSeq* seq = (TfSeq*)(ws + L.seq);
+  const int R = G.R;
+  const int64_t nRD = (int64_t)R * D;
   GemmProb* prow = (GemmProb*)(ws + L.prob_row);
-  GemmProb* tabs = (GemmProb*)(ws + L.prob_tabs);
   GemmProb* psk = (GemmProb*)(ws + L.prob_sk);
   float* g0 = (float*)(ws + L.g0); float* g1 = (float*)(ws + L.g1); float* g2 = (float*)(ws + L.g2);
   float* dQKV = (float*)(ws + L.dqkv); float* dFF = (float*)(ws + L.dff);
-  float* lnpart = (float*)(ws + L.lnpart); float* colpart = (float*)(ws + L.colpart); float* slab = (float*)(ws + L.slab);
+  float* lnpart = (float*)(ws + L.lnpart); float* slab = (float*)(ws + L.slab);
   const float* hfin = (const float*)(ws + L.hfin); const float* Z = (const float*)(ws + L.z);
   const float* sfin = (const float*)(ws + L.stats_fin); const float* scores = (const float*)(ws + L.scores);
   const Drop dl = make_drop(opts->layer_dropout_p, opts->seed), dhd = make_drop(opts->head_dropout_p, opts->seed);
   const Drop none = make_drop(0.f, 0);
-  const float att_scale = 1.0f / sqrtf((float)dh);
   int nw = 0;
+  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream};
   auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
   auto nn = [&](const float* A, const float* B, float* C, int prob, GemmEpi epi, int N) -> int {   // C (op)= A . B, B stored (K, N)
     GemmLaunch g; g.precision = opts->precision;
@@ -572,52 +667,15 @@ extern "C" int sumk_transformer_backward(const float* x, int32_t D, int32_t F, i
     // norm2
     SUMK_TRY(launch_ln_bwd_rows(D, R, T1b, stats + 2 * (size_t)R, W.norm2_w, W.norm2_b, dH, fa, lnpart, none, 0u, &nw, stream));
     SUMK_TRY(ln_bwd_reduce(lnpart, nw, D, Gd.norm2_w, Gd.norm2_b, nullptr, nullptr, nullptr, stream));
-    // fa = dT1b (also the residual gradient into hmid).  dropout2 mask -> fb = d(linear2 output)
-    const float* dL2 = fa;
-    if (dl.thr) { hipLaunchKernelGGL(mask_scale_kernel, blocks(nRD), dim3(256), 0, stream, fb, fa, nRD, dl, site + 3); dL2 = fb; }
-    SUMK_TRY(colsum_accum(dL2, D, R, D, colpart, TF_COLSUM_CHUNKS, Gd.lin2_b, stream));
-    SUMK_TRY(wgrad(dL2, D, D, FFa, F, F, Gd.lin2_w, nullptr, nullptr, D));
-    SUMK_TRY(nn(dL2, W.lin2_w, dFF, P_NN_DF, EPI_NONE, F));                     // dFF = dL2 . W2   (W2 stored (D,F) = (K,N))
-    hipLaunchKernelGGL(relu_drop_bwd_kernel, blocks(nRF), dim3(256), 0, stream, dFF, FFa, nRF, dl.scale);
-    SUMK_TRY(colsum_accum(dFF, F, R, F, colpart, TF_COLSUM_CHUNKS, Gd.lin1_b, stream));
-    SUMK_TRY(wgrad(dFF, F, F, hmid, D, D, Gd.lin1_w, nullptr, nullptr, F));
-    SUMK_TRY(nn(dFF, W.lin1_w, fa, P_NN_FD, EPI_ACCUM, D));                     // fa = dT1b + dFF . W1 = dHmid   (W1 stored (F,D) = (K,N))
+    // fa = dT1b (also the residual gradient into hmid) -> fa = dT1b + the feed-forward path = dHmid
+    SUMK_TRY(tf_ff_bwd(run, TfFfW{W.lin1_w, W.lin1_b, W.lin2_w, W.lin2_b}, TfFfG{Gd.lin1_w, Gd.lin1_b, Gd.lin2_w, Gd.lin2_b}, hmid, FFa,
+                       fa, fb, dFF, dl, site + 2, site + 3));
     // norm1
     SUMK_TRY(launch_ln_bwd_rows(D, R, T1a, stats, W.norm1_w, W.norm1_b, fa, dH, lnpart, none, 0u, &nw, stream));   // dH buffer reused: dT1a
     SUMK_TRY(ln_bwd_reduce(lnpart, nw, D, Gd.norm1_w, Gd.norm1_b, nullptr, nullptr, nullptr, stream));
-    float* dT1a = dH;
-    const float* dAO = dT1a;
-    if (dl.thr) { hipLaunchKernelGGL(mask_scale_kernel, blocks(nRD), dim3(256), 0, stream, fb, dT1a, nRD, dl, site + 1); dAO = fb; }
-    SUMK_TRY(colsum_accum(dAO, D, R, D, colpart, TF_COLSUM_CHUNKS, Gd.out_proj_b, stream));
-    SUMK_TRY(wgrad(dAO, D, D, CTX, D, D, Gd.out_proj_w, nullptr, nullptr, D));
-    SUMK_TRY(nn(dAO, W.out_proj_w, fa, P_DD, EPI_NONE, D));                  // fa = dCTX
-    // multi-head attention backward, per (video, head)
-    const float* Pd = dl.thr ? (const float*)E2 : P;
-    {
-      GemmLaunch g; g.precision = opts->precision;
-      g.A = Pd; g.B[0] = fa; g.C = dQKV; g.probs = tabs + (size_t)TT_DV * np; g.nprob = np; g.small_tile = 1; g.total_tiles = G.tiles_pv;
-      SUMK_TRY(launch_gemm(GEMM_TN, EPI_NONE, g, stream));
-    }
-    {
-      GemmLaunch g; g.precision = opts->precision;
-      g.A = fa; g.B[0] = QKV; g.C = E2; g.probs = tabs + (size_t)TT_DP * np; g.nprob = np; g.small_tile = 1; g.total_tiles = G.tiles_s;
-      SUMK_TRY(launch_gemm(GEMM_NT, EPI_NONE, g, stream));
-    }
-    hipLaunchKernelGGL(tf_softmax_bwd_kernel, dim3((unsigned)(((int64_t)R * n_heads + 3) / 4)), dim3(256), 0, stream, P, E2, seq,
-                       seq_off_dev, n_seq, R, n_heads, att_scale, dl, site + 0);
-    {
-      GemmLaunch g; g.precision = opts->precision;
-      g.A = E2; g.B[0] = QKV; g.C = dQKV; g.probs = tabs + (size_t)TT_DQ * np; g.nprob = np; g.small_tile = 1; g.total_tiles = G.tiles_pv;
-      SUMK_TRY(launch_gemm(GEMM_NN, EPI_NONE, g, stream));
-    }
-    {
-      GemmLaunch g; g.precision = opts->precision;
-      g.A = E2; g.B[0] = QKV; g.C = dQKV; g.probs = tabs + (size_t)TT_DK * np; g.nprob = np; g.small_tile = 1; g.total_tiles = G.tiles_pv;
-      SUMK_TRY(launch_gemm(GEMM_TN, EPI_NONE, g, stream));
-    }
-    SUMK_TRY(colsum_accum(dQKV, 3 * D, R, 3 * D, colpart, TF_COLSUM_CHUNKS, Gd.in_proj_b, stream));
-    SUMK_TRY(wgrad(dQKV, 3 * D, 3 * D, hin, D, D, Gd.in_proj_w, nullptr, nullptr, 3 * D));
-    SUMK_TRY(nn(dQKV, W.in_proj_w, dT1a, P_DQKV, EPI_ACCUM, D));             // dHin = dT1a + dQKV . Win   (Win stored (3D,D) = (K,N))
+    // dT1a (in dH) -> dHin: out-projection (dropout1 mask), per-(video, head) attention, in-projection backward; fa, fb scratch
+    SUMK_TRY(tf_sa_bwd(run, TfAttnW{W.in_proj_w, W.in_proj_b, W.out_proj_w, W.out_proj_b},
+                       TfAttnG{Gd.in_proj_w, Gd.in_proj_b, Gd.out_proj_w, Gd.out_proj_b}, hin, QKV, P, E2, CTX, dH, fa, fb, dQKV, dl, site));
     // dH (= dT1a buffer) now holds the gradient w.r.t. this layer's input = the previous layer's output
   }
   if (dx) {

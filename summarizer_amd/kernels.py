@@ -679,6 +679,159 @@ def transformer_backward_packed(x, sb, params, grads, n_layers, n_heads, dff, op
     return dx
 
 
+# ------------------------------------------------------------------------------------------------ Transformer stacks (SumGAN-Att)
+TF_DEC_LAYER_KEYS = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
+                     "multihead_attn.in_proj_weight", "multihead_attn.in_proj_bias", "multihead_attn.out_proj.weight",
+                     "multihead_attn.out_proj.bias", "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias",
+                     "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias", "norm3.weight", "norm3.bias")   # order of _lib.TF_DEC_LAYER_FIELDS
+
+
+def tf_encoder_param_names(prefix, n_layers, norm_prefix=None):
+    """Keys (under `prefix`, e.g. "transformer_encoder.layers.") the encoder-stack entry reads, layer by layer, then the final norm's."""
+    names = [f"{prefix}{l}.{k}" for l in range(n_layers) for _, k in TF_LAYER_FIELDS]
+    return names + ([f"{norm_prefix}weight", f"{norm_prefix}bias"] if norm_prefix else [])
+
+
+def tf_decoder_param_names(prefix, n_layers):
+    return [f"{prefix}{l}.{k}" for l in range(n_layers) for k in TF_DEC_LAYER_KEYS]
+
+
+def _ptr(t, what):
+    _require_gpu(t, what)
+    if not t.is_contiguous():
+        raise SumkError(f"{what} must be contiguous")
+    return t.data_ptr()
+
+
+def _stack_opts(opts):
+    o = dict(opts)
+    o.setdefault("final_eps", 1e-5)
+    return _tf_opts(o)
+
+
+def _check_rows(x, sb, what):
+    _require_gpu(x, what)
+    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != sb.n_rows:
+        raise SumkError(f"{what} must be contiguous (n_rows={sb.n_rows}, D), got {tuple(x.shape)}")
+
+
+def _enc_structs(tensors, n_layers):
+    """tensors: the encoder-stack's tensors in tf_encoder_param_names order -> (layer array, norm_w, norm_b)"""
+    nf = len(TF_LAYER_FIELDS)
+    layers = (_lib.TfLayerWeights * n_layers)()
+    for l in range(n_layers):
+        for i, (f, _) in enumerate(TF_LAYER_FIELDS):
+            setattr(layers[l], f, _ptr(tensors[l * nf + i], f"encoder layer {l} {f}"))
+    rest = tensors[n_layers * nf:]
+    return layers, (tensors_or_none(rest, 0), tensors_or_none(rest, 1))
+
+
+def tensors_or_none(seq, i):
+    return seq[i] if len(seq) > i else None
+
+
+def tf_encoder_forward(x, sb, tensors, n_layers, n_heads, dff, opts, training=False):
+    """Encoder stack (sumk_tf_encoder_forward): x (n_rows, D) packed -> (hidden (n_rows, D), workspace or None).  `tensors` in
+    tf_encoder_param_names order; with two trailing tensors the final LayerNorm is applied."""
+    lib = _lib.load()
+    _check_rows(x, sb, "encoder-stack input")
+    D = x.shape[1]
+    layers, (nw, nb) = _enc_structs(tensors, n_layers)
+    o = _stack_opts(opts)
+    nbytes = lib.sumk_tf_encoder_workspace_bytes(D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, int(training))
+    if nbytes == 0:
+        _lib.check(-1, "sumk_tf_encoder_workspace_bytes")
+    ws = workspace(nbytes, x.device, persistent=training)
+    out = torch.empty_like(x)
+    rc = lib.sumk_tf_encoder_forward(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p, C.cast(layers, C.c_void_p),
+                                     _p(nw), _p(nb), C.cast(C.pointer(o), C.c_void_p), _p(out), _p(ws), ws.numel(), int(training), _stream())
+    _lib.check(rc, "sumk_tf_encoder_forward")
+    return out, (ws if training else None)
+
+
+def tf_encoder_backward(x, sb, tensors, grads, n_layers, n_heads, dff, opts, dhidden, ws, want_dx=False):
+    """Accumulates into `grads` (same order as `tensors`); returns dx or None."""
+    lib = _lib.load()
+    D = x.shape[1]
+    layers, (nw, nb) = _enc_structs(tensors, n_layers)
+    glayers, (gnw, gnb) = _enc_structs(grads, n_layers)
+    o = _stack_opts(opts)
+    dx = torch.empty_like(x) if want_dx else None
+    dhidden = dhidden.contiguous()
+    rc = lib.sumk_tf_encoder_backward(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p, C.cast(layers, C.c_void_p),
+                                      _p(nw), _p(nb), C.cast(C.pointer(o), C.c_void_p), _p(dhidden), C.cast(glayers, C.c_void_p),
+                                      _p(gnw), _p(gnb), _p(dx), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "sumk_tf_encoder_backward")
+    return dx
+
+
+def _dec_structs(tensors, n_layers):
+    nf = len(_lib.TF_DEC_LAYER_FIELDS)
+    layers = (_lib.TfDecLayerWeights * n_layers)()
+    for l in range(n_layers):
+        for i, f in enumerate(_lib.TF_DEC_LAYER_FIELDS):
+            setattr(layers[l], f, _ptr(tensors[l * nf + i], f"decoder layer {l} {f}"))
+    return layers
+
+
+def tf_decoder_forward(tgt, memory, sb, tensors, n_layers, n_heads, dff, opts, training=False):
+    """Decoder stack (sumk_tf_decoder_forward): tgt, memory (n_rows, D) packed alike -> (out (n_rows, D), workspace).  `tensors`
+    in tf_decoder_param_names order."""
+    lib = _lib.load()
+    _check_rows(tgt, sb, "decoder-stack tgt")
+    _check_rows(memory, sb, "decoder-stack memory")
+    D = tgt.shape[1]
+    layers = _dec_structs(tensors, n_layers)
+    o = _stack_opts(opts)
+    nbytes = lib.sumk_tf_decoder_workspace_bytes(D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p)
+    if nbytes == 0:
+        _lib.check(-1, "sumk_tf_decoder_workspace_bytes")
+    ws = workspace(nbytes, tgt.device, persistent=training)
+    out = torch.empty_like(tgt)
+    rc = lib.sumk_tf_decoder_forward(_p(tgt), _p(memory), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
+                                     C.cast(layers, C.c_void_p), C.cast(C.pointer(o), C.c_void_p), _p(out), _p(ws), ws.numel(),
+                                     int(training), _stream())
+    _lib.check(rc, "sumk_tf_decoder_forward")
+    return out, (ws if training else None)
+
+
+def tf_decoder_backward(tgt, memory, sb, tensors, grads, n_layers, n_heads, dff, opts, dout, ws, want_dtgt=True, want_dmemory=True):
+    """Accumulates into `grads`; returns (dtgt or None, dmemory or None), dmemory summed over the layers."""
+    lib = _lib.load()
+    D = tgt.shape[1]
+    layers = _dec_structs(tensors, n_layers)
+    glayers = _dec_structs(grads, n_layers)
+    o = _stack_opts(opts)
+    dtgt = torch.empty_like(tgt) if want_dtgt else None
+    dmem = torch.empty_like(memory) if want_dmemory else None
+    dout = dout.contiguous()
+    rc = lib.sumk_tf_decoder_backward(_p(tgt), _p(memory), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
+                                      C.cast(layers, C.c_void_p), C.cast(C.pointer(o), C.c_void_p), _p(dout), C.cast(glayers, C.c_void_p),
+                                      _p(dtgt), _p(dmem), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "sumk_tf_decoder_backward")
+    return dtgt, dmem
+
+
+def row_scale_forward(x, s):
+    """y[r, :] = x[r, :] * s[r] for x (n_rows, D), s (n_rows,)."""
+    lib = _lib.load()
+    _require_gpu(x, "row_scale x"); _require_gpu(s, "row_scale s")
+    x, s = x.contiguous(), s.contiguous()
+    y = torch.empty_like(x)
+    _lib.check(lib.sumk_row_scale_forward(_p(x), _p(s), x.shape[0], x.shape[1], _p(y), _stream()), "sumk_row_scale_forward")
+    return y
+
+
+def row_scale_backward(x, s, g, want_dx=True, want_ds=True):
+    lib = _lib.load()
+    g = g.contiguous()
+    dx = torch.empty_like(x) if want_dx else None
+    ds = torch.empty_like(s) if want_ds else None
+    _lib.check(lib.sumk_row_scale_backward(_p(x), _p(s), _p(g), x.shape[0], x.shape[1], _p(dx), _p(ds), _stream()),
+               "sumk_row_scale_backward")
+    return dx, ds
+
+
 # ------------------------------------------------------------------------------------------------ unidirectional LSTM layer / dense layer
 def _lstm_dir_struct(cls, tensors):
     s = cls()
