@@ -1,4 +1,6 @@
 """Stock-PyTorch (CPU, fp32) functional port of the reference scorers.  TEST INFRASTRUCTURE ONLY.
+The SumGAN recurrences (lstm_stack_ref, dlstm_ref) and make_gru also run in float64: the high-precision oracles of
+tests/test_gpu_sumgan_full.py.
 
 This is (1) a second, autograd-capable checker for the HIP path (forward AND gradients), and
 (2) the `cpu_baseline` ("kind": "port") that bench.py times on the GPU node's host cores: it issues the
@@ -135,11 +137,75 @@ class TransformerPort(torch.nn.Module):
         return torch.sigmoid(self.k2(self.layer_norm(torch.relu(self.k1(e)))))
 
 
-def make_gru(p, prefix, input_size, hidden_size, num_layers):
-    """Stock nn.GRU carrying the given weights (the reference's optional DSN(cell="gru"), dsn.py:28-33)."""
-    m = torch.nn.GRU(input_size, hidden_size, num_layers=num_layers, bidirectional=True)
+def make_gru(p, prefix, input_size, hidden_size, num_layers, dtype=torch.float32):
+    """Stock nn.GRU carrying the given weights (the reference's optional DSN(cell="gru"), dsn.py:28-33), in `dtype`
+    (torch.float64 for a high-precision reference: the weights are converted, so feed it inputs of the same dtype)."""
+    m = torch.nn.GRU(input_size, hidden_size, num_layers=num_layers, bidirectional=True).to(dtype)
     m.load_state_dict({k[len(prefix):]: torch.as_tensor(v) for k, v in p.items() if k.startswith(prefix)})
     return m
+
+
+def _lstm_cell(gx, h, c, w_hh, b_hh):
+    """One nn.LSTM step: gx = x W_ih^T + b_ih (precomputed); gate order i, f, g, o as in torch."""
+    i, f, g, o = (gx + F.linear(h, w_hh, b_hh)).chunk(4, dim=-1)
+    c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+    return torch.sigmoid(o) * torch.tanh(c), c
+
+
+def _num_layers(params):
+    return sum(1 for k in params if k.startswith("weight_ih_l"))
+
+
+def lstm_stack_ref(x_list, params, h0=None, c0=None):
+    """Forward-running nn.LSTM(num_layers=L, bidirectional=False) over a ragged list of videos, in the dtype of the inputs.
+    x_list: [(T_i, In)]; params: nn.LSTM state_dict names (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, ...);
+    h0 / c0: (L, B, H) or None (zeros).  Returns ([out_i (T_i, H)] of the top layer, (h_n, c_n) (L, B, H)): the state after
+    each video's OWN last frame.  Videos run side by side, time-major; a video that has ended keeps its state.  Everything
+    is differentiable (inputs, parameters, initial state)."""
+    L, B = _num_layers(params), len(x_list)
+    H = params["weight_hh_l0"].shape[1]
+    lens = [int(x.shape[0]) for x in x_list]
+    T = max(lens)
+    ref = x_list[0]
+    act = torch.tensor([[t < n for n in lens] for t in range(T)]).unsqueeze(-1)      # (T, B, 1)
+    seq = torch.nn.utils.rnn.pad_sequence(list(x_list))                              # (T, B, In), zero padded
+    hn, cn = [], []
+    for l in range(L):
+        gx = F.linear(seq, params[f"weight_ih_l{l}"], params[f"bias_ih_l{l}"])           # input projection, all frames at once
+        h = h0[l] if h0 is not None else ref.new_zeros(B, H)
+        c = c0[l] if c0 is not None else ref.new_zeros(B, H)
+        outs = []
+        for t in range(T):
+            hs, cs = _lstm_cell(gx[t], h, c, params[f"weight_hh_l{l}"], params[f"bias_hh_l{l}"])
+            h, c = torch.where(act[t], hs, h), torch.where(act[t], cs, c)
+            outs.append(h)
+        seq = torch.stack(outs)
+        hn.append(h); cn.append(c)
+    return [seq[:n, b] for b, n in enumerate(lens)], (torch.stack(hn), torch.stack(cn))
+
+
+def dlstm_ref(params, recons, T, h0, c0):
+    """SumGAN's step-wise decoder (dLSTM, sumgan.py:74-115) in the dtype of h0: an nn.LSTM stack run one step at a time
+    whose input at step t is its own top-layer output of step t-1 (zeros at t = 0), then recons = (weight, bias) on every
+    output, then time reversed.  T: one length for every video, or a list of per-video lengths (each video decodes its own
+    steps; the others do not see them).  h0 / c0: (L, B, H).  Returns [x_hat_i (T_i, out)]; with recons=None, the top
+    layer's outputs [(T_i, H)] in time order (neither projected nor reversed: what the decoder kernels return)."""
+    L, B, H = h0.shape
+    lens = [int(T)] * B if isinstance(T, int) else [int(n) for n in T]
+    assert len(lens) == B and _num_layers(params) == L
+    x = h0.new_zeros(B, H)
+    h, c = list(h0.unbind(0)), list(c0.unbind(0))
+    outs = []
+    for t in range(max(lens)):
+        for l in range(L):
+            gx = F.linear(x, params[f"weight_ih_l{l}"], params[f"bias_ih_l{l}"])
+            h[l], c[l] = _lstm_cell(gx, h[l], c[l], params[f"weight_hh_l{l}"], params[f"bias_hh_l{l}"])
+            x = h[l]
+        outs.append(x)
+    seq = torch.stack(outs)                                                          # (T_max, B, H)
+    if recons is None:
+        return [seq[:n, b] for b, n in enumerate(lens)]
+    return [torch.flip(F.linear(seq[:n, b], recons[0], recons[1]), (0,)) for b, n in enumerate(lens)]
 
 
 def bigru_scores(x, p, prefix, head_w, head_b, gru):

@@ -193,3 +193,94 @@ def test_c1_summe_fold0_oracle_vs_the_reference_at_size():
         ref = g[f"test_{algo}"]
         np.testing.assert_allclose(np.mean(corrs), ref[0], atol=2e-5)
         np.testing.assert_allclose(np.mean(np.array(fs[algo]), axis=0), ref[1:], rtol=1e-6)
+
+
+def test_sumgan_lstm_refs_vs_reference_modules():
+    """torch_port.lstm_stack_ref / dlstm_ref -- the float64 oracles of tests/test_gpu_sumgan_full.py -- run in float32 on the
+    goldens of the REAL reference eLSTM / cLSTM / dLSTM (tests/golden/sumgan_lstm.npz): outputs, and the gradients of the
+    golden's scalar loss w.r.t. the input, the initial state and every parameter, within 1e-5."""
+    import torch.nn.functional as F
+    g = load_golden("sumgan_lstm")
+
+    def close(got, want, what):
+        np.testing.assert_allclose(got.detach().numpy(), want, atol=1e-5, rtol=1e-5, err_msg=what)
+
+    def weights(tag):
+        return {k.split("/w/")[1]: torch.from_numpy(g[k]).requires_grad_(True) for k in g.files if k.startswith(f"{tag}/w/")}
+
+    def lstm_params(w):
+        return {k[len("lstm."):]: v for k, v in w.items() if k.startswith("lstm.")}
+
+    tags = sorted({k.split("/")[0] for k in g.files if "/" in k})
+    assert {t.split("_")[0] for t in tags} == {"elstm", "clstm", "dlstm"}
+    for tag in tags:
+        w = weights(tag)
+        names = sorted(w)
+        if tag.startswith("dlstm"):
+            h0 = torch.from_numpy(g[f"{tag}/h0"]).requires_grad_(True)
+            c0 = torch.from_numpy(g[f"{tag}/c0"]).requires_grad_(True)
+            T = g[f"{tag}/y"].shape[0]
+            y = torch.stack(torch_port.dlstm_ref(lstm_params(w), (w["recons.weight"], w["recons.bias"]), T, h0, c0), dim=1)
+            close(y, g[f"{tag}/y"], f"{tag} x_hat")
+            grads = torch.autograd.grad((y * torch.from_numpy(g[f"{tag}/cw"])).sum(), [h0, c0] + [w[k] for k in names])
+            close(grads[0], g[f"{tag}/dh0"], f"{tag} dh0")
+            close(grads[1], g[f"{tag}/dc0"], f"{tag} dc0")
+            for k, gr in zip(names, grads[2:]):
+                close(gr, g[f"{tag}/g/{k}"], f"{tag} grad {k}")
+            continue
+        x = torch.from_numpy(g[f"{tag}/x"]).requires_grad_(True)
+        outs, (hn, cn) = torch_port.lstm_stack_ref(list(x.unbind(1)), lstm_params(w))
+        if tag.startswith("elstm"):
+            ys = [F.linear(hn, w["mu.weight"], w["mu.bias"]), F.linear(hn, w["logvar.weight"], w["logvar.bias"]), cn]
+        else:
+            ys = [torch.sigmoid(F.linear(hn[-1], w["out.0.weight"], w["out.0.bias"])), hn[-1]]
+        for i, (o, b) in enumerate(zip(outs, x.unbind(1))):
+            close(o[-1], g[f"{tag}/y1"][i] if tag.startswith("clstm") else hn[-1, i].detach().numpy(), f"{tag} out[-1] video {i}")
+        loss = 0
+        for i, y in enumerate(ys):
+            close(y, g[f"{tag}/y{i}"], f"{tag} output {i}")
+            loss = loss + (y * torch.from_numpy(g[f"{tag}/cw{i}"])).sum()
+        grads = torch.autograd.grad(loss, [x] + [w[k] for k in names])
+        close(grads[0], g[f"{tag}/dx"], f"{tag} dx")
+        for k, gr in zip(names, grads[1:]):
+            close(gr, g[f"{tag}/g/{k}"], f"{tag} grad {k}")
+
+
+def test_sumgan_lstm_refs_ragged_and_initial_state_vs_nn_lstm():
+    """lstm_stack_ref on a ragged batch with an initial state, and dlstm_ref with per-video lengths, against stock
+    torch (nn.LSTM on each video alone; the decoder's step loop written with nn.LSTM as the reference module does)."""
+    torch.manual_seed(8)
+    D, H, L, lens = 12, 10, 2, [5, 1, 9]
+    lstm = torch.nn.LSTM(D, H, num_layers=L).double()
+    p = dict(lstm.named_parameters())
+    xs = [torch.randn(T, D, dtype=torch.float64) for T in lens]
+    h0, c0 = torch.randn(L, len(lens), H, dtype=torch.float64), torch.randn(L, len(lens), H, dtype=torch.float64)
+    outs, (hn, cn) = torch_port.lstm_stack_ref(xs, p, h0, c0)
+    for i, x in enumerate(xs):
+        o, (h, c) = lstm(x.unsqueeze(1), (h0[:, i:i + 1].contiguous(), c0[:, i:i + 1].contiguous()))
+        torch.testing.assert_close(outs[i], o[:, 0], rtol=1e-12, atol=1e-12)
+        torch.testing.assert_close(hn[:, i], h[:, 0], rtol=1e-12, atol=1e-12)
+        torch.testing.assert_close(cn[:, i], c[:, 0], rtol=1e-12, atol=1e-12)
+    dl = torch.nn.LSTM(H, H, num_layers=L).double()
+    recons = torch.nn.Linear(H, D).double()
+    got = torch_port.dlstm_ref(dict(dl.named_parameters()), (recons.weight, recons.bias), lens, h0, c0)
+    raw = torch_port.dlstm_ref(dict(dl.named_parameters()), None, lens, h0, c0)
+    for i, T in enumerate(lens):
+        x, h, c = torch.zeros(1, 1, H, dtype=torch.float64), h0[:, i:i + 1].contiguous(), c0[:, i:i + 1].contiguous()
+        steps = []
+        for _ in range(T):
+            x, (h, c) = dl(x, (h, c))
+            steps.append(x[0, 0])
+        steps = torch.stack(steps)
+        torch.testing.assert_close(raw[i], steps, rtol=1e-12, atol=1e-12)
+        torch.testing.assert_close(got[i], torch.flip(recons(steps), (0,)), rtol=1e-12, atol=1e-12)
+
+
+def test_make_gru_float64():
+    torch.manual_seed(2)
+    m = torch.nn.GRU(6, 5, num_layers=2, bidirectional=True)
+    p = {f"rnn.{k}": v.detach() for k, v in m.state_dict().items()}
+    g64 = torch_port.make_gru(p, "rnn.", 6, 5, 2, dtype=torch.float64)
+    assert all(v.dtype == torch.float64 for v in g64.parameters())
+    x = torch.randn(7, 1, 6)
+    torch.testing.assert_close(g64(x.double())[0].float(), m(x)[0], rtol=0, atol=1e-6)
