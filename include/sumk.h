@@ -421,7 +421,9 @@ int sumk_gemm_bf16src(int32_t layout, const void* A_bf16, const void* B_bf16, fl
  * no reference counterpart (the reference multiplies fp32 tensors with torch.matmul, vasnet.py:114-131).
  * sumk_planes_bytes: device bytes of one plane array (0 = bad arguments).  sumk_split_planes: fp32 (rows x K, leading dimension ld)
  * -> planes.  sumk_gemm_planes (tests / bench probe): C(M,N) fp32 = A . B^T from two plane arrays built for a_rows / b_rows rows
- * (N % 256 == 0, K % 32 == 0, K >= 128); variant selects a schedule variant of the probe (0 = the product's). */
+ * (N % 256 == 0, K % 32 == 0, K >= 128).  variant: 1 = every wave of the 32x32x16 kernel refills its stage right behind the barrier,
+ * 10 = waves 0-3 do, any other value = the product's schedule; 32 also keeps two planes on the 32x32x16 kernel (the product runs them on
+ * the 16x16x32 kernel when K >= 160). */
 size_t sumk_planes_bytes(int64_t rows, int32_t K, int32_t n_planes);
 int sumk_split_planes(const float* src, int64_t rows, int32_t K, int32_t ld, int32_t n_planes, void* planes, void* stream);
 int sumk_gemm_planes(const void* A_planes, int64_t a_rows, const void* B_planes, int64_t b_rows, float* C, int32_t M, int32_t N, int32_t K,
@@ -534,9 +536,6 @@ int sumk_gemm_splitk(int32_t layout, const float* A, const float* B, float* C, i
                      void* workspace, size_t workspace_bytes, void* stream);
 int sumk_prof_enable(int32_t tag_mask);
 int sumk_prof_read(int32_t tag, double* total_ms, int64_t* launches, int32_t reset);
-/* Diagnostic (process started with SUMK_GEMM_DBG=2): the last GEMM launch's in-kernel shader-cycle stamps, 4 values per block
- * {whole block, k-loops, epilogues, tiles}; synchronises the device.  Returns SUMK_ERR_ARG when stamping is off. */
-int sumk_prof_gemm_stamps(uint64_t* out, int32_t n_blocks);
 
 /* Measurement utility (no reference counterpart; bench.py's `mfma_sustained`): the rate the matrix pipes of the current device SUSTAIN with nothing but
  * MFMAs in flight -- one workgroup of eight waves per CU, four independent accumulators per wave, operands in registers, no memory traffic.  One warm-up

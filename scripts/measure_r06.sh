@@ -37,5 +37,4 @@ python3 scripts/probes/wide2_probe.py > $OUT/wide2_probe.txt 2>&1
 python3 scripts/probes/dsn_probe.py > $OUT/dsn_probe.txt 2>&1
 python3 scripts/probes/dsn_train_probe.py > $OUT/dsn_train_probe.txt 2>&1
 python3 scripts/probes/slstm_train_probe.py > $OUT/slstm_train_probe.txt 2>&1
-SUMK_LIB_PATH=$PWD/summarizer_amd/libsumk_diag.so SUMK_LSTM_STAMPS=1 python3 scripts/probes/wide2_probe.py > $OUT/wide2_stamps.txt 2>&1
 ls $OUT

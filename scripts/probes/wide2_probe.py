@@ -1,7 +1,6 @@
 """Probe of the H = 1024 forward recurrence (csrc/lstm.hip: lstm_wide2_kernel vs lstm_wide_kernel): sLSTM scoring on the S-TVSum batch per
 precision -- whole call, and the recurrence launches alone (HIP events on the launch stream, sumk_prof_*) -- plus the scores' digest so that
-two processes (SUMK_LSTM_WIDE2=1 / 0) can be compared.  With the diagnostic library (SUMK_LIB_PATH=.../libsumk_diag.so SUMK_LSTM_STAMPS=1) the
-library prints the in-kernel phase stamps of every launch to stderr.
+two processes (SUMK_LSTM_WIDE2=1 / 0) can be compared.
 usage: python scripts/probes/wide2_probe.py [out.npz]"""
 import ctypes as C
 import os
@@ -25,15 +24,12 @@ torch.manual_seed(1234)
 x = torch.randn(frames, 1024, device=dev) * 0.5
 m = sLSTM(input_size=1024).to(dev).eval()
 out = {}
-stamps = bool(os.environ.get("SUMK_LSTM_STAMPS"))
 for prec in ["fp32", "bf16x6", "bf16x3"]:
     m.precision = prec
     with torch.no_grad():
-        for _ in range(1 if stamps else 3):
+        for _ in range(3):
             s = m.score_packed(x, lens)
         torch.cuda.synchronize()
-        if stamps:
-            continue
         n = 5
         t0 = time.perf_counter()
         for _ in range(n):

@@ -9,7 +9,7 @@ import os
 import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SUMK_LIB_PATH: load another build of the same library (the diagnostic build libsumk_diag.so of `make DIAG=1`, for scripts/probes)
+# SUMK_LIB_PATH: load another build of the same library (e.g. a copy built from another commit, for A/B runs)
 LIB_PATH = os.environ.get("SUMK_LIB_PATH") or os.path.join(_HERE, "libsumk.so")
 
 c_f32p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
@@ -219,7 +219,6 @@ _SIGS = {
     "sumk_prof_enable": (C.c_int, [C.c_int32]),
     "sumk_prof_read": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
     "sumk_probe_mfma_rate": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
-    "sumk_prof_gemm_stamps": (C.c_int, [C.POINTER(C.c_uint64), C.c_int32]),
 }
 
 PROF_GEMM_QKV, PROF_GEMM_ALL, PROF_LSTM_REC, PROF_GEMM_QKT, PROF_GEMM_PV, PROF_GEMM_OPROJ, PROF_GEMM_K1 = 0, 1, 2, 3, 4, 5, 6

@@ -24,12 +24,7 @@ namespace {
 
 constexpr int AP_ROWS = 64, AP_TMAX = 320;
 
-#ifndef SUMK_CTX_ABL
-#define SUMK_CTX_ABL 0               // kernel B timing probes (WRONG results; variant libraries only, scripts/probes/ctx_wide_ab.sh): 1 no MFMAs, 2 no DMA behind the prologue,
-#endif                               // 4 no fragment reads in the loop, 8 no barriers, 16 no pass epilogue
-#ifndef SUMK_ATTN_NLW
-#define SUMK_ATTN_NLW 8              // waves of a block that issue the LDS-DMA pieces of a stage (probe: scripts/attn_nlw_probe.sh)
-#endif
+constexpr int NLW = 8;               // waves of a block that issue the LDS-DMA pieces of a stage (all of them)
 
 struct AttnPwArgs {
   const char* QKV; uint32_t rp16;          // KB planes of [Q | K | V] (rows = packed frames, k = 3 D columns)
@@ -44,7 +39,6 @@ struct AttnPwArgs {
   const float* R; int32_t ldr;             // kernel B, folded VASNet path (V = x Wvo^T): context + R is what leaves as planes, with its LayerNorm moments
   float* moments;                          // float2[rows][D / 32] {sum v, sum v^2} per 32-column slot
   int32_t csplit;                          // kernel B, QT = 4 form: a block owns 128 query rows and 1 / csplit of the 256-column passes
-  unsigned long long* stamps;              // diagnostic build: per block {T, prologue, k-loop, row op, total} shader cycles + realtime
 };
 
 // ------------------------------------------------------------------------------------------------ A: logits + softmax
@@ -52,19 +46,18 @@ struct AttnPwArgs {
 // (tile slots past 2 NJ multiply whatever rows follow in the stage -- the query rows, finite -- and are masked as key >= T).
 // One k16 step of D per stage: NSUB sub-arrays (plane, k half) x (64 NJ key rows + 64 query rows) x 16 B, filled by LDS-DMA pieces of 64
 // rows; NS stages in a ring, ONE barrier per step behind all but the last key tile's MFMAs (gemm_pw.hip's loop).
-// VAR (when a wave issues the DMA pieces that refill the slot a barrier freed): 0 = after the step's last MFMAs, 1 = right behind the
-// barrier, 2 = spread: a share behind every key tile's MFMAs, from the step's last tile through the next step's tiles in front of the barrier.
+// A wave issues the DMA pieces that refill the slot a barrier freed after the step's last MFMAs (also measured: right behind the barrier, and spread
+// behind every key tile's MFMAs -- profiles/r05_attn_pw_dma_variants.txt).
 // NT: the K / Q loads carry the non-temporal policy.  Chosen by the host when the [Q | K | V] planes are larger than ~3/4 of the Infinity Cache: the logits
 // launch then streams its 2/3 of them without displacing V, which launch B reads next (three planes, S-TVSum: B 73 -> 63 us, A unchanged; two planes, where
 // all the planes fit the cache anyway: A 43.5 -> 52 us, B unchanged -- hence not unconditional; nt on B's own loads: slower in both.  profiles/r06_attn_ctx_ablation.txt)
-template <int NP, int NJ, int VAR, bool MH = false, bool NT = false>
+template <int NP, int NJ, bool MH = false, bool NT = false>
 __device__ __forceinline__ void attn_logits_body(const AttnPwArgs& a, const SeqInfo& si, const int strip, const int head, char* const lds) {
   constexpr int NSUB = 2 * NP, T64 = NJ * 64, ROWS = T64 + 64, STAGE = NSUB * ROWS * 16;
   // (deeper rings, 4 / 6 stages, were measured: no change -- the stream is not latency-bound).  MH (multi-head form: dh / 16 = 8 steps per block, the
   // prologue and the row op are most of a block's time): one stage less, so that TWO blocks fit a CU and overlap each other's phases
   constexpr int NS = (NP == 3 ? 3 : 4) - (MH ? 1 : 0);
   constexpr int NTW = (2 * NJ + 3) / 4;
-  constexpr int NLW = SUMK_ATTN_NLW;                                   // waves that issue the DMA pieces (the others only wait at the barrier)
   constexpr int NPIECE = NSUB * (NJ + 1), MAXP = (NPIECE + NLW - 1) / NLW;
   static_assert(NS * STAGE + 4096 <= 160 * 1024, "LDS map");
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
@@ -88,20 +81,15 @@ __device__ __forceinline__ void attn_logits_body(const AttnPwArgs& a, const SeqI
   const bool full = (NPIECE % NLW == 0) || wave < NPIECE % NLW;          // this wave issues MAXP pieces (else MAXP - 1)
   const bool loader = wave < NLW;
   const int vlane = lane * 16, k_step = NSUB * (int)a.rp16;
-  auto dma_share = [&](int kb, int slot, int share, int n_shares) {      // pieces i with i % n_shares == share
+  auto dma = [&](int kb, int slot) {
     if (!loader) return;
-#ifdef SUMK_DIAG
-    if (VAR == 4 && kb >= NS) return;                                     // timing probe: MFMAs + reads + barriers only (stale stages)
-#endif
     char* const st = lds + slot * STAGE;
 #pragma unroll
     for (int i = 0; i < MAXP; ++i) {
-      if (i % n_shares != share) continue;
       if (i == MAXP - 1 && !full) break;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_vptr)(st + pl[i]), 16, vlane, kb * k_step + pg[i], 0, NT ? 2 : 0);
     }
   };
-  auto dma = [&](int kb, int slot) { dma_share(kb, slot, 0, 1); };
   const int fk = (lh * ROWS + kg * 32 + li) * 16, fq = (lh * ROWS + T64 + qt * 32 + li) * 16;
   struct Frags { bf16x8 k[NP][NTW], q[NP]; };
   auto read_frags = [&](int slot, Frags& f) {
@@ -118,25 +106,8 @@ __device__ __forceinline__ void attn_logits_body(const AttnPwArgs& a, const SeqI
   for (int j = 0; j < NTW; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-  // (key tiles interleaved per plane product: consecutive MFMAs write different accumulators -- see kernel B's mfma_part)
-  auto mfma_tiles = [&](const Frags& f, int j_lo, int j_hi) {
-#pragma unroll
-    for (int sum = NP - 1; sum >= 0; --sum)              // (Q plane i, K plane j2), smallest products first: the order of the NT GEMM Q . K^T
-#pragma unroll
-      for (int i = NP - 1; i >= 0; --i) {
-        const int j2 = sum - i;
-        if (j2 < 0 || j2 >= NP) continue;
-#pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-          if (j < j_lo || j >= j_hi) continue;
-#ifdef SUMK_DIAG
-          if constexpr (VAR == 3) { asm volatile("" :: "v"(f.k[j2][j]), "v"(f.q[i])); continue; }      // timing probe: DMA + reads + barriers only
-#endif
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.k[j2][j], f.q[i], acc[j], 0, 0, 0);
-        }
-      }
-  };
-  // the step's MFMAs as two groups of PLANE PRODUCTS (every key tile in each): products [p_lo, p_hi) of the NP (NP + 1) / 2, in the order above
+  // the step's MFMAs as two groups of PLANE PRODUCTS (every key tile in each): products [p_lo, p_hi) of the NP (NP + 1) / 2, (Q plane i, K plane j2)
+  // smallest products first -- the order of the NT GEMM Q . K^T; key tiles interleaved per plane product: consecutive MFMAs write different accumulators
   constexpr int NPROD = NP * (NP + 1) / 2;
   auto mfma_prods = [&](const Frags& f, int p_lo, int p_hi) {
     int pi = 0;
@@ -151,46 +122,25 @@ __device__ __forceinline__ void attn_logits_body(const AttnPwArgs& a, const SeqI
         if (!on) continue;
 #pragma unroll
         for (int j = 0; j < NTW; ++j) {
-#ifdef SUMK_DIAG
-          if constexpr (VAR == 3) { asm volatile("" :: "v"(f.k[j2][j]), "v"(f.q[i])); continue; }
-#endif
           acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.k[j2][j], f.q[i], acc[j], 0, 0, 0);
         }
       }
   };
 
   const int nk = a.dh >> 4;
-#ifdef SUMK_DIAG
-  const unsigned long long st0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
 #pragma unroll
   for (int s = 0; s < NS; ++s) dma(s, s);
   wait_vm<0>();
   __builtin_amdgcn_s_barrier();
-#ifdef SUMK_DIAG
-  const unsigned long long st1 = __builtin_amdgcn_s_memtime();
-#endif
   Frags F0, F1;
   read_frags(0, F0);
   int slot = 0;
   // MH: ONE fragment set (two blocks per CU need <= 128 VGPRs): all of a step's MFMAs run in front of its barrier, the next fragments are read behind it into
   // the same registers -- the other block's waves cover the read latency
-  constexpr int P1 = MH ? NTW : (NTW > 1 ? NTW - 1 : 0);
   constexpr int PA = MH ? NPROD : (2 * NPROD + 2) / 3;        // products in front of the barrier (two thirds), the rest behind it
-  int pend_kb = -1, pend_slot = 0;               // VAR 2: the refill in progress (stage, slot)
   auto kstep = [&](const Frags& cur, Frags& nxt, int s) {
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (VAR == 2 && NTW > 1) {
-#pragma unroll
-      for (int j = 0; j < P1; ++j) {
-        mfma_tiles(cur, j, j + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (pend_kb >= 0) dma_share(pend_kb, pend_slot, j, NTW);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else {
-      mfma_prods(cur, 0, PA);
-    }
+    mfma_prods(cur, 0, PA);
     __builtin_amdgcn_sched_barrier(0);
     const bool more = s + 1 < nk, fill = s + NS < nk;
     const int nslot = slot + 1 == NS ? 0 : slot + 1;
@@ -201,28 +151,13 @@ __device__ __forceinline__ void attn_logits_body(const AttnPwArgs& a, const SeqI
       __builtin_amdgcn_s_barrier();
       read_frags(nslot, nxt);
       __builtin_amdgcn_sched_barrier(0);
-      if (VAR == 1 && fill) dma(s + NS, slot);
     }
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (VAR == 2 && NTW > 1) mfma_tiles(cur, P1, NTW); else mfma_prods(cur, PA, NPROD);
+    mfma_prods(cur, PA, NPROD);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (VAR == 2 && NTW > 1) {
-      pend_kb = (more && fill) ? s + NS : -1; pend_slot = slot;
-      if (pend_kb >= 0) dma_share(pend_kb, pend_slot, NTW - 1, NTW);
-    } else if (VAR != 1) {
-      if (more && fill) dma(s + NS, slot);
-    }
+    if (more && fill) dma(s + NS, slot);
     slot = nslot;
   };
-#ifdef SUMK_DIAG
-  if constexpr (VAR == 5) {      // timing probe: the DMA stream alone -- no fragment reads, no MFMAs, no barriers; NS - 1 stages kept in flight
-    for (int s = 0; s < nk; ++s) {
-      if (full) wait_vm<(NS - 1) * MAXP>(); else wait_vm<(NS - 1) * (MAXP - 1)>();
-      if (s + NS < nk) dma(s + NS, s % NS);
-    }
-    wait_vm<0>();
-  } else
-#endif
   for (int s = 0; s < nk; s += 2) {
     if constexpr (MH) {
       kstep(F0, F0, s);
@@ -235,9 +170,6 @@ __device__ __forceinline__ void attn_logits_body(const AttnPwArgs& a, const SeqI
 
   // ---- row op: acc[j][r]: key = (kg + 4 j) * 32 + 8 (r >> 2) + 4 lh + (r & 3), query = qt * 32 + li
   lds_barrier();                                  // every wave is past its last fragment read: the stages are free
-#ifdef SUMK_DIAG
-  const unsigned long long st2 = __builtin_amdgcn_s_memtime();
-#endif
   float* const red = reinterpret_cast<float*>(lds);        // [4 key groups][64 queries], twice
   const int qi = qt * 32 + li, i = i0 + qi;
   const bool row_ok = i < T;
@@ -289,15 +221,6 @@ __device__ __forceinline__ void attn_logits_body(const AttnPwArgs& a, const SeqI
 #pragma unroll
       for (int p = 0; p < NP; ++p) *reinterpret_cast<u32x2*>(op + (int64_t)p * 2 * a.ap_rp16) = pl2[p];
     }
-#ifdef SUMK_DIAG
-  if (a.stamps && tid == 0) {
-    wait_vm<0>();
-    const unsigned long long st3 = __builtin_amdgcn_s_memtime();
-    unsigned long long* o = a.stamps + (size_t)blockIdx.x * 8;
-    o[0] = T; o[1] = st1 - st0; o[2] = st2 - st1; o[3] = st3 - st2; o[4] = st3 - st0; o[5] = __builtin_amdgcn_s_memrealtime() - rt0; o[6] = rt0;
-    o[7] = __builtin_amdgcn_s_getreg((31 << 11) | 20) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 32);
-  }
-#endif
 }
 
 template <int NP, bool NT = false>
@@ -309,15 +232,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   if (!locate_block(a.seq, a.n_seq, [nh](int t) { return ((t + AP_ROWS - 1) / AP_ROWS) * nh; }, si, s, sub)) return;
   const int strip = sub / nh, head = sub - strip * nh;      // (the heads of one strip are neighbours in the list: they share the strip's query rows and the video's keys in L2)
   switch ((si.T + 63) >> 6) {
-    case 1: attn_logits_body<NP, 1, 0, true, NT>(a, si, strip, head, lds); break;
-    case 2: attn_logits_body<NP, 2, 0, true, NT>(a, si, strip, head, lds); break;
-    case 3: attn_logits_body<NP, 3, 0, true, NT>(a, si, strip, head, lds); break;
-    case 4: attn_logits_body<NP, 4, 0, true, NT>(a, si, strip, head, lds); break;
-    default: attn_logits_body<NP, 5, 0, true, NT>(a, si, strip, head, lds); break;
+    case 1: attn_logits_body<NP, 1, true, NT>(a, si, strip, head, lds); break;
+    case 2: attn_logits_body<NP, 2, true, NT>(a, si, strip, head, lds); break;
+    case 3: attn_logits_body<NP, 3, true, NT>(a, si, strip, head, lds); break;
+    case 4: attn_logits_body<NP, 4, true, NT>(a, si, strip, head, lds); break;
+    default: attn_logits_body<NP, 5, true, NT>(a, si, strip, head, lds); break;
   }
 }
 
-template <int NP, int VAR, bool NT = false>
+template <int NP, bool NT = false>
 __global__ __launch_bounds__(512) void attn_pw_logits_kernel(AttnPwArgs a) {       // single head (the multi-head form: attn_pw_logits_mh_kernel)
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int head = 0;
@@ -325,11 +248,11 @@ __global__ __launch_bounds__(512) void attn_pw_logits_kernel(AttnPwArgs a) {    
   SeqInfo si;
   if (!locate_block(a.seq, a.n_seq, [](int t) { return (t + AP_ROWS - 1) / AP_ROWS; }, si, s, strip)) return;      // every XCD the same number of strips
   switch ((si.T + 63) >> 6) {
-    case 1: attn_logits_body<NP, 1, VAR, false, NT>(a, si, strip, head, lds); break;
-    case 2: attn_logits_body<NP, 2, VAR, false, NT>(a, si, strip, head, lds); break;
-    case 3: attn_logits_body<NP, 3, VAR, false, NT>(a, si, strip, head, lds); break;
-    case 4: attn_logits_body<NP, 4, VAR, false, NT>(a, si, strip, head, lds); break;
-    default: attn_logits_body<NP, 5, VAR, false, NT>(a, si, strip, head, lds); break;
+    case 1: attn_logits_body<NP, 1, false, NT>(a, si, strip, head, lds); break;
+    case 2: attn_logits_body<NP, 2, false, NT>(a, si, strip, head, lds); break;
+    case 3: attn_logits_body<NP, 3, false, NT>(a, si, strip, head, lds); break;
+    case 4: attn_logits_body<NP, 4, false, NT>(a, si, strip, head, lds); break;
+    default: attn_logits_body<NP, 5, false, NT>(a, si, strip, head, lds); break;
   }
 }
 
@@ -356,7 +279,6 @@ __device__ __forceinline__ void attn_context_body(const AttnPwArgs& a, char* con
   constexpr int NSETS = HP2 ? 2 : 1;
   constexpr int QR = 32 * QT, QH = QT / 2;                             // query rows per block; 64-row alpha pieces per sub-array
   constexpr int NSUB = 2 * NP, A_SET = KH * NSUB * QR * 16, A_BYTES = NSETS * A_SET, V_BYTES = KH * 8 * NP * 1024, STAGE = A_BYTES + V_BYTES;
-  constexpr int NLW = SUMK_ATTN_NLW;
   constexpr int NA = NSETS * KH * NSUB * QH, NV = KH * 8 * NP, NPIECE = NA + NV, MAXP = (NPIECE + NLW - 1) / NLW;
   static_assert(NS * STAGE <= 160 * 1024, "LDS map");
   int sv, bsub;
@@ -397,7 +319,6 @@ __device__ __forceinline__ void attn_context_body(const AttnPwArgs& a, char* con
   const int vperm = ((lane >> 3) & 1) * NSUB * (int)a.rp16 + ((lane >> 2) & 1) * (int)a.rp16 + (4 * (lane >> 4) + (lane & 3)) * 16;
   auto dma = [&](int it, int slot) {
     if (!loader) return;
-    if ((SUMK_CTX_ABL & 2) && it >= NS) return;
     const int ncl = it / nks, ks = it - ncl * nks, nc = nc0 + ncl;
     char* const st = lds + slot * STAGE;
     const int ga = ks * KH * NSUB * (int)a.ap_rp16, gv = nc * 16 * NSUB * (int)a.rp16 + ks * KH * 256;
@@ -427,7 +348,7 @@ __device__ __forceinline__ void attn_context_body(const AttnPwArgs& a, char* con
   // the step's MFMAs in two parts around its barrier: part 0 = the first k16 block (KH = 2) or the first half of the plane products (KH = 1), part 1 = the rest
   // Issue order: inside a part the query tiles are interleaved per plane product -- consecutive MFMAs write different accumulators (measured against tile by
   // tile, each tile's products in a row: no difference; per accumulator the order of the products is the same either way: same bits).  What the loop's MFMAs cost
-  // by themselves: builds with everything else removed (SUMK_CTX_ABL) run the launch's 1 920 MFMAs per SIMD in ~46 us = 24 ns each, the rate the plane GEMM
+  // by themselves: builds with everything else removed run the launch's 1 920 MFMAs per SIMD in ~46 us = 24 ns each, the rate the plane GEMM
   // sustains as well (1.3 PFLOP/s over the chip) -- profiles/r06_attn_ctx_ablation.txt.
   constexpr int NPROD = NP * (NP + 1) / 2, PA = (NPROD + 1) / 2;     // KH = 1: part 0 = the first PA plane products of every query tile, part 1 = the rest
   auto mfma_part = [&](const Frags& f, int part) {
@@ -445,7 +366,6 @@ __device__ __forceinline__ void attn_context_body(const AttnPwArgs& a, char* con
           if ((KH == 2 ? kbh : ppart) != part) continue;
 #pragma unroll
           for (int u = 0; u < QT; ++u) {
-            if constexpr ((SUMK_CTX_ABL & 1) != 0) { asm volatile("" :: "v"(f.v[kbh][j]), "v"(f.al[kbh][i][u])); continue; }
             o[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.v[kbh][j], f.al[kbh][i][u], o[u], 0, 0, 0);
           }
         }
@@ -493,16 +413,15 @@ __device__ __forceinline__ void attn_context_body(const AttnPwArgs& a, char* con
       if (it + NS - 1 < n_it && !(ks == 0 && nc > nc0)) { if (full) wait_vm<(NS - 2) * MAXP>(); else wait_vm<(NS - 2) * (MAXP - 1)>(); }
       else wait_vm<0>();
       __builtin_amdgcn_s_waitcnt(0xC07F);                   // lgkmcnt(0): this wave holds every fragment of the stage whose slot is refilled behind the barrier
-      if constexpr ((SUMK_CTX_ABL & 8) == 0) __builtin_amdgcn_s_barrier();
-      if constexpr ((SUMK_CTX_ABL & 4) == 0) read_frags(nslot, nxt);
-      if constexpr ((SUMK_CTX_ABL & 4) != 0) nxt = cur;
+      __builtin_amdgcn_s_barrier();
+      read_frags(nslot, nxt);
     }
     __builtin_amdgcn_sched_barrier(0);
     mfma_part(cur, 1);
     __builtin_amdgcn_sched_barrier(0);
     if (more && fill) dma(it + NS, slot);
     slot = nslot;
-    if ((SUMK_CTX_ABL & 16) ? it + 1 == n_it : ++ks == nks) {                        // end of a 256-column pass: o[u][4 g + c] = CTX[query u * 32 + li][nc * 256 + 32 wave + 8 g + 4 lh + c]
+    if (++ks == nks) {                        // end of a 256-column pass: o[u][4 g + c] = CTX[query u * 32 + li][nc * 256 + 32 wave + 8 g + 4 lh + c]
 #pragma unroll
       for (int u = 0; u < QT; ++u) {
         const int q = i0 + u * 32 + li;
@@ -543,7 +462,6 @@ __global__ __launch_bounds__(512) void attn_pw_context_kernel(AttnPwArgs a) {
 }
 
 std::atomic<uint64_t> g_attr[28];
-constexpr int ATTN_VAR_A = 0;      // the product's schedule variant of the logits kernel (measured: profiles/r05_attn_pw_dma_variants.txt)
 
 template <typename K>
 int set_lds_once(K kernel, int inst, int bytes) {
@@ -582,57 +500,23 @@ int launch_attn_pw_logits(int np, const void* qkv_planes, int64_t rows, int D, f
   a.heads = heads; a.dh = D / heads; a.ap_head_bytes = heads == 1 ? 0 : (int64_t)align_up(pw_alpha_bytes(rows, t_max, np), 256);
   a.R = nullptr; a.ldr = 0; a.moments = nullptr; a.csplit = 1;
   const unsigned grid = (unsigned)(8 * ((n_seq + 7) / 8) * a.strips * heads);
-  a.stamps = nullptr;
-#ifdef SUMK_DIAG
-  static unsigned long long* stamp_buf = nullptr;
-  static int stamp_calls = 0;
-  if (getenv("SUMK_ATTN_STAMPS")) {
-    if (!stamp_buf) SUMK_HIP(hipMalloc(&stamp_buf, 4096 * 8 * sizeof(unsigned long long)));
-    SUMK_HIP(hipMemsetAsync(stamp_buf, 0, 4096 * 8 * sizeof(unsigned long long), stream));
-    a.stamps = grid <= 4096 ? stamp_buf : nullptr;
-  }
-#endif
-  [[maybe_unused]] static const int var = SUMK_TUNE_ENV("SUMK_ATTN_VAR_A") ? atoi(SUMK_TUNE_ENV("SUMK_ATTN_VAR_A")) : ATTN_VAR_A;      // (diagnostic build only)
   constexpr int LDS3 = 3 * (6 * 384 * 16) + 4096, LDS2 = 4 * (4 * 384 * 16) + 4096;
   // non-temporal K / Q loads when the planes do not fit the Infinity Cache beside what the next launch reads (SUMK_ATTN_NT=0 / 1 forces it: A/B)
   static const int nt_env = getenv("SUMK_ATTN_NT") ? atoi(getenv("SUMK_ATTN_NT")) : -1;
   // (single head only: on the Transformer's multi-head launches the rule measured 1 % slower at three planes)
   const bool nt = nt_env >= 0 ? nt_env != 0 : (heads == 1 && pw_planes_bytes(rows, 3 * D, np) > ((size_t)192 << 20));
-#define SUMK_A_CASE(NP_, V_, LDS_, I_) { SUMK_TRY(set_lds_once(attn_pw_logits_kernel<NP_, V_>, I_, LDS_)); hipLaunchKernelGGL((attn_pw_logits_kernel<NP_, V_>), dim3(grid), dim3(512), LDS_, stream, a); }
-#ifdef SUMK_DIAG
-  if (np == 3 && var == 3) { SUMK_A_CASE(3, 3, LDS3, 10) } else if (np == 3 && var == 4) { SUMK_A_CASE(3, 4, LDS3, 11) } else if (np == 3 && var == 5) { SUMK_A_CASE(3, 5, LDS3, 9) } else
-  if (np == 3 && (var == 1 || var == 2)) { if (var == 1) SUMK_A_CASE(3, 1, LDS3, 0) else SUMK_A_CASE(3, 2, LDS3, 1) } else
-  if (np == 2 && (var == 1 || var == 2)) { if (var == 1) SUMK_A_CASE(2, 1, LDS2, 3) else SUMK_A_CASE(2, 2, LDS2, 4) } else
-#endif
   if (heads > 1) {
     constexpr int LDSH3 = 2 * (6 * 384 * 16) + 4096, LDSH2 = 3 * (4 * 384 * 16) + 4096;      // 76 KB each: two blocks per CU
 #define SUMK_MH_CASE(NP_, NT_, LDS_, I_) { SUMK_TRY(set_lds_once(attn_pw_logits_mh_kernel<NP_, NT_>, I_, LDS_)); hipLaunchKernelGGL((attn_pw_logits_mh_kernel<NP_, NT_>), dim3(grid), dim3(512), LDS_, stream, a); }
     if (np == 3) { if (nt) SUMK_MH_CASE(3, true, LDSH3, 24) else SUMK_MH_CASE(3, false, LDSH3, 8) }
     else { if (nt) SUMK_MH_CASE(2, true, LDSH2, 25) else SUMK_MH_CASE(2, false, LDSH2, 14) }
 #undef SUMK_MH_CASE
-  } else
-  if (nt) {
-    if (np == 3) { SUMK_TRY(set_lds_once(attn_pw_logits_kernel<3, 0, true>, 26, LDS3)); hipLaunchKernelGGL((attn_pw_logits_kernel<3, 0, true>), dim3(grid), dim3(512), LDS3, stream, a); }
-    else { SUMK_TRY(set_lds_once(attn_pw_logits_kernel<2, 0, true>, 27, LDS2)); hipLaunchKernelGGL((attn_pw_logits_kernel<2, 0, true>), dim3(grid), dim3(512), LDS2, stream, a); }
-  } else
-  if (np == 3) SUMK_A_CASE(3, 0, LDS3, 2) else SUMK_A_CASE(2, 0, LDS2, 5)
+  } else {
+#define SUMK_A_CASE(NP_, NT_, LDS_, I_) { SUMK_TRY(set_lds_once(attn_pw_logits_kernel<NP_, NT_>, I_, LDS_)); hipLaunchKernelGGL((attn_pw_logits_kernel<NP_, NT_>), dim3(grid), dim3(512), LDS_, stream, a); }
+    if (np == 3) { if (nt) SUMK_A_CASE(3, true, LDS3, 26) else SUMK_A_CASE(3, false, LDS3, 2) }
+    else { if (nt) SUMK_A_CASE(2, true, LDS2, 27) else SUMK_A_CASE(2, false, LDS2, 5) }
 #undef SUMK_A_CASE
-#ifdef SUMK_DIAG
-  if (a.stamps && ++stamp_calls == 40) {       // one report, from a warm call
-    std::vector<unsigned long long> h((size_t)grid * 8);
-    SUMK_HIP(hipStreamSynchronize(stream));
-    SUMK_HIP(hipMemcpy(h.data(), stamp_buf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    unsigned long long rmin = ~0ull, rmax = 0;
-    for (unsigned b = 0; b < grid; ++b) if (h[b * 8]) { rmin = std::min(rmin, h[b * 8 + 6]); rmax = std::max(rmax, h[b * 8 + 6] + h[b * 8 + 5]); }
-    fprintf(stderr, "[attn logits stamps] grid %u, kernel window %.1f us (first block start to last block end)\n", grid, (rmax - rmin) / 100.0);
-    for (unsigned b = 0; b < grid; ++b) {
-      const unsigned long long* e = &h[b * 8];
-      if (!e[0] || (b % 9 != 0 && e[0] < 300)) continue;
-      fprintf(stderr, "  block %3u T %3llu start +%.1f us: prologue %6llu  k-loop %7llu (%.0f / k16 step)  row op + stores %6llu  total %7llu cycles = %.1f us, clock %.0f MHz, xcc %llu cu-id %llx\n",
-              b, e[0], (e[6] - rmin) / 100.0, e[1], e[2], e[2] / (double)(a.dh / 16), e[3], e[4], e[5] / 100.0, e[4] / (e[5] / 100.0), e[7] & 0xf, e[7] >> 32);
-    }
   }
-#endif
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
 }

@@ -23,8 +23,6 @@ struct GemmKArgs {
   int32_t xcd_tiles_m;   // > 0: single-problem launch with the XCD-aware tile map below; value = tiles along M
   int32_t group_remap;   // 1: grouped (per-video) launch, tile ids dealt so that one XCD walks a CONTIGUOUS range of tiles (decode_tile)
   float alpha;
-  int32_t dbg;           // diagnostic switches (SUMK_GEMM_DBG): 1 = skip the epilogue stores, 2 = in-kernel cycle stamps
-  unsigned long long* dbg_buf;   // dbg & 2: per block {total, k-loop, epilogue, tiles} shader cycles (scripts/gemm_stamp_probe.py)
   int32_t lean;                  // host-side only: 1 = NT 128x128 launch eligible for the buffer-load (VALU-free k-loop) instances
   float* moments;                // EPI_RESIDUAL_MOMENTS: float2[M][N / 32]
   unsigned short* C16;           // EPI_NONE: when set, bf16(C) is stored too, same offsets / leading dimension (operand of a later bf16-source GEMM); C may then be null

@@ -22,13 +22,6 @@
 
 namespace sumk {
 
-// one 64 KB stamp buffer per process, allocated on first use under SUMK_GEMM_DBG=2
-static unsigned long long* gemm_stamp_buffer() {
-  static unsigned long long* buf = nullptr;
-  if (!buf && hipMalloc(&buf, 2048 * 12 * sizeof(unsigned long long)) != hipSuccess) buf = nullptr;
-  return buf;
-}
-
 int launch_gemm(GemmLayout layout, GemmEpi epi, const GemmLaunch& g, hipStream_t stream) {
   SUMK_ARG(g.A && g.B[0] && (g.C || (g.C16 && epi == EPI_NONE)) && g.probs, "gemm: null operand");
   if (g.total_tiles <= 0) return SUMK_OK;
@@ -37,27 +30,15 @@ int launch_gemm(GemmLayout layout, GemmEpi epi, const GemmLaunch& g, hipStream_t
   for (int i = 0; i < 4; ++i) { ka.B[i] = g.B[i]; ka.bias0[i] = g.bias0[i]; ka.bias1[i] = g.bias1[i]; }
   ka.C = g.C; ka.R = g.R; ka.probs = g.probs; ka.nprob = g.nprob; ka.n_group = g.n_group; ka.alpha = g.alpha;
   ka.total_tiles = g.total_tiles; ka.xcd_tiles_m = 0;
-  // SUMK_GROUP_REMAP: 0 never; 1 (default) split-K slices in every arithmetic + the per-video products of the bf16-plane modes, which
-  // are bound by operand bytes (bf16 training step 1.35 -> 1.21 ms, bf16x3 / bf16x6 ~1 %); the exact-fp32 per-video products did
-  // not gain (alpha.V 85 -> 89 us) and keep the plain order; 2 every grouped launch
-  static const int group_remap = SUMK_TUNE_ENV("SUMK_GROUP_REMAP") ? atoi(SUMK_TUNE_ENV("SUMK_GROUP_REMAP")) : 1;
+  // Group remap: split-K slices in every arithmetic + the per-video products of the bf16-plane modes, which are bound by operand
+  // bytes (bf16 training step 1.35 -> 1.21 ms, bf16x3 / bf16x6 ~1 %); the exact-fp32 per-video products did not gain
+  // (alpha.V 85 -> 89 us) and keep the plain order
   // (per-video products only while a video is a handful of tiles: at T = 10 000 a sub-problem is thousands of tiles, a contiguous
   //  range is a band of one video and the plain order was 6 % faster)
   const bool small_groups = (int64_t)g.total_tiles <= (int64_t)256 * g.nprob;
-  ka.group_remap = (g.nprob > 1 && (group_remap == 2 || (group_remap == 1 && (g.group_remap || (g.precision != SUMK_PRECISION_FP32 && small_groups))))) ? 1 : 0;
-#ifdef SUMK_DIAG   // `make DIAG=1` only: SUMK_GEMM_DBG=1 skips the epilogue stores (wrong results by design), =2 in-kernel cycle stamps
-  static const int dbg = getenv("SUMK_GEMM_DBG") ? atoi(getenv("SUMK_GEMM_DBG")) : 0;
-#else
-  constexpr int dbg = 0;
-#endif
-  ka.dbg = dbg; ka.dbg_buf = nullptr;
-  if (dbg & 2) {   // diagnostic only (never on a product path); SUMK_STAMP_TAG=<prof tag>: stamp only that GEMM of a forward pass
-    static const int only_tag = getenv("SUMK_STAMP_TAG") ? atoi(getenv("SUMK_STAMP_TAG")) : -1;
-    if (only_tag < 0 || only_tag == g.prof_tag) ka.dbg_buf = gemm_stamp_buffer(); else ka.dbg &= ~2;
-  }
+  ka.group_remap = (g.nprob > 1 && (g.group_remap || (g.precision != SUMK_PRECISION_FP32 && small_groups))) ? 1 : 0;
   ka.drop.seed = g.drop_seed; ka.drop.thr = g.drop_thr; ka.drop.scale = g.drop_scale; ka.drop.seed_dev = nullptr; ka.drop_site = g.drop_site;
-  static const bool lean128_on = !(SUMK_TUNE_ENV("SUMK_LEAN128") && SUMK_TUNE_ENV("SUMK_LEAN128")[0] == '0');
-  ka.lean = (lean128_on && g.lean && g.nprob == 1 && layout == GEMM_NT && g.small_tile == 0 && g.precision == SUMK_PRECISION_FP32 &&
+  ka.lean = (g.lean && g.nprob == 1 && layout == GEMM_NT && g.small_tile == 0 && g.precision == SUMK_PRECISION_FP32 &&
              (g.n_group == 0 || g.n_group % 128 == 0)) ? 1 : 0;
   ka.C16 = (unsigned short*)g.C16;
   SUMK_ARG(!g.C16 || epi == EPI_NONE, "gemm: the bf16 copy of C goes with the plain epilogue");
@@ -67,8 +48,7 @@ int launch_gemm(GemmLayout layout, GemmEpi epi, const GemmLaunch& g, hipStream_t
   SUMK_ARG(!g.ln_stats || (epi == EPI_BIAS_RELU_HEAD && g.ln_c1 && g.ln_c2), "gemm: ln_stats goes with the head epilogue and c1 / c2");
   if (g.prof_tag >= 0) prof_begin(g.prof_tag, stream);
   prof_begin(SUMK_PROF_GEMM_ALL, stream);
-  static const bool xcd_map = !(SUMK_TUNE_ENV("SUMK_XCD_MAP") && SUMK_TUNE_ENV("SUMK_XCD_MAP")[0] == '0');
-  if (xcd_map && g.nprob == 1 && g.xcd_M > 0) {
+  if (g.nprob == 1 && g.xcd_M > 0) {
     const int bm = (g.src16 && g.wide16) ? g.wide16 : gemm_tile_m(g.small_tile), bn = (g.src16 && g.wide16) ? 256 : gemm_tile_n(g.small_tile);
     const int tm = (g.xcd_M + bm - 1) / bm, tn = (g.xcd_N + bn - 1) / bn;
     if (tn % 4 == 0 && tm >= 16) { ka.xcd_tiles_m = tm; ka.total_tiles = 8 * ((tm + 1) / 2) * (tn / 4); }
@@ -100,8 +80,6 @@ int launch_gemm(GemmLayout layout, GemmEpi epi, const GemmLaunch& g, hipStream_t
     SUMK_HIP(hipGetLastError());
     return SUMK_OK;
   }
-  // BK = 64 for the 64x64 tile measured no better than BK = 32 on S-TVSum (8.64 vs 8.68 M frames/s): kept selectable
-  static const bool bk64 = SUMK_TUNE_ENV("SUMK_BK64") && SUMK_TUNE_ENV("SUMK_BK64")[0] == '1';
   if (g.src16) {                              // bf16 operands in HBM: gemm_b16.hip
     SUMK_ARG(g.wide16 == 0 || g.wide16 == 192 || g.wide16 == 256, "gemm: wide16 must be 0, 192 or 256");
     rc = launch_gemm_b16(layout, epi, ka, ka.total_tiles, g.wide16, stream);
@@ -109,8 +87,8 @@ int launch_gemm(GemmLayout layout, GemmEpi epi, const GemmLaunch& g, hipStream_t
   if (g.precision != SUMK_PRECISION_FP32) {   // bf16-plane arithmetics: instantiated in gemm_split.hip
     rc = launch_gemm_split(g.precision, layout, epi, ka, ka.total_tiles, g.small_tile, stream);
   } else
-  if (g.small_tile == 1) rc = bk64 ? launch_layout<64, 64, 64>(layout, epi, ka, ka.total_tiles, stream)
-                                   : launch_layout<64, 64, 32>(layout, epi, ka, ka.total_tiles, stream);
+  // (BK = 64 for the 64x64 tile measured no better than BK = 32 on S-TVSum: 8.64 vs 8.68 M frames/s)
+  if (g.small_tile == 1) rc = launch_layout<64, 64, 32>(layout, epi, ka, ka.total_tiles, stream);
   else if (g.small_tile == 2) rc = launch_layout<128, 64, 32>(layout, epi, ka, ka.total_tiles, stream);
   else rc = launch_layout<128, 128, 32>(layout, epi, ka, ka.total_tiles, stream);
   prof_end(SUMK_PROF_GEMM_ALL, stream);
@@ -423,11 +401,7 @@ int plain_gemm(sumk::GemmLayout layout, const float* A, const float* B, float* C
   GemmProb* p = scratch_prob();
   SUMK_ARG(p != nullptr, "gemm: cannot allocate problem scratch");
   hipStream_t s = (hipStream_t)stream;
-  int small = (M <= 64 || N <= 64) ? 1 : 0;
-  if (const char* env = SUMK_TUNE_ENV("SUMK_ROW_CFG")) if (env[0] >= '0' && env[0] <= '2') small = env[0] - '0';
-#ifdef SUMK_DIAG
-  if (getenv("SUMK_FAKE_LD")) { lda = 0; ldb = 0; }   // `make DIAG=1` only: every row aliases row 0 (tiny footprint, all cache hits; wrong results by design)
-#endif
+  const int small = (M <= 64 || N <= 64) ? 1 : 0;
   SUMK_TRY(fill_single_prob(p, M, N, K, lda, ldb, N, 0, small, s));
   GemmLaunch g;
   g.A = A; g.B[0] = B; g.C = C; g.probs = p; g.nprob = 1; g.small_tile = small;
@@ -438,21 +412,6 @@ int plain_gemm(sumk::GemmLayout layout, const float* A, const float* B, float* C
   return launch_gemm(layout, EPI_NONE, g, s);
 }
 }  // namespace
-
-extern "C" int sumk_prof_gemm_stamps(uint64_t* out, int32_t n_blocks) {
-  using namespace sumk;
-#ifdef SUMK_DIAG
-  static const bool on = getenv("SUMK_GEMM_DBG") && (atoi(getenv("SUMK_GEMM_DBG")) & 2);
-#else
-  constexpr bool on = false;
-#endif
-  SUMK_ARG(on && out && n_blocks != 0 && n_blocks <= 2048 && n_blocks >= -2048, "gemm stamps: needs a diagnostic build (make -C summarizer_amd/csrc DIAG=1) started with SUMK_GEMM_DBG=2 (n_blocks <= 2048)");
-  SUMK_HIP(hipDeviceSynchronize());
-  // n_blocks < 0: the fine records of SUMK_GEMM_DBG & 4 (8 values per block, -n_blocks of them)
-  if (n_blocks < 0) { SUMK_HIP(hipMemcpy(out, gemm_stamp_buffer() + 2048 * 4, (size_t)(-n_blocks) * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost)); return SUMK_OK; }
-  SUMK_HIP(hipMemcpy(out, gemm_stamp_buffer(), (size_t)n_blocks * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return SUMK_OK;
-}
 
 extern "C" int sumk_gemm_nt(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K, void* stream) {
   return plain_gemm(sumk::GEMM_NT, A, B, C, M, N, K, K, K, stream);

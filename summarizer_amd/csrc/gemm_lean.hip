@@ -65,10 +65,6 @@ __global__ __launch_bounds__(256, 4) void gemm_lean_kernel(GemmKArgs ka) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
   const int kq = (tid & 7) * 4;                  // K-contiguous images: this thread's k offset inside a k-tile
-#ifdef SUMK_DIAG
-  unsigned long long st0 = 0, st_loop = 0, st_epi = 0, rt0 = 0, n_tiles = 0;
-  if (ka.dbg_buf) { st0 = __builtin_amdgcn_s_memtime(); rt0 = __builtin_amdgcn_s_memrealtime(); }
-#endif
 
   auto setup = [&](int tile, LeanTile& t) -> bool {
     TileCtx c; GemmProb P;
@@ -249,10 +245,6 @@ __global__ __launch_bounds__(256, 4) void gemm_lean_kernel(GemmKArgs ka) {
     swrite(im0);
     next_load(1);
     __syncthreads();
-#ifdef SUMK_DIAG
-    unsigned long long sa = 0;
-    if (ka.dbg_buf) sa = __builtin_amdgcn_s_memtime();
-#endif
     // steady state, unrolled by two (image addresses are immediates): k-tiles kt whose kt + 2 is a FULL k-tile -- no branch, no mask,
     // no VALU instruction
     const int n_steady = cur.has_tail ? nk - 3 : nk - 2;
@@ -278,10 +270,6 @@ __global__ __launch_bounds__(256, 4) void gemm_lean_kernel(GemmKArgs ka) {
       __syncthreads();
       float* t = cur_img; cur_img = oth_img; oth_img = t;
     }
-#ifdef SUMK_DIAG
-    unsigned long long sb = 0;
-    if (ka.dbg_buf) { asm volatile("" :: "v"(acc[0])); sb = __builtin_amdgcn_s_memtime(); }
-#endif
 
     // ---- SK: a tile cut into K slices.  Partial -> global (sc1), ticket; the last arriver adds the partials in slice order.
     bool finish = true;                       // does this block run the tile's epilogue?  (wave-uniform)
@@ -369,24 +357,10 @@ __global__ __launch_bounds__(256, 4) void gemm_lean_kernel(GemmKArgs ka) {
         }
       }
     }
-#ifdef SUMK_DIAG
-    if (ka.dbg_buf) { const unsigned long long sc = __builtin_amdgcn_s_memtime(); st_loop += sb - sa; st_epi += sc - sb; n_tiles += 1; }
-#endif
     if (!has_next) break;
     tile = next_tile;
     cur = nxt;
   }
-#ifdef SUMK_DIAG
-  if (ka.dbg_buf && tid == 0 && blockIdx.x < 2048) {   // {total, k-loops, epilogues, tiles | -, -, -, k-loops, start, end, hw, xcc}
-    __builtin_amdgcn_s_waitcnt(0);
-    const unsigned long long st4 = __builtin_amdgcn_s_memtime();
-    unsigned long long* o = ka.dbg_buf + (size_t)blockIdx.x * 4;
-    o[0] = st4 - st0; o[1] = st_loop; o[2] = st_epi; o[3] = n_tiles;
-    unsigned long long* q = ka.dbg_buf + (size_t)2048 * 4 + (size_t)blockIdx.x * 8;
-    q[0] = 0; q[1] = 0; q[2] = 0; q[3] = st_loop; q[4] = rt0; q[5] = __builtin_amdgcn_s_memrealtime();
-    q[6] = __builtin_amdgcn_s_getreg((31 << 11) | 4); q[7] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-  }
-#endif
 }
 
 // Takes a grouped or single-problem launch the generic dispatcher prepared (GemmKArgs: problem table, group_remap, alpha).
@@ -402,8 +376,7 @@ int launch_gemm_lean(GemmLayout layout, const GemmKArgs& ka, int tiles, hipStrea
   }
   SUMK_ARG(layout == GEMM_NT || layout == GEMM_NN, "gemm_lean: NT and NN layouts only");
   // persistent: at most 4 blocks per CU (what the two LDS images admit) are resident; block b walks tiles b, b + grid, ...
-  static const int lean_grid = SUMK_TUNE_ENV("SUMK_LEAN_GRID") ? atoi(SUMK_TUNE_ENV("SUMK_LEAN_GRID")) : 1024;
-  const dim3 grid(std::min(tiles, lean_grid)), block(256);
+  const dim3 grid(std::min(tiles, 1024)), block(256);
   if (layout == GEMM_NT) hipLaunchKernelGGL(gemm_lean_kernel<true>, grid, block, 0, s, ka);
   else hipLaunchKernelGGL(gemm_lean_kernel<false>, grid, block, 0, s, ka);
   return SUMK_OK;

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(512) void gemm_pw_kernel(PwArgs a) {
   const int wm = wave >> 2, wn = wave & 3;
   // Schedule variants (probes; the product runs VAR = 2).  When does a wave issue the DMA pieces that refill the slot a barrier freed?
   //   0: waves 0-3 right behind the barrier, waves 4-7 after the step's last MFMAs;  1: every wave right behind the barrier;
-  //   2: every wave after the step's last MFMAs;  3: as 2, with cycle stamps (diagnostic build only).
+  //   2: every wave after the step's last MFMAs.
   // Measured (profiles/r05_pw_gemm_variants.txt, QKV shape): 2 is the fastest at two planes and ties the rest at three; also tried and
   // within +-2 % of it: the barrier after one third of the step's MFMAs instead of two thirds, s_setprio(1) around the MFMA groups,
   // both, and the refill spread between the MFMA groups of the next step -- the loop runs at 83 % of its MFMA floor whatever the
@@ -137,10 +137,6 @@ __global__ __launch_bounds__(512) void gemm_pw_kernel(PwArgs a) {
   };
 
   const int nk = a.K >> 4;
-#ifdef SUMK_DIAG
-  unsigned long long t_start = 0, t_loop = 0, t_epi = 0, rt_start = 0, n_tiles = 0;
-  if constexpr (VAR == 3) { t_start = __builtin_amdgcn_s_memtime(); rt_start = __builtin_amdgcn_s_memrealtime(); }
-#endif
   // (a virtual tile id of an XCD map may name no tile: walk on to this block's next one)
   auto next_valid = [&](int t, int& m, int& n) -> int {
     for (; t < a.total_tiles; t += gridDim.x)
@@ -184,10 +180,6 @@ __global__ __launch_bounds__(512) void gemm_pw_kernel(PwArgs a) {
     // ---- k loop: stage s lives in slot s % NS; Frags[s & 1]
     wait_vm<0>();                      // (start of a tile: the previous epilogue's stores share the counter: drain; stages 1.. are mostly there by now)
     __builtin_amdgcn_s_barrier();
-#ifdef SUMK_DIAG
-    unsigned long long t0 = 0;
-    if constexpr (VAR == 3) t0 = __builtin_amdgcn_s_memtime();
-#endif
     Frags F0, F1;
     read_frags(0, F0);
     int slot = 0;
@@ -226,10 +218,6 @@ __global__ __launch_bounds__(512) void gemm_pw_kernel(PwArgs a) {
 
     // ---- next tile's first stages go out under this tile's epilogue
     lds_barrier();                     // every wave is past its last fragment read
-#ifdef SUMK_DIAG
-    unsigned long long t1 = 0;
-    if constexpr (VAR == 3) t1 = __builtin_amdgcn_s_memtime();
-#endif
     int m1 = 0, n1 = 0;
     const int next_tile = next_valid(tile + gridDim.x, m1, n1);
     const bool has_next = next_tile >= 0;
@@ -339,22 +327,9 @@ __global__ __launch_bounds__(512) void gemm_pw_kernel(PwArgs a) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-#ifdef SUMK_DIAG
-    if constexpr (VAR == 3) { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); t_loop += t1 - t0; t_epi += t2 - t1; n_tiles += 1; }
-#endif
     if (!has_next) break;
     tile = next_tile; m0 = m1; n0 = n1;
   }
-#ifdef SUMK_DIAG
-  if constexpr (VAR == 3 && EPI == PW_F32) {     // diagnostic build only: the stamps OVERWRITE the first floats of C (scripts/pw_bench.py reads them)
-    __syncthreads();
-    if (tid == 0) {
-      unsigned long long* o = reinterpret_cast<unsigned long long*>(a.C) + (size_t)blockIdx.x * 8;
-      o[0] = __builtin_amdgcn_s_memtime() - t_start; o[1] = t_loop; o[2] = t_epi; o[3] = n_tiles;
-      o[4] = __builtin_amdgcn_s_memrealtime() - rt_start; o[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20 /* XCC_ID */);
-    }
-  }
-#endif
 }
 
 std::atomic<uint64_t> g_attr_done[64];      // per kernel instance (index below): bit d = device d has the dynamic-LDS opt-in
@@ -384,7 +359,6 @@ int launch_np(PwEpi epi, const PwArgs& a, int variant, hipStream_t s) {
       switch (variant) {
         case 10: return launch_one<NP, 192, PW_F32, NS, 0>(a, base + 4, s);      // (probe: waves 0-3 issue their DMA early)
         case 1: return launch_one<NP, 192, PW_F32, NS, 1>(a, base + 5, s);
-        case 3: return launch_one<NP, 192, PW_F32, NS, 3>(a, base + 6, s);
         default: return launch_one<NP, 192, PW_F32, NS, 2>(a, base + 0, s);
       }
     case PW_PLANES: return launch_one<NP, 192, PW_PLANES, NS, 2>(a, base + 1, s);
@@ -615,9 +589,8 @@ int launch_gemm_pw(PwEpi epi, const PwLaunch& g, hipStream_t stream) {
   a.a_rp16 = (uint32_t)(pw_rows_pitch(g.a_rows) * 16); a.b_rp16 = (uint32_t)(pw_rows_pitch(g.b_rows) * 16);
   a.M = g.M; a.N = g.N; a.K = g.K;
   a.tiles_m = (g.M + 191) / 192; a.tiles_n = g.N / 256;
-  static const int map_env = SUMK_TUNE_ENV("SUMK_PW_XCD_MAP") ? atoi(SUMK_TUNE_ENV("SUMK_PW_XCD_MAP")) : 2;      // (diagnostic build only)
-  a.xcd_map = (a.tiles_n % 4 == 0 && a.tiles_m >= 16) ? map_env : 0;
-  a.total_tiles = a.xcd_map == 2 ? 8 * ((a.tiles_m + 7) / 8) * a.tiles_n : a.xcd_map == 1 ? 8 * ((a.tiles_m + 1) / 2) * (a.tiles_n / 4) : a.tiles_m * a.tiles_n;
+  a.xcd_map = (a.tiles_n % 4 == 0 && a.tiles_m >= 16) ? 2 : 0;
+  a.total_tiles = a.xcd_map == 2 ? 8 * ((a.tiles_m + 7) / 8) * a.tiles_n : a.tiles_m * a.tiles_n;
   a.C = g.C; a.ldc = g.ldc; a.O = (char*)g.O; a.o_rp16 = pw_rows_pitch(g.o_rows) * 16;
   a.o_store_rows = (int32_t)std::max<int64_t>(g.M, std::min<int64_t>(g.o_store_rows, std::min<int64_t>(pw_rows_pitch(g.o_rows), pw_rows_pitch(g.a_rows)))); a.R = g.R; a.ldr = g.ldr; a.moments = g.moments;
   a.bias = g.bias; a.gw = g.gw; a.ln_c1 = g.ln_c1; a.ln_stats = g.ln_stats; a.head_part = g.head_part; a.relu = g.relu;
@@ -634,9 +607,7 @@ int launch_gemm_pw(PwEpi epi, const PwLaunch& g, hipStream_t stream) {
   prof_begin(SUMK_PROF_GEMM_ALL, stream);
   // two planes run on the 16x16x32 MFMA shape (gemm_pw16.hip: -13 % on the same operands); three planes do not fit its five-stage ring
   int rc;
-  static const bool pw16_on = !(SUMK_TUNE_ENV("SUMK_PW16") && SUMK_TUNE_ENV("SUMK_PW16")[0] == '0');      // (diagnostic build only: scripts/pw16_step_probe.sh)
-  if (g.np == 2 && g.K >= 160 && g.variant != 32 && pw16_on) {
-    if (a.xcd_map == 1) { a.xcd_map = 2; a.total_tiles = 8 * ((a.tiles_m + 7) / 8) * a.tiles_n; }
+  if (g.np == 2 && g.K >= 160 && g.variant != 32) {
     rc = launch_gemm_pw16((int)epi, a, stream);
   } else {
     rc = g.np == 3 ? launch_np<3, 3>(epi, a, g.variant, stream) : launch_np<2, 4>(epi, a, g.variant, stream);

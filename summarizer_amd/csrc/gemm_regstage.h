@@ -318,15 +318,8 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_kernel(GemmKArgs ka) {
   TileCtx cur, nxt;
   if (!setup(tile, cur)) return;   // (remapped walk: a rectangle's tiles are exhausted in increasing order)
   gload(cur, 0);
-  unsigned long long t_begin = 0, t_k = 0, t_e = 0, n_t = 0;
-#ifdef SUMK_DIAG
-  const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime();
-#endif
-  if (ka.dbg & 2) t_begin = __builtin_amdgcn_s_memtime();
 
   while (true) {
-    unsigned long long ta = 0;
-    if (ka.dbg & 2) ta = __builtin_amdgcn_s_memtime();
     f32x16 acc[TM][TN];
     if constexpr (EPI == EPI_RESIDUAL || EPI == EPI_RESIDUAL_MOMENTS) {
       residual_init<TM, TN>(ka, cur, acc, cur.m0 + wm * WTM, cur.n0 + wn * WTN, li, lh);
@@ -365,31 +358,17 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_kernel(GemmKArgs ka) {
     }
 
     // ---- epilogue of `cur` (gemm_device.h)
-    unsigned long long tb = 0;
-    if (ka.dbg & 2) tb = __builtin_amdgcn_s_memtime();
     if constexpr (EPI == EPI_BIAS_RELU_HEAD) {
       epilogue_head_moments<TM, TN>(ka, cur, acc, cur.m0 + wm * WTM, cur.n0 + wn * WTN, li, lh, reinterpret_cast<float2*>(lds), cur.m0, tid);
     } else if constexpr (EPI == EPI_RESIDUAL_MOMENTS) {
       epilogue_row_moments<TM, TN>(ka, cur, acc, cur.m0 + wm * WTM, cur.n0 + wn * WTN, li, lh);
       epilogue_store<EPI, TM, TN, true>(ka, cur, acc, cur.m0 + wm * WTM, cur.n0 + wn * WTN, li, lh);
-    } else
-    if (!(ka.dbg & 1) || acc[0][0][0] == 12345.f)
-    epilogue_store<EPI, TM, TN, true>(ka, cur, acc, cur.m0 + wm * WTM, cur.n0 + wn * WTN, li, lh);
-    if (ka.dbg & 2) { const unsigned long long tc = __builtin_amdgcn_s_memtime(); t_k += tb - ta; t_e += tc - tb; n_t += 1; }
+    } else {
+      epilogue_store<EPI, TM, TN, true>(ka, cur, acc, cur.m0 + wm * WTM, cur.n0 + wn * WTN, li, lh);
+    }
     if (!has_next) break;
     tile = next_tile;
     cur = nxt;
-  }
-  if ((ka.dbg & 2) && ka.dbg_buf && tid == 0 && blockIdx.x < 2048) {
-    unsigned long long* o = ka.dbg_buf + (size_t)blockIdx.x * 4;
-    o[0] = __builtin_amdgcn_s_memtime() - t_begin; o[1] = t_k; o[2] = t_e; o[3] = n_t;
-#ifdef SUMK_DIAG
-    if (ka.dbg & 4) {   // second record, behind the 2048 first ones: k-loop shares, wall-clock window (100 MHz), placement
-      unsigned long long* q = ka.dbg_buf + (size_t)2048 * 4 + (size_t)blockIdx.x * 8;
-      q[0] = 0; q[1] = 0; q[2] = 0; q[3] = t_k; q[4] = rt_begin; q[5] = __builtin_amdgcn_s_memrealtime();
-      q[6] = __builtin_amdgcn_s_getreg((31 << 11) | 4); q[7] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-    }
-#endif
   }
 }
 
@@ -398,8 +377,7 @@ static int launch_epi(GemmEpi epi, const GemmKArgs& ka, int tiles, hipStream_t s
   // persistent grid: no more blocks than can be resident (256 CUs x blocks/CU for this tile's LDS/VGPR footprint);
   // every block then loops over tiles  b, b+grid, ...
   constexpr int occ = (BM == 128 && BN == 128) ? 3 : (BM == 128 ? 4 : (BK == 64 ? 4 : 8));
-  static const bool persist = !(SUMK_TUNE_ENV("SUMK_PERSIST") && SUMK_TUNE_ENV("SUMK_PERSIST")[0] == '0');
-  dim3 grid(persist ? std::min(tiles, 256 * occ) : tiles), block(256);
+  dim3 grid(std::min(tiles, 256 * occ)), block(256);
   if constexpr (BM == 128 && BN == 128 && BK == 32 && A_KC && B_KC && X3 == 0) {
     if (ka.lean) {   // buffer-load instances (launch_gemm checked: one problem, NT, fp32, K % 32 == 0, one B group per tile)
 #define SUMK_LEAN_CASE(E) case E: hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, BK, true, true, E, 0, true>), grid, block, 0, s, ka); return SUMK_OK;

@@ -30,7 +30,9 @@ typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int PSTATE_WORDS = 16 + 16384;  // word 0: error flag; words 16..: step counters per work item (one word; lstm_wide2_kernel: four shards on
-                                          // lines of their own, 128 words per item); the last 512 words: phase stamps of the diagnostic build
+                                          // lines of their own, 128 words per item)
+constexpr int PSTATE_SPARE_WORDS = 512;   // the last words of the block, unused: the sharded counter layouts stay clear of them (their eligibility
+                                          // bounds, and so which kernel a batch gets, are as measured)
 
 struct LstmWs {
   size_t g, cstate, prob, pstate, gates, call, hprev, dg, slab, dhrec, dcstate, prob_sk, colpart, pstate_b, xchg, partial, total;
@@ -590,9 +592,8 @@ __device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p
 
 // CPW = 8-wide k chunks per wave: the block's 8 waves cover K = 64 * CPW >= H (4 for DSN's H = 256, 16 for sLSTM's 1024).
 // The member's W_hh fragments (32 gate rows x its wave's k range) live in REGISTERS for the whole work item -- exactly the
-// MFMA B operands every step needs -- so LDS holds only the staged h_{t-1} panel and the split-K partial tiles.
-// DIRECT: the A fragments (h_{t-1}[video li][k..k+3]) go straight from the sc1 buffer loads into the MFMAs, as in
-// lstm_wide_kernel below -- no LDS panel, one workgroup barrier less per step.
+// MFMA B operands every step needs -- so LDS holds only the split-K partial tiles.  The A fragments (h_{t-1}[video li][k..k+3]) go
+// straight from the sc1 buffer loads into the MFMAs, as in lstm_wide_kernel below (staging h through an LDS panel measured slower).
 // LL ("flag in the data", the low-latency protocol of collective libraries): h_t is published as ONE 8-byte {value, step tag} store per
 // element into a double-buffered exchange array, and the consumers' OWN loads of h_{t-1} are the poll -- reloaded until every tag
 // they need says t.  An aligned 8-byte store is single-copy atomic, so a matching tag proves its value; no other ordering is needed.
@@ -605,18 +606,16 @@ __device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p
 // upper half would multiply zeros: half the matrix-pipe time of a step.  Lane group g = lane / 16 takes the CONTIGUOUS k range
 // [32 wave + 8 g, + 8) of both operands (the sum over k does not care which lane group carries which k), so a lane's eight h values are
 // four 16-byte loads.
-template <int CPW, bool DIRECT, bool LL = false, bool M16 = false>
+template <int CPW, bool LL = false, bool M16 = false>
 __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a) {
-  static_assert(!LL || DIRECT, "the flag-in-data hand-off feeds the MFMAs straight from the loads");
   static_assert(!M16 || (LL && CPW == 4), "the 16-row form exists for the flag-in-data kernel with 32 k per wave");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int H = a.H, P = H + 4;
-  float* sH = smem;                       // [gsize][P]  h_{t-1} of the group's videos
   // [8 waves][32 rows][PP] split-K partial tiles; PP = 32: the epilogue's float4 read (a 16-lane group = 2 videos x 8 units x 16 B)
   // covers the 64 banks exactly once -- the pitch 33 + scalar reads of the first version were 8-way conflicted (ei + eu collides
   // along anti-diagonals); the MFMA-side scalar writes are 2-way at most, which a ds_write_b32 absorbs
   constexpr int PP = 32;
-  float* part = sH + a.gsize * P;
+  float* part = smem + a.gsize * P;       // (behind gsize x P unused floats, where an h_{t-1} panel once was: the layout as measured)
   int* sR0 = reinterpret_cast<int*>(part + 8 * 32 * PP);   // [32] first row of each video
   int* sT = sR0 + 32;                     // [32] length of each video
   int* sTg = sT + 32;                     // [1]  longest video of the group
@@ -634,10 +633,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a)
   bool dead = false;   // (thread 0 only; LL: every wave) a wait timed out: results are invalid, state[0] says so
 
   float4 wreg[CPW];
-#ifdef SUMK_DIAG   // `make DIAG=1`: per-phase shader cycles of the flag-in-data 16-row path, waves 0 and 7 of member 0 of team 0 -> state words 600..
-  unsigned long long dg_wait = 0, dg_mfma = 0, dg_bar1 = 0, dg_epi = 0, dg_bar2 = 0, dg_spins = 0;
-  const unsigned long long dg_t0 = __builtin_amdgcn_s_memtime();
-#endif
   for (int item = team; item < n_items; item += a.n_teams) {
     const int g = item >> 1, d = item & 1;
     const int v0 = g * a.gsize, nv = min(a.gsize, a.n_seq - v0);
@@ -709,9 +704,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         if constexpr (LL && M16) {
-#ifdef SUMK_DIAG
-          const unsigned long long st0 = __builtin_amdgcn_s_memtime();
-#endif
           // h_{t-1}[video lane % 16][k .. k+7], k = 32 wave + 8 (lane / 16): four 16-byte loads of {value, tag} pairs, repeated until
           // every tag this lane needs says t
           const bool need_row = t < Tl;
@@ -740,10 +732,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a)
               dead = true;
             }
           }
-#ifdef SUMK_DIAG
-          const unsigned long long st1 = __builtin_amdgcn_s_memtime();
-          dg_wait += st1 - st0; dg_spins += spins;
-#endif
           f32x4 hv[4];
 #pragma unroll
           for (int p = 0; p < 4; ++p) hv[p] = __builtin_bit_cast(f32x4, va[p]);     // {h_k, tag, h_k+1, tag}
@@ -767,9 +755,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) part[(wave * 32 + 4 * (lane >> 4) + r) * PP + 16 * tile + (lane & 15)] = acc16[tile][r];
           (void)acc;
-#ifdef SUMK_DIAG
-          dg_mfma += __builtin_amdgcn_s_memtime() - st1;
-#endif
         } else
         if constexpr (LL) {
           // h_{t-1}[video li][k .. k+3] = two 16-byte loads of {value, tag} pairs, repeated until every tag this lane needs says t
@@ -809,8 +794,7 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a)
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(p1[0], bv.z, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(p1[2], bv.w, acc, 0, 0, 0);
           }
-        } else
-        if constexpr (DIRECT) {
+        } else {
           constexpr unsigned OOB = 0x7ffffff0u;   // beyond num_records: the buffer load returns zeros
           const unsigned basel = t < Tl ? (unsigned)(((int64_t)(d == 0 ? r0l + t - 1 : r0l + Tl - t) * (2 * H) + d * H) * 4) : OOB;
           u32x4 va[CPW];
@@ -828,61 +812,13 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a)
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], bv.z, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], bv.w, acc, 0, 0, 0);
           }
-        } else {
-        // h_{t-1} of every video of the group -> LDS.  sc1 (write-through / L1-bypassing) 16-B buffer loads ONLY, four in
-        // flight per thread before the first LDS write.
-        {
-          const int H4 = H >> 2, n4 = nv * H4;
-          for (int base = 0; base < n4; base += 4 * PK_THREADS) {
-            u32x4 v[4];
-            int dst[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-              const int idx = base + tid + p * PK_THREADS;
-              dst[p] = -1; v[p] = u32x4{0u, 0u, 0u, 0u};
-              if (idx < n4) {
-                const int i = idx / H4, k = (idx - i * H4) * 4;
-                const int r0 = sR0[i], T = sT[i];
-                dst[p] = i * P + k;
-                if (t < T) {
-                  const unsigned boff = (unsigned)(((int64_t)(d == 0 ? r0 + t - 1 : r0 + T - t) * (2 * H) + d * H + k) * 4);
-                  v[p] = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, boff, 0, 16 /* sc1 */);
-                }
-              }
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-              if (dst[p] >= 0) *reinterpret_cast<u32x4*>(&sH[dst[p]]) = v[p];
-          }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < CPW; ++c) {
-          const int k = (wave * CPW + c) * 8 + 4 * lh;
-          float4 av = make_float4(0.f, 0.f, 0.f, 0.f);
-          const float4 bv = wreg[c];
-          if (k < H && li < nv) av = *reinterpret_cast<const float4*>(&sH[li * P + k]);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-        }
         }
         if constexpr (!M16) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) part[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * PP + li] = acc[r];
         }
-#ifdef SUMK_DIAG
-        const unsigned long long sb0 = __builtin_amdgcn_s_memtime();
-#endif
         __syncthreads();
-#ifdef SUMK_DIAG
-        dg_bar1 += __builtin_amdgcn_s_memtime() - sb0;
-#endif
       }
-#ifdef SUMK_DIAG
-      const unsigned long long se0 = __builtin_amdgcn_s_memtime();
-#endif
       if (erole && t < eT) {
         const int64_t row = d == 0 ? er0 + t : er0 + eT - 1 - t;
         float pre[4] = {gcur[0], gcur[1], gcur[2], gcur[3]};
@@ -920,14 +856,7 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a)
         }
       }
       if constexpr (LL) {
-#ifdef SUMK_DIAG
-        const unsigned long long se1 = __builtin_amdgcn_s_memtime();
-        dg_epi += se1 - se0;
-#endif
         __syncthreads();   // the split-K partial tiles in LDS are free again (the published h needs no further signal)
-#ifdef SUMK_DIAG
-        dg_bar2 += __builtin_amdgcn_s_memtime() - se1;
-#endif
       } else {
         // publish step t: every storing wave drains its stores, then one lane signals
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -936,12 +865,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a)
       }
     }
   }
-#ifdef SUMK_DIAG
-  if (LL && M16 && blockIdx.x < 12 && lane == 0 && (wave == 0 || wave == 7)) {
-    unsigned long long* q = reinterpret_cast<unsigned long long*>(a.state + 600) + (blockIdx.x * 2 + (wave == 7)) * 8;
-    q[0] = __builtin_amdgcn_s_memtime() - dg_t0; q[1] = dg_wait; q[2] = dg_mfma; q[3] = dg_bar1; q[4] = dg_epi; q[5] = dg_bar2; q[6] = dg_spins;
-  }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------- persistent recurrence with the input projection inside (round 6)
@@ -957,7 +880,7 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a)
 // 128-byte line (the x PLANES would be a gather here: one 16-byte chunk per 128-byte line, eight frames of a video to a line -- measured
 // 8.4 us per step, 786 KB per member and step through L2); it is split into the planes in registers (the roundings of split_planes).
 // The partial tiles are double-buffered by step parity, so the step has ONE workgroup barrier.  Same hand-off (flag in the data), same
-// 16-row MFMAs, same gate arithmetic as lstm_persist_kernel<4, true, true, true>; term order of the split products as gemm_regstage.h.
+// 16-row MFMAs, same gate arithmetic as lstm_persist_kernel<4, true, true>; term order of the split products as gemm_regstage.h.
 #ifndef SUMK_PROJ_KA
 #define SUMK_PROJ_KA 4
 #endif
@@ -1441,7 +1364,6 @@ struct Wide2Args {
 };
 constexpr int W2_SLICE_FLOATS = 256 * 64 * 4;   // one (parity, direction) slice of the exchange: [k4 256][row 64][4 floats] = 256 KB
 constexpr int W2_ITEM_WORDS = 128;              // state words per work item: four counter shards, 32 words (128 B) apart
-[[maybe_unused]] constexpr int W2_STAMP_WORD = PSTATE_WORDS - 512;   // diagnostic build: phase stamps at the end of the state block
 
 
 template <int MODE>   // 0: exact fp32 MFMA, 1: bf16x3 (hi / lo), 2: bf16x6 (three planes)
@@ -1492,10 +1414,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_wide2_kernel(Wide2Args a) {
     }
   }
   constexpr unsigned OOB = 0x7ffffff0u;   // beyond num_records: the buffer load returns zeros
-#ifdef SUMK_DIAG
-  unsigned long long dg_poll = 0, dg_mfma = 0, dg_bar1 = 0, dg_epi = 0, dg_pub = 0, dg_steps = 0, dg_two = 0;
-  const unsigned long long dg_t0 = __builtin_amdgcn_s_memtime();
-#endif
 
   for (int g = 0; g < a.n_groups; ++g) {
     const int item = 2 * g + d;
@@ -1540,9 +1458,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_wide2_kernel(Wide2Args a) {
     const unsigned xrow_w = (unsigned)(((j >> 2) * 64 + ei) * 4 + (j & 3));   // this thread's float inside a slice
 
     for (int t = 0; t < Tg; ++t) {
-#ifdef SUMK_DIAG
-      const unsigned long long s0 = __builtin_amdgcn_s_memtime();
-#endif
       float gnext[4] = {0.f, 0.f, 0.f, 0.f};
       if (t + 1 < eT) {   // next step's input-projection slice: requested a whole step before it is used
         const int64_t nrow = d == 0 ? er0 + t + 1 : er0 + eT - 2 - t;
@@ -1568,10 +1483,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_wide2_kernel(Wide2Args a) {
           }
         }
         __syncthreads();
-#ifdef SUMK_DIAG
-        const unsigned long long s1 = __builtin_amdgcn_s_memtime();
-        dg_poll += s1 - s0;
-#endif
         // A fragments: h_{t-1}[row][k..], sc1 (L1-bypassing) 16-B buffer loads of the exchange slice ONLY; finished rows read zeros.
         // Sixteen loads (the first tile) are in flight; the second tile's loads take each register pair as it is consumed.
         const __amdgpu_buffer_rsrc_t xr = ((t - 1) & 1) ? xr1 : xr0;
@@ -1665,18 +1576,8 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_wide2_kernel(Wide2Args a) {
         if (two)
 #pragma unroll
           for (int r = 0; r < 16; ++r) part[(wave * 64 + 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * PP + li] = acc1[r];
-#ifdef SUMK_DIAG
-        const unsigned long long s2 = __builtin_amdgcn_s_memtime();
-        dg_mfma += s2 - s1;
-#endif
         __syncthreads();
-#ifdef SUMK_DIAG
-        dg_bar1 += __builtin_amdgcn_s_memtime() - s2; dg_steps += 1; dg_two += two ? 1 : 0;
-#endif
       }
-#ifdef SUMK_DIAG
-      const unsigned long long s3 = __builtin_amdgcn_s_memtime();
-#endif
       const bool live = t < eT;     // (eT = 0 for threads without a role; rows >= 32 are never live when the second tile was skipped)
       const int64_t row = d == 0 ? er0 + t : er0 + eT - 1 - t;
       float ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, h = 0.f;
@@ -1706,17 +1607,10 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_wide2_kernel(Wide2Args a) {
       } else if (live) {
         st_sc1(xg + wslice + xrow_w, h);
       }
-#ifdef SUMK_DIAG
-      const unsigned long long s4 = __builtin_amdgcn_s_memtime();
-      dg_epi += s4 - s3;
-#endif
       // every storing wave drains its stores (and nothing younger than the G loads of the step's top), then one lane signals
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (tid == 0) __hip_atomic_fetch_add(bar + 32 * (slot & 3), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef SUMK_DIAG
-      dg_pub += __builtin_amdgcn_s_memtime() - s4;
-#endif
       if (live) {   // the layer's output and the training saves: nobody reads them in this launch, they leave behind the signal
         a.Hout[row * (2 * H) + d * H + j] = h;
         if constexpr (MODE != 2) {     // (the bf16x6 recurrence is an inference mode: the host never selects it with training saves)
@@ -1733,12 +1627,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_wide2_kernel(Wide2Args a) {
       for (int q = 0; q < 4; ++q) gcur[q] = gnext[q];
     }
   }
-#ifdef SUMK_DIAG
-  if (blockIdx.x < 12 && lane == 0 && (wave == 0 || wave == 7)) {
-    unsigned long long* q = reinterpret_cast<unsigned long long*>(a.state + W2_STAMP_WORD) + (blockIdx.x * 2 + (wave == 7)) * 8;
-    q[0] = __builtin_amdgcn_s_memtime() - dg_t0; q[1] = dg_poll; q[2] = dg_mfma; q[3] = dg_bar1; q[4] = dg_epi; q[5] = dg_pub; q[6] = dg_steps; q[7] = dg_two;
-  }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------- BPTT step kernel
@@ -1894,10 +1782,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwd
   int loaded_dir = -1;
   bool dead = false;
   float wB[2][8];     // M16: this lane's W_hh fragments
-#ifdef SUMK_DIAG   // `make DIAG=1`: per-phase shader cycles of a step, wave 0 (counter poll + epilogue role) and wave 7 of the first members -> state words 600..
-  unsigned long long bg_wait = 0, bg_cell = 0, bg_bar = 0, bg_mfma = 0, bg_drain = 0, bg_steps = 0;
-  const unsigned long long bg_t0 = __builtin_amdgcn_s_memtime();
-#endif
 
   for (int item = team; item < a.n_items; item += PK_TEAMS) {
     const int g = item >> 1, d = item & 1;
@@ -1957,9 +1841,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwd
     }
 
     for (int t = Tg - 1; t >= 0; --t) {
-#ifdef SUMK_DIAG
-      const unsigned long long bs0 = __builtin_amdgcn_s_memtime();
-#endif
       // next step's saved activations: seven strided loads per thread, requested here so that they have the whole step -- the producer's
       // vmcnt(0) drain in front of the signal used to wait for them (they were issued behind the cell update)
       const bool have_next = erole && t - 1 >= 0 && t - 1 < eT;
@@ -1984,9 +1865,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwd
         }
       }
       __syncthreads();
-#ifdef SUMK_DIAG
-      const unsigned long long bs1 = __builtin_amdgcn_s_memtime();
-#endif
       float rec_ll = 0.f;
       if constexpr (LL) {   // the 32 members' partials of step t+1: the loads are the poll (every wave of the epilogue role spins for itself)
         if (tid < 256) {
@@ -2074,13 +1952,7 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwd
         sA[ei * 36 + eu] = d_i; sA[ei * 36 + 8 + eu] = d_f; sA[ei * 36 + 16 + eu] = d_g; sA[ei * 36 + 24 + eu] = d_o;
       }
       if (have_next) { sv_i = nx_i; sv_f = nx_f; sv_g = nx_g; sv_o = nx_o; sv_c = nx_c; sv_cp = nx_cp; sv_dh = nx_dh; }
-#ifdef SUMK_DIAG
-      const unsigned long long bs2 = __builtin_amdgcn_s_memtime();
-#endif
       __syncthreads();
-#ifdef SUMK_DIAG
-      const unsigned long long bs3 = __builtin_amdgcn_s_memtime();
-#endif
       if (t > 0) {   // partial_m(t) is only ever read by step t-1
         if constexpr (M16) {
           // 16 videos x (this wave's 32 columns, two 16-column tiles) x K = 32: lane group g = lane / 16 carries k = 8 g .. 8 g + 7
@@ -2181,9 +2053,6 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwd
         }
         }
       }
-#ifdef SUMK_DIAG
-      const unsigned long long bs4 = __builtin_amdgcn_s_memtime();
-#endif
       if constexpr (LL) {
         __syncthreads();   // the A tile in LDS is free again (the published partials need no further signal)
       } else {
@@ -2191,17 +2060,8 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwd
         __syncthreads();
         if (tid == 0) __hip_atomic_fetch_add(bar + 32 * (slot % a.n_shards), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
-#ifdef SUMK_DIAG
-      bg_wait += bs1 - bs0; bg_cell += bs2 - bs1; bg_bar += bs3 - bs2; bg_mfma += bs4 - bs3; bg_drain += __builtin_amdgcn_s_memtime() - bs4; bg_steps += 1;
-#endif
     }
   }
-#ifdef SUMK_DIAG
-  if (!LL && M16 && blockIdx.x < 96 && (blockIdx.x % PK_TEAMS) == 0 && lane == 0 && (wave == 0 || wave == 7)) {      // members 0 .. 11 of team 0
-    unsigned long long* q = reinterpret_cast<unsigned long long*>(a.state + 600) + ((blockIdx.x / PK_TEAMS) * 2 + (wave == 7)) * 8;
-    q[0] = __builtin_amdgcn_s_memtime() - bg_t0; q[1] = bg_wait; q[2] = bg_cell; q[3] = bg_bar; q[4] = bg_mfma; q[5] = bg_drain; q[6] = bg_steps;
-  }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------- wide persistent BPTT
@@ -2595,26 +2455,21 @@ extern "C" int sumk_bilstm_layer_forward(const float* x, int32_t In, int32_t H, 
     pa.n_teams = H <= 256 ? PK_TEAMS : 2;
     const int team_size = 256 / pa.n_teams;
     pa.upm = std::min(8, (H + team_size - 1) / team_size); pa.n_active = (H + pa.upm - 1) / pa.upm;
-    const int gmax = H <= 256 ? 32 : 24;       // videos per work item, bounded by the LDS panel gsize x (H+4) floats
+    const int gmax = H <= 256 ? 32 : 24;       // videos per work item (the LDS map keeps gsize x (H+4) floats in front of the partial tiles)
     int gsize = std::min(gmax, std::max(1, (2 * n_seq + pa.n_teams - 1) / pa.n_teams));
     pa.gsize = gsize; pa.n_groups = (n_seq + gsize - 1) / gsize;
     if (2 * pa.n_groups <= PSTATE_WORDS - 16 && pa.n_active <= team_size) {
       const size_t shmem = std::max<size_t>(((size_t)gsize * (H + 4) + 8 * 32 * 32 + 96) * sizeof(float), 96 * 1024);  // >80 KB: one block per CU
-      static const bool direct = !(SUMK_TUNE_ENV("SUMK_LSTM_PANEL") && SUMK_TUNE_ENV("SUMK_LSTM_PANEL")[0] == '1');   // 1: stage h through LDS
       // SUMK_LSTM_LL=0: the counter hand-off (A/B switch); the flag-in-data one needs the exchange buffer's byte offsets in 31 bits
       static const bool ll_on = !(getenv("SUMK_LSTM_LL") && getenv("SUMK_LSTM_LL")[0] == '0');
-      const bool ll = direct && ll_on && L.ll_bytes > 0 && L.ll_bytes < 0x7fffffe0;
+      const bool ll = ll_on && L.ll_bytes > 0 && L.ll_bytes < 0x7fffffe0;
       static const bool m16_on = !(getenv("SUMK_LSTM_M16") && getenv("SUMK_LSTM_M16")[0] == '0');
       const bool m16 = ll && m16_on && gsize <= 16;
-      const int which = m16 ? 3 : ll ? 2 : direct ? 1 : 0;
-      const void* fn = m16 ? (const void*)lstm_persist_kernel<4, true, true, true>
-                     : ll ? (const void*)lstm_persist_kernel<4, true, true>
-#ifdef SUMK_DIAG
-                          : direct ? (const void*)lstm_persist_kernel<4, true> : (const void*)lstm_persist_kernel<4, false>;   // (LDS-panel staging: measured slower, diagnostic build only)
-#else
-                          : (const void*)lstm_persist_kernel<4, true>;
-#endif
-      static bool attr_set[4] = {false, false, false, false};
+      const int which = m16 ? 2 : ll ? 1 : 0;
+      const void* fn = m16 ? (const void*)lstm_persist_kernel<4, true, true>
+                     : ll ? (const void*)lstm_persist_kernel<4, true>
+                          : (const void*)lstm_persist_kernel<4>;
+      static bool attr_set[3] = {false, false, false};
       if (!attr_set[which]) {
         SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set[which] = true;
@@ -2623,19 +2478,6 @@ extern "C" int sumk_bilstm_layer_forward(const float* x, int32_t In, int32_t H, 
       prof_begin(SUMK_PROF_LSTM_REC, stream);
       SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(256), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
       prof_end(SUMK_PROF_LSTM_REC, stream);
-#ifdef SUMK_DIAG
-      if (getenv("SUMK_LSTM_STAMPS") && m16) {
-        unsigned long long q[12 * 2 * 8];
-        SUMK_HIP(hipStreamSynchronize(stream));
-        SUMK_HIP(hipMemcpy(q, (const char*)(ws + L.pstate) + 600 * 4, sizeof(q), hipMemcpyDeviceToHost));
-        for (int b = 0; b < 12; b += 5)
-          for (int wv = 0; wv < 2; ++wv) {
-            const unsigned long long* e = q + (b * 2 + wv) * 8;
-            fprintf(stderr, "[lstm stamps] block %d wave %d: total %llu  wait %llu (spins %llu)  mfma+part %llu  barrier1 %llu  epilogue %llu  barrier2 %llu\n",
-                    b, wv ? 7 : 0, e[0], e[1], e[6], e[2], e[3], e[4], e[5]);
-          }
-      }
-#endif
       return SUMK_OK;
     }
   }
@@ -2653,7 +2495,7 @@ extern "C" int sumk_bilstm_layer_forward(const float* x, int32_t In, int32_t H, 
     // round 6: the re-partitioned form (exchange buffer laid out for the consumers, rows sorted by length, sharded counter, bf16x6 mode);
     // SUMK_LSTM_WIDE2=0 keeps lstm_wide_kernel (A/B switch: tests/test_gpu_lstm.py::test_wide_recurrence_forms_agree)
     static const bool wide2_on = !(getenv("SUMK_LSTM_WIDE2") && getenv("SUMK_LSTM_WIDE2")[0] == '0');
-    if (wide2_on && L.wx_bytes > 0 && 2 * wa.n_groups * W2_ITEM_WORDS <= PSTATE_WORDS - 16 - 512) {
+    if (wide2_on && L.wx_bytes > 0 && 2 * wa.n_groups * W2_ITEM_WORDS <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS) {
       Wide2Args w2;
       w2.G = wa.G; w2.whh[0] = wa.whh[0]; w2.whh[1] = wa.whh[1]; w2.Hout = h_out;
       w2.gates = wa.gates; w2.c_all = wa.c_all; w2.hprev = wa.hprev; w2.off = wa.off; w2.state = wa.state;
@@ -2674,21 +2516,6 @@ extern "C" int sumk_bilstm_layer_forward(const float* x, int32_t In, int32_t H, 
       prof_begin(SUMK_PROF_LSTM_REC, stream);
       SUMK_HIP(hipLaunchCooperativeKernel(fn2, dim3(256), dim3(PK_THREADS), kargs2, (unsigned)shmem2, stream));
       prof_end(SUMK_PROF_LSTM_REC, stream);
-#ifdef SUMK_DIAG
-      if (getenv("SUMK_LSTM_STAMPS")) {
-        unsigned long long q[12 * 2 * 8];
-        SUMK_HIP(hipStreamSynchronize(stream));
-        SUMK_HIP(hipMemcpy(q, (const char*)(ws + L.pstate) + W2_STAMP_WORD * 4, sizeof(q), hipMemcpyDeviceToHost));
-        for (int b = 0; b < 12; b += 5)
-          for (int wv = 0; wv < 2; ++wv) {
-            const unsigned long long* e = q + (b * 2 + wv) * 8;
-            const double n = e[6] ? (double)e[6] : 1.0;
-            fprintf(stderr, "[wide2 stamps] mode %d block %d wave %d: steps %llu (two tiles in %llu)  cycles/step: total %.0f = poll + barrier %.0f + loads, MFMAs, partial tiles %.0f + "
-                            "barrier %.0f + cell update, exchange stores %.0f + drain, barrier, signal %.0f\n",
-                    mode, b, wv ? 7 : 0, e[6], e[7], (double)e[0] / n, e[1] / n, e[2] / n, e[3] / n, e[4] / n, e[5] / n);
-          }
-      }
-#endif
       return SUMK_OK;
     }
     const size_t shmem = 96 * 1024;   // 68 KB used; > 80 KB keeps one block per CU
@@ -2775,10 +2602,10 @@ extern "C" int sumk_bilstm_layer_backward(const float* x, const float* h_out, co
     pa.upm = std::min(8, (H + 31) / 32); pa.n_active = (H + pa.upm - 1) / pa.upm;
     int gsize = std::min(32, std::max(1, (2 * n_seq + PK_TEAMS - 1) / PK_TEAMS));
     pa.gsize = gsize; pa.n_groups = (n_seq + gsize - 1) / gsize; pa.n_items = 2 * pa.n_groups;
-    // round 6: sharded step counter (while the items fit the state block; the last 512 words hold the diagnostic stamps) and the reader-shaped
+    // round 6: sharded step counter (while the items fit the state block, short of its spare words) and the reader-shaped
     // exchange (members own 8 aligned units); SUMK_LSTM_BWD_R6=0 keeps the round-5 forms (A/B: tests/test_gpu_lstm.py)
     static const bool r6_on = !(getenv("SUMK_LSTM_BWD_R6") && getenv("SUMK_LSTM_BWD_R6")[0] == '0');
-    const bool shard = r6_on && pa.n_items * 128 <= PSTATE_WORDS - 16 - 512;
+    const bool shard = r6_on && pa.n_items * 128 <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS;
     pa.item_words = shard ? 128 : 1; pa.n_shards = shard ? 4 : 1;
     pa.coal = (r6_on && pa.upm == 8 && pa.n_active * 8 == H) ? 1 : 0;
     if (pa.n_items <= PSTATE_WORDS - 16) {
@@ -2801,25 +2628,9 @@ extern "C" int sumk_bilstm_layer_backward(const float* x, const float* h_out, co
       void* kargs[] = {&pa};
       SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(PK_TEAMS * 32), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
       done = true;
-#ifdef SUMK_DIAG
-      if (getenv("SUMK_LSTM_STAMPS") && !ll && m16) {      // phase table of the BPTT step (scripts/probes: profiles/r04_lstm_bptt_phase_stamps.txt)
-        unsigned long long q[12 * 2 * 8];
-        SUMK_HIP(hipStreamSynchronize(stream));
-        SUMK_HIP(hipMemcpy(q, (const char*)pa.state + 600 * 4, sizeof(q), hipMemcpyDeviceToHost));
-        for (int b = 0; b < 12; b += 5)
-          for (int wv = 0; wv < 2; ++wv) {
-            const unsigned long long* e = q + (b * 2 + wv) * 8;
-            const double n = e[6] ? (double)e[6] : 1.0;
-            fprintf(stderr, "[lstm bptt stamps] member %d wave %d: steps %llu  cycles/step: total %.0f = wait for the counter %.0f + partial sums, cell backward, dG stores %.0f + "
-                            "barrier %.0f + MFMAs, partial stores %.0f + drain, barrier, signal %.0f\n",
-                    b, wv ? 7 : 0, e[6], (double)(e[1] + e[2] + e[3] + e[4] + e[5]) / n, e[1] / n, e[2] / n, e[3] / n, e[4] / n, e[5] / n);
-          }
-      }
-#endif
     }
   }
-  static const bool wide_bwd = !(SUMK_TUNE_ENV("SUMK_LSTM_WIDE_BWD") && SUMK_TUNE_ENV("SUMK_LSTM_WIDE_BWD")[0] == '0');
-  if (!done && persist_ok && wide_bwd && n_seq > GV_MAXB && H > 256 && H <= 1024 && H % 128 == 0 && L.xchg_bytes > 0 &&
+  if (!done && persist_ok && n_seq > GV_MAXB && H > 256 && H <= 1024 && H % 128 == 0 && L.xchg_bytes > 0 &&
       2 * ((n_seq + WK_GROUP - 1) / WK_GROUP) <= PSTATE_WORDS - 16) {
     WideBwdArgs wa;
     wa.whh[0] = w->w_hh[0]; wa.whh[1] = w->w_hh[1]; wa.dHout = dh_out; wa.gates = (const float*)(ws + L.gates);
@@ -2830,7 +2641,7 @@ extern "C" int sumk_bilstm_layer_backward(const float* x, const float* h_out, co
     wa.xchg_dir_bytes = (int32_t)(L.xchg_bytes / 2);
     {   // round 6: sharded step counter while the items fit the state block (SUMK_LSTM_BWD_R6=0: one word per item, as round 5)
       static const bool r6_on = !(getenv("SUMK_LSTM_BWD_R6") && getenv("SUMK_LSTM_BWD_R6")[0] == '0');
-      const bool shard = r6_on && 2 * wa.n_groups * 128 <= PSTATE_WORDS - 16 - 512;
+      const bool shard = r6_on && 2 * wa.n_groups * 128 <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS;
       wa.item_words = shard ? 128 : 1; wa.n_shards = shard ? 4 : 1;
     }
     static bool wb_attr_set = false;

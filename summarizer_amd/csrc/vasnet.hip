@@ -146,7 +146,6 @@ struct RowProbSpec { int32_t M, N, K, lda, ldb, ldc, ldr, small; };
 struct SetupArgs {
   int32_t* row_seq;      // [n_rows] video index of every packed row
   int32_t p16;           // 1: the attention operand of the PV / dV / dQ / dK tables is the bf16 block (e16off, ld16) instead of (eoff, ldE)
-  int32_t fake_seq0;     // diagnostic builds only: every video READS video 0's Q / K / V rows (operands stay L2-resident)
   const int32_t* off; int32_t n_seq, D;
   SeqInfo* seq; GemmProb* tabs;   // tabs[TB_COUNT][n_seq]
   int32_t s_tm, s_tn, pv_tm, pv_tn;  // block-tile dims of the (T x T) and (T x D) per-video products
@@ -234,10 +233,9 @@ __global__ void vasnet_setup_kernel(SetupArgs a) {
   a.seq[s] = si;
   const int64_t q0 = (int64_t)row0 * 3 * D, c0 = (int64_t)row0 * D;
   const int n = a.n_seq;
-  const int64_t qr = a.fake_seq0 ? 0 : q0;     // where Q / K / V are READ (q0 except in the diagnostic aliasing experiment)
   // forward
-  put_prob(a.tabs + TB_S * n + s, qr, qr + D, eoff, T, T, D, 3 * D, 3 * D, ldE, ts, tm);            // E = Q K^T        (NT)
-  put_prob(a.tabs + TB_PV * n + s, po, qr + 2 * D, c0, T, D, T, ldp, 3 * D, D, tpv, tn);             // C = alpha V      (NN)
+  put_prob(a.tabs + TB_S * n + s, q0, q0 + D, eoff, T, T, D, 3 * D, 3 * D, ldE, ts, tm);            // E = Q K^T        (NT)
+  put_prob(a.tabs + TB_PV * n + s, po, q0 + 2 * D, c0, T, D, T, ldp, 3 * D, D, tpv, tn);             // C = alpha V      (NN)
   a.tabs[TB_PV * n + s].r_off = c0; a.tabs[TB_PV * n + s].ldr = D;   // folded inference path: + X in the epilogue (same rows as C)
   // backward
   put_prob(a.tabs + TB_DV * n + s, po, c0, q0 + 2 * D, T, D, T, ldp, D, 3 * D, tpv, tn);             // dV = alpha^T dC  (TN)
@@ -1048,8 +1046,6 @@ __global__ void add_pos_kernel(float* x, const float* table, const int32_t* pos_
 }
 
 static int rowwise_small_tile(int M, int N) {
-  static const char* env = SUMK_TUNE_ENV("SUMK_ROW_CFG");   // tuning override: 0 = 128x128, 1 = 64x64, 2 = 128x64
-  if (env && env[0] >= '0' && env[0] <= '2') return env[0] - '0';
   return gemm_tiles(M, N, 0) >= 512 ? 0 : 1;
 }
 
@@ -1086,10 +1082,8 @@ static void sk_plan(int R, int D, int n_seq, const int32_t* off, const VasnetWs&
     int kc, S;
     int S_req = smax > 0 ? std::max(1, std::min(smax, K / 128)) : sk_slices(tiles * groups, K, &kc);
     // (R, D) projections consumed by the LayerNorm kernels: 4 slabs measured 2.4 us per video better than 8 -- the row kernel's extra loads cost
-    // what the shorter GEMM chains gain -- and equal to 2; Q.K^T / dAlpha stay at 8 (scripts/probes/sk_smax_sweep.py, third / fourth digit)
-    int slab_cap = 4;
-    if (const char* e = SUMK_TUNE_ENV("SUMK_SK_SMAX")) if (e[0] && e[1] && (e[2] == '1' || e[2] == '2' || e[2] == '4' || e[2] == '8')) slab_cap = e[2] - '0';
-    if (slab) for (S_req = slab_cap; S_req > 1; S_req >>= 1) {        // slab sets: exactly 1, 2, 4 or 8 slices (slab_sum), each at least four k-tiles
+    // what the shorter GEMM chains gain -- and equal to 2; Q.K^T / dAlpha stay at 8
+    if (slab) for (S_req = 4; S_req > 1; S_req >>= 1) {        // slab sets: exactly 1, 2, 4 or 8 slices (slab_sum), each at least four k-tiles
       sk_slice(K, S_req, &kc, &S);
       if (S == S_req && kc >= 128) break;
     }
@@ -1097,16 +1091,13 @@ static void sk_plan(int R, int D, int n_seq, const int32_t* off, const VasnetWs&
     P->spec[r] = SkRowSpec{M, N, K, lda, ldb, ldc, ldr, layout, groups, S_req, a_goff, c_goff, bsel, csel, slab ? (int64_t)M * ldc : 0, 0, 0};
     P->row[r] = SkTab{groups * S, groups * S * tiles, groups * tiles, S_req, S};
   };
-  // (diagnostic build: SUMK_SK_SMAX="<qkv><dctx>" overrides the two slice caps of the launches whose slices meet in the launch)
   // QKV: 240 tiles at T = 300 already give every CU a block; 4 slices + the in-launch meeting measured the same 26 us as one chain per
-  // tile (scripts/probes/sk_smax_sweep.py: 112.9 vs 112.7 us per video), so it stays unsliced -- the same k order as the large-batch kernel
-  int smax_qkv = 1, smax_dctx = 8;
-  if (const char* e = SUMK_TUNE_ENV("SUMK_SK_SMAX")) if (e[0] >= '1' && e[0] <= '8' && e[1] >= '1' && e[1] <= '8') { smax_qkv = e[0] - '0'; smax_dctx = e[1] - '0'; }
-  row(SR_QKV, GEMM_NT, R, D, D, D, D, 3 * D, 0, 3, 0, D, 1, 0, smax_qkv);   // [Q|K|V] = X [Wq;Wk;Wv]^T: group g = B pointer g, columns g D..
+  // tile (112.9 vs 112.7 us per video), so it stays unsliced -- the same k order as the large-batch kernel
+  row(SR_QKV, GEMM_NT, R, D, D, D, D, 3 * D, 0, 3, 0, D, 1, 0, 1);   // [Q|K|V] = X [Wq;Wk;Wv]^T: group g = B pointer g, columns g D..
   row(SR_OPROJ, GEMM_NT, R, D, D, D, D, D, D, 1, 0, 0, 0, 0, 8, true);      // Y0 = CTX Wo^T + X        (slabs -> LayerNorm kernel, which adds X)
   row(SR_K1, GEMM_NT, R, D, D, D, D, D, 0, 1, 0, 0, 0, 0, 8, true);         // Z = relu(Y1 W1^T + b1)   (slabs -> LayerNorm + head kernel: + b1, ReLU)
   row(SR_DY1, GEMM_NN, R, D, D, D, D, D, 0, 1, 0, 0, 0, 0, 8, true);        // dY1 = dZ W1              (slabs -> LayerNorm backward kernel)
-  row(SR_DCTX, GEMM_NN, R, D, D, D, D, D, 0, 1, 0, 0, 0, 0, smax_dctx);     // dCTX = dY0 Wo
+  row(SR_DCTX, GEMM_NN, R, D, D, D, D, D, 0, 1, 0, 0, 0, 0, 8);     // dCTX = dY0 Wo
   // dWo += dY0^T CTX and dW1 += dZ^T Y1 in ONE launch: group 1's operands are addressed relative to group 0's (dZ - dY0, Y1 - CTX: all four
   // are regions of the workspace), its output is C pointer 1
   row(SR_DWO1, GEMM_TN, D, D, R, D, D, D, 0, 2, 0, 0, 0, 1, 0);
@@ -1118,9 +1109,7 @@ static void sk_plan(int R, int D, int n_seq, const int32_t* off, const VasnetWs&
     // (per-video products: the request is the cap; vasnet_sk_setup_kernel / sk_slice_seq give a video with K = T_s frames min(4, T_s / 128)
     //  slices -- a function of that video alone)
     int S_req = 4;
-    int slab_cap = 8;
-    if (const char* e = SUMK_TUNE_ENV("SUMK_SK_SMAX")) if (e[0] && e[1] && e[2] && (e[3] == '1' || e[3] == '2' || e[3] == '4' || e[3] == '8')) slab_cap = e[3] - '0';   // (fourth digit: Q.K^T / dAlpha)
-    if (t == TB_S || t == TB_DP) for (S_req = slab_cap; S_req > 1; S_req >>= 1) {     // slab sets (K = D for every video): 1, 2, 4 or 8 slices
+    if (t == TB_S || t == TB_DP) for (S_req = 8; S_req > 1; S_req >>= 1) {     // slab sets (K = D for every video): 1, 2, 4 or 8 slices
       int S; sk_slice_seq(D, S_req, &kc, &S);          // (the rule vasnet_sk_setup_kernel applies to each video)
       if (S == S_req) break;
     }
@@ -1147,10 +1136,7 @@ static int geometry(int D, int n_seq, const int32_t* off, int training, int prec
   // with 128x128 for the (T x D) products and 8.28 with 128x128 for both -- bigger tiles waste more on ragged T and
   // under-fill the resident slots); long videos (mean T >= 1024, e.g. BASELINE config 5) take the 128x128 tile, whose
   // 2x2 register blocking halves the LDS traffic per MFMA.
-  static const char* env = SUMK_TUNE_ENV("SUMK_ATTN_CFG");   // tuning override "<cfg_s><cfg_pv>", e.g. "20"
-  const int cfg_auto = (G->R / n_seq >= 1024) ? 0 : 1;
-  G->cfg_s = cfg_auto; G->cfg_pv = cfg_auto;
-  if (env && env[0] >= '0' && env[0] <= '2' && env[1] >= '0' && env[1] <= '2') { G->cfg_s = env[0] - '0'; G->cfg_pv = env[1] - '0'; }
+  G->cfg_s = G->cfg_pv = (G->R / n_seq >= 1024) ? 0 : 1;
   G->t_max = 0;
   for (int s = 0; s < n_seq; ++s) G->t_max = std::max(G->t_max, off[s + 1] - off[s]);
   // A function of the batch and the options ONLY (never of workspace_bytes: forward and backward must take the same path -- the
@@ -1199,10 +1185,6 @@ enum { RP_QKV = 0, RP_DD = 1, RP_DX = 2, RP_QKV_W = 3, RP_DD_W = 4, RP_DX_W = 5 
 
 static void launch_setup(const Geometry& G, int D, int n_seq, const int32_t* off_dev, char* ws, hipStream_t stream) {     // ws: the TABLE base (workspace front, or the caller's table buffer)
   SetupArgs a;
-  a.fake_seq0 = 0;
-#ifdef SUMK_DIAG
-  if (getenv("SUMK_FAKE_SEQ0")) a.fake_seq0 = 1;    // wrong results by design: timing experiment (are the per-video GEMMs bound by where their operands come from?)
-#endif
   a.p16 = G.b16 ? 1 : 0;
   a.off = off_dev; a.n_seq = n_seq; a.D = D;
   a.row_seq = (int32_t*)(ws + G.L.row_seq);
