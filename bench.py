@@ -6,6 +6,10 @@ One "step" = one pass of the scorer over one packed batch of synthetic TVSum-sha
 N > 1: one process per GPU (torchrun), each rank scores its OWN 50 videos (sharded by video, no data-path
 collective) -> "scaling": "weak"; value = frames all ranks scored / max-over-ranks time.
 Prints ONE JSON line on rank 0.
+
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds
+everything else: the side legs (other precisions, models, sizes, training and single-video modes), the per-kernel GEMM pass, the
+MFMA rate probe and the CPU baseline with its parity check against the oracle port.
 """
 import argparse
 import ctypes as C
@@ -665,6 +669,9 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--videos", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: side legs, per-kernel pass, MFMA rate probe, CPU baseline and parity "
+                         "check.  --headline-only / --no-probe / --no-cpu-baseline trim a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--notes", action="store_true",
                     help="keep every leg's free-text note / provenance fields in the JSON line (about 2x its length).  Default: numbers only, so that "
@@ -696,6 +703,8 @@ def main():
                     help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32/float64, "
                          "64 MB at most: larger outputs as a fixed seeded sample) plus DIR/manifest.json; inputs are identical for identical arguments.  bench_outputs/ is git-ignored")
     args = ap.parse_args()
+    if not args.full:
+        args.headline_only = args.no_probe = args.no_cpu_baseline = True
     if args.fold_vo:
         args.headline_only = True          # (the side legs toggle fold_vo themselves)
 
@@ -1203,7 +1212,7 @@ def main():
                 out["cpu_baseline"] = dict(error=f"{type(e).__name__}: {e}"[:300])
         if not args.notes:
             out = _compact(out)
-            out["notes"] = "per-leg notes and provenance: python bench.py --notes (a copy of that line: profiles/r06_bench_default_line_notes.json)"
+            out["notes"] = "per-leg notes and provenance: python bench.py --full --notes (a copy of that line: profiles/r06_bench_default_line_notes.json)"
         print(json.dumps(out), flush=True)
         pd = out.get("parity_max_abs_diff_vs_port")
         if pd is not None and not pd < out["parity_gate"]:

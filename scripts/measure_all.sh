@@ -3,8 +3,8 @@
 # usage (through gpurun): bash scripts/measure_all.sh <tag>     -> gpurun_out/<tag>/
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 TAG=${1:-meas}; OUT=gpurun_out/$TAG; mkdir -p $OUT
-run() { name=$1; shift; timeout 300 python3 bench.py "$@" 2>/dev/null | tail -1 > $OUT/$name.json; }
-timeout 400 python3 bench.py 2>/dev/null | tail -1 > $OUT/headline.json
+run() { name=$1; shift; timeout 300 python3 bench.py --full "$@" 2>/dev/null | tail -1 > $OUT/$name.json; }
+timeout 400 python3 bench.py --full 2>/dev/null | tail -1 > $OUT/headline.json
 run vasnet_score_bf16x3 --no-cpu-baseline --precision bf16x3
 run vasnet_train --no-cpu-baseline --mode train
 run vasnet_train_bf16x3 --no-cpu-baseline --mode train --precision bf16x3

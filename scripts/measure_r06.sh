@@ -3,8 +3,8 @@
 # gpurun_out/r06_final (copied into profiles/ by hand).  PMC passes: scripts/pmc_pass.sh (separate call).
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 OUT=${OUT:-gpurun_out/r06_final}; mkdir -p $OUT
-timeout 900 python3 bench.py 2>$OUT/default.err | tail -1 > $OUT/bench_default_line.json
-timeout 900 python3 bench.py --notes 2>/dev/null | tail -1 > $OUT/bench_default_line_notes.json
+timeout 900 python3 bench.py --full 2>$OUT/default.err | tail -1 > $OUT/bench_default_line.json
+timeout 900 python3 bench.py --full --notes 2>/dev/null | tail -1 > $OUT/bench_default_line_notes.json
 timeout 600 python3 bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_driver_flags_line.json
 prof() {   # name, bench args...
   local name=$1; shift
@@ -31,7 +31,7 @@ prof transformer_score_bf16x6 --model transformer --precision bf16x6
 prof transformer_score_bf16x3 --model transformer --precision bf16x3
 prof vasnet_score_folded_bf16x6 --precision bf16x6 --fold-vo
 for args in "" "--precision bf16x6" "--precision bf16x3" "--mode train" "--mode train --precision bf16" "--model dsn" "--model dsn --precision bf16x6" "--model dsn --precision bf16x3" "--model dsn --mode train" "--model dsn --mode reinforce" "--model dsn --mode reinforce --precision bf16x6" "--model dsn --mode train --precision bf16x6" "--mode train --precision bf16x6" "--model slstm" "--model slstm --precision bf16x6" "--model slstm --precision bf16x3" "--model slstm --mode train --steps 5 --warmup 2" "--model transformer" "--model transformer --precision bf16x6" "--model transformer --precision bf16x3" "--precision bf16x6 --fold-vo" "--precision bf16x3 --fold-vo" "--workload stress --steps 3 --warmup 1" "--workload stress --precision bf16x6 --steps 3 --warmup 1" "--workload stress --precision bf16x3 --steps 3 --warmup 1" "--mode stream"; do
-  timeout 300 python3 bench.py --no-cpu-baseline --headline-only --steps 30 --warmup 5 $args 2>/dev/null | tail -1 | grep '^{' >> $OUT/bench_lines.jsonl
+  timeout 300 python3 bench.py --full --no-cpu-baseline --headline-only --steps 30 --warmup 5 $args 2>/dev/null | tail -1 | grep '^{' >> $OUT/bench_lines.jsonl
 done
 python3 scripts/probes/wide2_probe.py > $OUT/wide2_probe.txt 2>&1
 python3 scripts/probes/dsn_probe.py > $OUT/dsn_probe.txt 2>&1

@@ -3,8 +3,8 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r06b; mkdir -p $OUT
 if [ -z "$ONLY_PROF" ]; then
-timeout 900 python3 bench.py 2>$OUT/default.err | tail -1 > $OUT/bench_default_line.json
-timeout 900 python3 bench.py --notes 2>/dev/null | tail -1 > $OUT/bench_default_line_notes.json
+timeout 900 python3 bench.py --full 2>$OUT/default.err | tail -1 > $OUT/bench_default_line.json
+timeout 900 python3 bench.py --full --notes 2>/dev/null | tail -1 > $OUT/bench_default_line_notes.json
 timeout 600 python3 bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_driver_flags_line.json
 fi
 prof() {   # name, bench args...
@@ -20,6 +20,6 @@ prof vasnet_train_bf16 --mode train --precision bf16
 prof transformer_score_bf16x6 --model transformer --precision bf16x6
 prof transformer_score_bf16x3 --model transformer --precision bf16x3
 [ -n "$ONLY_PROF" ] || for args in "" "--precision bf16x6" "--precision bf16x3" "--precision bf16x6 --fold-vo" "--precision bf16x3 --fold-vo" "--mode train --precision bf16" "--mode train --precision bf16x6" "--model dsn --mode reinforce" "--model dsn --mode reinforce --precision bf16x6" "--model transformer --precision bf16x6" "--model transformer --precision bf16x3" "--workload stress --precision bf16x6 --steps 3 --warmup 1"; do
-  timeout 300 python3 bench.py --no-cpu-baseline --headline-only --steps 30 --warmup 5 $args 2>/dev/null | tail -1 | grep '^{' >> $OUT/bench_lines.jsonl
+  timeout 300 python3 bench.py --full --no-cpu-baseline --headline-only --steps 30 --warmup 5 $args 2>/dev/null | tail -1 | grep '^{' >> $OUT/bench_lines.jsonl
 done
 wc -c $OUT/bench_default_line.json; ls $OUT

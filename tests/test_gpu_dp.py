@@ -152,7 +152,7 @@ def test_bench_train_mode_two_ranks_on_one_gpu():
 
 
 def test_bench_multi_rank_control_flow_on_one_gpu():
-    """`bench.py` as the driver launches it for N > 1 (torch.distributed.run, one rank per GPU) -- here with both ranks on the
+    """`bench.py --full` launched for N > 1 (torch.distributed.run, one rank per GPU) -- here with both ranks on the
     one GPU of the test box over gloo (SUMK_BENCH_ONE_GPU=1): barriers, max-over-ranks timing, ONE JSON line from rank 0 whose
     value counts the frames of all ranks."""
     import json, os, socket, subprocess, sys
@@ -160,7 +160,7 @@ def test_bench_multi_rank_control_flow_on_one_gpu():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, SUMK_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--videos", "6"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--videos", "6", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -206,3 +206,27 @@ def test_bench_plain_python_gpus_2_spawns_its_own_ranks():
     assert out["n_gpus"] == 2 and out["ranks_seen"] == 2 and out["steps"] == 4
     per_rank = out["config"]["frames_per_step_per_gpu"]
     assert abs(out["value"] - 2 * per_rank * 4 / (out["ms_per_step"] * 4 / 1e3)) / out["value"] < 1e-3
+
+
+def test_bench_plain_run_carries_the_headline_only():
+    """A plain `bench.py --gpus 1` does set-up, warm-up, the timed steps and the line, nothing else: the headline fields, the roofline
+    of the timed QKV launches and the per-step device times are there; side legs, the per-kernel pass, the MFMA probe and the CPU
+    baseline with its parity check are `--full` only (the multi-rank test above runs that)."""
+    import json, subprocess, sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--videos", "6"],
+                       env=env, capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "frames scored/sec (T x 1024)" and out["unit"] == "frames/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 1
+    assert abs(out["value"] - out["config"]["frames_per_step_per_gpu"] * 3 / (out["ms_per_step"] * 3 / 1e3)) / out["value"] < 1e-3
+    assert out["roofline"]["frac"] > 0 and out["step_ms_device_events"]["median"] > 0
+    for k in ("cpu_baseline", "parity_max_abs_diff_vs_port", "mfma_sustained", "gemm_kernels", "bf16x3_mode", "bf16x6_mode",
+              "folded_vo_mode", "train_step_mode", "single_video_mode", "trainer_test_mode", "stream_mode", "dsn_score_mode",
+              "slstm_score_mode", "stress_mode", "transformer_score_mode"):
+        assert k not in out, k
+    assert "frac_of_sustained" not in out["roofline"]
