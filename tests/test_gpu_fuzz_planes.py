@@ -1,5 +1,5 @@
 """GPU: the plane paths against the exact-fp32 path on random ragged batches whose sizes sit on the kernels' boundaries -- frame counts around
-multiples of 32 / 64 / 192 / 256 (row tiles, plane pitch, strips), videos of 1 .. 321 frames (the attention on planes ends at 320), batches
+multiples of 32 / 64 / 192 / 256 (row tiles, plane pitch, strips), videos of 1 .. 320 frames (the attention on planes ends at 320) with one longer video (321 .. 1 536) in every fifth batch, batches
 below and above the XCD-map thresholds of the plane GEMM.  Scores must stay within the split arithmetics' distance from the fp32 scores and be
 repeatable bit for bit."""
 import numpy as np
@@ -23,7 +23,8 @@ def _batches(rng, n):
         k = int(rng.integers(1, 24))
         lens = [int(rng.choice(edge_T)) if rng.random() < 0.6 else int(rng.integers(1, 321)) for _ in range(k)]
         if i % 5 == 0:
-            lens[int(rng.integers(0, k))] = int(rng.choice([321, 400, 650]))          # one long video: the whole batch takes the fallback products
+            # one long video: the whole batch takes the fallback products (softmax forms switch at 256 / 512 / 1024; pw_long needs every T >= 1536)
+            lens[int(rng.integers(0, k))] = int(rng.choice([321, 400, 512, 513, 650, 1024, 1025, 1535, 1536]))
         target = int(rng.choice([0, 0, 256, 384, 576, 768, 3072, 3264]))               # pad the batch to a frame count on a tile boundary (+-1)
         if target and sum(lens) < target - 2:
             rest = target + int(rng.integers(-1, 2)) - sum(lens)

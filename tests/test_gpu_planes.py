@@ -286,9 +286,9 @@ def test_lstm_scorers_input_projection_on_planes(dev, kind):
             wpl = m.__dict__["_sumk_wpl"][1]
             h_pl, _ = kernels.bilstm_layer_forward(x, sb, p, prefix, 0, H, precision=prec, wplanes=wpl[0], dataset_input=True)
             h_old, _ = kernels.bilstm_layer_forward(x, sb, p, prefix, 0, H, precision=prec)
-            # (round 6: with planes at hand DSN's projection runs INSIDE the persistent recurrence -- csrc/lstm.hip, lstm_persist_proj_kernel --
-            #  whose k order differs from the GEMM's: equal to rounding there; tests/test_gpu_lstm.py holds that path to the plane GEMM and the oracle)
-            assert torch.equal(h_pl, h_old) if (prec == "bf16x6" and kind == "slstm") else float((h_pl - h_old).abs().max()) < 2e-6
+            # (both kinds run the plane GEMM in front of lstm_persist_kernel: the projection inside the recurrence,
+            #  lstm_persist_proj_kernel, is opt-in -- SUMK_LSTM_PROJ=1 -- and tests/test_gpu_lstm.py holds it to the plane GEMM and the oracle)
+            assert torch.equal(h_pl, h_old) if prec == "bf16x6" else float((h_pl - h_old).abs().max()) < 2e-6
         key0 = m.__dict__["_sumk_wpl"][0]
         dict(m.named_parameters())[prefix + "weight_ih_l0"].mul_(1.1)
         got2 = m.score_packed(x, lens)
@@ -300,8 +300,8 @@ def test_lstm_scorers_input_projection_on_planes(dev, kind):
 
 @pytest.mark.parametrize("precision", ["bf16x6", "bf16x3"])
 def test_plane_path_at_stress_size_and_batching_independence(dev, precision):
-    """(1) BASELINE config 5's shape on the plane path: ONE (T = 10 000, D = 2048) sequence -- T > 320, so the plane GEMMs run around the in-loop
-    attention kernels -- against the exact-fp32 HIP path (itself held to the oracle port at this size by
+    """(1) BASELINE config 5's shape on the plane path: ONE (T = 10 000, D = 2048) sequence -- T >= 1536, so the per-video products run on the
+    plane GEMM as well (csrc/vasnet.hip `pw_long`; R < Tn = 10 240: Q and K split per video, qk_direct = 0) -- against the exact-fp32 HIP path (itself held to the oracle port at this size by
     test_gpu_vasnet.py::test_vasnet_full_stress_size_vs_torch_port): scores within 1e-5 (bf16x6) / 1e-4 (bf16x3), logits within 5e-3 where they
     resolve.  (2) Batching independence of the whole plane path (GEMM row tiles mix videos, attention strips do not): videos scored together
     equal their separate scores bit for bit (each padded into a batch of the same plane-path eligibility)."""
