@@ -400,6 +400,24 @@ int sumk_sumsq(const float* v, int64_t n, float* out, void* workspace, void* str
 int sumk_cast_f32_bf16(const float* src, void* dst_bf16, int64_t n, void* stream);
 int sumk_cast_bf16_f32(const void* src_bf16, float* dst, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ logistic-regression step
+ * One optimiser step of the logistic baseline (logistic.py:67-88) in ONE launch (csrc/logistic.hip): for the packed rows x (n_rows, D),
+ * D % 4 == 0 and D <= 2048, and the min-max normalised target (n_rows,):
+ *   s_r = sigmoid(x_r . w + b),  mse_per_video[v] = mean_t (s - t)^2,  loss[0] = scale * sum_v mse_per_video[v]  (scale = 1 / videos of
+ *   the step: the step loss of sumk_segment_mse_mean_forward),  dW = sum_r g_r x_r,  db = sum_r g_r,
+ *   g_r = 2 (s_r - t_r) / T_v * scale * s_r (1 - s_r).
+ * The parameters are a flat bucket [w (D) | b | 3 floats of padding] (FlatAdam's layout for nn.Linear(D, 1)); flat_grad, exp_avg and
+ * exp_avg_sq have the same D + 4 floats, all 16-byte aligned.  apply_adam != 0: torch.optim.Adam(lr, betas, eps, weight_decay) applied
+ * to [w | b] with the arithmetic of sumk_adam_step_dev (state: its 16-byte device block; state[0] incremented), flat_grad not used.
+ * apply_adam == 0: [dW | db] is ADDED to flat_grad (.grad semantics) and nothing else changes -- the data-parallel form (all-reduce,
+ * then sumk_adam_step_dev).  scores: NULL or (n_rows,) for s.  Bit-deterministic (partials added in block order).  The call zeroes the
+ * first 16 bytes of the workspace with hipMemsetAsync before the launch (one launch at a time per workspace). */
+size_t sumk_logistic_step_workspace_bytes(int32_t n_rows, int32_t D);
+int sumk_logistic_step(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                       const float* target, float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq, int32_t* state,
+                       float lr, float beta1, float beta2, float eps, float weight_decay, float scale, int32_t apply_adam,
+                       float* loss, float* mse_per_video, float* scores, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ generic
  * fp32 MFMA GEMM (the dominant kernel), exposed for tests and for bench.py's roofline probe:
  * C(M,N) = A(M,K) * B^T  with B given as (N,K) row-major ("NT", both operands K-contiguous). */

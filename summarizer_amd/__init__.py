@@ -7,8 +7,9 @@ PyTorch is used for device memory, streams, autograd plumbing and torch.distribu
 __version__ = "0.1.0"
 
 # Reference dotted path -> module of this package that replaces it.  Only the hot-path modules are
-# aliased: `summarizer.models.rand / logistic`, `summarizer.utils.config / io` and `main.py` stay the reference's.  SumGAN-Att is
-# opt-in (OPT_IN_ALIASES, `install_as_reference(opt_in=("sumgan_att",))`): by default the reference's own module runs.
+# aliased: `summarizer.utils.config / io` and `main.py` stay the reference's.  SumGAN-Att and the two baselines (logistic regression,
+# random scores) are opt-in (OPT_IN_ALIASES, e.g. `install_as_reference(opt_in=("logistic", "random"))`): by default the reference's
+# own modules run.
 REFERENCE_ALIASES = {
     "summarizer.models.vasnet": "summarizer_amd.models.vasnet",            # VASNet, VASNetTrainer
     "summarizer.models.dsn": "summarizer_amd.models.dsn",                  # DSN, DSNTrainer
@@ -19,6 +20,8 @@ REFERENCE_ALIASES = {
 }
 OPT_IN_ALIASES = {
     "sumgan_att": ("summarizer.models.sumgan_att", "summarizer_amd.models.sumgan_att"),   # SumGANAtt, SumGANAttTrainer
+    "logistic": ("summarizer.models.logistic", "summarizer_amd.models.logistic"),         # LogisticRegression, LogisticRegressionTrainer
+    "random": ("summarizer.models.rand", "summarizer_amd.models.rand"),                   # Random, RandomTrainer
 }
 
 
@@ -28,7 +31,7 @@ def install_as_reference(opt_in=()):
     transformer, utils.eval, utils.knapsack -- resolve to this package, so `summarizer/utils/config.py` (HParameters, the
     `-m vasnet|dsn|sumgan|transformer` registry, config.py:68-77), `summarizer/main.py` and `benchmark.py` work unchanged.
     Call it before anything imports `summarizer.utils.config`; idempotent.  `opt_in` names further aliases of OPT_IN_ALIASES
-    (e.g. ("sumgan_att",)).  Returns the list of installed aliases."""
+    (e.g. ("sumgan_att",) or ("logistic", "random")).  Returns the list of installed aliases."""
     import importlib
     import sys
     unknown = [k for k in opt_in if k not in OPT_IN_ALIASES]

@@ -494,6 +494,48 @@ def sumsq(v, out=None):
     return out
 
 
+def logistic_step_workspace_bytes(n_rows, D):
+    return int(_lib.load().sumk_logistic_step_workspace_bytes(int(n_rows), int(D)))
+
+
+def logistic_step(x, sb, target, flat_param, flat_grad, exp_avg, exp_avg_sq, state, lr, betas=(0.9, 0.999), eps=1e-8,
+                  weight_decay=0.0, scale=1.0, apply_adam=True, want_scores=False, loss=None, mse=None, scores=None, ws=None):
+    """One optimiser step of the logistic baseline in one launch (sumk_logistic_step, csrc/logistic.hip) on FlatAdam-shaped buckets
+    ([w (D) | b | padding], D + 4 floats each).  apply_adam: torch's Adam applied in the kernel (state: FlatAdam._state, incremented);
+    otherwise [dW | db] is added to flat_grad.  Returns (loss (1,), mse per video (n_seq,), scores (n_rows,) or None), all on the device.
+    loss / mse / scores / ws: caller-owned outputs and workspace (a captured step keeps fixed addresses); allocated when None."""
+    lib = _lib.load()
+    _require_gpu(x, "logistic_step x"); _require_gpu(target, "logistic_step target")
+    n_rows, D = x.shape
+    if n_rows != sb.n_rows or target.shape != (sb.n_rows,):
+        raise SumkError(f"logistic_step: x {tuple(x.shape)} / target {tuple(target.shape)} do not fit {sb.n_rows} rows")
+    bufs = (flat_param, flat_grad) if not apply_adam else (flat_param, exp_avg, exp_avg_sq)
+    for t in bufs:
+        _require_gpu(t, "logistic_step bucket")
+        if t.numel() < D + 4 or not t.is_contiguous():
+            raise SumkError(f"logistic_step: flat buckets must be contiguous with >= D + 4 = {D + 4} floats, got {t.numel()}")
+    if apply_adam and (not state.is_cuda or state.dtype != torch.int32 or state.numel() < 4):
+        raise SumkError("logistic_step: state must be an int32 GPU tensor of 4 elements")
+    dev = x.device
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    if mse is None:
+        mse = torch.empty(sb.n_seq, dtype=torch.float32, device=dev)
+    if want_scores and scores is None:
+        scores = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    nb = lib.sumk_logistic_step_workspace_bytes(n_rows, D)
+    if ws is None:
+        ws = workspace(nb, dev)
+    rc = lib.sumk_logistic_step(_p(x.contiguous()), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, _p(target.contiguous()), _p(flat_param),
+                                _p(flat_grad), _p(exp_avg), _p(exp_avg_sq), _p(state), float(lr), float(betas[0]), float(betas[1]),
+                                float(eps), float(weight_decay), float(scale), 1 if apply_adam else 0, _p(loss), _p(mse), _p(scores),
+                                _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "sumk_logistic_step")
+    if apply_adam:
+        WEIGHTS_EPOCH[0] += 1
+    return loss, mse, scores
+
+
 def bilstm_layer_backward(x, h, dh, sb, params, grads, prefix, layer, H, ws, want_dx, precision=None, tail_event=None):
     """BPTT of one bidirectional layer; accumulates into grads[<prefix>{weight,bias}_{ih,hh}_l{layer}[_reverse]].
     tail_event (torch.cuda.Event, data-parallel trainers): recorded by the library once the biases' and the reverse direction's gradients

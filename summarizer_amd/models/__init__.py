@@ -56,7 +56,14 @@ class Trainer:
         raise Exception("train has not been implemented")
 
     def _device(self):
-        return next(self.model.parameters()).device
+        p = next(self.model.parameters(), None)
+        if p is not None:
+            return p.device
+        # a model without parameters (the random baseline): the device the configuration asks for
+        if self.hps.use_cuda:
+            dev = getattr(self.hps, "cuda_device", None)
+            return torch.device("cuda", torch.cuda.current_device() if dev is None else int(dev))
+        return torch.device("cpu")
 
     # ------------------------------------------------------------------ per-fold bookkeeping shared by every trainer
     @staticmethod
