@@ -1,6 +1,6 @@
 """Stock-PyTorch (CPU, fp32) functional port of the reference scorers.  TEST INFRASTRUCTURE ONLY.
 The SumGAN recurrences (lstm_stack_ref, dlstm_ref) and make_gru also run in float64: the high-precision oracles of
-tests/test_gpu_sumgan_full.py.
+tests/test_gpu_sumgan_full.py; transformer_ref likewise for tests/test_gpu_transformer_f64.py.
 
 This is (1) a second, autograd-capable checker for the HIP path (forward AND gradients), and
 (2) the `cpu_baseline` ("kind": "port") that bench.py times on the GPU node's host cores: it issues the
@@ -135,6 +135,67 @@ class TransformerPort(torch.nn.Module):
         if self.more_residuals:
             e = e + x
         return torch.sigmoid(self.k2(self.layer_norm(torch.relu(self.k1(e)))))
+
+
+def transformer_ref(xs, params, n_layers, n_heads, layer_eps=1e-5, final_eps=1e-5, more_residuals=False, pos=None, masks=None,
+                    relu_log=None):
+    """Functional restatement of the reference Transformer scorer (transformer.py:74-103 over stock post-norm
+    nn.TransformerEncoderLayer, FF = D) for a ragged list of videos, in the dtype of the inputs, with plain torch ops.
+    The high-precision oracle of tests/test_gpu_transformer_f64.py (run there in float64); differentiable in xs, params, pos.
+
+    xs: [(T_i, D)]; params: the model's state_dict keys (kernels.transformer_param_names).
+    pos: optional (table (n, D), rows (sum T_i,) int): row r of the packed batch adds table[rows[r]] (Transformer._pos).
+    masks: optional already-scaled keep-masks (0 or 1/(1-p)) as built by recipes.transformer_drop_masks:
+      {"attn": [[(heads, T_i, T_i) per video] per layer], "out" / "ff1" / "ff2": [(R, D) / (R, F) / (R, D) per layer],
+       "head": (R, D)} -- rows are PACKED rows, as the kernels index them.
+    relu_log: optional list; for every ReLU (linear1 of each layer, then k1) appends (pre-activation, sum_k |w_k a_k| + |b|) -- the scale of
+    the rounding error an fp32 evaluation of that pre-activation carries (how close to the kink a unit may lie before it can flip).
+    Returns (scores, logits): packed (R,) each."""
+    def relu(a, w, b):
+        pre = F.linear(a, w, b)
+        if relu_log is not None:
+            relu_log.append((pre.detach(), F.linear(a.detach().abs(), w.detach().abs(), b.detach().abs())))
+        return torch.relu(pre)
+    g = lambda k: params[k]
+    lens = [int(x.shape[0]) for x in xs]
+    x = torch.cat(list(xs))
+    if pos is not None:
+        x = x + pos[0][torch.as_tensor(pos[1], device=x.device).long()]
+    R, D = x.shape
+    dh = D // n_heads
+    h = x
+    for l in range(n_layers):
+        pre = f"transformer_encoder.layers.{l}."
+        mk = (lambda site: masks[site][l]) if masks is not None else (lambda site: None)
+        qkv = F.linear(h, g(pre + "self_attn.in_proj_weight"), g(pre + "self_attn.in_proj_bias"))
+        ctx, r0 = [], 0
+        for i, T in enumerate(lens):
+            q, k, v = (qkv[r0:r0 + T, j * D:(j + 1) * D].reshape(T, n_heads, dh).transpose(0, 1) for j in range(3))
+            a = torch.softmax(q @ k.transpose(1, 2) / math.sqrt(dh), dim=-1)             # (heads, T, T)
+            if masks is not None:
+                a = a * masks["attn"][l][i]
+            ctx.append((a @ v).transpose(0, 1).reshape(T, D))
+            r0 += T
+        o = F.linear(torch.cat(ctx), g(pre + "self_attn.out_proj.weight"), g(pre + "self_attn.out_proj.bias"))
+        if mk("out") is not None:
+            o = o * mk("out")
+        h = F.layer_norm(h + o, (D,), g(pre + "norm1.weight"), g(pre + "norm1.bias"), layer_eps)
+        f = relu(h, g(pre + "linear1.weight"), g(pre + "linear1.bias"))
+        if mk("ff1") is not None:
+            f = f * mk("ff1")
+        f = F.linear(f, g(pre + "linear2.weight"), g(pre + "linear2.bias"))
+        if mk("ff2") is not None:
+            f = f * mk("ff2")
+        h = F.layer_norm(h + f, (D,), g(pre + "norm2.weight"), g(pre + "norm2.bias"), layer_eps)
+    h = F.layer_norm(h, (D,), g("layer_norm.weight"), g("layer_norm.bias"), final_eps)       # encoder's final norm = the shared LN
+    if more_residuals:
+        h = h + x
+    z = relu(h, g("k1.weight"), g("k1.bias"))
+    if masks is not None:
+        z = z * masks["head"]
+    z = F.layer_norm(z, (D,), g("layer_norm.weight"), g("layer_norm.bias"), final_eps)        # the same LN again
+    u = F.linear(z, g("k2.weight"), g("k2.bias"))[:, 0]
+    return torch.sigmoid(u), u
 
 
 def make_gru(p, prefix, input_size, hidden_size, num_layers, dtype=torch.float32):

@@ -136,6 +136,37 @@ def vasnet_drop_masks(seed, p, lens, D):
     return out
 
 
+def transformer_drop_masks(seed, p_layer, p_head, lens, D, F, heads, n_layers):
+    """Scaled keep-masks (0 or 1/(1-p)) of every dropout site of the Transformer scorer's training forward for a packed batch, in the
+    layout oracle/torch_port.transformer_ref takes: {"attn": [[(heads, T, T) per video] per layer], "out": [(R, D)], "ff1": [(R, F)],
+    "ff2": [(R, D)] per layer, "head": (R, D)}, float32.  `seed` is sumk_tf_opts.seed.  Index conventions, as the kernels compute them
+    (`row` is always the PACKED row):
+      site 10*l + 0  attention probabilities   ((row*heads + h) << 20) | j    csrc/transformer.hip tf_softmax_kernel (wid = row*heads + h)
+      site 10*l + 1  out-proj (dropout1)       row * D + col                  csrc/gemm_device.h:22 (GEMM epilogue), tf_sa_fwd site + 1
+      site 10*l + 2  linear1 after ReLU        row * F + col                  same epilogue (EPI_BIAS_RELU), tf_ff_fwd site_a
+      site 10*l + 3  linear2 (dropout2)        row * D + col                  same epilogue (EPI_BIAS_RESIDUAL), tf_ff_fwd site_b
+      site 1000      after ReLU(k1)            row * D + col                  csrc/vasnet.hip launch_ln_rows (layernorm_kernel, drop.thr branch)"""
+    def scaled(p, site, idx):
+        sc = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+        return dropout_keep(seed, site, idx, p).astype(np.float32) * sc
+    R = int(sum(lens))
+    rows = np.arange(R, dtype=np.uint64)
+    flat = lambda N: rows[:, None] * np.uint64(N) + np.arange(N, dtype=np.uint64)[None, :]
+    out = {"attn": [], "out": [], "ff1": [], "ff2": []}
+    for l in range(n_layers):
+        site, per_video, r0 = 10 * l, [], 0
+        for T in lens:
+            wid = (rows[r0:r0 + T][None, :] * np.uint64(heads) + np.arange(heads, dtype=np.uint64)[:, None])      # (heads, T)
+            per_video.append(scaled(p_layer, site, (wid[:, :, None] << np.uint64(20)) | np.arange(T, dtype=np.uint64)[None, None, :]))
+            r0 += T
+        out["attn"].append(per_video)
+        out["out"].append(scaled(p_layer, site + 1, flat(D)))
+        out["ff1"].append(scaled(p_layer, site + 2, flat(F)))
+        out["ff2"].append(scaled(p_layer, site + 3, flat(D)))
+    out["head"] = scaled(p_head, 1000, flat(D))
+    return out
+
+
 class DetRandom:
     """Counter-based stand-in for torch.randn_like / torch.rand, used to run the reference's SumGAN trainer and the HIP one
     on the SAME draws (their generators -- torch CPU vs device -- cannot be matched): draw n comes from

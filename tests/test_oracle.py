@@ -284,3 +284,111 @@ def test_make_gru_float64():
     assert all(v.dtype == torch.float64 for v in g64.parameters())
     x = torch.randn(7, 1, 6)
     torch.testing.assert_close(g64(x.double())[0].float(), m(x)[0], rtol=0, atol=1e-6)
+
+
+def _tf_params(w, dtype=torch.float64):
+    return {k: torch.from_numpy(np.asarray(v)).to(dtype) for k, v in w.items()}
+
+
+def test_transformer_ref_vs_reference_goldens():
+    """torch_port.transformer_ref (float64, ragged list API) against the REAL reference: every transformer_small config (B > 1 and
+    the 'simple' table included) at the file's tolerance; the transformer_train step's loss and every grad0 entry through float64
+    autograd (relative to the tensor's largest entry; the key-bias slice of in_proj_bias is rounding noise of a zero gradient in
+    the golden, so it is compared against the whole vector's scale like every other entry)."""
+    g = load_golden("transformer_small")
+    meta = js(g["meta"])
+    assert set(meta) == {"small", "small_res", "small_pos"}
+    for name, kw in meta.items():
+        w = {k.split("/w/")[1]: g[k] for k in g.files if k.startswith(f"{name}/w/")}
+        p = _tf_params(w)
+        for c in _cases(g, name):
+            x = torch.from_numpy(g[f"{name}/x/{c}"]).double()
+            T, B, D = x.shape
+            pos = (p["pos_embed.weight"], np.tile(np.arange(T), B)) if kw.get("max_length") else None
+            s, u = torch_port.transformer_ref([x[:, b] for b in range(B)], p, kw["encoder_layers"], kw["attention_heads"],
+                                              final_eps=kw.get("epsilon", 1e-5), more_residuals=kw.get("more_residuals", False), pos=pos)
+            assert torch.allclose(torch.sigmoid(u), s)
+            y = s.view(B, T).t().unsqueeze(-1).numpy()
+            np.testing.assert_allclose(y, g[f"{name}/y/{c}"], atol=TOL, rtol=0, err_msg=f"{name} {c}")
+    g = load_golden("transformer_train")
+    for tag, kw in {"tf": dict(layers=2, heads=4), "tf_res": dict(layers=1, heads=8, more_residuals=True)}.items():
+        w = {k.split("/w/")[1]: g[k] for k in g.files if k.startswith(f"{tag}/w/")}
+        p = {k: v.requires_grad_(True) for k, v in _tf_params(w).items()}
+        x = torch.from_numpy(g["x"]).double()[:, 0]
+        s, _ = torch_port.transformer_ref([x], p, kw["layers"], kw["heads"], more_residuals=kw.get("more_residuals", False))
+        loss = ((s - torch.from_numpy(g["target"]).double().view(-1)) ** 2).mean()
+        loss.backward()
+        np.testing.assert_allclose(loss.item(), g[f"{tag}/loss0"], rtol=2e-5)
+        keys = [k.split("/grad0/")[1] for k in g.files if k.startswith(f"{tag}/grad0/")]
+        assert len(keys) == 12 * kw["layers"] + 6, keys
+        for k in keys:
+            ref = g[f"{tag}/grad0/{k}"]
+            got = p[k].grad.numpy()
+            assert np.abs(got - ref).max() <= 1e-4 * np.abs(ref).max(), (tag, k, np.abs(got - ref).max(), np.abs(ref).max())
+
+
+def test_transformer_ref_vs_transformer_port_ragged():
+    """transformer_ref against the nn.TransformerEncoder-based TransformerPort, both float64, dropout off: a ragged list (each video
+    through the port on its own), more_residuals and a 'simple' positional table (row t of every video).  Scores, and the gradients of
+    every parameter, of the table and of x."""
+    D, L, H = 128, 2, 4
+    lens = [1, 5, 33, 64]
+    w = R.transformer_weights(D, L, 77, max_length=64)
+    port = torch_port.TransformerPort(D, L, H, max_length=64, more_residuals=True).double()
+    port.load_state_dict(_tf_params(w))
+    port.eval()
+    rng = np.random.default_rng(3)
+    xs = [torch.from_numpy(rng.standard_normal((T, D)) * 0.5).requires_grad_(True) for T in lens]
+    cw = torch.from_numpy(rng.standard_normal(sum(lens)))
+    p = {k: v.detach().clone().requires_grad_(True) for k, v in port.state_dict().items()}
+    rows = np.concatenate([np.arange(T) for T in lens])
+    s, u = torch_port.transformer_ref(xs, p, L, H, more_residuals=True, pos=(p["pos_embed.weight"], rows))
+    (s * cw).sum().backward()
+    xs2 = [x.detach().clone().requires_grad_(True) for x in xs]
+    s2 = torch.cat([port(x.unsqueeze(1))[:, 0, 0] for x in xs2])
+    (s2 * cw).sum().backward()
+    assert float((s - s2).detach().abs().max()) < 1e-12
+    named = dict(port.named_parameters())
+    for k, v in named.items():
+        if k.startswith("transformer_encoder.norm."):
+            continue                                            # the shared LN: the same Parameter as layer_norm.*
+        ref = v.grad
+        assert ref is not None and float((p[k].grad - ref).abs().max()) <= 1e-10 * max(float(ref.abs().max()), 1e-30), k
+    for a, b in zip(xs, xs2):
+        assert float((a.grad - b.grad).abs().max()) <= 1e-10 * float(b.grad.abs().max())
+
+
+def test_transformer_drop_masks_recipe():
+    """recipes.transformer_drop_masks: keep fraction of every site within 5 sigma of 1 - p (binomial) at p = 0.1 and 0.5, kept entries
+    scaled by 1 / (1 - p), shapes as transformer_ref takes them, and no two sites (or layers) with the same mask."""
+    lens, D, Fd, H, L = [1, 37, 200], 64, 96, 4, 2
+    for p in (0.1, 0.5):
+        m = R.transformer_drop_masks(12345, p, p, lens, D, Fd, H, L)
+        sc = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+        flat = {}
+        for l in range(L):
+            assert [a.shape for a in m["attn"][l]] == [(H, T, T) for T in lens]
+            flat[f"attn{l}"] = np.concatenate([a.ravel() for a in m["attn"][l]])
+            for k, N in (("out", D), ("ff1", Fd), ("ff2", D)):
+                assert m[k][l].shape == (sum(lens), N)
+                flat[f"{k}{l}"] = m[k][l].ravel()
+        assert m["head"].shape == (sum(lens), D)
+        flat["head"] = m["head"].ravel()
+        for k, a in flat.items():
+            assert set(np.unique(a)) <= {np.float32(0), sc}, k
+            frac = float((a != 0).mean())
+            assert abs(frac - (1 - p)) <= 5 * np.sqrt(p * (1 - p) / a.size), (k, p, frac)
+        ks = sorted(flat)
+        for i, a in enumerate(ks):
+            for b in ks[i + 1:]:
+                n = min(flat[a].size, flat[b].size)
+                assert not np.array_equal(flat[a][:n] != 0, flat[b][:n] != 0), (a, b)
+    # seed and index conventions: another seed draws other masks; the attention index of (row, h, j) is ((row*heads + h) << 20) | j
+    m0 = R.transformer_drop_masks(1, 0.5, 0.5, lens, D, Fd, H, L)
+    m1 = R.transformer_drop_masks(2, 0.5, 0.5, lens, D, Fd, H, L)
+    assert not np.array_equal(m0["head"], m1["head"])
+    row, h, j = 1 + 5, 3, 7                                   # video 1, frame 5
+    keep = R.dropout_keep(1, 10, np.array([((row * H + h) << 20) | j], dtype=np.uint64), 0.5)[0]
+    assert (m0["attn"][1][1][h, 5, j] != 0) == keep
+    keep = R.dropout_keep(1, 12, np.array([row * Fd + 9], dtype=np.uint64), 0.5)[0]
+    assert (m0["ff1"][1][row, 9] != 0) == keep
