@@ -373,9 +373,10 @@ int sumk_segment_mse_mean_backward(const float* scores, const float* target, con
  * torch.optim.Adam(lr, betas, eps, weight_decay) exactly as the trainers construct it (vasnet.py:181,
  * dsn.py:70-73): L2 weight decay folded into the gradient, bias-corrected moments.  One flat launch over
  * n elements; `step` is the 1-based step count.  grad_scale multiplies the gradient first (used for
- * clip_grad_norm_, dsn.py:145, and for the 1/world_size of a data-parallel average). */
+ * clip_grad_norm_, dsn.py:145, and for the 1/world_size of a data-parallel average).  The betas are doubles: torch takes 1 - beta in
+ * double before it rounds to fp32, and 1 - (float)0.999 is 1.3e-5 relative away from (float)0.001. */
 int sumk_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                   float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+                   float lr, double beta1, double beta2, float eps, float weight_decay, int32_t step,
                    float grad_scale, void* stream);
 /* The same step with NOTHING on the host: `state` is a 16-byte device block the caller zeroes once -- state[0] (int32) counts
  * the optimiser steps and is incremented by the call, state[1..3] are scratch -- so the bias correction follows a counter that
@@ -383,12 +384,12 @@ int sumk_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
  * given, torch.nn.utils.clip_grad_norm_(params, max_norm) (dsn.py:145) is folded in without reading the norm back.  No host
  * synchronisation, captures into a HIP graph and replays with the right step count.  Same arithmetic as sumk_adam_step. */
 int sumk_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                       float lr, float beta1, float beta2, float eps, float weight_decay, int32_t* state,
+                       float lr, double beta1, double beta2, float eps, float weight_decay, int32_t* state,
                        float grad_scale, const float* sumsq, float max_norm, void* stream);
 /* The same, and `grad` is left ZERO: the next step's optimizer.zero_grad() (vasnet.py:210, dsn.py:143) folded into the pass that reads
  * the gradient last -- one 21 MB fill launch less per step of a captured (HIP graph) training step. */
 int sumk_adam_step_dev_zero_grad(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                                 float lr, float beta1, float beta2, float eps, float weight_decay, int32_t* state,
+                                 float lr, double beta1, double beta2, float eps, float weight_decay, int32_t* state,
                                  float grad_scale, const float* sumsq, float max_norm, void* stream);
 /* out[0] += sum of squares of a flat buffer (for clip_grad_norm_), deterministic two-stage reduction.
  * workspace: sumk_sumsq_workspace_bytes() bytes of device scratch. */
@@ -415,7 +416,7 @@ int sumk_cast_bf16_f32(const void* src_bf16, float* dst, int64_t n, void* stream
 size_t sumk_logistic_step_workspace_bytes(int32_t n_rows, int32_t D);
 int sumk_logistic_step(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
                        const float* target, float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq, int32_t* state,
-                       float lr, float beta1, float beta2, float eps, float weight_decay, float scale, int32_t apply_adam,
+                       float lr, double beta1, double beta2, float eps, float weight_decay, float scale, int32_t apply_adam,
                        float* loss, float* mse_per_video, float* scores, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ generic

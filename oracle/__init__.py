@@ -11,6 +11,8 @@ Nothing under summarizer_amd/ imports it; the product path fails loudly when the
 Pinning status (see DESIGN.md section "Oracle"):
   * vasnet_np / lstm_np / reward_np / eval_np / torch_port : PINNED against outputs of the real reference,
     imported read-only in the build container (tests/golden/make_golden.py -> tests/golden/*.npz).
+  * optim_np : float64 restatement of torch.optim.Adam + clip_grad_norm_ over a flat vector; pinned to stock torch run in
+    float64 (tests/test_oracle.py), the reference of tests/test_gpu_optim.py.
   * knapsack_np : PARITY UNPINNED.  The reference delegates to ortools==7.5.7466 (not vendored, not
     installable here) and no reference test holds a knapsack vector.  The DP here restates the published
     OR-tools KnapsackDynamicProgrammingSolver from memory; only the optimal VALUE is checked (brute force).

@@ -179,15 +179,15 @@ _SIGS = {
     "sumk_segment_mse_backward": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, c_i32p, c_f32p, C.c_void_p]),
     "sumk_segment_mse_mean_forward": (C.c_int, [c_f32p, c_f32p, C.c_int32, c_i32p, C.c_float, c_f32p, c_f32p, C.c_void_p, C.c_void_p]),
     "sumk_segment_mse_mean_backward": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_float, C.c_int32, c_i32p, c_f32p, C.c_void_p]),
-    "sumk_adam_step": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_float, C.c_float, C.c_float,
+    "sumk_adam_step": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_float, C.c_double, C.c_double,
                                  C.c_float, C.c_float, C.c_int32, C.c_float, C.c_void_p]),
-    "sumk_adam_step_dev": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_float, C.c_float, C.c_float,
+    "sumk_adam_step_dev": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_float, C.c_double, C.c_double,
                                      C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p]),
-    "sumk_adam_step_dev_zero_grad": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_float, C.c_float, C.c_float,
+    "sumk_adam_step_dev_zero_grad": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_float, C.c_double, C.c_double,
                                                C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p]),
     "sumk_logistic_step_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "sumk_logistic_step": (C.c_int, [c_f32p, C.c_int32, C.c_int32, HOST_I32P, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p,
-                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, c_f32p, c_f32p, c_f32p,
+                                     C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_float, C.c_int32, c_f32p, c_f32p, c_f32p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
     "sumk_gemm_splitk_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "sumk_gemm_splitk": (C.c_int, [C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

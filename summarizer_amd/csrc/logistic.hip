@@ -61,7 +61,8 @@ LgWs lg_carve(int n_rows, int D) {
 struct LgArgs {
   const float* x; const float* target; const int32_t* off; int32_t n_seq, n_rows, D;
   float* param; float* grad; float* m; float* v; int32_t* state;
-  float lr, b1, b2, eps, wd, scale, grad_scale;
+  float lr, b1, b2, omb1, omb2, eps, wd, scale, grad_scale;   // omb = 1 - beta, taken in double (optim.hip)
+  double b1d, b2d;
   float* loss; float* mse; float* scores;
   unsigned* ticket; float* slab; float* err;
   int32_t apply_adam;
@@ -172,8 +173,8 @@ __global__ __launch_bounds__(LG_THREADS) void logistic_step_kernel(LgArgs a) {
     if (tid == 0) {
       const int step = a.state[0] + 1;
       a.state[0] = step;
-      const double bc1 = 1.0 - pow((double)a.b1, (double)step);
-      const double bc2 = 1.0 - pow((double)a.b2, (double)step);
+      const double bc1 = 1.0 - pow(a.b1d, (double)step);
+      const double bc2 = 1.0 - pow(a.b2d, (double)step);
       float* f = reinterpret_cast<float*>(a.state);
       f[1] = (float)((double)a.lr / bc1);
       f[2] = (float)(1.0 / sqrt(bc2));
@@ -206,12 +207,12 @@ __global__ __launch_bounds__(LG_THREADS) void logistic_step_kernel(LgArgs a) {
     // adam_kernel's update (optim.hip), the same expression per element
     float4 pp = reinterpret_cast<float4*>(a.param)[c], gg = g;
     float4 mm = reinterpret_cast<float4*>(a.m)[c], vv = reinterpret_cast<float4*>(a.v)[c];
-    const float b1 = a.b1, b2 = a.b2, eps = a.eps, wd = a.wd, grad_scale = a.grad_scale;
+    const float b1 = a.b1, b2 = a.b2, omb1 = a.omb1, omb2 = a.omb2, eps = a.eps, wd = a.wd, grad_scale = a.grad_scale;
 #define LG_ADAM1(c)                                                     \
     {                                                                   \
       float gr = gg.c * grad_scale + wd * pp.c;                         \
-      mm.c = b1 * mm.c + (1.f - b1) * gr;                               \
-      vv.c = b2 * vv.c + (1.f - b2) * gr * gr;                          \
+      mm.c = b1 * mm.c + omb1 * gr;                                     \
+      vv.c = b2 * vv.c + omb2 * gr * gr;                                \
       pp.c -= step_size * (mm.c / (sqrtf(vv.c) * inv_sqrt_bc2 + eps));  \
     }
     LG_ADAM1(x) LG_ADAM1(y) LG_ADAM1(z) LG_ADAM1(w)
@@ -253,7 +254,7 @@ extern "C" size_t sumk_logistic_step_workspace_bytes(int32_t n_rows, int32_t D) 
 
 extern "C" int sumk_logistic_step(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
                                   const float* target, float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq,
-                                  int32_t* state, float lr, float beta1, float beta2, float eps, float weight_decay, float scale,
+                                  int32_t* state, float lr, double beta1, double beta2, float eps, float weight_decay, float scale,
                                   int32_t apply_adam, float* loss, float* mse_per_video, float* scores, void* workspace,
                                   size_t workspace_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
@@ -285,7 +286,7 @@ extern "C" int sumk_logistic_step(const float* x, int32_t D, int32_t n_seq, cons
   LgArgs a;
   a.x = x; a.target = target; a.off = seq_off_dev; a.n_seq = n_seq; a.n_rows = n_rows; a.D = D;
   a.param = flat_param; a.grad = flat_grad; a.m = exp_avg; a.v = exp_avg_sq; a.state = state;
-  a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.scale = scale; a.grad_scale = 1.f;
+  a.lr = lr; a.b1 = (float)beta1; a.b2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2); a.b1d = beta1; a.b2d = beta2; a.eps = eps; a.wd = weight_decay; a.scale = scale; a.grad_scale = 1.f;
   a.loss = loss; a.mse = mse_per_video; a.scores = scores;
   a.ticket = (unsigned*)ws; a.slab = (float*)(ws + L.slab); a.err = (float*)(ws + L.err);
   a.apply_adam = apply_adam ? 1 : 0;

@@ -8,6 +8,9 @@
 namespace sumk {
 
 // torch (non-amsgrad, maximize=False):  g = grad*grad_scale + wd*p ; m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g*g
+// 1 - b1 and 1 - b2 (omb1, omb2) are taken in DOUBLE from the double betas on the host and rounded once, as torch does with its python
+// floats: `1.f - b2` on the fp32 beta cancels (1 - 0.999f = 0.00099998713, 1.3e-5 relative away from 0.001 -- every exp_avg_sq was that
+// much too small; tests/test_gpu_optim.py).
 //   p -= (lr / (1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
 // dyn != nullptr: step size, bias correction and gradient scale come from the device block adam_prep_kernel wrote (the
 // sync-free / graph-capturable form: the step counter and the clip coefficient never visit the host).
@@ -16,8 +19,8 @@ namespace sumk {
 // vasnet.py:210-212, leaves the same state).
 template <bool ZERO>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
-                                                   float wd, float step_size, float inv_sqrt_bc2, float grad_scale,
+                                                   float* __restrict__ v, int64_t n, float lr, float b1, float b2, float omb1, float omb2,
+                                                   float eps, float wd, float step_size, float inv_sqrt_bc2, float grad_scale,
                                                    const float* __restrict__ dyn) {
   if (dyn != nullptr) { step_size = dyn[1]; inv_sqrt_bc2 = dyn[2]; grad_scale = dyn[3]; }
   const int64_t n4 = n >> 2;
@@ -28,8 +31,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
 #define ADAM1(c)                                                        \
     {                                                                   \
       float gr = gg.c * grad_scale + wd * pp.c;                         \
-      mm.c = b1 * mm.c + (1.f - b1) * gr;                               \
-      vv.c = b2 * vv.c + (1.f - b2) * gr * gr;                          \
+      mm.c = b1 * mm.c + omb1 * gr;                                     \
+      vv.c = b2 * vv.c + omb2 * gr * gr;                                \
       pp.c -= step_size * (mm.c / (sqrtf(vv.c) * inv_sqrt_bc2 + eps));  \
     }
     ADAM1(x) ADAM1(y) ADAM1(z) ADAM1(w)
@@ -39,7 +42,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
   // tail (n not a multiple of 4)
   for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float gr = g[i] * grad_scale + wd * p[i];
-    float mi = b1 * m[i] + (1.f - b1) * gr, vi = b2 * v[i] + (1.f - b2) * gr * gr;
+    float mi = b1 * m[i] + omb1 * gr, vi = b2 * v[i] + omb2 * gr * gr;
     m[i] = mi; v[i] = vi;
     p[i] -= step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
     if constexpr (ZERO) g[i] = 0.f;
@@ -49,12 +52,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
 // state[0] (int32): optimiser steps taken so far, incremented here; state[1..3] (float): lr / (1 - b1^t), 1 / sqrt(1 - b2^t) and
 // the effective gradient scale = grad_scale * min(1, max_norm / (sqrt(sumsq) * grad_scale + 1e-6)) -- torch's clip_grad_norm_ --
 // all in double like the host path of sumk_adam_step.
-__global__ void adam_prep_kernel(int32_t* state, float lr, float b1, float b2, float grad_scale, const float* sumsq, float max_norm) {
+__global__ void adam_prep_kernel(int32_t* state, float lr, double b1, double b2, float grad_scale, const float* sumsq, float max_norm) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const int step = state[0] + 1;
   state[0] = step;
-  const double bc1 = 1.0 - pow((double)b1, (double)step);
-  const double bc2 = 1.0 - pow((double)b2, (double)step);
+  const double bc1 = 1.0 - pow(b1, (double)step);
+  const double bc2 = 1.0 - pow(b2, (double)step);
   float* f = reinterpret_cast<float*>(state);
   f[1] = (float)((double)lr / bc1);
   f[2] = (float)(1.0 / sqrt(bc2));
@@ -126,23 +129,23 @@ extern "C" int sumk_cast_bf16_f32(const void* src_bf16, float* dst, int64_t n, v
 }
 
 extern "C" int sumk_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                              float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale,
+                              double beta1, double beta2, float eps, float weight_decay, int32_t step, float grad_scale,
                               void* stream) {
   SUMK_ARG(param && grad && exp_avg && exp_avg_sq, "adam: null pointer");
   SUMK_ARG(n > 0 && step >= 1, "adam: n=%lld step=%d", (long long)n, step);
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
   const float step_size = (float)((double)lr / bc1);
   const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   int blocks = (int)std::min<int64_t>((n / 4 + 255) / 256 + 1, 2048);
   hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, const_cast<float*>(grad), exp_avg, exp_avg_sq, n, lr,
-                     beta1, beta2, eps, weight_decay, step_size, inv_sqrt_bc2, grad_scale, (const float*)nullptr);
+                     (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, step_size, inv_sqrt_bc2, grad_scale, (const float*)nullptr);
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
 }
 
 static int adam_step_dev_impl(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                             float beta1, float beta2, float eps, float weight_decay, int32_t* state, float grad_scale,
+                             double beta1, double beta2, float eps, float weight_decay, int32_t* state, float grad_scale,
                              const float* sumsq, float max_norm, void* stream, bool zero_grad) {
   SUMK_ARG(param && grad && exp_avg && exp_avg_sq && state, "adam_dev: null pointer");
   SUMK_ARG(n > 0, "adam_dev: n=%lld", (long long)n);
@@ -150,20 +153,20 @@ static int adam_step_dev_impl(float* param, float* grad, float* exp_avg, float* 
   hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, lr, beta1, beta2, grad_scale, sumsq, max_norm);
   int blocks = (int)std::min<int64_t>((n / 4 + 255) / 256 + 1, 2048);
   if (zero_grad) hipLaunchKernelGGL(adam_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,
-                                    beta1, beta2, eps, weight_decay, 0.f, 0.f, 0.f, (const float*)state);
+                                    (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, 0.f, 0.f, 0.f, (const float*)state);
   else hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,
-                          beta1, beta2, eps, weight_decay, 0.f, 0.f, 0.f, (const float*)state);
+                          (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, 0.f, 0.f, 0.f, (const float*)state);
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
 }
 extern "C" int sumk_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                                  float beta1, float beta2, float eps, float weight_decay, int32_t* state, float grad_scale,
+                                  double beta1, double beta2, float eps, float weight_decay, int32_t* state, float grad_scale,
                                   const float* sumsq, float max_norm, void* stream) {
   return adam_step_dev_impl(param, const_cast<float*>(grad), exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, state, grad_scale, sumsq,
                             max_norm, stream, false);
 }
 extern "C" int sumk_adam_step_dev_zero_grad(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                                            float beta1, float beta2, float eps, float weight_decay, int32_t* state, float grad_scale,
+                                            double beta1, double beta2, float eps, float weight_decay, int32_t* state, float grad_scale,
                                             const float* sumsq, float max_norm, void* stream) {
   return adam_step_dev_impl(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, state, grad_scale, sumsq, max_norm, stream, true);
 }

@@ -108,6 +108,124 @@ def synthetic_video(T, seed, n_users=15, D=None):
     return d
 
 
+# ---- evaluation-tail geometries the plain synthetic_video never has (tests/test_oracle.py shows each edge is present; tests/test_gpu_evaltail.py
+# runs them on the device).  Every edge keeps picks ascending and at most 4096 of them: the videos stay eligible for the device tail.
+EVAL_EDGES = ("picks_from_7", "picks_from_15", "last_pick_is_n_frames", "repeated_picks", "one_more_interval", "cps_start_below_0",
+              "cps_end_past_video", "segment_lengths", "pick_spacing_2", "n_frames_1", "n_frames_5", "n_frames_9")
+EDGE_SEGMENT_LENGTHS = (1, 7, 8, 9, 128, 129, 257, 1100)      # numpy's pairwise sum: < 8 plain loop, <= 128 one block, above: split once, ... , split 4 times
+
+
+def edge_video(v, edge):
+    """`v` (a synthetic_video dict, or the result of an earlier edge_video: edges combine) with one named edge of the evaluation geometry
+    applied.  The result carries "n_steps", the number of scores the video is evaluated with; annotator data is redrawn for the new length."""
+    import zlib
+    if edge not in EVAL_EDGES:
+        raise KeyError(edge)
+    picks = np.asarray(v["picks"]).astype(np.int64).copy()
+    cps = np.asarray(v["change_points"]).astype(np.int64).copy()
+    n_frames, n_steps = int(v["n_frames"]), int(v.get("n_steps", len(picks)))
+    n_users = v["user_summary"].shape[0]
+    rng = np.random.default_rng([zlib.crc32(edge.encode()), n_frames, n_users])
+    step = int(picks[-1] - picks[-2]) if len(picks) > 1 and picks[-1] > picks[-2] else 15
+    if edge in ("picks_from_7", "picks_from_15"):                    # frames in front of the first pick: covered by no interval, value 0
+        k = 7 if edge == "picks_from_7" else 15
+        picks += k; n_frames += k; cps += k; cps[0, 0] = 0
+    elif edge == "last_pick_is_n_frames":                            # no sentinel appended (eval.py:27-28): n_picks - 1 intervals
+        n_frames = int(picks[-1]) + step
+        picks = np.append(picks, n_frames)
+        cps[-1, 1] = n_frames - 1
+    elif edge == "repeated_picks":                                   # empty intervals: a run of 2 and a run of 3 equal picks
+        assert len(picks) >= 10
+        picks[3] = picks[2]
+        picks[8] = picks[9] = picks[7]
+    elif edge == "one_more_interval":                                # n_int == n_steps + 1: the last interval has no score and takes 0 (eval.py:31-32)
+        picks = np.append(picks, picks[-1] + step)
+        n_frames = int(picks[-1]) + 9
+        cps[-1, 1] = n_frames - 1
+    elif edge == "cps_start_below_0":
+        cps[0, 0] = -5
+    elif edge == "cps_end_past_video":
+        cps[-1, 1] = n_frames + 10
+    elif edge == "segment_lengths":
+        assert n_frames > sum(EDGE_SEGMENT_LENGTHS) + 16
+        starts = np.concatenate([[0], np.cumsum(EDGE_SEGMENT_LENGTHS)])
+        ends = np.concatenate([starts[1:] - 1, [n_frames - 1]])
+        cps = np.stack([starts, ends], axis=1)
+    elif edge == "pick_spacing_2":                                   # thousands of scoring steps in a video of ~2 x n_steps frames
+        picks = 2 * np.arange(n_steps, dtype=np.int64)
+        n_frames = 2 * n_steps + 1
+        cuts = np.sort(rng.choice(np.arange(8, n_frames - 8), size=max(1, n_frames // 100) - 1, replace=False))
+        cps = np.stack([np.concatenate([[0], cuts]), np.concatenate([cuts - 1, [n_frames - 1]])], axis=1)
+    else:                                                            # n_frames_1 / _5 / _9: fewer frames than a thread block, a wave, a chunk
+        n_frames = int(edge.rsplit("_", 1)[1])
+        picks = np.arange(0, n_frames, 4, dtype=np.int64)
+        n_steps = len(picks)
+        cps = np.array([[0, n_frames - 1]], dtype=np.int64)
+    lo, hi = np.clip(cps[:, 0], 0, n_frames), np.clip(cps[:, 1] + 1, 0, n_frames)
+    nfps = np.maximum(hi - lo, 0).astype(np.int32)
+    user_summary = (rng.random((n_users, n_frames)) < 0.15).astype(np.float32)
+    coarse = rng.random((n_users, (n_frames + 14) // 15)).astype(np.float32)
+    user_scores = np.repeat(coarse, 15, axis=1)[:, :n_frames].copy()
+    if n_frames < 30:                                                # (one or two constant stretches would leave the annotators' ranks all tied)
+        user_scores = rng.random((n_users, n_frames)).astype(np.float32)
+    return dict(n_frames=n_frames, picks=picks.astype(np.int32), change_points=cps.astype(np.int32), n_frame_per_seg=nfps,
+                user_summary=user_summary, user_scores=user_scores, n_steps=n_steps)
+
+
+def edge_scores(kind, n_steps, seed):
+    """Step scores for the evaluation edges: "random" in [0, 1); "zeros": every third score exactly 0.0 (ties with frames no interval covers);
+    "negative": signed scores with some +0.0 and -0.0; "all_zero": every score 0.0."""
+    rng = np.random.default_rng(seed)
+    s = rng.random(n_steps).astype(np.float32)
+    if kind == "zeros":
+        s[::3] = 0.0
+    elif kind == "negative":
+        s = rng.standard_normal(n_steps).astype(np.float32)
+        s[1::5] = np.float32(-0.0)
+        s[3::7] = np.float32(0.0)
+    elif kind == "all_zero":
+        s[:] = np.float32(0.0)
+    elif kind != "random":
+        raise KeyError(kind)
+    return s
+
+
+def eval_edge_batch():
+    """The edge batch of tests/test_oracle.py (host tail vs the numpy oracle) and tests/test_gpu_evaltail.py (device tail vs both): one
+    video per edge plus two that combine edges; annotator counts 1, 2, 31, 32.  Returns [(name, video dict, scores (n_steps,) float32)]."""
+    spec = [  # (name, base n_steps, annotators, edges, scores)
+        ("picks_from_7", 60, 1, ["picks_from_7"], "random"),
+        ("picks_from_15+zeros", 45, 2, ["picks_from_15"], "zeros"),
+        ("last_pick_is_n_frames", 80, 31, ["last_pick_is_n_frames"], "random"),
+        ("repeated_picks", 50, 32, ["repeated_picks"], "random"),
+        ("one_more_interval", 40, 2, ["one_more_interval"], "random"),
+        ("cps_start_below_0", 70, 31, ["cps_start_below_0"], "random"),
+        ("cps_end_past_video", 70, 32, ["cps_end_past_video"], "random"),
+        ("segment_lengths", 130, 1, ["segment_lengths"], "random"),
+        ("steps_4000", 4000, 2, ["pick_spacing_2"], "random"),
+        ("steps_4095", 4095, 31, ["pick_spacing_2"], "negative"),
+        ("n_frames_1", 1, 32, ["n_frames_1"], "random"),
+        ("n_frames_5", 2, 1, ["n_frames_5"], "random"),
+        ("n_frames_9", 3, 2, ["n_frames_9"], "random"),
+        ("negative_scores", 90, 31, [], "negative"),
+        ("picks_from_7+repeated_picks+zeros", 55, 32, ["picks_from_7", "repeated_picks"], "zeros"),
+        ("steps_4095+one_more_interval", 4095, 1, ["pick_spacing_2", "one_more_interval"], "random"),     # 4096 intervals: the device limit
+        ("all_zero+picks_from_7", 33, 2, ["picks_from_7"], "all_zero"),      # every interval ties with the uncovered frames: one rank group, NaN
+    ]
+    out = []
+    for i, (name, T, U, edges, kind) in enumerate(spec):
+        if T > 1000:                                                # (only the length and the annotator count of the base video survive pick_spacing_2)
+            v = dict(n_frames=15 * T, picks=(15 * np.arange(T)).astype(np.int32), change_points=np.array([[0, 15 * T - 1]], np.int32),
+                     user_summary=np.zeros((U, 1), np.float32))
+        else:
+            v = synthetic_video(max(T, 1), 8300 + i, n_users=U)
+        v = dict(v, n_steps=T)
+        for e in edges:
+            v = edge_video(v, e)
+        out.append((name, v, edge_scores(kind, v["n_steps"], 8400 + i)))
+    return out
+
+
 def dropout_keep(seed, site, idx, p):
     """numpy twin of sumk::dropout_keep (csrc/sumk_internal.h): keep-mask of training-mode dropout as a pure
     function of (seed, site, element index).  idx: uint64 array.  Returns a bool array (True = kept)."""

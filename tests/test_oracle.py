@@ -1,6 +1,9 @@
 """CPU: pins the oracle (numpy restatements + torch port) against vectors produced by the REAL reference
 (tests/golden/make_golden.py).  Tolerances: fp32 restatement vs fp32 reference -> 2e-5 abs on scores in (0,1)."""
+import warnings
+
 import numpy as np
+import pytest
 import torch
 
 import recipes as R
@@ -392,3 +395,135 @@ def test_transformer_drop_masks_recipe():
     assert (m0["attn"][1][1][h, 5, j] != 0) == keep
     keep = R.dropout_keep(1, 12, np.array([row * Fd + 9], dtype=np.uint64), 0.5)[0]
     assert (m0["ff1"][1][row, 9] != 0) == keep
+
+
+# ------------------------------------------------------------------------------------------------ optimiser step: float64 restatement vs stock torch
+@pytest.mark.parametrize("weight_decay", [0.0, 1e-5])
+@pytest.mark.parametrize("case", ["clip_bites", "clip_idle", "grad_scale_eighth", "no_clip"])
+def test_adam_f64_restatement_vs_torch_adam_and_clip_grad_norm(case, weight_decay):
+    """oracle/optim_np.AdamF64 against torch.optim.Adam + torch.nn.utils.clip_grad_norm_ in float64 on the CPU, 5 steps: the gradient is
+    scaled first (the 1/world of a data-parallel mean), then clipped on the norm of the scaled gradient, then stepped."""
+    from oracle import optim_np
+    n, lr = 1237, 5e-3
+    rng = np.random.default_rng(77)
+    p0 = rng.standard_normal(n)
+    grads = [rng.standard_normal(n) * 0.3 for _ in range(5)]                      # norm of each ~ 0.3 sqrt(1237) = 10.5
+    grad_scale, max_norm = {"clip_bites": (1.0, 5.0), "clip_idle": (1.0, 50.0), "grad_scale_eighth": (0.125, 5.0), "no_clip": (0.5, None)}[case]
+    ref = optim_np.AdamF64(p0, lr, weight_decay=weight_decay)
+    tp = torch.nn.Parameter(torch.from_numpy(p0.copy()))
+    opt = torch.optim.Adam([tp], lr=lr, weight_decay=weight_decay)
+    for g in grads:
+        coef = ref.step(g, grad_scale=grad_scale, max_norm=max_norm)
+        tp.grad = torch.from_numpy(g * grad_scale)
+        if max_norm is not None:
+            torch.nn.utils.clip_grad_norm_([tp], max_norm)
+        opt.step()
+        # the case is what its name says (decided by the float64 norm of the scaled gradient)
+        norm = float(np.linalg.norm(g * grad_scale))
+        assert {"clip_bites": norm > 2 * max_norm if max_norm else False, "clip_idle": coef == 1.0 and norm < max_norm if max_norm else False,
+                "grad_scale_eighth": coef == 1.0 and norm < max_norm < norm * 8 if max_norm else False, "no_clip": coef == 1.0}[case]
+        st = opt.state[tp]
+        for name, got, want in (("param", ref.p, tp.detach().numpy()), ("exp_avg", ref.m, st["exp_avg"].numpy()),
+                                ("exp_avg_sq", ref.v, st["exp_avg_sq"].numpy())):
+            # float64 rounding: a handful of operations per element in another order (torch: lerp for m, addcdiv of m by sqrt(v)/sqrt(bc2) + eps).
+            # Each element is a sum of two terms that may cancel (b1 m + (1 - b1) g near 0), so its error is a few float64 ulps of the
+            # TERMS, not of the result: 4 ulps of the buffer's largest magnitude absolute, next to 1e-13 relative
+            np.testing.assert_allclose(got, want, rtol=1e-13, atol=4 * 2.0 ** -53 * np.abs(want).max(), err_msg=f"{case} {name} step {ref.t}")
+        assert ref.t == int(st["step"])
+    assert optim_np.clip_coef(np.zeros(5), 1.0, 5.0) == 1.0                      # 5 / (0 + 1e-6) clamped: no NaN from a zero gradient
+
+
+# ------------------------------------------------------------------------------------------------ evaluation edges: host tail vs the numpy oracle
+_EDGE_PRESENT = {
+    "picks_from_7": lambda v: v["picks"][0] == 7,
+    "picks_from_15": lambda v: v["picks"][0] == 15,
+    "last_pick_is_n_frames": lambda v: v["picks"][-1] == v["n_frames"] and len(v["picks"]) == v["n_steps"] + 1,
+    "repeated_picks": lambda v: sorted(np.unique(v["picks"], return_counts=True)[1].tolist())[-2:] == [2, 3],
+    "one_more_interval": lambda v: v["picks"][-1] != v["n_frames"] and len(v["picks"]) == v["n_steps"] + 1,
+    "cps_start_below_0": lambda v: v["change_points"][0, 0] < 0,
+    "cps_end_past_video": lambda v: v["change_points"][-1, 1] > v["n_frames"] - 1,
+    "segment_lengths": lambda v: (v["n_frame_per_seg"][:8].tolist() == [1, 7, 8, 9, 128, 129, 257, 1100]
+                                  and (v["n_frame_per_seg"] < 8).any()),
+    "pick_spacing_2": lambda v: (np.diff(v["picks"][:v["n_steps"]]) == 2).all() and v["n_steps"] >= 4000 and v["n_frames"] < 8300,
+    "n_frames_1": lambda v: v["n_frames"] == 1,
+    "n_frames_5": lambda v: v["n_frames"] == 5 and v["n_steps"] == 2,
+    "n_frames_9": lambda v: v["n_frames"] == 9 and v["n_steps"] == 3,
+}
+
+
+def test_every_evaluation_edge_is_present_in_its_video():
+    assert set(_EDGE_PRESENT) == set(R.EVAL_EDGES)
+    base = R.synthetic_video(130, 5, n_users=3)
+    assert base["picks"][0] == 0 and base["picks"][-1] != base["n_frames"] and len(base["picks"]) == 130      # what every plain video looks like
+    for edge in R.EVAL_EDGES:
+        b = dict(base, n_steps=4000, picks=(15 * np.arange(4000)).astype(np.int32)) if edge == "pick_spacing_2" else base
+        v = R.edge_video(b, edge)
+        assert _EDGE_PRESENT[edge](v), edge
+        assert (np.diff(v["picks"]) >= 0).all() and v["user_scores"].shape == v["user_summary"].shape == (3, v["n_frames"])
+    seen = set()
+    batch = R.eval_edge_batch()
+    for name, v, s in batch:
+        assert s.shape == (v["n_steps"],) and s.dtype == np.float32
+        n_int = len(v["picks"]) - 1 + int(v["picks"][-1] != v["n_frames"])
+        assert v["n_steps"] <= n_int <= min(v["n_steps"] + 1, 4096)
+        seen |= {e for e in R.EVAL_EDGES if _EDGE_PRESENT[e](v)}
+    assert seen == set(R.EVAL_EDGES)                                             # the batch holds every edge
+    by = {name: (v, s) for name, v, s in batch}
+    assert {v["user_summary"].shape[0] for _, v, _ in batch} == {1, 2, 31, 32}
+    v, s = by["picks_from_15+zeros"]
+    assert (s == 0).sum() >= 10 and v["picks"][0] == 15                          # intervals whose score ties with the uncovered frames' 0
+    v, s = by["steps_4095+one_more_interval"]
+    assert len(v["picks"]) == 4096 and v["picks"][-1] != v["n_frames"] and v["n_steps"] == 4095      # 4096 intervals: ED_MAX_INT exactly
+    v, s = by["negative_scores"]
+    assert (s < 0).any() and np.signbit(s[s == 0]).any() and not np.signbit(s[s == 0]).all()
+    assert (by["all_zero+picks_from_7"][1] == 0).all()
+
+
+@pytest.mark.parametrize("method", ["knapsack", "rank"])
+def test_host_eval_tail_on_the_edge_batch_vs_numpy_oracle(method):
+    """The native host tail (eval_native.evaluate_batch) on R.eval_edge_batch() against the literal oracle (eval_np: upsample,
+    segment_scores, generate_summary, evaluate_summary, evaluate_scores = scipy rankdata + spearmanr): summaries and F-scores bit for
+    bit, Spearman at test_host_eval.py's gate.  This pins the host tail as the reference tests/test_gpu_evaltail.py compares the device
+    tail with.  One video is not the reference's to define: a change point that starts below 0 is a numpy slice that wraps round to
+    the video's end (an empty slice here: mean NaN, then `int(nan)` raises ValueError in the reference's knapsack); the host and
+    device tails clamp it to frame 0, and the oracle is given the clamped start."""
+    from summarizer_amd.utils import eval as E
+    from summarizer_amd.utils import eval_native
+    batch = R.eval_edge_batch()
+    vids = [eval_native.prepare_video(v["n_frames"], v["picks"], v["change_points"], v["n_frame_per_seg"], v["user_summary"],
+                                      E.rank_users(v["user_scores"])) for _, v, _ in batch]
+    corr, f_avg, f_max, summ = eval_native.evaluate_batch(vids, [s for _, _, s in batch], 0.15, method, want_summaries=True, n_threads=3)
+    n_nan = 0
+    for i, (name, v, s) in enumerate(batch):
+        cps = v["change_points"].copy()
+        if name == "cps_start_below_0":
+            assert cps[0, 0] < 0
+            cps[0, 0] = 0
+        else:
+            assert cps.min() >= 0
+        s_ref = eval_np.generate_summary(s, cps, v["n_frames"], v["n_frame_per_seg"].tolist(), v["picks"], 0.15, method)
+        np.testing.assert_array_equal(summ[i], s_ref, err_msg=name)
+        fa, fm = eval_np.evaluate_summary(s_ref, v["user_summary"])
+        assert float(fa) == f_avg[i] and float(fm) == f_max[i], (name, method, fa, f_avg[i], fm, f_max[i])
+        with np.errstate(invalid="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore")                                      # scipy's ConstantInputWarning on the all-tied videos
+            c_ref = eval_np.evaluate_scores(eval_np.upsample(s, v["n_frames"], v["picks"]), v["user_scores"])
+        np.testing.assert_allclose(corr[i], c_ref, rtol=1e-12, atol=1e-14, equal_nan=True, err_msg=name)
+        n_nan += int(np.isnan(c_ref))
+    assert n_nan == 2                                                            # n_frames_1 and all_zero+picks_from_7, by construction
+
+
+def test_host_eval_tail_refuses_scores_two_short_of_the_intervals():
+    """lens two or more short of the interval count: the reference's loop raises IndexError (eval.py:29-34, scores[i] past the end),
+    the oracle does the same, the host tail returns an error."""
+    from summarizer_amd import _lib
+    from summarizer_amd.utils import eval as E
+    from summarizer_amd.utils import eval_native
+    v = R.synthetic_video(40, 8250, n_users=2)
+    pv = eval_native.prepare_video(v["n_frames"], v["picks"], v["change_points"], v["n_frame_per_seg"], v["user_summary"], E.rank_users(v["user_scores"]))
+    s = np.linspace(0, 1, 38, dtype=np.float32)
+    with pytest.raises(IndexError):
+        eval_np.upsample(s, v["n_frames"], v["picks"])
+    with pytest.raises(_lib.SumkError, match="more pick intervals than scores"):
+        eval_native.evaluate_batch([pv], [s], 0.15, "knapsack")
+    eval_native.evaluate_batch([pv], [np.linspace(0, 1, 39, dtype=np.float32)], 0.15, "knapsack")        # one short is the defined case
