@@ -221,11 +221,43 @@ int sumk_bilstm_layer_backward(const float* x, const float* h_out, const float* 
  * r, z, n (torch): gx = x_t W_ih^T + b_ih and gh = h_prev W_hh^T + b_hh are (B, 3H) (the host computes them with
  * sumk_linear_forward); mask (B) or NULL: 0 = the sequence has ended (h passes through, no gradient).  rzn (B, 3H) keeps the
  * gate values for sumk_gru_cell_backward, which returns d(gx), d(gh) and the DIRECT part of d(h_prev) (the caller adds dgh . W_hh).
- * Functional path, not a tuned one: DSNTrainer never builds the GRU cell. */
+ * This is the step path: it serves H > 256; smaller cells run the persistent layer below. */
 int sumk_gru_cell_forward(const float* gx, const float* gh, const float* h_prev, const float* mask, float* h_out, float* rzn,
                           int32_t B, int32_t H, void* stream);
 int sumk_gru_cell_backward(const float* dh, const float* rzn, const float* gh, const float* h_prev, const float* mask,
                            float* dgx, float* dgh, float* dh_prev, int32_t B, int32_t H, void* stream);
+
+/* ------------------------------------------------------------------------------------------------ BiGRU
+ * One bidirectional GRU layer (torch.nn.GRU semantics: gates r,z,n; h0 = 0) of `DSN(cell="gru")` on a packed batch, H <= 256, H % 4 == 0,
+ * In % 4 == 0: the input projection as one GEMM per direction, then ONE cooperative launch for every time step of every video and both
+ * directions (csrc/gru_persist.hip); the backward call is one cooperative launch for the BPTT plus the weight-gradient GEMMs.
+ * Same conventions as the BiLSTM calls above: dir 0 = forward, dir 1 = reverse, h (n_rows, 2H) = [h_fwd || h_rev], borrowed pointers,
+ * caller-owned workspace.  A hidden size outside the domain is SUMK_ERR_ARG and a short workspace SUMK_ERR_WORKSPACE: the call never
+ * takes another route by itself -- the caller chooses (summarizer_amd.kernels.bigru_eligible).  training = 0 saves nothing. */
+typedef struct sumk_gru_layer_weights {
+  const float* w_ih[2]; /* (3H, In)  weight_ih_l{k}[_reverse] */
+  const float* w_hh[2]; /* (3H, H)   weight_hh_l{k}[_reverse] */
+  const float* b_ih[2]; /* (3H)      bias_ih_l{k}[_reverse]   */
+  const float* b_hh[2]; /* (3H)      bias_hh_l{k}[_reverse]   */
+} sumk_gru_layer_weights;
+typedef struct sumk_gru_layer_grads {
+  float* w_ih[2]; float* w_hh[2]; float* b_ih[2]; float* b_hh[2];
+} sumk_gru_layer_grads;
+size_t sumk_bigru_workspace_bytes(int32_t In, int32_t H, int32_t n_seq, const int32_t* seq_off_host, int32_t training);
+/* precision: the arithmetic of the projection and gradient GEMMs (as sumk_bilstm_layer_forward); the recurrent products are exact fp32 MFMA. */
+int sumk_bigru_layer_forward(const float* x, int32_t In, int32_t H, int32_t n_seq,
+                             const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                             const sumk_gru_layer_weights* w, float* h_out,
+                             void* workspace, size_t workspace_bytes, int32_t training, int32_t precision, void* stream);
+/* dh_out (n_rows,2H) -> ACCUMULATES the weight gradients; dx (n_rows,In) written if non-NULL.  Needs the workspace of a training-mode
+ * sumk_bigru_layer_forward and that call's h_out. */
+int sumk_bigru_layer_backward(const float* x, const float* h_out, const float* dh_out, int32_t In, int32_t H,
+                              int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                              const sumk_gru_layer_weights* w, const sumk_gru_layer_grads* grads, float* dx,
+                              void* workspace, size_t workspace_bytes, int32_t precision, void* stream);
+/* sumk_bilstm_check for a BiGRU workspace. */
+int sumk_bigru_check(const void* workspace, int32_t In, int32_t H, int32_t n_seq, const int32_t* seq_off_host,
+                     int32_t training, int32_t after_backward, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ unidirectional LSTM layer
  * One forward-running nn.LSTM(bidirectional=False) layer with an optional initial state and the final state as an output:

@@ -90,6 +90,14 @@ class LstmLayerGrads(C.Structure):
                 ("tail_ready_event", C.c_void_p)]
 
 
+class GruLayerWeights(C.Structure):
+    _fields_ = [("w_ih", C.c_void_p * 2), ("w_hh", C.c_void_p * 2), ("b_ih", C.c_void_p * 2), ("b_hh", C.c_void_p * 2)]
+
+
+class GruLayerGrads(C.Structure):
+    _fields_ = [("w_ih", C.c_void_p * 2), ("w_hh", C.c_void_p * 2), ("b_ih", C.c_void_p * 2), ("b_hh", C.c_void_p * 2)]
+
+
 _SIGS = {
     # name: (restype, argtypes)
     "sumk_last_error": (C.c_char_p, []),
@@ -135,6 +143,14 @@ _SIGS = {
                                              C.c_void_p]),
     "sumk_gru_cell_forward": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p]),
     "sumk_gru_cell_backward": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p]),
+    "sumk_bigru_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, HOST_I32P, C.c_int32]),
+    "sumk_bigru_layer_forward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
+                                           C.POINTER(GruLayerWeights), c_f32p, C.c_void_p, C.c_size_t, C.c_int32,
+                                           C.c_int32, C.c_void_p]),
+    "sumk_bigru_layer_backward": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, HOST_I32P,
+                                            c_i32p, C.POINTER(GruLayerWeights), C.POINTER(GruLayerGrads), c_f32p,
+                                            C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    "sumk_bigru_check": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, C.c_int32, C.c_int32, C.c_void_p]),
     "sumk_linear_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "sumk_linear_forward": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
                                       C.c_int32, C.c_void_p]),

@@ -101,6 +101,31 @@ class BiLstmScorerFunction(torch.autograd.Function):
         return (gx, None, None, None, None, None, None, None, None, None) + tuple(ret)
 
 
+class BiGruLayerFunction(torch.autograd.Function):
+    """One bidirectional nn.GRU layer on a packed batch, H <= 256: x (n_rows, In) -> h (n_rows, 2H) = [h_fwd | h_rev], the whole
+    recurrence and the whole BPTT as one cooperative launch each (csrc/gru_persist.hip).  params: (w_ih, w_hh, b_ih, b_hh) of the
+    forward direction, then of the reverse one -- the signature of models._bilstm.GruLayerFunction, the step path it replaces."""
+
+    @staticmethod
+    def forward(ctx, xp, sb, H, precision, *params):
+        h, ws = kernels.bigru_layer_forward(xp, sb, params, H, training=True, precision=precision)
+        ctx.meta = (sb, H, precision)
+        ctx.ws, ctx.params = ws, params
+        ctx.save_for_backward(xp, h)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        xp, h = ctx.saved_tensors
+        sb, H, precision = ctx.meta
+        params = ctx.params
+        grads, ret = _grad_targets([str(i) for i in range(8)], params)
+        dx = kernels.bigru_layer_backward(xp, h, dh, sb, params, [grads[str(i)] for i in range(8)], H, ctx.ws,
+                                          ctx.needs_input_grad[0], precision=precision)
+        ctx.ws = ctx.params = None
+        return (dx, None, None, None) + tuple(ret)
+
+
 class TransformerFunction(torch.autograd.Function):
     """scores = Transformer-encoder scorer(x) for a packed batch (transformer.py:74-103)."""
 

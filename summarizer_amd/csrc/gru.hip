@@ -1,5 +1,5 @@
-// GRU cell of the reference's optional `DSN(cell="gru")` (summarizer/models/dsn.py:28-33: nn.GRU, bidirectional).  DSNTrainer never
-// builds it, so this is the functional path, not a tuned one: the host (summarizer_amd/models/_bilstm.py) walks the time steps
+// GRU cell of the reference's optional `DSN(cell="gru")` (summarizer/models/dsn.py:28-33: nn.GRU, bidirectional): the STEP path.
+// H <= 256 runs the persistent recurrence of gru_persist.hip; this file serves larger cells: the host (summarizer_amd/models/_bilstm.py) walks the time steps
 // and per step calls the MFMA GEMM for Gh = h_{t-1} W_hh^T + b_hh and ONE fused element-wise kernel below; every arithmetic result
 // still comes from this library.  torch.nn.GRU semantics (gate order r, z, n):
 //   r = sigmoid(Gx_r + Gh_r)   z = sigmoid(Gx_z + Gh_z)   n = tanh(Gx_n + r * Gh_n)   h = (1 - z) * n + z * h_prev

@@ -14,6 +14,7 @@
 //    W_hh (1 MB for DSN) stays L2-resident across steps; h_prev is read from the output rows written one step
 //    earlier (t-1 for the forward direction, t+1 for the reverse one), so no separate state buffer exists.
 #include "sumk_internal.h"
+#include "persist_common.h"
 #include <cstring>
 #include <cstdio>
 #include <math.h>
@@ -23,9 +24,6 @@
 
 namespace sumk {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -122,13 +120,6 @@ static int lstm_carve(int In, int H, int n_seq, const int32_t* off, int training
 }
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
-// Gate math of the persistent H <= 256 recurrence, whose per-step latency chain contains it: v_exp_f32 / v_rcp_f32 forms (a few ulp:
-// ~3e-7 relative for the sigmoid, ~1e-7 ABSOLUTE for tanh) instead of the library expf / IEEE division / tanhf (~170 instructions per
-// step and thread against ~30).  tanh(x) = 1 - 2 / (1 + e^{2x}) saturates correctly at both ends (e^{2x} -> inf gives 1, -> 0 gives -1).
-// (round 6: __frcp_rn is the CORRECTLY ROUNDED reciprocal -- hipcc expands it to the v_div_scale / v_div_fmas / v_div_fixup sequence, 5 x ~10
-//  instructions in every cell update; __builtin_amdgcn_rcpf is the bare v_rcp_f32 these forms were written for: 1 ulp)
-__device__ __forceinline__ float fast_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-__device__ __forceinline__ float fast_tanh(float v) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * v)); }
 
 // x = hi + lo with hi = bf16(x), lo = bf16(x - hi): the operand split of the bf16x3 arithmetic (gemm_f32.hip)
 __device__ __forceinline__ void split8(f32x4 x0, f32x4 x1, bf16x8& hi, bf16x8& lo) {
@@ -572,23 +563,6 @@ __global__ void zero_words_kernel(unsigned* p, int n) {
 // and resets it; the Python host calls that at the synchronisation points it already has (score D2H, per-epoch loss).
 __device__ unsigned g_sumk_health = 0u;
 
-constexpr int PK_THREADS = 512;
-constexpr int PK_TEAMS = 8;
-constexpr unsigned PK_SPIN_LIMIT = 1u << 20;   // ~1 s of polling; after one timeout the block stops waiting altogether
-// The flag-in-data hand-offs poll with their OWN data loads (a turn = four to thirty-two sc1 loads, ~1 us), so a turn count is a poor
-// clock: they share the counter protocol's ~1 s budget in WALL time -- s_memrealtime, the 100 MHz constant counter -- read every 256
-// turns, the first time at turn 256 (a healthy wait ends long before).  (A count of PK_SPIN_LIMIT / 16 turns was tens of ms: resume skew after a CWSR preemption, or several ranks time-slicing
-// one GPU, could have tripped it on a healthy run.)
-constexpr unsigned long long PK_WAIT_TICKS = 100000000ull;
-__device__ __forceinline__ bool pk_ll_timed_out(unsigned& spins, unsigned long long& t0) {     // (the clock is first read at turn 256: nothing on the fast path)
-  if ((++spins & 255u) != 0u) return false;
-  const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-  if (spins == 256u) { t0 = now; return false; }
-  return now - t0 > PK_WAIT_TICKS;
-}
-
-__device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // CPW = 8-wide k chunks per wave: the block's 8 waves cover K = 64 * CPW >= H (4 for DSN's H = 256, 16 for sLSTM's 1024).
 // The member's W_hh fragments (32 gate rows x its wave's k range) live in REGISTERS for the whole work item -- exactly the
@@ -2310,7 +2284,7 @@ using namespace sumk;
 
 // The persistent recurrences are written for the full chip: 256 co-resident blocks, one per CU.  On a partitioned device
 // (CPX / fewer CUs) or with SUMK_LSTM_PERSIST=0 the launch-per-step kernels run instead -- same arithmetic.
-static bool persistent_kernels_usable() {
+bool sumk::persistent_kernels_usable() {
   static const bool ok = [] {
     if (getenv("SUMK_LSTM_PERSIST") && getenv("SUMK_LSTM_PERSIST")[0] == '0') return false;
     int dev = 0, cus = 0;
@@ -2319,6 +2293,18 @@ static bool persistent_kernels_usable() {
     return cus >= 256;
   }();
   return ok;
+}
+
+// for the persistent kernels of other translation units (gru_persist.hip): the device address of the sticky health word, and the
+// kernel-side zeroing of hand-off words (see zero_words_kernel)
+unsigned* sumk::persist_health_word() {
+  static unsigned* p = [] { void* q = nullptr; return hipGetSymbolAddress(&q, HIP_SYMBOL(g_sumk_health)) == hipSuccess ? (unsigned*)q : nullptr; }();
+  return p;
+}
+int sumk::persist_zero_words(unsigned* p, size_t words, hipStream_t stream) {
+  hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)std::min<size_t>(256, (words + 255) / 256)), dim3(256), 0, stream, p, (int)words);
+  SUMK_HIP(hipGetLastError());
+  return SUMK_OK;
 }
 
 extern "C" size_t sumk_bilstm_workspace_bytes(int32_t In, int32_t H, int32_t n_seq, const int32_t* seq_off_host,

@@ -1036,3 +1036,85 @@ def gru_cell_backward(dh, rzn, gh, h_prev, mask):
     _lib.check(lib.sumk_gru_cell_backward(_p(dh.contiguous()), _p(rzn), _p(gh), _p(h_prev), _p(mask), _p(dgx), _p(dgh), _p(dhp), B, H,
                                           _stream()), "sumk_gru_cell_backward")
     return dgx, dgh, dhp
+
+
+# ------------------------------------------------------------------------------------------------ BiGRU layer (persistent recurrence, H <= 256)
+BIGRU_MAX_H = 256
+
+
+def bigru_eligible(In, H):
+    """The domain of the persistent GRU layer (csrc/gru_persist.hip) on a device whose persistent kernels are usable; other shapes run
+    the step path (gru_cell_forward / gru_cell_backward under the host loop of models/_bilstm.py)."""
+    return 0 < H <= BIGRU_MAX_H and H % 4 == 0 and In > 0 and In % 4 == 0 and _persistent_ok()
+
+
+_PERSIST_OK = {}
+
+
+def _persistent_ok():
+    """What csrc/lstm.hip's persistent_kernels_usable() answers: the full chip (256 CUs) and SUMK_LSTM_PERSIST != 0."""
+    dev = torch.cuda.current_device()
+    ok = _PERSIST_OK.get(dev)
+    if ok is None:
+        ok = _PERSIST_OK[dev] = (torch.cuda.get_device_properties(dev).multi_processor_count >= 256 and
+                                 _os.environ.get("SUMK_LSTM_PERSIST", "1")[:1] != "0")
+    return ok
+
+
+def _gru_structs(weights, grads=None):
+    """weights / grads: (w_ih, w_hh, b_ih, b_hh) of the forward direction, then of the reverse one."""
+    w = _lib.GruLayerWeights()
+    g = _lib.GruLayerGrads() if grads is not None else None
+    for d in range(2):
+        for i, f in enumerate(("w_ih", "w_hh", "b_ih", "b_hh")):
+            t = weights[4 * d + i]
+            _require_gpu(t, f"GRU {f} (direction {d})")
+            if not t.is_contiguous():
+                raise SumkError(f"GRU {f} (direction {d}) must be contiguous")
+            getattr(w, f)[d] = t.data_ptr()
+            if g is not None:
+                getattr(g, f)[d] = grads[4 * d + i].data_ptr()
+    return w, g
+
+
+def bigru_workspace_bytes(In, H, sb, training):
+    nbytes = _lib.load().sumk_bigru_workspace_bytes(int(In), int(H), sb.n_seq, sb.off_host_p, int(training))
+    if nbytes == 0:
+        _lib.check(-1, "sumk_bigru_workspace_bytes")
+    return nbytes
+
+
+def bigru_layer_forward(x, sb, weights, H, training=False, precision=None, ws=None):
+    """x: (n_rows, In) packed -> h (n_rows, 2H) = [h_fwd || h_rev] of one bidirectional nn.GRU layer.  Returns (h, workspace or None).
+    ws: a caller-owned workspace (tests); otherwise inference shares the per-stream scratch and a training forward gets its own."""
+    lib = _lib.load()
+    _require_gpu(x, "bigru input")
+    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != sb.n_rows:
+        raise SumkError(f"bigru input must be contiguous (n_rows={sb.n_rows}, In), got {tuple(x.shape)}")
+    In = x.shape[1]
+    w, _ = _gru_structs(weights)
+    if ws is None:
+        ws = workspace(bigru_workspace_bytes(In, H, sb, training), x.device, persistent=training)
+    h = torch.empty(sb.n_rows, 2 * H, dtype=torch.float32, device=x.device)
+    rc = lib.sumk_bigru_layer_forward(_p(x), In, H, sb.n_seq, sb.off_host_p, sb.off_dev_p, C.byref(w), _p(h), _p(ws), ws.numel(),
+                                      int(training), precision_code(precision), _stream())
+    _lib.check(rc, "sumk_bigru_layer_forward")
+    if CHECK_LSTM:
+        _lib.check(lib.sumk_bigru_check(_p(ws), In, H, sb.n_seq, sb.off_host_p, int(training), 0, _stream()), "sumk_bigru_check")
+    return h, (ws if training else None)
+
+
+def bigru_layer_backward(x, h, dh, sb, weights, grads, H, ws, want_dx, precision=None):
+    """BPTT of one bidirectional GRU layer; ACCUMULATES into grads (same order as weights).  Returns dx (n_rows, In) or None."""
+    lib = _lib.load()
+    In = x.shape[1]
+    w, g = _gru_structs(weights, grads)
+    dx = torch.empty_like(x) if want_dx else None
+    if not dh.is_contiguous():
+        dh = dh.contiguous()
+    rc = lib.sumk_bigru_layer_backward(_p(x), _p(h), _p(dh), In, H, sb.n_seq, sb.off_host_p, sb.off_dev_p, C.byref(w), C.byref(g),
+                                       _p(dx), _p(ws), ws.numel(), precision_code(precision), _stream())
+    _lib.check(rc, "sumk_bigru_layer_backward")
+    if CHECK_LSTM:
+        _lib.check(lib.sumk_bigru_check(_p(ws), In, H, sb.n_seq, sb.off_host_p, 1, 1, _stream()), "sumk_bigru_check")
+    return dx

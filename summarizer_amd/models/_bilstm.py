@@ -96,7 +96,8 @@ class GruLayerFunction(torch.autograd.Function):
     params: (w_ih, w_hh, b_ih, b_hh) of the forward direction, then of the reverse one (nn.GRU's names / shapes).
     The host walks the steps (time-major, ended videos masked); per step the recurrent projection is an MFMA GEMM
     (`sumk_linear_forward`) and the gates one fused kernel (`sumk_gru_cell_forward`); BPTT mirrors it step by step and the
-    input-side gradients are three GEMM calls at the end.  Functional, not tuned (csrc/gru.hip)."""
+    input-side gradients are three GEMM calls at the end.  This is the STEP path: it serves H > 256 (and devices without the
+    persistent kernels); bigru_scores sends every other shape to autograd.BiGruLayerFunction (csrc/gru_persist.hip)."""
 
     @staticmethod
     def forward(ctx, xp, sb, H, precision, *params):
@@ -156,11 +157,20 @@ class GruLayerFunction(torch.autograd.Function):
 
 def bigru_scores(model, xp, sb, num_layers, H, head_w, head_b):
     """Stacked bidirectional GRU + per-frame Linear(2H, 1) + sigmoid (DSN(cell="gru"), dsn.py:28-47)."""
-    from ..autograd import FrameHeadFunction
+    from ..autograd import BiGruLayerFunction, FrameHeadFunction
     precision = getattr(model, "precision", "fp32")
     p = dict(model.named_parameters())
+    training = torch.is_grad_enabled() and (xp.requires_grad or any(t.requires_grad for t in p.values()))
     h = xp
     for l in range(num_layers):
         names = [f"rnn.{n}_l{l}{suf}" for suf in ("", "_reverse") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
-        h = GruLayerFunction.apply(h, sb, H, precision, *[p[n] for n in names])
+        weights = [p[n] for n in names]
+        if not kernels.bigru_eligible(h.shape[1], H):
+            h = GruLayerFunction.apply(h, sb, H, precision, *weights)        # H > 256: the host walks the steps
+        elif training:
+            h = BiGruLayerFunction.apply(h, sb, H, precision, *weights)
+        else:                                                                 # without grad the forward saves nothing
+            h, _ = kernels.bigru_layer_forward(h, sb, [t.detach() for t in weights], H, training=False, precision=precision)
+    if not training:
+        return kernels.frame_head_forward(h, p[head_w], p[head_b])
     return FrameHeadFunction.apply(h, p[head_w], p[head_b])

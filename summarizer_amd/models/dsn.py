@@ -31,8 +31,8 @@ class DSN(nn.Module):
         self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
         self.precision = "fp32"          # GEMM arithmetic: "fp32" (exact) | "bf16x3" (kernels.precision_code); not in the reference
         # parameter containers only (same names / shapes / init as the reference); never called.  The optional GRU cell
-        # (dsn.py:28-33) runs on a functional step-by-step path (models/_bilstm.py: GruLayerFunction, csrc/gru.hip) -- the
-        # reference's own DSNTrainer always builds DSN(), i.e. the LSTM, which has the persistent kernels.
+        # (dsn.py:28-33) has persistent recurrence kernels of its own for H <= 256 (csrc/gru_persist.hip: one cooperative
+        # launch per layer, forward and BPTT); larger cells keep the step path (models/_bilstm.py: GruLayerFunction, csrc/gru.hip).
         rnn = nn.LSTM if cell == "lstm" else nn.GRU
         self.rnn = rnn(input_size, hidden_size, num_layers=num_layers, bidirectional=True)
         self.out = nn.Sequential(nn.Linear(hidden_size * 2, 1), nn.Sigmoid())
