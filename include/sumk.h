@@ -544,6 +544,31 @@ size_t sumk_eval_device_spearman_scratch_bytes(int32_t n_videos);
 int sumk_eval_device_spearman(const float* scores_dev, const sumk_eval_dev_video* videos_dev, int32_t n_videos, double* scratch_dev,
                               double* corr_dev, void* stream);
 
+/* Kendall's tau-b instead of Spearman's rho (evaluate_scores with metric "kendalltau", eval.py:56-59 = scipy.stats.kendalltau, variant b,
+ * of the two rank vectors), per (video, annotator) from integer pair counts, n = n_frames:
+ *   tot = n (n - 1) / 2;  xtie / ytie / ntie = sum t (t - 1) / 2 over the tie groups of the machine frame scores / the annotator's scores /
+ *   the (x, y) pairs;  dis = discordant pairs;  cmd = tot - xtie - ytie + ntie - 2 dis;
+ *   tau = cmd / sqrt(tot - xtie) / sqrt(tot - ytie) (float64, in this order), clamped to [-1, 1]; NaN when xtie == tot or ytie == tot.
+ * A video's value is the mean over its annotators in numpy's summation order (NaN if any annotator's is).  O(n log n) everywhere.
+ *
+ * HOST, threaded like sumk_eval_videos: upsample + tau-b against user_ranks for every video; writes .corr only (NaN without user_ranks).
+ * counts (optional): {cmd, xtie, ytie, ntie} per (video, annotator), the annotators of video i after those of videos 0 .. i - 1. */
+int sumk_eval_videos_kendall(sumk_eval_video* videos, int32_t n_videos, int64_t* counts, int32_t n_threads);
+/* DEVICE: takes the place of sumk_eval_device_spearman behind sumk_eval_device_segments, on the same descriptors plus one
+ * sumk_eval_dev_kendall per video (a parallel array).  One workgroup per (video, annotator) sorts the video's frame keys in LDS: on top of
+ * the limits of sumk_eval_dev_video, n_frames <= 16384.  A descriptor past a limit gets NaN (and -1 in its counts) and nothing else is
+ * touched.  scratch: sumk_eval_device_kendall_scratch_bytes(n_videos, total frames of the batch) bytes, 8-byte aligned.
+ * counts_dev (optional): 4 int64 {cmd, xtie, ytie, ntie} per annotator, annotator u of a video at counts_dev[4 * (counts0 + u)].
+ * Results equal the host function's bit for bit (the same integers, the same float64 operations). */
+typedef struct sumk_eval_dev_kendall {
+  const int32_t* y_dense;                      /* (n_users, n_frames) dense ranks of each annotator's scores: 0-based, ascending with the score, equal scores share one */
+  const int64_t* ytie;                         /* (n_users) tied pairs of each annotator's scores                                              */
+  int64_t counts0;                             /* first annotator slot of this video in counts_dev                                             */
+} sumk_eval_dev_kendall;
+size_t sumk_eval_device_kendall_scratch_bytes(int32_t n_videos, int64_t total_frames);
+int sumk_eval_device_kendall(const float* scores_dev, const sumk_eval_dev_video* videos_dev, const sumk_eval_dev_kendall* kendall_dev,
+                             int32_t n_videos, void* scratch_dev, double* corr_dev, int64_t* counts_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ data-parallel exchange (RCCL)
  * The gradient all-reduce of data-parallel training as a library call: SUM, in place, over one flat bucket, on the caller's
  * HIP stream (one collective per optimiser step; the reference has no distributed code).  Bootstrap:

@@ -80,6 +80,10 @@ class EvalDevVideo(C.Structure):      # sumk_eval_dev_video: every pointer is a 
                 ("user_mean", C.c_void_p), ("user_ssq", C.c_void_p), ("n_users", C.c_int32)]
 
 
+class EvalDevKendall(C.Structure):    # sumk_eval_dev_kendall (device pointers), one per sumk_eval_dev_video
+    _fields_ = [("y_dense", C.c_void_p), ("ytie", C.c_void_p), ("counts0", C.c_int64)]
+
+
 class LstmLayerWeights(C.Structure):
     _fields_ = [("w_ih", C.c_void_p * 2), ("w_hh", C.c_void_p * 2), ("b_ih", C.c_void_p * 2), ("b_hh", C.c_void_p * 2),
                 ("x_planes", C.c_void_p), ("w_planes", C.c_void_p)]
@@ -221,6 +225,8 @@ _SIGS = {
     "sumk_eval_device_segments": (C.c_int, [c_f32p, C.c_void_p, C.c_int32, c_f32p, c_f32p, C.c_void_p]),
     "sumk_eval_device_spearman_scratch_bytes": (C.c_size_t, [C.c_int32]),
     "sumk_eval_device_spearman": (C.c_int, [c_f32p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sumk_eval_device_kendall_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "sumk_eval_device_kendall": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sumk_pack_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), HOST_I32P, C.c_int32, C.c_int32, C.c_int32]),
     "sumk_pack_rows_bf16": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), HOST_I32P, C.c_int32, C.c_int32, C.c_int32]),
     "sumk_gemm_prec": (C.c_int, [C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -236,6 +242,7 @@ _SIGS = {
     "sumk_knapsack_dp": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64,
                                    C.POINTER(C.c_uint8)]),
     "sumk_eval_videos": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32]),
+    "sumk_eval_videos_kendall": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "sumk_prof_enable": (C.c_int, [C.c_int32]),
     "sumk_prof_read": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
     "sumk_probe_mfma_rate": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),

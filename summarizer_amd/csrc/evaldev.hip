@@ -4,15 +4,12 @@
 // (eval.py:91-94; numpy's pairwise summation reproduced operation for operation, so the host knapsack sees the same integers) and
 // the mean Spearman correlation with the annotators (eval.py:49-72).  One small D2H (segment means + one double per video) then
 // feeds the host side (sumk_eval_videos with seg_means given: knapsack / rank selection, summary expansion, F-scores).
-#include "sumk_internal.h"
+#include "evaldev_common.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
 
 namespace sumk {
-
-constexpr int ED_MAX_INT = 4096;     // pick intervals per video the block keeps in LDS (T <= 4095 steps)
-constexpr int ED_MAX_USERS = 32;
 
 // numpy's pairwise summation (numpy/core/src/umath/loops_utils.h.src), float32 -- same tree as csrc/evaltail.hip
 __device__ float ed_pairwise_sum(const float* a, int n) {
@@ -143,16 +140,7 @@ __global__ __launch_bounds__(256) void eval_device_kernel(const float* __restric
 // float64 sums are re-associated with respect to the one-block form (~1e-16 relative).
 constexpr int ED_CHUNKS = 8;
 
-// the interval tables of a video (s_lo / s_hi / s_val of eval_device_kernel), shared by both kernels
-__device__ __forceinline__ void ed_intervals(const sumk_eval_dev_video& v, const float* __restrict__ scores, int n_int, int* s_lo, int* s_hi,
-                                             float* s_val) {
-  const int np_ = v.n_picks, n_frames = v.n_frames;
-  for (int i = threadIdx.x; i < n_int; i += 256) {
-    s_lo[i] = max(0, v.picks[i]);
-    s_hi[i] = min(n_frames, i + 1 < np_ ? v.picks[i + 1] : n_frames);
-    s_val[i] = i < v.n_steps ? scores[v.row0 + i] : 0.f;
-  }
-}
+// (the interval tables of a video -- s_lo / s_hi / s_val of eval_device_kernel -- are ed_intervals of evaldev_common.h)
 
 __global__ __launch_bounds__(256) void eval_segments_kernel(const float* __restrict__ scores, const sumk_eval_dev_video* __restrict__ vids,
                                                             float* __restrict__ frame_scratch, float* __restrict__ seg_means) {

@@ -3,13 +3,13 @@
 //   upsample            summarizer/utils/eval.py:15-35
 //   generate_summary    eval.py:74-123   (segment means -> knapsack / rank -> binary frame vector)
 //   evaluate_summary    eval.py:125-165  (precision / recall / F per annotator, mean and max)
-//   evaluate_scores     eval.py:49-72    (Spearman = Pearson of average ranks)
+//   evaluate_scores     eval.py:49-72    (Spearman = Pearson of average ranks; Kendall's tau-b from integer pair counts: sumk_eval_videos_kendall)
 // Bit-exactness contract (tests/test_host_eval.py): machine summaries and F-scores equal the numpy implementation BIT FOR
 // BIT -- which requires reproducing numpy's float32 PAIRWISE summation (8 accumulators, blocks of 128, recursive halves)
 // for the segment means that feed `int(mean * 1000)` and for the mean over annotators; the rank correlation is float64 and
 // agrees to ~1e-15 (summation order of the dot products differs from BLAS).  Compiled with -ffp-contract=off semantics
 // (no FMA contraction in this file: every operation rounds like numpy's).
-#include "sumk_internal.h"
+#include "evaldev_common.h"
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -94,11 +94,9 @@ void fscores(const T* m, const float* user_summary, int n_users, int n_frames, T
   *f_max = (double)*std::max_element(f.begin(), f.end());
 }
 
-int eval_one(sumk_eval_video& v, double proportion, int method, Scratch& S) {
+// upsample (eval.py:24-34) into S.frame_scores: literal interval assignment, sentinel n_frames appended when the last pick differs
+int upsample_frames(const sumk_eval_video& v, Scratch& S) {
   const int n_frames = v.n_frames;
-  const bool from_device = v.seg_means != nullptr;     // upsampling, segment means and correlation were done by sumk_eval_device
-  if (!from_device) {
-  // ---- upsample (eval.py:24-34): literal interval assignment, sentinel n_frames appended when the last pick differs
   S.frame_scores.assign((size_t)n_frames, 0.f);
   const int np_ = v.n_picks;
   const bool sentinel = np_ == 0 || v.picks[np_ - 1] != n_frames;
@@ -110,6 +108,14 @@ int eval_one(sumk_eval_video& v, double proportion, int method, Scratch& S) {
     const float val = i < v.n_steps ? v.scores[i] : 0.f;
     for (int f = lo; f < hi; ++f) S.frame_scores[f] = val;
   }
+  return 0;
+}
+
+int eval_one(sumk_eval_video& v, double proportion, int method, Scratch& S) {
+  const int n_frames = v.n_frames;
+  const bool from_device = v.seg_means != nullptr;     // upsampling, segment means and correlation were done by sumk_eval_device
+  if (!from_device) {
+  if (upsample_frames(v, S) != 0) return -1;
   // ---- rank correlation with the annotators (eval.py:49-72)
   v.corr = std::nan("");
   if (v.user_ranks != nullptr && v.n_users > 0) {
@@ -231,7 +237,143 @@ void eval_pool_run(int n_items, const std::function<void(int, Scratch&)>& f) {
   P->cv_done.wait(lk, [&] { return P->active == 0; });
 }
 
+// ---- Kendall's tau-b (scipy.stats.kendalltau(rankdata(-x), rankdata(-y)), variant b: ranking and negating both sides is monotone, so
+// this is tau-b of (frame scores, annotator ranks) themselves).  Integer pair counts, O(n log n): dense ranks of both sides, the
+// frames put in (x, y) order by two stable counting sorts, joint ties from runs of equal pairs, discordant pairs = inversions of the
+// y sequence (bottom-up merge sort).  The same definition, count for count, as the device kernel of csrc/evalkendall.hip.
+struct KendallScratch {
+  std::vector<int32_t> order, xr, yr, a, b, head;
+  std::vector<uint32_t> xkey;
+  std::vector<double> tau, yneg;
+};
+
+// dense ranks (0-based) of key[0..n) in `out`; returns the number of tied pairs sum t (t - 1) / 2
+template <typename K>
+int64_t dense_ranks(const K* key, int n, std::vector<int32_t>& order, std::vector<int32_t>& out, int* n_distinct) {
+  order.resize(n); out.resize(n);
+  std::iota(order.begin(), order.end(), 0);
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
+  int64_t ties = 0;
+  int r = -1, i = 0;
+  while (i < n) {
+    int j = i;
+    while (j + 1 < n && key[order[j + 1]] == key[order[i]]) ++j;
+    ++r;
+    for (int k = i; k <= j; ++k) out[order[k]] = r;
+    const int64_t t = j - i + 1;
+    ties += t * (t - 1) / 2;
+    i = j + 1;
+  }
+  *n_distinct = r + 1;
+  return ties;
+}
+
+// out = in reordered by rank[in[.]] (stable counting sort; ranks in [0, n_rank))
+void counting_pass(const std::vector<int32_t>& in, const std::vector<int32_t>& rank, int n_rank, std::vector<int32_t>& head, std::vector<int32_t>& out) {
+  head.assign((size_t)n_rank + 1, 0);
+  for (int f : in) ++head[rank[f] + 1];
+  for (int r = 0; r < n_rank; ++r) head[r + 1] += head[r];
+  out.resize(in.size());
+  for (int f : in) out[head[rank[f]]++] = f;
+}
+
+// inversions of a[0..n) (pairs i < j with a[i] > a[j]); a is sorted on return, b is scratch
+int64_t count_inversions(std::vector<int32_t>& a, std::vector<int32_t>& b) {
+  const int n = (int)a.size();
+  b.resize(n);
+  int64_t inv = 0;
+  int32_t* src = a.data(); int32_t* dst = b.data();
+  for (int w = 1; w < n; w *= 2) {
+    for (int s = 0; s < n; s += 2 * w) {
+      const int mid = std::min(s + w, n), end = std::min(s + 2 * w, n);
+      int i = s, j = mid, k = s;
+      while (i < mid && j < end) {
+        if (src[j] < src[i]) { inv += mid - i; dst[k++] = src[j++]; }
+        else dst[k++] = src[i++];
+      }
+      while (i < mid) dst[k++] = src[i++];
+      while (j < end) dst[k++] = src[j++];
+    }
+    std::swap(src, dst);
+  }
+  if (src != a.data()) std::copy(src, src + n, a.data());
+  return inv;
+}
+
+// counts (optional): {cmd, xtie, ytie, ntie} per annotator
+int kendall_one(sumk_eval_video& v, int64_t* counts, Scratch& S, KendallScratch& K) {
+  v.corr = std::nan("");
+  if (upsample_frames(v, S) != 0) return -1;
+  if (v.user_ranks == nullptr || v.n_users <= 0) return 0;
+  const int n = v.n_frames;
+  // x side, once per video: -0.0 and +0.0 are one value; the order-preserving integer image of the float keeps the comparison exact
+  K.xkey.resize(n);
+  for (int f = 0; f < n; ++f) K.xkey[f] = sumk::kendall_float_key(S.frame_scores[f]);
+  int nx = 0, ny = 0;
+  const int64_t xtie = dense_ranks(K.xkey.data(), n, K.order, K.xr, &nx);
+  const int64_t tot = (int64_t)n * (n - 1) / 2;
+  K.tau.resize(v.n_users);
+  for (int u = 0; u < v.n_users; ++u) {
+    // user_ranks rank the annotator's scores in DESCENDING order (rankdata(-y)), the machine side here ascends: the y order is that of -rank
+    K.yneg.resize(n);
+    for (int f = 0; f < n; ++f) K.yneg[f] = -v.user_ranks[(int64_t)u * n + f];
+    const int64_t ytie = dense_ranks(K.yneg.data(), n, K.order, K.yr, &ny);
+    K.a.resize(n);
+    std::iota(K.a.begin(), K.a.end(), 0);
+    counting_pass(K.a, K.yr, ny, K.head, K.b);          // by y, then (stable) by x: frames in (x, y) order
+    counting_pass(K.b, K.xr, nx, K.head, K.a);
+    int64_t ntie = 0;
+    for (int i = 0; i < n;) {
+      int j = i;
+      while (j + 1 < n && K.xr[K.a[j + 1]] == K.xr[K.a[i]] && K.yr[K.a[j + 1]] == K.yr[K.a[i]]) ++j;
+      const int64_t t = j - i + 1;
+      ntie += t * (t - 1) / 2;
+      i = j + 1;
+    }
+    for (int i = 0; i < n; ++i) K.a[i] = K.yr[K.a[i]];
+    const int64_t dis = count_inversions(K.a, K.b);
+    const int64_t cmd = tot - xtie - ytie + ntie - 2 * dis;
+    K.tau[u] = sumk::kendall_tau_b(cmd, tot, xtie, ytie);
+    if (counts != nullptr) { counts[4 * u] = cmd; counts[4 * u + 1] = xtie; counts[4 * u + 2] = ytie; counts[4 * u + 3] = ntie; }
+  }
+  v.corr = pairwise_sum(K.tau.data(), (int64_t)v.n_users) / (double)v.n_users;      // np.mean over the annotators (a NaN annotator: NaN)
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int sumk_eval_videos_kendall(sumk_eval_video* vids, int32_t n_videos, int64_t* counts, int32_t n_threads) {
+  using namespace sumk;
+  SUMK_ARG(n_videos >= 0 && (n_videos == 0 || vids != nullptr), "eval_videos_kendall: null batch");
+  std::vector<int64_t> at((size_t)std::max(1, n_videos), 0);      // first annotator of video i in `counts`
+  int64_t users = 0;
+  for (int i = 0; i < n_videos; ++i) {
+    SUMK_ARG(vids[i].scores && vids[i].picks && vids[i].n_steps > 0, "eval_videos_kendall: video %d is incomplete", i);
+    SUMK_ARG(vids[i].n_frames > 0, "eval_videos_kendall: video %d has no frames", i);
+    at[i] = users;
+    users += vids[i].user_ranks != nullptr && vids[i].n_users > 0 ? vids[i].n_users : 0;
+  }
+  std::vector<int> status((size_t)std::max(1, n_videos), 0);
+  auto one = [&](int i, Scratch& S, KendallScratch& K) {
+    try { status[i] = kendall_one(vids[i], counts != nullptr ? counts + 4 * at[i] : nullptr, S, K); } catch (...) { status[i] = -3; }
+  };
+  int nt = n_threads > 0 ? n_threads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  nt = std::max(1, std::min(nt, n_videos));
+  if (n_threads <= 0 && n_videos > 1) {
+    eval_pool_run(n_videos, [&](int i, Scratch& S) { KendallScratch K; one(i, S, K); });
+  } else {
+    auto work = [&](int t) { Scratch S; KendallScratch K; for (int i = t; i < n_videos; i += nt) one(i, S, K); };
+    if (nt == 1) work(0);
+    else {
+      std::vector<std::thread> pool;
+      for (int t = 0; t < nt; ++t) pool.emplace_back(work, t);
+      for (auto& th : pool) th.join();
+    }
+  }
+  for (int i = 0; i < n_videos; ++i)
+    if (status[i] != 0) { set_error("eval_videos_kendall: video %d failed (%s)", i, status[i] == -1 ? "more pick intervals than scores + 1" : "out of memory / exception in the evaluation worker"); return SUMK_ERR_ARG; }
+  return SUMK_OK;
+}
 
 extern "C" int sumk_eval_videos(sumk_eval_video* vids, int32_t n_videos, double proportion, int32_t method, int32_t n_threads) {
   using namespace sumk;

@@ -194,7 +194,8 @@ class Trainer:
         if dev.type != "cuda":
             return None
         metas = [self._native_meta(k) for k in keys]
-        if not all(eval_native.device_ready(m) for m in metas):
+        metric = self._correlation_metric()
+        if not all((eval_native.kendall_device_ready if metric == "kendalltau" else eval_native.device_ready)(m) for m in metas):
             return None
         # the fold's test set packed once and kept in HBM (a second copy of its features: 49 MB for 50 TVSum videos of 288 GB): every later
         # call of the same key list starts at the scoring launch
@@ -212,9 +213,17 @@ class Trainer:
         else:
             packed, lens = hit
         scores = self.model.score_packed(packed, lens).detach().contiguous()
-        corr, f_avg, f_max, _ = eval_native.evaluate_batch_device(metas, scores, lens, self.hps.summary_proportion, self.hps.selection_algorithm)
+        corr, f_avg, f_max, _ = eval_native.evaluate_batch_device(metas, scores, lens, self.hps.summary_proportion, self.hps.selection_algorithm,
+                                                                  metric=metric)
         kernels.health_check()      # the D2H inside synchronised: fail loudly if a persistent recurrence kernel timed out
         return corr, f_avg, f_max
+
+    def _correlation_metric(self):
+        """"spearmanr" (the reference's only choice, and the default) or "kendalltau": hps.correlation_metric."""
+        metric = getattr(self.hps, "correlation_metric", "spearmanr")
+        if metric not in eval_native.METRICS:
+            raise KeyError(f"Unknown metric {metric}")
+        return metric
 
     def _native_meta(self, key):
         m = self._video_meta(key, "scores")
@@ -225,15 +234,18 @@ class Trainer:
 
     def _evaluate_native(self, activations, keys, want_summaries=False):
         return eval_native.evaluate_batch([self._native_meta(k) for k in keys], [activations[k] for k in keys],
-                                          self.hps.summary_proportion, self.hps.selection_algorithm, want_summaries)
+                                          self.hps.summary_proportion, self.hps.selection_algorithm, want_summaries,
+                                          metric=self._correlation_metric())
 
     def _eval_scores(self, machine_summary_activations, test_keys):
-        """Mean over videos of the mean Spearman correlation with each annotator's scores."""
+        """Mean over videos of the mean rank correlation (hps.correlation_metric: Spearman's rho unless set to "kendalltau") with each
+        annotator's scores."""
+        metric = self._correlation_metric()
         per_video = []
         for key in test_keys:
             m = self._video_meta(key, "scores")
             frame_scores = ev.generate_scores(machine_summary_activations[key], m.n_frames, m.picks)
-            per_video.append(ev.evaluate_scores(frame_scores, m.user_scores, metric="spearmanr", user_ranks=m.user_ranks))
+            per_video.append(ev.evaluate_scores(frame_scores, m.user_scores, metric=metric, user_ranks=m.user_ranks))
         return np.mean(per_video)
 
     def _machine_summary(self, key, activations):

@@ -1,14 +1,29 @@
 """Batch evaluation tail in native threads (libsumk.so: `sumk_eval_videos`, csrc/evaltail.hip): for a list of videos it
 does what `utils/eval.py` does one video at a time in numpy -- upsample, key-shot summary (knapsack / rank), F-scores
-against the annotators and the Spearman correlation -- with bit-identical summaries and F-scores (tests/test_host_eval.py)
-and the correlation equal to ~1e-15.  This is what `Trainer.test` / `predict_dataset` call; the numpy functions stay the
-readable specification (and the fallback for `metric="kendalltau"`)."""
+against the annotators and the rank correlation -- with bit-identical summaries and F-scores (tests/test_host_eval.py)
+and the correlation equal to ~1e-15.  Both metrics of `evaluate_scores` run here: `metric="spearmanr"` (the default) and
+`metric="kendalltau"` (tau-b from integer pair counts in O(n log n): `sumk_eval_videos_kendall` in the host threads,
+`sumk_eval_device_kendall` -- csrc/evalkendall.hip -- with the scores still in HBM; tests/test_host_kendall.py,
+tests/test_gpu_kendall.py).  This is what `Trainer.test` / `predict_dataset` call; the numpy functions stay the readable
+specification."""
 import ctypes as C
 import numpy as np
 
 from .. import _lib
 
 METHODS = {"knapsack": 0, "rank": 1}
+METRICS = ("spearmanr", "kendalltau")
+KENDALL_MAX_FRAMES = 16384      # KD_MAX_FRAMES of csrc/evaldev_common.h: frames per video the device Kendall kernel sorts in LDS
+
+
+def _check_metric(metric):
+    if metric not in METRICS:
+        raise KeyError(f"Unknown metric {metric}")
+
+
+def _split_counts(flat, users):
+    """(sum(users), 4) int64 {cmd, xtie, ytie, ntie} rows -> one (n_users, 4) array per video."""
+    return [a.copy() for a in np.split(flat.reshape(-1, 4), np.cumsum(users)[:-1])] if users else []
 
 
 def prepare_video(n_frames, picks, cps=None, nfps=None, user_summary=None, user_ranks=None):
@@ -27,11 +42,15 @@ def prepare_video(n_frames, picks, cps=None, nfps=None, user_summary=None, user_
     return d
 
 
-def evaluate_batch(videos, scores, proportion=0.15, method="knapsack", want_summaries=False, n_threads=0):
+def evaluate_batch(videos, scores, proportion=0.15, method="knapsack", want_summaries=False, n_threads=0, metric="spearmanr", counts_out=None):
     """videos: list of `prepare_video` dicts; scores: list of (n_steps,) float32 arrays.
-    Returns (corr (n,), f_avg (n,), f_max (n,), summaries or None); entries are NaN where the inputs were not given."""
+    Returns (corr (n,), f_avg (n,), f_max (n,), summaries or None); entries are NaN where the inputs were not given.
+    metric: "spearmanr" | "kendalltau" (tau-b), as `eval.evaluate_scores`.  counts_out (Kendall only): a list that receives, per video, the
+    (n_users, 4) int64 pair counts {cmd, xtie, ytie, ntie} the values were computed from."""
     if method not in METHODS:
         raise KeyError(f"Unknown method {method}")
+    _check_metric(metric)
+    kendall = metric == "kendalltau"
     lib = _lib.load()
     n = len(videos)
     arr = (_lib.EvalVideo * max(n, 1))()
@@ -53,10 +72,23 @@ def evaluate_batch(videos, scores, proportion=0.15, method="knapsack", want_summ
                 raise ValueError(f"user_summary has {v['user_summary'].shape[1]} frames, video has {v['n_frames']}")
             e.user_summary, e.n_users = v["user_summary"].ctypes.data, v["user_summary"].shape[0]
         if "user_ranks" in v:
-            e.user_ranks = v["user_ranks"].ctypes.data
+            if not kendall:                   # (Kendall: handed over after sumk_eval_videos, which then leaves Spearman out)
+                e.user_ranks = v["user_ranks"].ctypes.data
             e.n_users = v["user_ranks"].shape[0] if e.n_users == 0 else e.n_users
     _lib.check(lib.sumk_eval_videos(C.cast(arr, C.c_void_p), n, float(proportion), METHODS[method], int(n_threads)),
                "sumk_eval_videos")
+    if kendall:
+        users = [v["user_ranks"].shape[0] if "user_ranks" in v else 0 for v in videos]
+        for e, v in zip(arr, videos):
+            if "user_ranks" in v:
+                if v["user_ranks"].shape[0] != e.n_users or v["user_ranks"].shape[1] != v["n_frames"]:
+                    raise ValueError(f"user_ranks is {v['user_ranks'].shape}, video has {e.n_users} annotators and {v['n_frames']} frames")
+                e.user_ranks = v["user_ranks"].ctypes.data
+        counts = np.zeros(4 * max(sum(users), 1), dtype=np.int64) if counts_out is not None else None
+        _lib.check(lib.sumk_eval_videos_kendall(C.cast(arr, C.c_void_p), n, counts.ctypes.data if counts is not None else None, int(n_threads)),
+                   "sumk_eval_videos_kendall")
+        if counts_out is not None:
+            counts_out[:] = _split_counts(counts[:4 * sum(users)], users)
     corr = np.array([arr[i].corr for i in range(n)]); f_avg = np.array([arr[i].f_avg for i in range(n)])
     f_max = np.array([arr[i].f_max for i in range(n)])
     return corr, f_avg, f_max, (summaries if want_summaries else None)
@@ -78,11 +110,37 @@ def device_ready(v):
 _DEV_BATCH_CACHE = {}      # (ids of the videos' dicts, lens, device) -> the batch's constant descriptors (device + host side); a few entries
 
 
-def _device_meta(v, device):
-    """The video's constant metadata as device tensors, uploaded once and cached inside the prepare_video dict."""
+def kendall_device_ready(v):
+    """device_ready, and few enough frames for the Kendall kernel's LDS-resident sort (longer videos take the native host path)."""
+    return device_ready(v) and v["n_frames"] <= KENDALL_MAX_FRAMES
+
+
+def _kendall_meta(v):
+    """Annotator side of Kendall's tau, constants of the video: dense ranks int32 (n_users, n_frames), ascending with the annotator's
+    score, and tied pairs int64 (n_users,)."""
+    m = v.get("_kendall")
+    if m is None:
+        ru = v["user_ranks"]
+        dense = np.empty(ru.shape, dtype=np.int32)
+        ytie = np.zeros(ru.shape[0], dtype=np.int64)
+        for u in range(ru.shape[0]):
+            _, inv, cnt = np.unique(-ru[u], return_inverse=True, return_counts=True)      # (user_ranks descend with the score: rankdata(-y))
+            dense[u] = inv.reshape(-1)
+            cnt = cnt.astype(np.int64)
+            ytie[u] = int((cnt * (cnt - 1) // 2).sum())
+        m = v["_kendall"] = (dense, ytie)
+    return m
+
+
+def _device_meta(v, device, kendall=False):
+    """The video's constant metadata as device tensors, uploaded once and cached inside the prepare_video dict
+    (kendall: with the annotators' dense ranks and tie counts, which only the Kendall launch reads)."""
     import torch
     cache = v.setdefault("_dev", {})
     d = cache.get(str(device))
+    if kendall and d is not None and "ydense" not in d:
+        dense, ytie = _kendall_meta(v)
+        d["ydense"], d["ytie"] = torch.from_numpy(dense).to(device), torch.from_numpy(ytie).to(device)
     if d is None:
         ru = v["user_ranks"]
         mu = ru.sum(axis=1) / ru.shape[1]
@@ -90,17 +148,24 @@ def _device_meta(v, device):
             picks=torch.from_numpy(v["picks"]).to(device), cps=torch.from_numpy(v["cps"]).to(device),
             ranks=torch.from_numpy(ru).to(device), mean=torch.from_numpy(mu).to(device),
             ssq=torch.from_numpy(((ru - mu[:, None]) ** 2).sum(axis=1)).to(device))
+        if kendall:
+            return _device_meta(v, device, True)
     return d
 
 
-def evaluate_batch_device(videos, scores_dev, lens, proportion=0.15, method="knapsack", want_summaries=False, n_threads=0):
+def evaluate_batch_device(videos, scores_dev, lens, proportion=0.15, method="knapsack", want_summaries=False, n_threads=0, metric="spearmanr",
+                          counts_out=None):
     """The same evaluation with the scores still in HBM: `scores_dev` = packed (sum(lens),) float32 device tensor, video i owning rows
     [sum(lens[:i]), sum(lens[:i + 1])).  One launch (a block per video) does upsample + float32 segment means + Spearman on the device
     (sumk_eval_device); one small D2H brings the segment means and correlations home; key-shot selection, summary expansion and
-    F-scores finish in the native host threads (sumk_eval_videos with seg_means given).  Same return value as evaluate_batch."""
+    F-scores finish in the native host threads (sumk_eval_videos with seg_means given).  Same return value as evaluate_batch.
+    metric="kendalltau": sumk_eval_device_kendall (a workgroup per video and annotator) takes the Spearman launch's place; every video
+    must then pass kendall_device_ready.  counts_out: as in evaluate_batch."""
     import torch
     if method not in METHODS:
         raise KeyError(f"Unknown method {method}")
+    _check_metric(metric)
+    kendall = metric == "kendalltau"
     lib = _lib.load()
     n, dev = len(videos), scores_dev.device
     if n == 0:
@@ -143,6 +208,21 @@ def evaluate_batch_device(videos, scores_dev, lens, proportion=0.15, method="kna
     descr_dev, row0, frame0, seg0 = ent["descr_dev"], ent["rows"], ent["frames"], ent["segs"]
     if row0 != scores_dev.numel():
         raise _lib.SumkError(f"evaluate_batch_device: lens sum to {row0}, scores hold {scores_dev.numel()}")
+    if kendall and "kendall" not in ent:
+        # the Kendall side of the entry (a parallel descriptor array, the annotators' dense ranks), added the first time it is asked for:
+        # Spearman calls on the same test set neither build nor read it
+        for i, v in enumerate(videos):
+            if not kendall_device_ready(v):
+                raise _lib.SumkError(f"evaluate_batch_device: video {i} has {v['n_frames']} frames, the device Kendall kernel takes "
+                                     f"{KENDALL_MAX_FRAMES}; use evaluate_batch")
+        kd = (_lib.EvalDevKendall * n)()
+        kmetas, users = [], 0
+        for i, v in enumerate(videos):
+            m = _device_meta(v, dev, kendall=True); kmetas.append(m)
+            kd[i].y_dense, kd[i].ytie, kd[i].counts0 = m["ydense"].data_ptr(), m["ytie"].data_ptr(), users
+            users += v["user_ranks"].shape[0]
+        ent["kendall"] = dict(metas=kmetas, descr_dev=torch.frombuffer(bytearray(bytes(kd)), dtype=torch.uint8).to(dev), users=users,
+                              per_video=[v["user_ranks"].shape[0] for v in videos])
     # Two stages on the device, two small transfers into pinned memory: the segment means come home after the short first kernel and the
     # host's key-shot selection + F-scores run while the device is still correlating (buffers are per batch and reused: the call ends
     # synchronised).
@@ -162,8 +242,22 @@ def evaluate_batch_device(videos, scores_dev, lens, proportion=0.15, method="kna
         _lib.check(lib.sumk_eval_device_segments(scores_dev.data_ptr(), descr_dev.data_ptr(), n, buf["scratch"].data_ptr(), buf["seg"].data_ptr(), st),
                    "sumk_eval_device_segments")
         buf["seg_host"].copy_(buf["seg"], non_blocking=True); buf["ev_seg"].record()
-        _lib.check(lib.sumk_eval_device_spearman(scores_dev.data_ptr(), descr_dev.data_ptr(), n, buf["part"].data_ptr(), buf["corr"].data_ptr(), st),
-                   "sumk_eval_device_spearman")
+        if kendall:
+            kent = ent["kendall"]
+            kbuf = kent.get("buffers")
+            if kbuf is None:
+                kbuf = kent["buffers"] = dict(
+                    tau=torch.empty(max(1, lib.sumk_eval_device_kendall_scratch_bytes(n, frame0) // 8), dtype=torch.float64, device=dev),
+                    counts=torch.empty(4 * max(kent["users"], 1), dtype=torch.int64, device=dev),
+                    counts_host=torch.empty(4 * max(kent["users"], 1), dtype=torch.int64).pin_memory())
+            _lib.check(lib.sumk_eval_device_kendall(scores_dev.data_ptr(), descr_dev.data_ptr(), kent["descr_dev"].data_ptr(), n, kbuf["tau"].data_ptr(),
+                                                    buf["corr"].data_ptr(), kbuf["counts"].data_ptr() if counts_out is not None else None, st),
+                       "sumk_eval_device_kendall")
+            if counts_out is not None:
+                kbuf["counts_host"].copy_(kbuf["counts"], non_blocking=True)
+        else:
+            _lib.check(lib.sumk_eval_device_spearman(scores_dev.data_ptr(), descr_dev.data_ptr(), n, buf["part"].data_ptr(), buf["corr"].data_ptr(), st),
+                       "sumk_eval_device_spearman")
         buf["corr_host"].copy_(buf["corr"], non_blocking=True); buf["ev_corr"].record()
         seg_means = buf["seg_host"].numpy()[:seg0]       # (a view of the pinned buffer: valid once ev_seg has passed)
         arr = (_lib.EvalVideo * n)()
@@ -187,5 +281,7 @@ def evaluate_batch_device(videos, scores_dev, lens, proportion=0.15, method="kna
         finally:
             buf["ev_corr"].synchronize()      # the call never returns with its pinned buffers still being written
         corr = buf["corr_host"].numpy().copy()
+        if kendall and counts_out is not None:
+            counts_out[:] = _split_counts(ent["kendall"]["buffers"]["counts_host"].numpy()[:4 * ent["kendall"]["users"]], ent["kendall"]["per_video"])
         f_avg = np.array([arr[i].f_avg for i in range(n)]); f_max = np.array([arr[i].f_max for i in range(n)])
     return corr, f_avg, f_max, (summaries if want_summaries else None)
