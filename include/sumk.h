@@ -465,6 +465,24 @@ int sumk_gemm_prec(int32_t layout, const float* A, const float* B, float* C, int
  * bytes): deterministic split-K over a long K and C += product -- the weight-gradient form of vasnet.py:193-212's backward. */
 int sumk_gemm_bf16src(int32_t layout, const void* A_bf16, const void* B_bf16, float* C, int32_t M, int32_t N, int32_t K,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* ---- Positional embeddings on packed batches (csrc/posembed.hip; vasnet.py:106-112, transformer.py:82-88 with one video per call).
+ * sumk_pos_add_packed: y[off[v] + t, :] = x[off[v] + t, :] + table[t, :] for every video v of the batch, OUT OF PLACE (x is never
+ * written; the position comes from the sequence offsets, there is no row-index array).  Up to three outputs, NULL = not wanted:
+ *   out_f32   (n_rows, D) fp32 -- bit-equal to a plain fp32 add;
+ *   out_bf16  (n_rows, D) bf16 -- the rounding of sumk_cast_f32_bf16 applied to that sum (sumk_vasnet_opts::x16);
+ *   out_planes  the "KB planes" (below) of the (n_rows x D) sum with n_planes = 2 or 3, byte-equal to sumk_split_planes of it: every
+ *             row up to the pitch is written (zeros behind n_rows); the caller clears the last 8192 bytes of the array as for
+ *             sumk_split_planes.  The planes are made from x and the table in registers, not from an fp32 sum in memory.
+ * D % 4 == 0 (planes: D % 16 == 0); 16-byte aligned buffers.  A video longer than table_rows, or any other bad argument, returns
+ * SUMK_ERR_ARG and launches nothing.
+ * sumk_pos_table_grad: dtable[t, :] += sum over the videos with more than t frames of dx[off[v] + t, :] -- the gradient of a learnable
+ * table (nn.Embedding, vasnet.py:42).  One thread owns each (t, 4 columns): it starts from the value dtable holds and adds the videos
+ * in ascending order with plain fp32 adds (no atomics: bit-deterministic).  Rows at or above the longest video are not touched. */
+int sumk_pos_add_packed(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                        const float* table, int32_t table_rows, float* out_f32, void* out_bf16, void* out_planes,
+                        int32_t n_planes, void* stream);
+int sumk_pos_table_grad(const float* dx, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                        float* dtable, int32_t table_rows, void* stream);
 /* ---- "KB planes": the operand format of the plane-aware wide GEMM behind SUMK_PRECISION_BF16X6 / BF16X3 scoring (csrc/gemm_pw.hip).
  * An fp32 matrix (rows x K, K % 16 == 0) as n_planes = 3 (x = x1 + x2 + x3 exactly) or 2 (hi + lo) bf16 planes, k-blocked:
  *   byte offset of (row, k, plane p) = (((k / 16) * n_planes + p) * 2 + (k / 8) % 2) * 16 * pitch + row * 16 + (k % 8) * 2,

@@ -231,6 +231,9 @@ _SIGS = {
     "sumk_pack_rows_bf16": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), HOST_I32P, C.c_int32, C.c_int32, C.c_int32]),
     "sumk_gemm_prec": (C.c_int, [C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sumk_gemm_bf16src": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_pos_add_packed": (C.c_int, [c_f32p, C.c_int32, C.c_int32, HOST_I32P, c_i32p, c_f32p, C.c_int32, c_f32p, C.c_void_p, C.c_void_p,
+                                      C.c_int32, C.c_void_p]),
+    "sumk_pos_table_grad": (C.c_int, [c_f32p, C.c_int32, C.c_int32, HOST_I32P, c_i32p, c_f32p, C.c_int32, C.c_void_p]),
     "sumk_planes_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "sumk_split_planes": (C.c_int, [c_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sumk_gemm_planes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

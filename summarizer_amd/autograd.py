@@ -31,6 +31,34 @@ def _table_grad(table, rows, dx):
         table.grad.index_add_(0, rows.long(), dx)
 
 
+class PosAddPacked(torch.autograd.Function):
+    """xp = x + table[position] for a packed batch, out of place (sumk_pos_add_packed): (x, table, SeqBatch, want_bf16) -> xp, or
+    (xp, bf16(xp)) when want_bf16 (the mixed-precision step's shadow, sumk_vasnet_opts::x16; not differentiable).  Backward: a learnable
+    table's gradient is the deterministic gather sumk_pos_table_grad, accumulated IN PLACE into table.grad (FlatAdam's .grad is a view of
+    its flat bucket, see _table_grad); dx passes through to x."""
+
+    @staticmethod
+    def forward(ctx, x, table, sb, want_bf16=False):
+        xp, x16, _ = kernels.pos_add_packed(x, sb, table, want_f32=True, want_bf16=want_bf16)
+        ctx.sb, ctx.table = sb, table
+        ctx.table_is_param = isinstance(table, torch.nn.Parameter) and table.requires_grad
+        if want_bf16:
+            ctx.mark_non_differentiable(x16)
+            return xp, x16
+        return xp
+
+    @staticmethod
+    def backward(ctx, dxp, *_):
+        if ctx.table_is_param:
+            table = ctx.table
+            with torch.no_grad():
+                if table.grad is None:
+                    table.grad = torch.zeros_like(table)
+                kernels.pos_table_grad(dxp, ctx.sb, table.grad)
+        ctx.table = None
+        return (dxp if ctx.needs_input_grad[0] else None), None, None, None
+
+
 class VasnetFunction(torch.autograd.Function):
     """scores = VASNet(x) for a packed batch.  inputs: x, SeqBatch, opts, pos table/rows, param names, *params."""
 

@@ -207,6 +207,21 @@ def drop_shadows(x):
         x._sumk_shadows.clear()
 
 
+def pos_shadow(x, key, build):
+    """The positional sum (fp32 and / or planes) of a packed INFERENCE batch, kept ON the tensor object x like tensor_shadow's entries, but
+    ONE entry per x (a second copy of the batch: a table change replaces it instead of piling up beside it).  `key` carries everything the
+    sum depends on beside x's address: x's version, the table's identity / version, WEIGHTS_EPOCH, the stream that built it."""
+    hit = getattr(x, "_sumk_pos", None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    val = build()
+    try:
+        x._sumk_pos = (key, val)
+    except AttributeError:          # (an object that takes no attributes: no caching)
+        pass
+    return val
+
+
 def vasnet_x16(x, sb=None):
     """bf16(x) for the mixed-precision training step (sumk_vasnet_opts.x16): kept with the tensor OBJECT while its contents are unchanged
     (tensor_shadow) -- features packed once are constant over the epochs of a run; a loop that packs a fresh batch every step converts per
@@ -247,6 +262,42 @@ def gemm_planes(a_planes, a_rows, b_planes, b_rows, M, N, K, n_planes, variant=0
         out = torch.empty(M, N, dtype=torch.float32, device=a_planes.device)
     _lib.check(lib.sumk_gemm_planes(_p(a_planes), a_rows, _p(b_planes), b_rows, _p(out), M, N, K, n_planes, variant, _stream()), "sumk_gemm_planes")
     return out
+
+
+def pos_add_packed(x, sb, table, want_f32=True, want_bf16=False, n_planes=0):
+    """Positional embedding of a packed batch, out of place (csrc/posembed.hip): row off[v] + t gets table[t].  Returns
+    (fp32 sum or None, its bf16 rounding or None, its KB planes or None) -- whichever of the three were asked for, from ONE launch;
+    x is never written."""
+    lib = _lib.load()
+    _require_gpu(x, "pos_add_packed input"); _require_gpu(table, "pos_add_packed table")
+    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != sb.n_rows:
+        raise SumkError(f"pos_add_packed: input must be contiguous (n_rows={sb.n_rows}, D), got {tuple(x.shape)}")
+    D = x.shape[1]
+    if table.dim() != 2 or table.shape[1] != D or not table.is_contiguous() or table.device != x.device:
+        raise SumkError(f"pos_add_packed: table must be contiguous (max_length, {D}) on {x.device}, got {tuple(table.shape)} on {table.device}")
+    y32 = torch.empty_like(x) if want_f32 else None
+    y16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
+    planes = None
+    if n_planes:
+        nb = lib.sumk_planes_bytes(sb.n_rows, D, n_planes)
+        if nb == 0:
+            raise SumkError(f"pos_add_packed: rows={sb.n_rows} D={D} planes={n_planes} is not representable (D % 16, 2 or 3 planes)")
+        planes = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        planes[nb - 8192:].zero_()          # (as split_planes: the slack behind the last sub-array, which row tiles read past)
+    _lib.check(lib.sumk_pos_add_packed(_p(x), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, _p(table), table.shape[0], _p(y32), _p(y16), _p(planes),
+                                       int(n_planes), _stream()), "sumk_pos_add_packed")
+    return y32, y16, planes
+
+
+def pos_table_grad(dx, sb, dtable):
+    """dtable[t] += sum over the batch's videos longer than t of dx[off[v] + t], videos in ascending order (deterministic; csrc/posembed.hip)."""
+    _require_gpu(dx, "pos_table_grad dx"); _require_gpu(dtable, "pos_table_grad dtable")
+    if not dx.is_contiguous():
+        dx = dx.contiguous()
+    if dx.dim() != 2 or dx.shape[0] != sb.n_rows or dtable.dim() != 2 or dtable.shape[1] != dx.shape[1] or not dtable.is_contiguous():
+        raise SumkError(f"pos_table_grad: dx {tuple(dx.shape)} / dtable {tuple(dtable.shape)} do not fit {sb.n_rows} rows (contiguous, same D)")
+    _lib.check(_lib.load().sumk_pos_table_grad(_p(dx), dx.shape[1], sb.n_seq, sb.off_host_p, sb.off_dev_p, _p(dtable), dtable.shape[0], _stream()),
+               "sumk_pos_table_grad")
 
 
 def fold_vo(w_o, w_v, out=None):

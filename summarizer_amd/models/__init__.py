@@ -142,14 +142,8 @@ class Trainer:
     # ------------------------------------------------------------------ batched scoring (the hot path)
     def _score_keys(self, keys, max_frames_per_launch=1 << 17):
         """{key: (seq_len,) float32 numpy}.  Videos are packed back to back and scored in as few launches as the frame
-        budget allows; models with positional embeddings go through the per-video interface (they index by position)."""
+        budget allows (models with positional embeddings too: score_packed adds them per video, out of place)."""
         dev, out = self._device(), {}
-        if getattr(self.model, "max_length", None):
-            for key in keys:
-                feats = self._video_on_device(key, dev)[0]
-                out[key] = self.model(feats.unsqueeze(1).clone()).squeeze().detach().cpu().numpy()
-            kernels.health_check()
-            return out
         groups, cur, frames = [], [], 0
         for key in keys:
             T = self._video_on_device(key, dev)[0].shape[0]
@@ -186,9 +180,9 @@ class Trainer:
     def _test_on_device(self, keys, max_frames_per_launch=1 << 17):
         """Device-side evaluation tail: ONE packed scoring launch, then sumk_eval_device on the scores where they
         are; a single small D2H carries segment means + correlations to the host knapsack / F-score threads.  None when the batch does
-        not qualify (positional embeddings, more frames than one launch takes, metadata the kernel does not cover): the caller then
-        takes the host tail, which computes the same numbers."""
-        if getattr(self.model, "max_length", None) or not keys or not hasattr(self.model, "score_packed"):
+        not qualify (more frames than one launch takes, metadata the kernel does not cover): the caller then takes the host tail, which
+        computes the same numbers."""
+        if not keys or not hasattr(self.model, "score_packed"):
             return None
         dev = self._device()
         if dev.type != "cuda":

@@ -17,7 +17,7 @@ import torch.nn.init as init
 from .. import kernels
 from ..autograd import SegmentMseMeanFunction
 from . import Trainer
-from .vasnet import _sinusoid_table
+from .vasnet import _sinusoid_table, packed_pos_input
 from ..training import FlatAdam, dist_info, plan_shards, step_video_total
 
 
@@ -94,8 +94,19 @@ class Transformer(nn.Module):
         return s.view(batch_size, seq_len, 1).permute(1, 0, 2)
 
     def score_packed(self, x_packed, lens):
-        assert self.max_length is None, "score_packed does not take positional embeddings (use forward)"
-        return self._score(x_packed, kernels.SeqBatch.get(lens, x_packed.device), None, None)
+        """x_packed: (sum(lens), D) frames of several videos back to back -> (sum(lens),) scores.  With `max_length`, frame t of every
+        video gets row t of the positional table (transformer.py:82-88 at batch size 1) through an OUT-OF-PLACE add: score_packed never
+        mutates x_packed (only `forward` reproduces the reference's in-place add)."""
+        sb = kernels.SeqBatch.get(lens, x_packed.device)
+        if self.max_length is None:
+            return self._score(x_packed, sb, None, None)
+        # (the split-bf16 encoder splits its layer inputs itself: the fp32 sum is all it takes)
+        xp, _ = packed_pos_input(self, x_packed, sb, getattr(self, "precision", "fp32"), 0)
+        return self._score(xp, sb, None, None)
+
+    def load_state_dict(self, *args, **kwargs):
+        self._pos_gen = getattr(self, "_pos_gen", 0) + 1      # (packed_pos_input's cached sums)
+        return super().load_state_dict(*args, **kwargs)
 
     def _score(self, xp, sb, table, rows):
         p = dict(self.named_parameters())
@@ -169,7 +180,6 @@ class TransformerTrainer(Trainer):
         self.optimizer.broadcast()                 # identical weights on every rank: ONE collective over the flat bucket
         my_keys, sizes, steps_per_epoch = plan_shards(train_keys, lambda: [self.dataset[k]["features"].shape[0] for k in train_keys], bv)
         best = self._fold_best()
-        packed = self.model.max_length is None
         for epoch in range(self.hps.epochs):
             losses, dist_scores = [], {}
             random.shuffle(my_keys)
@@ -178,21 +188,15 @@ class TransformerTrainer(Trainer):
                 self.optimizer.zero_grad()
                 if keys:
                     vids = [self._video_on_device(k, dev, want_target=True) for k in keys]
-                    if packed:
-                        lens_b = [v[0].shape[0] for v in vids]
-                        x = vids[0][0] if len(vids) == 1 else torch.cat([v[0] for v in vids])
-                        target = vids[0][1] if len(vids) == 1 else torch.cat([v[1] for v in vids])
-                        scores = self.model.score_packed(x, lens_b)
-                        n_total = len(lens_b) if world == 1 else step_video_total(sizes, bv, step)
-                        loss = SegmentMseMeanFunction.apply(scores, target, kernels.SeqBatch.get(lens_b, dev), 1.0 / n_total)   # mean over videos of the MSE per video (transformer.py:161)
-                        for k, piece in zip(keys, torch.split(scores.detach(), lens_b)):
-                            dist_scores[k] = piece.view(-1, 1, 1)
-                    else:
-                        loss = 0
-                        for k, (seq, target) in zip(keys, vids):
-                            sc = self.model(seq.unsqueeze(1).clone())
-                            loss = loss + torch.mean((sc.view(-1) - target) ** 2) / (len(vids) if world == 1 else step_video_total(sizes, bv, step))
-                            dist_scores[k] = sc.detach()
+                    # (a model with max_pos takes this packed route too: score_packed adds the positions out of place)
+                    lens_b = [v[0].shape[0] for v in vids]
+                    x = vids[0][0] if len(vids) == 1 else torch.cat([v[0] for v in vids])
+                    target = vids[0][1] if len(vids) == 1 else torch.cat([v[1] for v in vids])
+                    scores = self.model.score_packed(x, lens_b)
+                    n_total = len(lens_b) if world == 1 else step_video_total(sizes, bv, step)
+                    loss = SegmentMseMeanFunction.apply(scores, target, kernels.SeqBatch.get(lens_b, dev), 1.0 / n_total)   # mean over videos of the MSE per video (transformer.py:161)
+                    for k, piece in zip(keys, torch.split(scores.detach(), lens_b)):
+                        dist_scores[k] = piece.view(-1, 1, 1)
                     loss.backward(gradient=_k_one(loss))
                     losses.append(loss.detach())
                 self.optimizer.step(grad_scale=self.optimizer.all_reduce_grads(average=False))

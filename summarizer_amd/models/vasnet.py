@@ -131,19 +131,29 @@ class VASNet(nn.Module):
 
     # ------------------------------------------------------------------ batched extension
     def score_packed(self, x_packed, lens):
-        """x_packed: (sum(lens), D) frames of several videos back to back -> (sum(lens),) scores."""
-        assert self.max_length is None, "score_packed does not take positional embeddings (use forward)"
+        """x_packed: (sum(lens), D) frames of several videos back to back -> (sum(lens),) scores.  Each video is one batch-size-1 call of
+        the reference: with `max_length`, frame t of every video gets row t of the positional table (vasnet.py:106-112).  The sum is
+        computed OUT OF PLACE: score_packed never mutates x_packed (only `forward` reproduces the reference's in-place add)."""
         sb = kernels.SeqBatch.get(lens, x_packed.device)
-        return self._score(x_packed, sb, None, None)
+        if self.max_length is None:
+            return self._score(x_packed, sb, None, None)
+        plane_path = self.precision in kernels.PLANES_OF and self.input_size % 256 == 0 and sb.n_rows >= 256      # (_score's own conditions)
+        xp, extra = packed_pos_input(self, x_packed, sb, self.precision, kernels.PLANES_OF[self.precision] if plane_path else 0)
+        return self._score(xp, sb, None, None, extra)
 
-    def _score(self, xp, sb, table, rows):
+    def _score(self, xp, sb, table, rows, extra=None):
+        """extra: entries for the call's options that the caller derived from xp itself (score_packed: the bf16 shadow / the planes that
+        came out of the positional add's launch)."""
         training = self.training and torch.is_grad_enabled()
         if training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             from ..autograd import VasnetFunction
             names = [k for _, k in kernels.VASNET_FIELDS]
             p = self._params()
-            return VasnetFunction.apply(xp, sb, self._opts(self.training), table, rows, names, *[p[n] for n in names])
+            opts = self._opts(self.training)
+            opts.update(extra or {})
+            return VasnetFunction.apply(xp, sb, opts, table, rows, names, *[p[n] for n in names])
         opts = self._opts(False)
+        opts.update(extra or {})
         wvo = self._folded() if self.fold_vo else None
         if self.precision in kernels.PLANES_OF and table is None and self.input_size % 256 == 0 and sb.n_rows >= 256:
             opts["wplanes"] = self._wplanes(wvo)          # split-bf16 scoring on operand planes (csrc/gemm_pw.hip)
@@ -198,6 +208,7 @@ class VASNet(nn.Module):
     def load_state_dict(self, *args, **kwargs):
         self._wvo_key = None
         self._wpl_key = None
+        self._pos_gen = getattr(self, "_pos_gen", 0) + 1      # (packed_pos_input's cached sums)
         return super().load_state_dict(*args, **kwargs)
 
 
@@ -209,6 +220,43 @@ def _sinusoid_table(max_length, d):
     tab[:, 0::2] = np.sin(pos / (10000 ** ((2 * i) / d)))
     tab[:, 1::2] = np.cos(pos / (10000 ** ((2 * (i + 1)) / d)))
     return torch.from_numpy(tab)
+
+
+def packed_pos_input(model, x, sb, precision, n_planes):
+    """(xp, extra options) for a packed batch of a model with `max_length` (VASNet and the Transformer scorer): xp = x + table[position]
+    from sumk_pos_add_packed, after which the packed pipeline runs as for a model without positions.
+    Under autograd (training, or any call that records a graph) the add is a PosAddPacked node and runs every call -- the learnable table
+    changes with each optimiser step; mixed-precision training takes bf16(xp) out of the same launch (options "x16").
+    Inference: n_planes > 0 (the caller's plane path will be taken) adds the KB planes of xp out of the same launch (options "xplanes");
+    the fp32 sum is still produced, the plane path reads it for the residual of the output projection.  The result is kept with the tensor
+    OBJECT x (kernels.pos_shadow, one entry per x) and rebuilt whenever x or the table may have changed: tensor versions, the table's
+    storage address, kernels.WEIGHTS_EPOCH (optimiser steps through the C ABI), load_state_dict, another stream."""
+    assert model.max_length >= max(sb.lens), "input sequence has higher length than max_length"     # vasnet.py:107 / transformer.py:83
+    kernels._require_gpu(x, f"{type(model).__name__}.score_packed")
+    if model.pos_embed_type == "simple":
+        table = model.pos_embed.weight
+    else:
+        if model.pos_embed.device != x.device:
+            model.pos_embed = model.pos_embed.to(x.device)
+        table = model.pos_embed
+    if torch.is_grad_enabled() and (model.training or any(p.requires_grad for p in model.parameters())):
+        from ..autograd import PosAddPacked
+        if model.training and precision == "bf16" and x.numel() % 4 == 0:
+            xp, x16 = PosAddPacked.apply(x, table, sb, True)
+            return xp, {"x16": x16}
+        return PosAddPacked.apply(x, table, sb, False), None
+
+    def build():
+        with torch.no_grad():
+            y32, _, planes = kernels.pos_add_packed(x, sb, table.detach(), want_f32=True, n_planes=n_planes)
+        return y32, planes
+    if torch.cuda.is_current_stream_capturing():
+        y32, planes = build()
+    else:
+        key = (x._version, id(model), getattr(model, "_pos_gen", 0), table.data_ptr(), table._version, kernels.WEIGHTS_EPOCH[0] if table.requires_grad or isinstance(table, nn.Parameter) else -1, id(sb), int(n_planes),
+               torch.cuda.current_stream(x.device).cuda_stream)
+        y32, planes = kernels.pos_shadow(x, key, build)
+    return y32, ({"xplanes": planes} if planes is not None else None)
 
 
 class _NotResident(RuntimeError):
@@ -274,9 +322,8 @@ class VASNetTrainer(Trainer):
         self.model.tail_grads_ready_event = torch.cuda.Event() if world > 1 else None
 
         best = self._fold_best()
-        use_packed = self.model.max_length is None
         # reference schedule as HIP graphs: one captured step per video, replayed from the second epoch on (class docstring)
-        use_graph = (world == 1 and bv == 1 and use_packed and dev.type == "cuda"
+        use_graph = (world == 1 and bv == 1 and dev.type == "cuda"
                      and str(self.hps.extra_params.get("hip_graph", "1")) not in ("0", "False", "false"))
         graphs, graph_pool, graphs_zeroed = {}, None, False
         if use_graph:
@@ -308,27 +355,21 @@ class VASNetTrainer(Trainer):
                 self.optimizer.zero_grad(zeroed_by_step=True)
                 if keys:
                     vids = [self._load_video(k, dev) for k in keys]
-                    if use_packed:
-                        lens_b = [v[0].shape[0] for v in vids]
-                        scores = self.model.score_packed(torch.cat([v[0] for v in vids]) if len(vids) > 1 else vids[0][0], lens_b)
-                        off = np.concatenate([[0], np.cumsum(lens_b)])
-                        # mean over videos of the per-video MSE (== nn.MSELoss per video, vasnet.py:209, when bv == 1)
-                        target = torch.cat([v[1] for v in vids]) if len(vids) > 1 else vids[0][1]
-                        # world == 1: plain mean; data-parallel: every video of the GLOBAL step weighs 1/n_total (ranks whose
-                        # shard has run out contribute nothing and the divisor shrinks with them)
-                        n_total = len(lens_b) if world == 1 else step_video_total(sizes, bv, step)
-                        loss = SegmentMseMeanFunction.apply(scores, target, kernels.SeqBatch.get(lens_b, dev), 1.0 / n_total)
-                        for i, k in enumerate(keys):
-                            dist_scores[k] = scores[off[i]:off[i + 1]].detach().view(-1, 1, 1)
-                    else:
-                        loss = 0
-                        for k, (seq, target) in zip(keys, vids):
-                            sc = self.model(seq.unsqueeze(1).clone())   # clone: the positional add is in place, seq is the HBM-cached copy
-                            loss = loss + torch.mean((sc.view(-1) - target) ** 2) / (len(vids) if world == 1 else step_video_total(sizes, bv, step))
-                            dist_scores[k] = sc.detach()
+                    # (a model with max_pos takes this packed route too: score_packed adds the positions out of place)
+                    lens_b = [v[0].shape[0] for v in vids]
+                    scores = self.model.score_packed(torch.cat([v[0] for v in vids]) if len(vids) > 1 else vids[0][0], lens_b)
+                    off = np.concatenate([[0], np.cumsum(lens_b)])
+                    # mean over videos of the per-video MSE (== nn.MSELoss per video, vasnet.py:209, when bv == 1)
+                    target = torch.cat([v[1] for v in vids]) if len(vids) > 1 else vids[0][1]
+                    # world == 1: plain mean; data-parallel: every video of the GLOBAL step weighs 1/n_total (ranks whose
+                    # shard has run out contribute nothing and the divisor shrinks with them)
+                    n_total = len(lens_b) if world == 1 else step_video_total(sizes, bv, step)
+                    loss = SegmentMseMeanFunction.apply(scores, target, kernels.SeqBatch.get(lens_b, dev), 1.0 / n_total)
+                    for i, k in enumerate(keys):
+                        dist_scores[k] = scores[off[i]:off[i + 1]].detach().view(-1, 1, 1)
                     loss.backward(gradient=_k_one(loss))
                     losses.append(loss.detach())
-                if tail_from is not None and use_packed:          # every rank issues the same two collectives, videos or not
+                if tail_from is not None:          # every rank issues the same two collectives, videos or not
                     if not keys:
                         self.model.tail_grads_ready_event.record()
                     self.optimizer.reduce_tail_async(tail_from, self.model.tail_grads_ready_event)
