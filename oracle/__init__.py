@@ -13,6 +13,8 @@ Pinning status (see DESIGN.md section "Oracle"):
     imported read-only in the build container (tests/golden/make_golden.py -> tests/golden/*.npz).
   * optim_np : float64 restatement of torch.optim.Adam + clip_grad_norm_ over a flat vector; pinned to stock torch run in
     float64 (tests/test_oracle.py), the reference of tests/test_gpu_optim.py.
+  * policy_np : the REINFORCE loss glue (dsn.py:113-140) and its gradient in any dtype; pinned to Bernoulli.log_prob + autograd in
+    float64 (tests/test_oracle.py), the reference of tests/test_gpu_reward_f64.py together with reward_np.reward_terms.
   * knapsack_np : PARITY UNPINNED.  The reference delegates to ortools==7.5.7466 (not vendored, not
     installable here) and no reference test holds a knapsack vector.  The DP here restates the published
     OR-tools KnapsackDynamicProgrammingSolver from memory; only the optimal VALUE is checked (brute force).

@@ -77,6 +77,179 @@ def features(T, B, D, seed):
     return (0.5 * np.abs(rng.standard_normal((T, B, D)))).astype(np.float32)
 
 
+def reward_features(kind, T, D, seed):
+    """(T, D) float32 features on which BOTH terms of DSN's reward are visible in fp32.  With `features` as it is the squared distance
+    between two frames grows with D (about 118 at D = 1024), so R_rep = exp(-mean min d2) underflows and a reward test compares R_div / 2
+    alone.  Both kinds scale the features by 2.35 / sqrt(D): distances are O(1) for every D (about 1 between unrelated frames) and the
+    cosine term is unchanged.
+      "scaled": `features` times that scale.
+      "shots":  a shot centre drawn like `features`, held for 8..16 frames (about 12), plus 0.05 N(0, 1) noise per frame: neighbouring
+                frames are near duplicates, so d2 = G[t][t] + G[p][p] - 2 G[t][p] is a small difference of large Gram entries."""
+    scale = np.float32(2.35 / np.sqrt(D))
+    if kind == "scaled":
+        return features(T, 1, D, seed)[:, 0, :] * scale
+    if kind != "shots":
+        raise KeyError(kind)
+    rng = np.random.default_rng([seed, 77])
+    rows = []
+    while len(rows) < T:
+        centre = 0.5 * np.abs(rng.standard_normal(D))
+        rows += [centre] * int(rng.integers(8, 17))
+    x = np.stack(rows[:T]) + 0.05 * rng.standard_normal((T, D))
+    return x.astype(np.float32) * scale
+
+
+def _reward_picks(rng, T, rate):
+    """(T,) float32 0/1 actions at pick rate `rate` with at least one pick."""
+    a = (rng.random(T) < rate).astype(np.float32)
+    if not a.any():
+        a[int(rng.integers(T))] = 1.0
+    return a
+
+
+REWARD_KINDS = ("scaled", "shots")
+REWARD_TILE_T = (1, 2, 3, 5, 63, 64, 65, 127, 128, 129, 257, 320)      # T % 4 != 0: the Gram row pitch (T + 3) & ~3; 64 k +- 1: its 64 x 64 tiles
+REWARD_TILE_D = (4, 8, 36, 100, 1024)                                   # D % 4 == 0 is required; 36 and 100 leave a K tail
+REWARD_EPISODE_LENS = (60, 1, 37, 130, 64)
+REWARD_FAMILIES = ("tiles", "isolation", "threshold", "many_videos", "episodes")
+
+
+def reward_family(name):
+    """The calls of one family of tests/test_gpu_reward_f64.py (tests/test_oracle.py checks on the float64 oracle that every one of them has
+    a visible R_rep).  A call is a dict: id, lens, D, xs (one (T, D) float32 array per video), acts ((E, sum(lens)) float32), far_sim, thre,
+    and for some families `expect`: {(episode, video): what the case isolates}."""
+    calls = []
+
+    def add(cid, xs, acts, thre=20, **extra):
+        acts = np.ascontiguousarray(np.atleast_2d(acts), dtype=np.float32)
+        if any(c["id"] == f"{cid}_far0" for c in calls):
+            return
+        for far in (False, True):
+            calls.append(dict(id=f"{cid}_far{int(far)}", lens=[x.shape[0] for x in xs], D=xs[0].shape[1], xs=xs, acts=acts, far_sim=far,
+                              thre=thre, **extra))
+
+    if name == "tiles":                                             # one video per call: tile and padding edges of the Gram GEMM
+        for ki, kind in enumerate(REWARD_KINDS):
+            for D in REWARD_TILE_D:
+                for T in REWARD_TILE_T:
+                    x = reward_features(kind, T, D, 5000 + 13 * T + D)
+                    for rate in (0.05, 0.4, 1.0):
+                        rng = np.random.default_rng([T, D, int(rate * 100), ki])
+                        add(f"{kind}_T{T}_D{D}_p{rate}", [x], _reward_picks(rng, T, rate))
+    elif name == "isolation":                                       # one pick: R_div = 0, reward = R_rep / 2; every frame picked: R_rep = 1
+        for kind in REWARD_KINDS:
+            for T, D in ((3, 8), (64, 100), (129, 36), (320, 100)):
+                x = reward_features(kind, T, D, 5100 + T + D)
+                for where, t in (("first", 0), ("middle", T // 2), ("last", T - 1)):
+                    a = np.zeros(T, np.float32)
+                    a[t] = 1.0
+                    add(f"{kind}_T{T}_D{D}_one_pick_{where}", [x], a, expect={(0, 0): "one_pick"})
+                add(f"{kind}_T{T}_D{D}_all_picked", [x], np.ones(T, np.float32), expect={(0, 0): "all_picked"})
+    elif name == "threshold":                                       # two picks `thre` and `thre + 1` frames apart, wherever a video of T = 70 has room
+        T, D = 70, 36
+        for kind in REWARD_KINDS:
+            x = reward_features(kind, T, D, 5200)
+            for thre in (0, 1, 20, T - 1, T + 5):
+                for dist, first in ((thre, 0), (thre + 1, 0), (thre, T - 1 - thre), (thre + 1, T - 2 - thre), (thre, 7), (thre + 1, 11),
+                                    (T - 1, 0)):
+                    if dist < 1 or first < 0 or first + dist > T - 1:
+                        continue
+                    a = np.zeros(T, np.float32)
+                    a[[first, first + dist]] = 1.0
+                    add(f"{kind}_thre{thre}_picks{first}_{first + dist}", [x], a, thre=thre,
+                        expect={(0, 0): "beyond_thre" if dist > thre else "within_thre"})
+    elif name == "many_videos":                                     # the second and third block of reward_setup_kernel; the offset search over many videos
+        D, E = 8, 3
+        for kind in REWARD_KINDS:
+            for n_seq in (64, 65, 130):
+                rng = np.random.default_rng([n_seq, REWARD_KINDS.index(kind)])
+                lens = [int(t) for t in rng.integers(1, 10, n_seq)]
+                if n_seq == 130:
+                    lens[70] = 129                                  # one long video behind the first block's 64
+                xs = [reward_features(kind, T, D, 5300 + 7 * i + n_seq) for i, T in enumerate(lens)]
+                acts = np.concatenate([np.stack([_reward_picks(rng, T, 0.7) for _ in range(E)]) for T in lens], axis=1)
+                add(f"{kind}_n{n_seq}", xs, acts)
+    elif name == "episodes":                                        # E episodes of a ragged batch in one call
+        D = 36
+        for kind in REWARD_KINDS:
+            xs = [reward_features(kind, T, D, 5400 + i) for i, T in enumerate(REWARD_EPISODE_LENS)]
+            off = np.concatenate([[0], np.cumsum(REWARD_EPISODE_LENS)])
+            for E in (1, 5, 9):
+                rng = np.random.default_rng([E, REWARD_KINDS.index(kind)])
+                acts = np.concatenate([np.stack([_reward_picks(rng, T, (0.4, 0.1, 0.7)[e % 3]) for e in range(E)]) for T in REWARD_EPISODE_LENS], axis=1)
+                expect = {}
+                # action values other than 1.0 are picks too, -0.0 is none (episode 0 of every E)
+                picked = np.flatnonzero(acts[0])
+                acts[0, picked[0::3]] = 2.0
+                acts[0, picked[1::3]] = -1.0
+                acts[0, np.flatnonzero(acts[0] == 0)[::2]] = -0.0
+                if E >= 5:
+                    acts[1, :] = 0.0                                # nothing picked anywhere: reward exactly 0
+                    acts[1, ::3] = -0.0
+                    acts[2, :] = 0.0                                # one pick per video
+                    for s, T in enumerate(REWARD_EPISODE_LENS):
+                        acts[2, off[s] + (7 * s) % T] = 1.0
+                    acts[3, :] = 1.0                                # every frame picked
+                    for s in range(len(REWARD_EPISODE_LENS)):
+                        expect.update({(1, s): "no_pick", (2, s): "one_pick", (3, s): "all_picked"})
+                add(f"{kind}_E{E}", xs, acts, expect=expect)
+    else:
+        raise KeyError(name)
+    return calls
+
+
+POLICY_BATCHES = ("ragged", "short")
+POLICY_CLAMP = np.float32(np.finfo(np.float32).eps)                 # clamp_probs of torch.distributions in fp32
+
+
+def policy_case(batch, E):
+    """Inputs of the REINFORCE loss kernels for tests/test_gpu_reward_f64.py: dict(lens, probs (R,), actions (E, R), rewards (E, V), base (V,),
+    dlv (V,), outside: rows whose probability lies outside the clamp).  All float32.
+      "ragged": T = 1, 255, 256, 257, 513, 1100 -- one to five passes of the kernels' 256-frame stride; "short": 70 videos of 1..9 frames.
+    The inputs are WELL CONDITIONED on purpose, so that the float64 comparison measures the kernels' rounding and not a cancellation that the
+    fp32 yardstick would share only by chance:
+      * probabilities of a video lie in [0.02, 0.3] (even videos) or [0.7, 0.98] (odd videos), so mean p - 0.5 (target 0.5) keeps at least
+        0.2 of its operands' size -- the length penalty's gradient 2 beta (mean p - eps) is the WHOLE gradient outside the clamp;
+      * per video the advantages r - b are all positive (baseline 0.1 under rewards in [0.3, 0.8]), all negative (baseline 2.0: beyond the length penalty at beta = 1, which has the other sign) or, for every
+        third video without a special probability (E >= 3), positive but for one episode (reward 0.05 under a baseline of 0.25).
+    Special probabilities sit on their video's side: 0, eps, one ulp below eps, 1e-9 in low videos; 1, 1 - eps, one ulp above 1 - eps in high
+    ones -- in the ragged batch behind the first, second and fourth 256-frame pass as well as in front.  The upstream gradient has both signs
+    and is exactly 0 for every fifth video."""
+    c = POLICY_CLAMP
+    below, above = np.nextafter(c, np.float32(0)), np.nextafter(np.float32(1) - c, np.float32(1))
+    if batch == "ragged":
+        lens = [1, 255, 256, 257, 513, 1100]
+        special = {2: {255: 0.0}, 3: {256: 1.0, 0: np.float32(1) - c},
+                   4: {2: 0.0, 256: c, 400: below, 512: 1e-9, 511: c}, 5: {3: 1.0, 300: np.float32(1) - c, 600: above, 1099: 1.0, 1024: np.float32(1) - c}}
+    elif batch == "short":
+        rng_t = np.random.default_rng(41)
+        lens = [int(t) for t in rng_t.integers(1, 10, 70)]
+        lens[0], lens[3] = 1, 1                                     # a video that is one clamped frame: no log-prob gradient at all
+        special = {0: {0: 0.0}, 3: {0: 1.0}, 4: {0: c}, 7: {lens[7] - 1: np.float32(1) - c}, 12: {0: 1e-9}, 65: {0: above}, 68: {lens[68] - 1: below}}
+    else:
+        raise KeyError(batch)
+    V, off = len(lens), np.concatenate([[0], np.cumsum(lens)])
+    rng = np.random.default_rng([E, POLICY_BATCHES.index(batch), 9])
+    probs = np.empty(off[-1], np.float32)
+    for v in range(V):
+        lo = 0.02 if v % 2 == 0 else 0.7
+        probs[off[v]:off[v + 1]] = rng.uniform(lo, lo + 0.28, lens[v]).astype(np.float32)
+        for t, val in special.get(v, {}).items():
+            probs[off[v] + t] = np.float32(val)
+    actions = (rng.random((E, off[-1])) < 0.4).astype(np.float32)
+    rewards = rng.uniform(0.3, 0.8, (E, V)).astype(np.float32)
+    base = np.empty(V, np.float32)
+    for v in range(V):
+        pattern = v % 3 if v not in special and E >= 3 else v % 2
+        base[v] = (0.1, 2.0, 0.25)[pattern]
+        if pattern == 2:
+            rewards[v % E, v] = 0.05
+    dlv = (rng.uniform(0.5, 1.5, V) * np.where(rng.random(V) < 0.5, -1.0, 1.0)).astype(np.float32)
+    dlv[1::5] = 0.0
+    outside = np.flatnonzero((probs < c) | (probs > np.float32(1) - c))
+    return dict(lens=lens, probs=probs, actions=actions, rewards=rewards, base=base, dlv=dlv, outside=outside)
+
+
 def digest(arrs):
     h = hashlib.sha256()
     for k in sorted(arrs):

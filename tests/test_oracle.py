@@ -527,3 +527,89 @@ def test_host_eval_tail_refuses_scores_two_short_of_the_intervals():
     with pytest.raises(_lib.SumkError, match="more pick intervals than scores"):
         eval_native.evaluate_batch([pv], [s], 0.15, "knapsack")
     eval_native.evaluate_batch([pv], [np.linspace(0, 1, 39, dtype=np.float32)], 0.15, "knapsack")        # one short is the defined case
+
+
+# ------------------------------------------------------------------------------------------------ DSN reward terms and REINFORCE loss
+def test_reward_terms_is_what_compute_reward_returns():
+    g = load_golden("reward")
+    for ci in range(5):
+        for far in (False, True):
+            for dt in (np.float32, np.float64):
+                d, r, rew = reward_np.reward_terms(g[f"c{ci}/seq"], g[f"c{ci}/actions"], far, 20, dt)
+                got = reward_np.compute_reward(g[f"c{ci}/seq"], g[f"c{ci}/actions"], far_sim=far, dtype=dt)
+                assert type(got) is dt and got.tobytes() == rew.tobytes()
+                assert rew == dt((d + r) * dt(0.5)) and 0 <= r <= 1
+    assert reward_np.reward_terms(g["c3/seq"], g["c3/actions"], False, 20, np.float64) == (0.0, 0.0, 0.0)
+
+
+@pytest.mark.parametrize("family", R.REWARD_FAMILIES)
+def test_reward_recipes_show_both_terms_in_fp32(family):
+    """The conditions tests/test_gpu_reward_f64.py relies on, on the oracle alone: every reward it compares has 0.2 <= R_rep <= 1 (both
+    terms are far above the gate of about 1e-6), the fp32 oracle -- the yardstick -- is within 1e-6 of the float64 one, and the cases
+    that isolate a term do so in float64."""
+    worst, n = 0.0, 0
+    for call in R.reward_family(family):
+        off = np.concatenate([[0], np.cumsum(call["lens"])])
+        for e in range(call["acts"].shape[0]):
+            for s, x in enumerate(call["xs"]):
+                a = call["acts"][e, off[s]:off[s + 1]]
+                d64, r64, rew64 = reward_np.reward_terms(x, a, call["far_sim"], call["thre"], np.float64)
+                rew32 = reward_np.compute_reward(x, a, call["far_sim"], call["thre"], np.float32)
+                what = call.get("expect", {}).get((e, s))
+                cid = (call["id"], e, s, what)
+                if what == "no_pick":
+                    assert not np.nonzero(a)[0].size and rew64 == 0 and rew32 == 0, cid
+                    continue
+                assert np.nonzero(a)[0].size >= 1 and np.isfinite(rew64), cid
+                assert 0.2 <= r64 <= 1 + 1e-12, (cid, r64)
+                assert abs(float(rew32) - rew64) <= 1e-6, (cid, rew32, rew64)
+                worst, n = max(worst, abs(float(rew32) - rew64)), n + 1
+                if what == "one_pick":
+                    assert d64 == 0 and rew64 == r64 / 2, cid
+                elif what == "all_picked":
+                    assert abs(r64 - 1) < 1e-12, (cid, r64)
+                elif what == "beyond_thre":                          # two picks more than `thre` apart: R_div = 1 unless far_sim
+                    assert (abs(d64 - 1) < 1e-12) != call["far_sim"], (cid, d64)
+                elif what == "within_thre":                          # R_div = 1 - cos: the features are non-negative, so well below 1
+                    assert 0 < d64 < 0.9, (cid, d64)
+    print("REWARD-RECIPES", family, "cases", n, "largest |fp32 oracle - float64 oracle|", worst)
+    assert n > 0
+
+
+@pytest.mark.parametrize("beta", [0.0, 0.01, 1.0])
+@pytest.mark.parametrize("E", [1, 17])
+def test_policy_np_vs_bernoulli_log_prob_autograd_in_float64(E, beta):
+    """oracle/policy_np (forward and gradient, the closed clamp range included) against torch.distributions.Bernoulli.log_prob with
+    autograd in float64.  The probabilities are clamped with finfo(float32).eps in front of the distribution (whose own float64 clamp
+    is then idle): the kernels mirror the fp32 program."""
+    from torch.distributions import Bernoulli
+    from oracle import policy_np
+    c = R.policy_case("short", E)
+    lens, eps = c["lens"], 0.5
+    off = np.concatenate([[0], np.cumsum(lens)])
+    ce = float(np.finfo(np.float32).eps)
+    assert policy_np.CLAMP == ce == float(R.POLICY_CLAMP)
+    p = torch.from_numpy(c["probs"].astype(np.float64)).requires_grad_(True)
+    a, r, b, w = (torch.from_numpy(c[k].astype(np.float64)) for k in ("actions", "rewards", "base", "dlv"))
+    logp = Bernoulli(probs=p.clamp(ce, 1 - ce), validate_args=False).log_prob(a)                                   # (E, R)
+    lv = torch.stack([beta * (p[off[v]:off[v + 1]].mean() - eps) ** 2 - (logp[:, off[v]:off[v + 1]].mean(dim=1) * (r[:, v] - b[v])).sum()
+                      for v in range(len(lens))]) / E
+    (lv * w).sum().backward()
+    got_l, cond = policy_np.forward(c["probs"], lens, c["actions"], c["rewards"], c["base"], beta, eps, np.float64)
+    got_g, mag = policy_np.backward(c["probs"], lens, c["actions"], c["rewards"], c["base"], beta, eps, c["dlv"], np.float64)
+    np.testing.assert_allclose(got_l, lv.detach().numpy(), rtol=1e-12, atol=0)
+    np.testing.assert_allclose(got_g, p.grad.numpy(), rtol=1e-11, atol=1e-300)
+    assert (np.abs(got_g) <= mag * (1 + 1e-12)).all() and cond.min() >= 1 - 1e-12
+    # outside the closed clamp range only the length penalty is left; ON its ends (eps, 1 - eps) the log-prob gradient passes
+    out = c["outside"]
+    assert out.size >= 5 and np.isin(np.flatnonzero((c["probs"] == R.POLICY_CLAMP) | (c["probs"] == 1 - R.POLICY_CLAMP)), out).sum() == 0
+    vid = np.searchsorted(off, out, side="right") - 1
+    mp = np.array([c["probs"][off[v]:off[v + 1]].astype(np.float64).mean() for v in range(len(lens))])
+    want = c["dlv"].astype(np.float64)[vid] * 2 * beta * (mp[vid] - eps) / (E * np.asarray(lens)[vid])
+    np.testing.assert_allclose(p.grad.numpy()[out], want, rtol=1e-12, atol=0)
+    on_end = np.flatnonzero((c["probs"] == R.POLICY_CLAMP) | (c["probs"] == 1 - R.POLICY_CLAMP))
+    live = on_end[c["dlv"][np.searchsorted(off, on_end, side="right") - 1] != 0]
+    vl = np.searchsorted(off, live, side="right") - 1
+    pen = c["dlv"].astype(np.float64)[vl] * 2 * beta * (mp[vl] - eps) / (E * np.asarray(lens)[vl])
+    # (|sum_e adv_e (a - pc) / (pc (1 - pc))| >= 0.2 there: these videos' advantages have one sign and |a - pc| / (pc (1 - pc)) >= 1)
+    assert live.size and (np.abs(p.grad.numpy()[live] - pen) >= 0.2 * np.abs(c["dlv"][vl]) / (E * np.asarray(lens)[vl])).all()
