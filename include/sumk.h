@@ -510,6 +510,36 @@ int sumk_gemm_nn(const float* A, const float* B, float* C, int32_t M, int32_t N,
 /* C(M,N) = A^T * B with A given as (K,M), B as (K,N) */
 int sumk_gemm_tn(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ change points (KTS)
+ * Kernel temporal segmentation (Potapov et al. 2014) of every video of a packed batch (csrc/kts.hip).  No reference counterpart: the
+ * reference READS `change_points` / `n_frame_per_seg` (summarizer/utils/eval.py:74-94) that were prepared offline with KTS
+ * (summarizer/datasets/README.md); these calls are that step, so scores become key shots for videos that come without the fields.
+ * Per video of n = seq_off[v + 1] - seq_off[v] steps, with K = X X^T (exact fp32 MFMA) and everything behind it in float64:
+ *   J[i,j]  = sum_{t=i..j} K[t,t] - (1 / (j - i + 1)) sum_{s,t=i..j} K[s,t]                       scatter of the segment i..j
+ *   I[0,l]  = J[0,l-1] for lmin <= l < lmax (EXCLUSIVE upper bound: the original's quirk), 1e101 elsewhere
+ *   I[k,l]  = min_{max(k lmin, l - lmax) <= t < l} I[k-1,t] + J[t,l-1],  p[k,l] = the SMALLEST minimising t        (cpd_nonlin)
+ *   cost[k] = I[k,n] / n + (vmax k / (2 n)) (ln(n / k) + 1),  m_best = the SMALLEST minimising k; infinite scores never win   (cpd_auto)
+ *   cps     = backtrack through p from (m_best, n): ascending step indices, each the first step of a new segment.
+ * A video shorter than max_ncp + 1 steps is treated as max_ncp = n - 1 (n == 1: no change point).  Outputs (device): n_cps (n_seq) =
+ * m_best; cps (n_seq, max_ncp), -1 behind n_cps[v]; scores (n_seq, max_ncp + 1) or NULL = I[k,n] for k <= n_cps[v], +inf where it
+ * exceeds 1e99 and behind n_cps[v].  Limits: 1 <= n <= 16384 per video, D % 4 == 0, 1 <= lmin <= lmax, 0 <= max_ncp <= longest
+ * video - 1; anything else -- a short workspace included -- returns SUMK_ERR_ARG and launches nothing.  One workgroup per video runs
+ * the max_ncp dependent steps; ties resolve to the smallest index and nothing is accumulated with atomics: results are
+ * bit-deterministic.  No host synchronisation inside the calls.
+ * sumk_kts_workspace_bytes: pure host arithmetic (0 = bad arguments); the size serves all three calls.
+ * sumk_kts_gram: the classic interface -- the caller's float64 kernel matrices, (n_v x n_v) blocks back to back, any kernel.
+ * sumk_kts_gram_nonlin: cpd_nonlin itself -- the backtrack from row min(ncp, n - 1) with no penalty; scores = the whole row I[., n]. */
+size_t sumk_kts_workspace_bytes(int32_t D, int32_t n_seq, const int32_t* seq_off_host, int32_t max_ncp);
+int sumk_kts(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, int32_t max_ncp,
+             int32_t lmin, int32_t lmax, double vmax, int32_t* n_cps, int32_t* cps, double* scores, void* workspace,
+             size_t workspace_bytes, void* stream);
+int sumk_kts_gram(const double* K, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, int32_t max_ncp,
+                  int32_t lmin, int32_t lmax, double vmax, int32_t* n_cps, int32_t* cps, double* scores, void* workspace,
+                  size_t workspace_bytes, void* stream);
+int sumk_kts_gram_nonlin(const double* K, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, int32_t ncp,
+                         int32_t lmin, int32_t lmax, int32_t* n_cps, int32_t* cps, double* scores, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ shot selection
  * HOST function (no GPU work).  Replaces knapsack_ortools (summarizer/utils/knapsack.py:5-23): maximise
  * sum(values[i]) subject to sum(weights[i]) <= capacity; selected[i] = 1 for chosen items.  values/weights are the

@@ -25,6 +25,18 @@ OPT_IN_ALIASES = {
 }
 
 
+__all__ = ["Summarizer", "install_as_reference", "REFERENCE_ALIASES", "OPT_IN_ALIASES"]
+
+
+def __getattr__(name):
+    # `from summarizer_amd import Summarizer` (features in, summary out: summarize.py); resolved on first use so that importing the
+    # package stays free of torch
+    if name == "Summarizer":
+        from .summarize import Summarizer
+        return Summarizer
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def install_as_reference(opt_in=()):
     """Make the reference's OWN files run on the HIP path without editing them: after this call
     `from summarizer.models.vasnet import VASNetTrainer` (summarizer/utils/config.py:12-18) -- and the same for dsn, sumgan,

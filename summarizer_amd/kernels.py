@@ -646,6 +646,64 @@ def dsn_reward(x, sb, actions, far_sim=False, temp_dist_thre=20):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ change points (KTS)
+KTS_MAX_STEPS = 16384      # per video: sumk_kts (include/sumk.h)
+
+
+def kts_workspace_bytes(D, sb, max_ncp):
+    return _lib.load().sumk_kts_workspace_bytes(int(D), sb.n_seq, sb.off_host_p, int(max_ncp))
+
+
+def _kts_call(name, src, sb, D, max_ncp, lmin, lmax, vmax, want_scores):
+    lib = _lib.load()
+    max_ncp, lmin, lmax = int(max_ncp), int(min(lmin, 2 ** 31 - 1)), int(min(lmax, 2 ** 31 - 1))
+    nb = lib.sumk_kts_workspace_bytes(D, sb.n_seq, sb.off_host_p, max_ncp)
+    if nb == 0:
+        _lib.check(-1, "sumk_kts_workspace_bytes")
+    ws = workspace(nb, src.device)
+    n_cps = torch.empty(sb.n_seq, dtype=torch.int32, device=src.device)
+    cps = torch.empty(sb.n_seq, max(max_ncp, 1), dtype=torch.int32, device=src.device)[:, :max_ncp]
+    scores = torch.empty(sb.n_seq, max_ncp + 1, dtype=torch.float64, device=src.device) if want_scores else None
+    tail = (_p(n_cps), _p(cps), _p(scores), _p(ws), ws.numel(), _stream())
+    if name == "sumk_kts":
+        rc = lib.sumk_kts(_p(src), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, max_ncp, lmin, lmax, float(vmax), *tail)
+    elif name == "sumk_kts_gram":
+        rc = lib.sumk_kts_gram(_p(src), sb.n_seq, sb.off_host_p, sb.off_dev_p, max_ncp, lmin, lmax, float(vmax), *tail)
+    else:
+        rc = lib.sumk_kts_gram_nonlin(_p(src), sb.n_seq, sb.off_host_p, sb.off_dev_p, max_ncp, lmin, lmax, *tail)
+    _lib.check(rc, name)
+    return n_cps, cps, scores
+
+
+def kts(x, sb, max_ncp, vmax=1.0, lmin=1, lmax=100000, want_scores=True):
+    """cpd_auto of every video of a packed batch from its features x (n_rows, D): (n_cps (n_seq,) int32, cps (n_seq, max_ncp) int32 with -1
+    behind n_cps[v], scores (n_seq, max_ncp + 1) float64 with +inf behind n_cps[v] or None) as device tensors (sumk_kts, include/sumk.h).
+    Only enqueues work on the current stream."""
+    _require_gpu(x, "kts features")
+    if x.dim() != 2 or x.shape[0] != sb.n_rows or not x.is_contiguous():
+        raise SumkError(f"kts: features must be contiguous ({sb.n_rows}, D), got {tuple(x.shape)}")
+    return _kts_call("sumk_kts", x, sb, x.shape[1], max_ncp, lmin, lmax, vmax, want_scores)
+
+
+def _kts_gram_check(K, sb):
+    want = sum(n * n for n in sb.lens)
+    if not K.is_cuda or K.dtype != torch.float64 or K.dim() != 1 or K.numel() != want or not K.is_contiguous():
+        raise SumkError(f"kts_gram: expected a flat contiguous float64 GPU tensor of {want} elements ((n x n) blocks back to back), got "
+                        f"{K.dtype} {tuple(K.shape)} on {K.device}")
+
+
+def kts_gram(K, sb, max_ncp, vmax=1.0, lmin=1, lmax=100000, want_scores=True):
+    """The same from the caller's float64 kernel matrices: K is flat, the (n_v x n_v) blocks back to back (sumk_kts_gram)."""
+    _kts_gram_check(K, sb)
+    return _kts_call("sumk_kts_gram", K, sb, 4, max_ncp, lmin, lmax, vmax, want_scores)
+
+
+def kts_gram_nonlin(K, sb, ncp, lmin=1, lmax=100000, want_scores=True):
+    """cpd_nonlin: the fixed-m backtrack from row min(ncp, n - 1), no penalty; scores = the whole row I[., n] (sumk_kts_gram_nonlin)."""
+    _kts_gram_check(K, sb)
+    return _kts_call("sumk_kts_gram_nonlin", K, sb, 4, ncp, lmin, lmax, 1.0, want_scores)
+
+
 def dsn_policy_loss_forward(probs, sb, actions, rewards, base, beta, eps_target):
     """(loss_per_video (n_seq,), mean_probs (n_seq,)) of sumk_dsn_policy_loss_forward (include/sumk.h)."""
     lib = _lib.load()

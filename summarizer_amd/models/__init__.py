@@ -130,11 +130,20 @@ class Trainer:
                 m.user_scores = rec["user_scores"][...]
                 m.user_ranks = ev.rank_users(m.user_scores)       # constant per video: ranked once, not per evaluation
             else:
-                if "change_points" not in rec:
+                source = getattr(self.hps, "change_points", "dataset")
+                if source not in ("dataset", "kts"):
+                    raise KeyError(f"Unknown change_points source {source}")
+                if "change_points" in rec:
+                    m.cps = rec["change_points"][...]
+                    m.nfps = rec["n_frame_per_seg"][...].tolist()
+                elif source == "kts":
+                    # opt-in (hps.change_points = "kts"): segment the video's own features on the device, once (utils/kts.py)
+                    from ..utils import kts
+                    cps, nfps = kts.segment(self._video_on_device(key, self._device())[0], picks=m.picks, n_frames=m.n_frames)
+                    m.cps, m.nfps = cps, nfps.tolist()
+                else:
                     raise Exception(f"No /change_points in video {key} for summary evaluation, "
                                     "make sure you have up-to-date .h5 dataset files.")
-                m.cps = rec["change_points"][...]
-                m.nfps = rec["n_frame_per_seg"][...].tolist()
                 m.user_summary = rec["user_summary"][...]
             m.loaded.add(need)
         return m
