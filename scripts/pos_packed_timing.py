@@ -85,7 +85,7 @@ tr.model.train()
 tr.optimizer = FlatAdam(tr.model.parameters(), lr=1e-5)
 tr.model.graph_seed = torch.zeros(1, dtype=torch.int64, device=dev)
 key = keys[0]
-seq, target = tr._load_video(key, dev)
+seq, target = tr._video_on_device(key, dev, want_target=True)
 for _ in range(3):
     tr._single_video_step(key, dev)
 graph = tr._capture_step(key, dev, None)

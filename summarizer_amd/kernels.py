@@ -2,6 +2,7 @@
 torch.autograd.Function wrappers.  Every arithmetic result comes from libsumk.so; nothing here computes on
 the CPU or through torch ops (torch only allocates the buffers and carries the stream)."""
 import ctypes as C
+import os
 import numpy as np
 import torch
 
@@ -15,6 +16,26 @@ def _require_gpu(t, what):
                         "HIP path (no CPU fallback); move the model and inputs to cuda.")
     if t.dtype != torch.float32:
         raise SumkError(f"{what}: expected float32, got {t.dtype}")
+
+
+def _ptr(t, what):
+    _require_gpu(t, what)
+    if not t.is_contiguous():
+        raise SumkError(f"{what} must be contiguous")
+    return t.data_ptr()
+
+
+def _check_rows(x, sb, what, col="D"):
+    _require_gpu(x, what)
+    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != sb.n_rows:
+        raise SumkError(f"{what} must be contiguous (n_rows={sb.n_rows}, {col}), got {tuple(x.shape)}")
+
+
+def _nonzero(nbytes, name):
+    """A workspace-size query's answer; 0 is the library's refusal (its message is in sumk_last_error)."""
+    if nbytes == 0:
+        _lib.check(-1, name)
+    return nbytes
 
 
 def _stream():
@@ -95,8 +116,34 @@ def one(device):
     return t
 
 
+def one_for(loss):
+    """The root gradient for `loss.backward(gradient=...)`: one(device) for a float32 GPU scalar, None (autograd's default) otherwise."""
+    return one(loss.device) if loss.is_cuda and loss.dim() == 0 and loss.dtype == torch.float32 else None
+
+
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _aligned_block(nb, device, out=None):
+    """A 256-byte aligned uint8 view of at least nb bytes that carries its backing tensor as `_sumk_keep`.  out: an earlier backing tensor,
+    re-used when it is large enough and on `device`."""
+    if out is None or out.numel() < nb + 256 or out.device != device:
+        out = torch.empty(nb + 256, dtype=torch.uint8, device=device)
+    view = out[(out.data_ptr() + 255) // 256 * 256 - out.data_ptr():]
+    view._sumk_keep = out
+    return view
+
+
+def _planes_buffer(rows, K, n_planes, device, what, col="K"):
+    """An uninitialised KB-plane array (include/sumk.h "KB planes") for a kernel that writes every row up to the pitch, zeros behind `rows`:
+    only the slack behind the last sub-array, which row tiles read past, is filled here."""
+    nb = _lib.load().sumk_planes_bytes(rows, K, n_planes)
+    if nb == 0:
+        raise SumkError(f"{what}: rows={rows} {col}={K} planes={n_planes} is not representable ({col} % 16, 2 or 3 planes)")
+    out = torch.empty(nb, dtype=torch.uint8, device=device)
+    out[nb - 8192:].zero_()
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ VASNet
@@ -129,25 +176,18 @@ def vasnet_tables(sb, D, training, precision_id):
     t = tabs.get(key)
     if t is None:
         lib = _lib.load()
-        nb = lib.sumk_vasnet_tables_bytes(int(D), sb.n_seq, sb.off_host_p)
-        if nb == 0:
-            _lib.check(-1, "sumk_vasnet_tables_bytes")
-        t = torch.empty(nb + 256, dtype=torch.uint8, device=sb.device)
-        base = (t.data_ptr() + 255) // 256 * 256
-        _lib.check(lib.sumk_vasnet_build_tables(int(D), sb.n_seq, sb.off_host_p, sb.off_dev_p, key[1], key[2], C.c_void_p(base), nb, _stream()),
+        nb = _nonzero(lib.sumk_vasnet_tables_bytes(int(D), sb.n_seq, sb.off_host_p), "sumk_vasnet_tables_bytes")
+        t = _aligned_block(nb, sb.device)
+        _lib.check(lib.sumk_vasnet_build_tables(int(D), sb.n_seq, sb.off_host_p, sb.off_dev_p, key[1], key[2], _p(t), nb, _stream()),
                    "sumk_vasnet_build_tables")
-        t = tabs[key] = (t, base)
-    return t[1]
+        tabs[key] = t
+    return t.data_ptr()
 
 
 def _vasnet_structs(params, opts):
     w = _lib.VasnetWeights()
     for f, k in VASNET_FIELDS:
-        t = params[k]
-        _require_gpu(t, f"VASNet weight {k}")
-        if not t.is_contiguous():
-            raise SumkError(f"VASNet weight {k} must be contiguous")
-        setattr(w, f, t.data_ptr())
+        setattr(w, f, _ptr(params[k], f"VASNet weight {k}"))
     o = _lib.VasnetOpts(float(opts["scale"]), float(opts["eps"]), int(bool(opts.get("ignore_self", False))),
                         -1 if opts.get("aperture") is None else int(opts["aperture"]),
                         float(opts.get("dropout_p", 0.0)), int(opts.get("seed", 0)), precision_code(opts.get("precision")),
@@ -168,13 +208,8 @@ def vasnet_wplanes(params, D, n_planes, wvo=None, out=None):
     w = _lib.VasnetWeights()
     for f, k in VASNET_FIELDS:
         setattr(w, f, params[k].data_ptr())
-    dev = params[VASNET_FIELDS[0][1]].device
-    if out is None or out.numel() < nb + 256 or out.device != dev:
-        out = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-    base = (out.data_ptr() + 255) // 256 * 256
-    _lib.check(lib.sumk_vasnet_wplanes_build(int(D), C.byref(w), _p(wvo), int(n_planes), C.c_void_p(base), nb, _stream()), "sumk_vasnet_wplanes_build")
-    view = out[base - out.data_ptr():]
-    view._sumk_keep = out
+    view = _aligned_block(nb, params[VASNET_FIELDS[0][1]].device, out)
+    _lib.check(lib.sumk_vasnet_wplanes_build(int(D), C.byref(w), _p(wvo), int(n_planes), _p(view), nb, _stream()), "sumk_vasnet_wplanes_build")
     return view
 
 
@@ -199,6 +234,29 @@ def tensor_shadow(x, name, build):
     val = build()
     d[name] = (x._version, val, stream)
     return val
+
+
+def weights_key(tensors, *extra):
+    """What a block derived from weights is keyed by: storage addresses and tensor versions (what torch can see), WEIGHTS_EPOCH (bumped by
+    every optimiser step through the C ABI, invisible to torch), `extra` (precision ...) and, last, the current stream: the block is built
+    by kernels on it, a call on another stream builds its own."""
+    t0 = tensors[0]
+    return tuple(t.data_ptr() for t in tensors) + tuple(t._version for t in tensors) + (WEIGHTS_EPOCH[0],) + extra + (
+        torch.cuda.current_stream(t0.device).cuda_stream if t0.is_cuda else 0,)
+
+
+def cached_block(owner, slot, key, build):
+    """The block (or list of blocks) `build(out)` makes from owner's weights, kept in owner.<slot> under owner.<slot>_key (a weights_key) and
+    rebuilt when the key differs or the block is gone -- stale planes give wrong results, not errors (include/sumk.h).  out: the backing
+    tensors of the previous block (`_sumk_keep`) for re-use, but only on the stream that built them: kernels another stream has queued
+    may still read the old planes."""
+    d = owner.__dict__
+    if d.get(slot) is None or d.get(slot + "_key") != key:
+        with torch.no_grad():
+            val = d[slot] = build(d.get(slot + "_buf") if d.get(slot + "_stream") == key[-1] else None)
+        d[slot + "_buf"] = [getattr(b, "_sumk_keep", None) for b in val] if isinstance(val, list) else getattr(val, "_sumk_keep", None)
+        d[slot + "_key"], d[slot + "_stream"] = key, key[-1]
+    return d[slot]
 
 
 def drop_shadows(x):
@@ -246,12 +304,8 @@ def split_planes(x, n_planes):
     if x.dim() != 2 or x.stride(1) != 1 or x.stride(0) % 4 != 0:
         raise SumkError("split_planes: a 2-D row-major tensor with a leading dimension that is a multiple of 4")
     rows, K = x.shape
-    nb = lib.sumk_planes_bytes(rows, K, n_planes)
-    if nb == 0:
-        raise SumkError(f"split_planes: rows={rows} K={K} planes={n_planes} is not representable (K % 16, 2 or 3 planes)")
-    out = torch.empty(nb, dtype=torch.uint8, device=x.device)
-    out[nb - 8192:].zero_()          # (the kernel writes every row up to the pitch, zeros behind `rows`; only the slack behind the last sub-array,
-    _lib.check(lib.sumk_split_planes(_p(x), rows, K, x.stride(0), n_planes, _p(out), _stream()), "sumk_split_planes")      #  which row tiles read past, needs a fill)
+    out = _planes_buffer(rows, K, n_planes, x.device, "split_planes")
+    _lib.check(lib.sumk_split_planes(_p(x), rows, K, x.stride(0), n_planes, _p(out), _stream()), "sumk_split_planes")
     return out
 
 
@@ -270,20 +324,13 @@ def pos_add_packed(x, sb, table, want_f32=True, want_bf16=False, n_planes=0):
     x is never written."""
     lib = _lib.load()
     _require_gpu(x, "pos_add_packed input"); _require_gpu(table, "pos_add_packed table")
-    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != sb.n_rows:
-        raise SumkError(f"pos_add_packed: input must be contiguous (n_rows={sb.n_rows}, D), got {tuple(x.shape)}")
+    _check_rows(x, sb, "pos_add_packed: input")
     D = x.shape[1]
     if table.dim() != 2 or table.shape[1] != D or not table.is_contiguous() or table.device != x.device:
         raise SumkError(f"pos_add_packed: table must be contiguous (max_length, {D}) on {x.device}, got {tuple(table.shape)} on {table.device}")
     y32 = torch.empty_like(x) if want_f32 else None
     y16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
-    planes = None
-    if n_planes:
-        nb = lib.sumk_planes_bytes(sb.n_rows, D, n_planes)
-        if nb == 0:
-            raise SumkError(f"pos_add_packed: rows={sb.n_rows} D={D} planes={n_planes} is not representable (D % 16, 2 or 3 planes)")
-        planes = torch.empty(nb, dtype=torch.uint8, device=x.device)
-        planes[nb - 8192:].zero_()          # (as split_planes: the slack behind the last sub-array, which row tiles read past)
+    planes = _planes_buffer(sb.n_rows, D, n_planes, x.device, "pos_add_packed", col="D") if n_planes else None
     _lib.check(lib.sumk_pos_add_packed(_p(x), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, _p(table), table.shape[0], _p(y32), _p(y16), _p(planes),
                                        int(n_planes), _stream()), "sumk_pos_add_packed")
     return y32, y16, planes
@@ -315,9 +362,7 @@ def vasnet_forward_packed(x, sb, params, opts, pos_table=None, pos_rows=None, tr
     """x: (n_rows, D) packed, contiguous, on GPU.  Returns (scores (n_rows,), workspace or None).
     wvo: folded Wo.Wv (inference only) -> the output projection is absorbed into the packed projection (fold_vo)."""
     lib = _lib.load()
-    _require_gpu(x, "vasnet input")
-    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != sb.n_rows:
-        raise SumkError(f"vasnet input must be contiguous (n_rows={sb.n_rows}, D), got {tuple(x.shape)}")
+    _check_rows(x, sb, "vasnet input")
     D = x.shape[1]
     # Entries this function derives (tables of the batch geometry, the bf16 / plane shadows of x) are written back into `opts` so that the
     # backward pass of the same step finds them; they are tied to THIS (x, batch): a caller that re-uses the dict for another batch gets
@@ -334,7 +379,7 @@ def vasnet_forward_packed(x, sb, params, opts, pos_table=None, pos_rows=None, tr
         # of the same geometry built before (a replay runs where the eager calls ran); none yet -> the setup kernel is captured instead
         want = (int(D), int(bool(training)), precision_code(opts.get("precision")))
         hit = [v for k, v in getattr(sb, "_vasnet_tables", {}).items() if k[:3] == want]
-        opts["tables"] = hit[-1][1] if hit else None; opts["_derived"].append("tables")
+        opts["tables"] = hit[-1].data_ptr() if hit else None; opts["_derived"].append("tables")
     if (training and "x16" not in opts and precision_code(opts.get("precision")) == precision_code("bf16") and pos_table is None
             and x.numel() % 4 == 0 and not x.requires_grad and not torch.cuda.is_current_stream_capturing()):
         opts["x16"] = vasnet_x16(x, sb); opts["_derived"].append("x16")        # (an input that asks for dX is an activation, not a dataset: cast per call)
@@ -344,9 +389,7 @@ def vasnet_forward_packed(x, sb, params, opts, pos_table=None, pos_rows=None, tr
         # plane path (csrc/gemm_pw.hip): the operand planes of x are kept with the tensor object (constant per dataset)
         opts["xplanes"] = tensor_shadow(x, f"planes{n_planes}", lambda: split_planes(x, n_planes)); opts["_derived"].append("xplanes")
     w, o = _vasnet_structs(params, opts)
-    nbytes = lib.sumk_vasnet_workspace_bytes_for(D, sb.n_seq, sb.off_host_p, int(training), int(o.precision))
-    if nbytes == 0:
-        _lib.check(-1, "sumk_vasnet_workspace_bytes_for")
+    nbytes = _nonzero(lib.sumk_vasnet_workspace_bytes_for(D, sb.n_seq, sb.off_host_p, int(training), int(o.precision)), "sumk_vasnet_workspace_bytes_for")
     ws = workspace(nbytes, x.device, persistent=training)
     scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
     if wvo is not None:
@@ -364,19 +407,14 @@ def vasnet_forward_packed(x, sb, params, opts, pos_table=None, pos_rows=None, tr
 # ------------------------------------------------------------------------------------------------ BiLSTM scorers
 # SUMK_CHECK=1 (set by the test-suite): synchronise after every recurrent layer and verify that the persistent kernel's
 # bounded waits did not time out.  Off by default (it costs a host sync per layer).
-import os as _os
-CHECK_LSTM = _os.environ.get("SUMK_CHECK", "0") == "1"
+CHECK_LSTM = os.environ.get("SUMK_CHECK", "0") == "1"
 
 
 def _lstm_layer_struct(params, prefix, layer):
     w = _lib.LstmLayerWeights()
     for d, suf in enumerate(("", "_reverse")):
         for f, n in (("w_ih", "weight_ih"), ("w_hh", "weight_hh"), ("b_ih", "bias_ih"), ("b_hh", "bias_hh")):
-            t = params[f"{prefix}{n}_l{layer}{suf}"]
-            _require_gpu(t, f"LSTM weight {prefix}{n}_l{layer}{suf}")
-            if not t.is_contiguous():
-                raise SumkError(f"LSTM weight {prefix}{n}_l{layer}{suf} must be contiguous")
-            getattr(w, f)[d] = t.data_ptr()
+            getattr(w, f)[d] = _ptr(params[f"{prefix}{n}_l{layer}{suf}"], f"LSTM weight {prefix}{n}_l{layer}{suf}")
     return w
 
 
@@ -387,13 +425,8 @@ def bilstm_wplanes(params, prefix, layer, In, H, n_planes, out=None):
     if nb == 0:
         return None
     w = _lstm_layer_struct(params, prefix, layer)
-    dev = params[f"{prefix}weight_ih_l{layer}"].device
-    if out is None or out.numel() < nb + 256 or out.device != dev:
-        out = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-    base = (out.data_ptr() + 255) // 256 * 256
-    _lib.check(lib.sumk_bilstm_wplanes_build(int(In), int(H), C.byref(w), int(n_planes), C.c_void_p(base), nb, _stream()), "sumk_bilstm_wplanes_build")
-    view = out[base - out.data_ptr():]
-    view._sumk_keep = out
+    view = _aligned_block(nb, params[f"{prefix}weight_ih_l{layer}"].device, out)
+    _lib.check(lib.sumk_bilstm_wplanes_build(int(In), int(H), C.byref(w), int(n_planes), _p(view), nb, _stream()), "sumk_bilstm_wplanes_build")
     return view
 
 
@@ -402,9 +435,7 @@ def bilstm_layer_forward(x, sb, params, prefix, layer, H, training=False, precis
     wplanes (inference in bf16x6 / bf16x3): the layer's weight-plane block -- the input projection then runs on operand planes
     (csrc/gemm_pw.hip); x's planes are kept with the tensor object when dataset_input (layer 0: features), split per call otherwise."""
     lib = _lib.load()
-    _require_gpu(x, "bilstm input")
-    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != sb.n_rows:
-        raise SumkError(f"bilstm input must be contiguous (n_rows={sb.n_rows}, In), got {tuple(x.shape)}")
+    _check_rows(x, sb, "bilstm input", col="In")
     In = x.shape[1]
     w = _lstm_layer_struct(params, prefix, layer)
     n_planes = PLANES_OF.get(precision)
@@ -413,9 +444,7 @@ def bilstm_layer_forward(x, sb, params, prefix, layer, H, training=False, precis
         xplanes = (tensor_shadow(x, f"planes{n_planes}", lambda: split_planes(x, n_planes)) if dataset_input and not torch.cuda.is_current_stream_capturing()
                    else split_planes(x, n_planes))
         w.x_planes, w.w_planes = xplanes.data_ptr(), wplanes.data_ptr()
-    nbytes = lib.sumk_bilstm_workspace_bytes(In, H, sb.n_seq, sb.off_host_p, int(training))
-    if nbytes == 0:
-        _lib.check(-1, "sumk_bilstm_workspace_bytes")
+    nbytes = _nonzero(lib.sumk_bilstm_workspace_bytes(In, H, sb.n_seq, sb.off_host_p, int(training)), "sumk_bilstm_workspace_bytes")
     ws = workspace(nbytes, x.device, persistent=training)
     h = torch.empty(sb.n_rows, 2 * H, dtype=torch.float32, device=x.device)
     rc = lib.sumk_bilstm_layer_forward(_p(x), In, H, sb.n_seq, sb.off_host_p, sb.off_dev_p, C.byref(w), _p(h), _p(ws),
@@ -635,9 +664,7 @@ def dsn_reward(x, sb, actions, far_sim=False, temp_dist_thre=20):
     if actions.dim() != 2 or actions.shape[1] != sb.n_rows or not actions.is_contiguous():
         raise SumkError(f"dsn_reward: actions must be contiguous (E, {sb.n_rows}), got {tuple(actions.shape)}")
     D = x.shape[1]
-    nb = lib.sumk_dsn_reward_workspace_bytes(D, sb.n_seq, sb.off_host_p, E)
-    if nb == 0:
-        _lib.check(-1, "sumk_dsn_reward_workspace_bytes")
+    nb = _nonzero(lib.sumk_dsn_reward_workspace_bytes(D, sb.n_seq, sb.off_host_p, E), "sumk_dsn_reward_workspace_bytes")
     ws = workspace(nb, x.device)
     out = torch.empty(E, sb.n_seq, dtype=torch.float32, device=x.device)
     rc = lib.sumk_dsn_reward(_p(x), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, _p(actions), E, int(bool(far_sim)),
@@ -657,9 +684,7 @@ def kts_workspace_bytes(D, sb, max_ncp):
 def _kts_call(name, src, sb, D, max_ncp, lmin, lmax, vmax, want_scores):
     lib = _lib.load()
     max_ncp, lmin, lmax = int(max_ncp), int(min(lmin, 2 ** 31 - 1)), int(min(lmax, 2 ** 31 - 1))
-    nb = lib.sumk_kts_workspace_bytes(D, sb.n_seq, sb.off_host_p, max_ncp)
-    if nb == 0:
-        _lib.check(-1, "sumk_kts_workspace_bytes")
+    nb = _nonzero(lib.sumk_kts_workspace_bytes(D, sb.n_seq, sb.off_host_p, max_ncp), "sumk_kts_workspace_bytes")
     ws = workspace(nb, src.device)
     n_cps = torch.empty(sb.n_seq, dtype=torch.int32, device=src.device)
     cps = torch.empty(sb.n_seq, max(max_ncp, 1), dtype=torch.int32, device=src.device)[:, :max_ncp]
@@ -751,11 +776,7 @@ def transformer_param_names(n_layers):
 
 def _tf_structs(tensors, n_layers, what, layer_cls, head_cls):
     def ptr(k):
-        t = tensors[k]
-        _require_gpu(t, f"Transformer {what} {k}")
-        if not t.is_contiguous():
-            raise SumkError(f"Transformer {what} {k} must be contiguous")
-        return t.data_ptr()
+        return _ptr(tensors[k], f"Transformer {what} {k}")
     layers = (layer_cls * n_layers)()
     for l in range(n_layers):
         for f, k in TF_LAYER_FIELDS:
@@ -779,30 +800,21 @@ def transformer_wplanes(params, D, dff, n_layers, n_planes, out=None):
     if nb == 0:
         return None
     layers, head = _tf_structs(params, n_layers, "weight", _lib.TfLayerWeights, _lib.TfHeadWeights)
-    dev = params[TF_HEAD_FIELDS[0][1]].device
-    if out is None or out.numel() < nb + 256 or out.device != dev:
-        out = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-    base = (out.data_ptr() + 255) // 256 * 256
+    view = _aligned_block(nb, params[TF_HEAD_FIELDS[0][1]].device, out)
     _lib.check(lib.sumk_transformer_wplanes_build(int(D), int(dff), int(n_layers), C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
-                                                  int(n_planes), C.c_void_p(base), nb, _stream()), "sumk_transformer_wplanes_build")
-    view = out[base - out.data_ptr():]
-    view._sumk_keep = out
+                                                  int(n_planes), _p(view), nb, _stream()), "sumk_transformer_wplanes_build")
     return view
 
 
 def transformer_forward_packed(x, sb, params, n_layers, n_heads, dff, opts, pos_table=None, pos_rows=None, training=False):
     """x: (n_rows, D) packed -> (scores (n_rows,), workspace or None).  params: state_dict-keyed tensors."""
     lib = _lib.load()
-    _require_gpu(x, "transformer input")
-    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != sb.n_rows:
-        raise SumkError(f"transformer input must be contiguous (n_rows={sb.n_rows}, D), got {tuple(x.shape)}")
+    _check_rows(x, sb, "transformer input")
     D = x.shape[1]
     layers, head = _tf_structs(params, n_layers, "weight", _lib.TfLayerWeights, _lib.TfHeadWeights)
     o = _tf_opts(opts)
-    nbytes = lib.sumk_transformer_workspace_bytes_for(D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, int(training),
-                                                      o.precision if o.wplanes else 0)
-    if nbytes == 0:
-        _lib.check(-1, "sumk_transformer_workspace_bytes_for")
+    nbytes = _nonzero(lib.sumk_transformer_workspace_bytes_for(D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, int(training),
+                                                               o.precision if o.wplanes else 0), "sumk_transformer_workspace_bytes_for")
     ws = workspace(nbytes, x.device, persistent=training)
     scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
     rc = lib.sumk_transformer_forward(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
@@ -847,23 +859,10 @@ def tf_decoder_param_names(prefix, n_layers):
     return [f"{prefix}{l}.{k}" for l in range(n_layers) for k in TF_DEC_LAYER_KEYS]
 
 
-def _ptr(t, what):
-    _require_gpu(t, what)
-    if not t.is_contiguous():
-        raise SumkError(f"{what} must be contiguous")
-    return t.data_ptr()
-
-
 def _stack_opts(opts):
     o = dict(opts)
     o.setdefault("final_eps", 1e-5)
     return _tf_opts(o)
-
-
-def _check_rows(x, sb, what):
-    _require_gpu(x, what)
-    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != sb.n_rows:
-        raise SumkError(f"{what} must be contiguous (n_rows={sb.n_rows}, D), got {tuple(x.shape)}")
 
 
 def _enc_structs(tensors, n_layers):
@@ -889,9 +888,7 @@ def tf_encoder_forward(x, sb, tensors, n_layers, n_heads, dff, opts, training=Fa
     D = x.shape[1]
     layers, (nw, nb) = _enc_structs(tensors, n_layers)
     o = _stack_opts(opts)
-    nbytes = lib.sumk_tf_encoder_workspace_bytes(D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, int(training))
-    if nbytes == 0:
-        _lib.check(-1, "sumk_tf_encoder_workspace_bytes")
+    nbytes = _nonzero(lib.sumk_tf_encoder_workspace_bytes(D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, int(training)), "sumk_tf_encoder_workspace_bytes")
     ws = workspace(nbytes, x.device, persistent=training)
     out = torch.empty_like(x)
     rc = lib.sumk_tf_encoder_forward(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p, C.cast(layers, C.c_void_p),
@@ -934,9 +931,7 @@ def tf_decoder_forward(tgt, memory, sb, tensors, n_layers, n_heads, dff, opts, t
     D = tgt.shape[1]
     layers = _dec_structs(tensors, n_layers)
     o = _stack_opts(opts)
-    nbytes = lib.sumk_tf_decoder_workspace_bytes(D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p)
-    if nbytes == 0:
-        _lib.check(-1, "sumk_tf_decoder_workspace_bytes")
+    nbytes = _nonzero(lib.sumk_tf_decoder_workspace_bytes(D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p), "sumk_tf_decoder_workspace_bytes")
     ws = workspace(nbytes, tgt.device, persistent=training)
     out = torch.empty_like(tgt)
     rc = lib.sumk_tf_decoder_forward(_p(tgt), _p(memory), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
@@ -987,10 +982,7 @@ def row_scale_backward(x, s, g, want_dx=True, want_ds=True):
 def _lstm_dir_struct(cls, tensors):
     s = cls()
     for f, t in zip(("w_ih", "w_hh", "b_ih", "b_hh"), tensors):
-        _require_gpu(t, f"LSTM {f}")
-        if not t.is_contiguous():
-            raise SumkError(f"LSTM {f} must be contiguous")
-        setattr(s, f, t.data_ptr())
+        setattr(s, f, _ptr(t, f"LSTM {f}"))
     return s
 
 
@@ -1008,15 +1000,11 @@ def lstm_layer_forward(x, sb, weights, H, h0=None, c0=None, training=False, prec
     x (n_rows, In); weights = (w_ih (4H,In), w_hh (4H,H), b_ih, b_hh); h0 / c0 (n_seq, H) or None.
     Returns (h_out (n_rows, H), h_last (n_seq, H), c_last (n_seq, H), workspace or None)."""
     lib = _lib.load()
-    _require_gpu(x, "lstm input")
-    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != sb.n_rows:
-        raise SumkError(f"lstm input must be contiguous (n_rows={sb.n_rows}, In), got {tuple(x.shape)}")
+    _check_rows(x, sb, "lstm input", col="In")
     In = x.shape[1]
     w = _lstm_dir_struct(_lib.LstmDirWeights, weights)
     h0, c0 = _state(h0, sb.n_seq, H, "h0"), _state(c0, sb.n_seq, H, "c0")
-    nbytes = lib.sumk_lstm_workspace_bytes(In, H, sb.n_seq, sb.off_host_p, int(training))
-    if nbytes == 0:
-        _lib.check(-1, "sumk_lstm_workspace_bytes")
+    nbytes = _nonzero(lib.sumk_lstm_workspace_bytes(In, H, sb.n_seq, sb.off_host_p, int(training)), "sumk_lstm_workspace_bytes")
     ws = workspace(nbytes, x.device, persistent=training)
     h = torch.empty(sb.n_rows, H, dtype=torch.float32, device=x.device)
     h_last = torch.empty(sb.n_seq, H, dtype=torch.float32, device=x.device)
@@ -1083,10 +1071,7 @@ def _dir_array(cls, per_layer):
     arr = (cls * len(per_layer))()
     for l, tensors in enumerate(per_layer):
         for f, t in zip(("w_ih", "w_hh", "b_ih", "b_hh"), tensors):
-            _require_gpu(t, f"decoder LSTM {f} (layer {l})")
-            if not t.is_contiguous():
-                raise SumkError(f"decoder LSTM {f} (layer {l}) must be contiguous")
-            setattr(arr[l], f, t.data_ptr())
+            setattr(arr[l], f, _ptr(t, f"decoder LSTM {f} (layer {l})"))
     return arr
 
 
@@ -1102,9 +1087,7 @@ def lstm_decoder_forward(sb, layers, H, h0=None, c0=None):
             _require_gpu(t, f"decoder {name}")
             if tuple(t.shape) != (L, sb.n_seq, H) or not t.is_contiguous():
                 raise SumkError(f"decoder {name} must be contiguous ({L}, {sb.n_seq}, {H}), got {tuple(t.shape)}")
-    nbytes = lib.sumk_lstm_decoder_workspace_bytes(H, L, sb.n_seq, sb.off_host_p)
-    if nbytes == 0:
-        _lib.check(-1, "sumk_lstm_decoder_workspace_bytes")
+    nbytes = _nonzero(lib.sumk_lstm_decoder_workspace_bytes(H, L, sb.n_seq, sb.off_host_p), "sumk_lstm_decoder_workspace_bytes")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     out = torch.empty(sb.n_rows, H, dtype=torch.float32, device=dev)
     _lib.check(lib.sumk_lstm_decoder_forward(H, L, sb.n_seq, sb.off_host_p, sb.off_dev_p, w, _p(h0), _p(c0), _p(out), _p(ws), nbytes,
@@ -1166,7 +1149,7 @@ def _persistent_ok():
     ok = _PERSIST_OK.get(dev)
     if ok is None:
         ok = _PERSIST_OK[dev] = (torch.cuda.get_device_properties(dev).multi_processor_count >= 256 and
-                                 _os.environ.get("SUMK_LSTM_PERSIST", "1")[:1] != "0")
+                                 os.environ.get("SUMK_LSTM_PERSIST", "1")[:1] != "0")
     return ok
 
 
@@ -1176,30 +1159,21 @@ def _gru_structs(weights, grads=None):
     g = _lib.GruLayerGrads() if grads is not None else None
     for d in range(2):
         for i, f in enumerate(("w_ih", "w_hh", "b_ih", "b_hh")):
-            t = weights[4 * d + i]
-            _require_gpu(t, f"GRU {f} (direction {d})")
-            if not t.is_contiguous():
-                raise SumkError(f"GRU {f} (direction {d}) must be contiguous")
-            getattr(w, f)[d] = t.data_ptr()
+            getattr(w, f)[d] = _ptr(weights[4 * d + i], f"GRU {f} (direction {d})")
             if g is not None:
                 getattr(g, f)[d] = grads[4 * d + i].data_ptr()
     return w, g
 
 
 def bigru_workspace_bytes(In, H, sb, training):
-    nbytes = _lib.load().sumk_bigru_workspace_bytes(int(In), int(H), sb.n_seq, sb.off_host_p, int(training))
-    if nbytes == 0:
-        _lib.check(-1, "sumk_bigru_workspace_bytes")
-    return nbytes
+    return _nonzero(_lib.load().sumk_bigru_workspace_bytes(int(In), int(H), sb.n_seq, sb.off_host_p, int(training)), "sumk_bigru_workspace_bytes")
 
 
 def bigru_layer_forward(x, sb, weights, H, training=False, precision=None, ws=None):
     """x: (n_rows, In) packed -> h (n_rows, 2H) = [h_fwd || h_rev] of one bidirectional nn.GRU layer.  Returns (h, workspace or None).
     ws: a caller-owned workspace (tests); otherwise inference shares the per-stream scratch and a training forward gets its own."""
     lib = _lib.load()
-    _require_gpu(x, "bigru input")
-    if not x.is_contiguous() or x.dim() != 2 or x.shape[0] != sb.n_rows:
-        raise SumkError(f"bigru input must be contiguous (n_rows={sb.n_rows}, In), got {tuple(x.shape)}")
+    _check_rows(x, sb, "bigru input", col="In")
     In = x.shape[1]
     w, _ = _gru_structs(weights)
     if ws is None:

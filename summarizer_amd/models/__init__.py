@@ -88,6 +88,17 @@ class Trainer:
             best[0] = corr
             self.best_weights = self.model.state_dict()
 
+    def _keep_scores(self, dist_scores, keys, scores, lens):
+        """The step's packed scores, cut per video into the (T, 1, 1) views draw_scores takes."""
+        for key, piece in zip(keys, torch.split(scores.detach(), lens)):
+            dist_scores[key] = piece.view(-1, 1, 1)
+
+    def _log_epoch(self, fold, epoch, **named):
+        """The epoch's training line and its `<dataset>/Fold_<n>/Train/<name>` scalars, in the order given."""
+        self.log.info(f"Epoch: {f'{epoch+1}/{self.hps.epochs}':6}   " + "  ".join(f"{name}: {value:.05f}" for name, value in named.items()))
+        for name, value in named.items():
+            self.hps.writer.add_scalar(f"{self.dataset_name}/Fold_{fold+1}/Train/{name}", value, epoch)
+
     # ------------------------------------------------------------------ feature ingest
     def _video_on_device(self, key, dev, want_target=False):
         """(features (T,D), min-max normalised gtscore (T,) or None) as device tensors, uploaded once.  The reference
@@ -111,6 +122,18 @@ class Trainer:
             self._hbm[slot] = hit
             self._hbm_bytes += feats.numel() * 4
         return hit
+
+    def _packed_batch(self, keys, dev, want_target=True):
+        """(features (sum T, D), targets (sum T,) or None, lens, SeqBatch) of the step's videos back to back.  One video: the cached
+        tensors THEMSELVES, no copy -- kernels.tensor_shadow and captured steps go by that identity."""
+        vids = [self._video_on_device(k, dev, want_target=True) for k in keys]
+        lens = [v[0].shape[0] for v in vids]
+        if len(vids) == 1:
+            x, target = vids[0]
+        else:
+            x = torch.cat([v[0] for v in vids])
+            target = torch.cat([v[1] for v in vids]) if want_target else None      # (want_target=False spares the copy)
+        return x, target, lens, kernels.SeqBatch.get(lens, dev)
 
     def _video_meta(self, key, need):
         """Evaluation-side fields of one video, read from the dataset once.  `need` = "scores" | "summary" selects which

@@ -34,22 +34,14 @@ def bilstm_scores(model, xp, sb, prefix, num_layers, H, head_w, head_b):
 
 def _layer_wplanes(model, p, prefix, num_layers, In, H, precision):
     """Per-layer weight-plane blocks of the input projections for the split-bf16 arithmetics (kernels.bilstm_wplanes), cached on the
-    model and rebuilt when a weight changes (storage addresses, tensor versions, kernels.WEIGHTS_EPOCH: the rules of VASNet._wplanes)."""
+    model (model._wpl: one block per layer)."""
     n_planes = kernels.PLANES_OF.get(precision)
     if not n_planes:
         return None
-    ps = [v for k, v in sorted(p.items()) if k.startswith(prefix)]
-    key = tuple(t.data_ptr() for t in ps) + tuple(t._version for t in ps) + (kernels.WEIGHTS_EPOCH[0], precision,
-                                                                               torch.cuda.current_stream(ps[0].device).cuda_stream if ps[0].is_cuda else 0)
-    cache = model.__dict__.get("_sumk_wpl")
-    if cache is None or cache[0] != key:
-        with torch.no_grad():
-            old = cache[2] if cache is not None and cache[0][-1] == key[-1] else [None] * num_layers      # (VASNet._wplanes: no re-use across streams)
-            blocks = [kernels.bilstm_wplanes({k: v.detach() for k, v in p.items()}, prefix, layer, In if layer == 0 else 2 * H, H, n_planes,
-                                             out=old[layer]) for layer in range(num_layers)]
-        cache = (key, blocks, [getattr(b, "_sumk_keep", None) if b is not None else None for b in blocks])
-        model.__dict__["_sumk_wpl"] = cache
-    return cache[1]
+    key = kernels.weights_key([v for k, v in sorted(p.items()) if k.startswith(prefix)], precision)
+    return kernels.cached_block(model, "_wpl", key, lambda out: [
+        kernels.bilstm_wplanes({k: v.detach() for k, v in p.items()}, prefix, layer, In if layer == 0 else 2 * H, H, n_planes,
+                               out=out[layer] if out is not None else None) for layer in range(num_layers)])
 
 
 def lstm_stack(lstm, xp, sb, h0=None, c0=None, precision="fp32"):

@@ -5,7 +5,6 @@ Same constructor (dsn.py:19), same state_dict keys (`rnn.weight_ih_l0[_reverse]`
 """
 import math
 import random
-import numpy as np
 import torch
 import torch.nn as nn
 from torch.distributions import Bernoulli
@@ -15,11 +14,7 @@ from ..autograd import PolicyLossFunction
 from .._lib import SumkError
 from . import Trainer
 from ._bilstm import pack_time_major, bilstm_scores, bigru_scores
-from ..training import FlatAdam, dist_info, plan_shards, step_video_total
-
-
-def _k_one(loss):
-    return kernels.one(loss.device) if loss.is_cuda and loss.dim() == 0 and loss.dtype == torch.float32 else None
+from ..training import FlatAdam, dist_info, plan_shards, resolve_batch_videos, step_video_total
 
 
 class DSN(nn.Module):
@@ -91,9 +86,6 @@ class DSNTrainer(Trainer):
                                far_sim=far_sim, temp_dist_thre=temp_dist_thre)
         return r.reshape(())
 
-    def _load_video(self, key, dev):
-        return self._video_on_device(key, dev, want_target=True)
-
     def _sample_actions(self, dist, n_episodes, keys):
         """(n_episodes, n_rows) 0/1 draws from the frame-selection distribution (dsn.py:125, one `dist.sample()` per
         episode there).  A separate method so tests can replay the draws the reference's torch-CPU generator made."""
@@ -106,7 +98,6 @@ class DSNTrainer(Trainer):
         self.log.debug("Parameters: {}".format(sum([_.numel() for _ in self.model.parameters()])))
         dev = self._device()
         rank, world = dist_info()
-        from ..training import resolve_batch_videos
         bv = resolve_batch_videos(self.hps.extra_params, "dsn", "fp32", train_keys, self.log)
         self.optimizer = FlatAdam(self.model.parameters(), lr=self.hps.lr, weight_decay=self.hps.weight_decay,
                                   comm_dtype=torch.bfloat16 if getattr(self.model, "precision", "fp32") == "bf16" else None)
@@ -138,16 +129,12 @@ class DSNTrainer(Trainer):
                 keys = my_keys[step * bv:(step + 1) * bv]
                 self.optimizer.zero_grad(zeroed_by_step=True)
                 if keys:
-                    vids = [self._load_video(k, dev) for k in keys]
-                    lens_b = [v[0].shape[0] for v in vids]
-                    x = torch.cat([v[0] for v in vids]) if len(vids) > 1 else vids[0][0]
-                    sb = kernels.SeqBatch.get(lens_b, dev)
+                    x, target, lens_b, sb = self._packed_batch(keys, dev, want_target=self.sup)
                     probs = self.model.score_packed(x, lens_b)            # (sum T,)
                     dist = Bernoulli(probs, validate_args=False)          # (argument validation is a D2H sync; probs come from the sigmoid kernel)
                     actions = self._sample_actions(dist, E, keys)         # (E, sum T)   dsn.py:125
                     rewards = kernels.dsn_reward(x, sb, actions.contiguous(), far_sim=self.far_sim,
                                                  temp_dist_thre=self.temp_dist_thre)       # (E, n_videos)  dsn.py:129-131
-                    off = np.concatenate([[0], np.cumsum(lens_b)])
                     idx = order[step * bv:step * bv + len(keys)]
                     base = baselines[idx].float()
                     # all videos of the step at once; for one video this is exactly dsn.py:115-140:
@@ -156,13 +143,11 @@ class DSNTrainer(Trainer):
                     # kernels (forward / backward: sumk_dsn_policy_loss_*) instead of ~35 element-wise launches and their autograd twins
                     l_v = PolicyLossFunction.apply(probs, sb, actions, rewards, base, self.beta, self.eps)      # (n_videos,)
                     if self.sup:
-                        target = torch.cat([v[1] for v in vids]) if len(vids) > 1 else vids[0][1]
                         l_v = l_v + sb.segment_mean(torch.nn.functional.binary_cross_entropy(probs, target, reduction="none")) / float(E)  # dsn.py:117-119,140
                     # data-parallel: every video of the GLOBAL step weighs 1/n_total (see training.step_video_total)
                     loss = l_v.mean() if world == 1 else l_v.sum() / step_video_total(sizes, bv, step)
-                    for i, k in enumerate(keys):
-                        dist_scores[k] = probs[off[i]:off[i + 1]].detach().view(-1, 1, 1)
-                    loss.backward(gradient=_k_one(loss))
+                    self._keep_scores(dist_scores, keys, probs, lens_b)
+                    loss.backward(gradient=kernels.one_for(loss))
                     losses.append(loss.detach())
                     mean_r = rewards.detach().mean(dim=0).double()
                     baselines.index_copy_(0, idx, 0.9 * baselines[idx] + 0.1 * mean_r)     # dsn.py:149
@@ -177,9 +162,7 @@ class DSNTrainer(Trainer):
             epoch_avg_reward = float(torch.nanmean(last_reward)) if my_keys else float("nan")      # the epoch's host sync
             epoch_avg_loss = float(torch.stack(losses).mean()) if losses else float("nan")
             kernels.health_check()               # the epoch's host sync: did any persistent recurrence kernel time out?
-            self.log.info(f"Epoch: {f'{epoch+1}/{self.hps.epochs}':6}   Reward: {epoch_avg_reward:.05f}  Loss: {epoch_avg_loss:.05f}")
-            self.hps.writer.add_scalar(f"{self.dataset_name}/Fold_{fold+1}/Train/Reward", epoch_avg_reward, epoch)
-            self.hps.writer.add_scalar(f"{self.dataset_name}/Fold_{fold+1}/Train/Loss", epoch_avg_loss, epoch)
+            self._log_epoch(fold, epoch, Reward=epoch_avg_reward, Loss=epoch_avg_loss)
 
             self._evaluate_epoch(fold, epoch, best)
 

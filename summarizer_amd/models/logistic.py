@@ -128,14 +128,10 @@ class LogisticRegressionTrainer(Trainer):
                     opt.step(grad_scale=scale)
                 if keys:
                     losses.append(loss)
-                    off = np.concatenate([[0], np.cumsum(lens)])
-                    for i, k in enumerate(keys):
-                        dist_scores[k] = scores[off[i]:off[i + 1]].view(-1, 1, 1)
+                    self._keep_scores(dist_scores, keys, scores, lens)
 
             # one D2H per epoch; the mean in float64 like the reference's np.mean over float(loss) values
-            train_avg_loss = float(np.mean(torch.cat(losses).cpu().numpy().astype(np.float64))) if losses else float("nan")
-            self.log.info(f"Epoch: {f'{epoch+1}/{self.hps.epochs}':6}   Loss: {train_avg_loss:.05f}")
-            self.hps.writer.add_scalar(f"{self.dataset_name}/Fold_{fold+1}/Train/Loss", train_avg_loss, epoch)
+            self._log_epoch(fold, epoch, Loss=float(np.mean(torch.cat(losses).cpu().numpy().astype(np.float64))) if losses else float("nan"))
 
             self._evaluate_epoch(fold, epoch, best)
 
@@ -144,12 +140,9 @@ class LogisticRegressionTrainer(Trainer):
 
     def _step(self, keys, dev, ws, scale, apply_adam):
         """One sumk_logistic_step over `keys` packed: (loss (1,), scores (n_rows,), lens)."""
-        vids = [self._video_on_device(k, dev, want_target=True) for k in keys]
-        lens = [v[0].shape[0] for v in vids]
-        x = vids[0][0] if len(vids) == 1 else torch.cat([v[0] for v in vids])
-        t = vids[0][1] if len(vids) == 1 else torch.cat([v[1] for v in vids])
+        x, t, lens, sb = self._packed_batch(keys, dev)
         opt = self.optimizer
-        loss, _, scores = kernels.logistic_step(x, kernels.SeqBatch.get(lens, dev), t, opt.flat_param, opt.flat_grad, opt.exp_avg,
+        loss, _, scores = kernels.logistic_step(x, sb, t, opt.flat_param, opt.flat_grad, opt.exp_avg,
                                                 opt.exp_avg_sq, opt._state, opt.lr, opt.betas, opt.eps, opt.weight_decay, scale,
                                                 apply_adam=apply_adam, want_scores=True, ws=ws)
         return loss, scores, lens

@@ -62,8 +62,7 @@ class RandomTrainer(Trainer):
                 train_avg_loss = float(np.mean(mse.cpu().numpy().astype(np.float64)))
             else:
                 train_avg_loss = float("nan")
-            self.log.info(f"Epoch: {f'{epoch+1}/{self.hps.epochs}':6}   Loss: {train_avg_loss:.05f}")
-            self.hps.writer.add_scalar(f"{self.dataset_name}/Fold_{fold+1}/Train/Loss", train_avg_loss, epoch)
+            self._log_epoch(fold, epoch, Loss=train_avg_loss)
 
             self._evaluate_epoch(fold, epoch, best)
 

@@ -9,7 +9,6 @@ its dropouts (0.1 inside the encoder layers, 0.5 after k1) use the deterministic
 """
 import math
 import random
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.init as init
@@ -17,29 +16,17 @@ import torch.nn.init as init
 from .. import kernels
 from ..autograd import SegmentMseMeanFunction
 from . import Trainer
-from .vasnet import _sinusoid_table, packed_pos_input
+from ._positional import PositionalInput, packed_pos_input
 from ..training import FlatAdam, dist_info, plan_shards, step_video_total
 
 
-def _k_one(loss):
-    return kernels.one(loss.device) if loss.is_cuda and loss.dim() == 0 and loss.dtype == torch.float32 else None
-
-
-class Transformer(nn.Module):
+class Transformer(PositionalInput, nn.Module):
     def __init__(self, input_size=1024, encoder_layers=6, attention_heads=8, more_residuals=False, max_length=None,
                  pos_embed="simple", epsilon=1e-5, weight_init=None):
         super().__init__()
         self.input_size = input_size
         self.encoder_layers, self.attention_heads, self.epsilon = encoder_layers, attention_heads, epsilon
-        self.max_length = max_length
-        if self.max_length:
-            self.pos_embed_type = pos_embed
-            if pos_embed == "simple":
-                self.pos_embed = nn.Embedding(self.max_length, self.input_size)
-            elif pos_embed == "attention":
-                self.pos_embed = _sinusoid_table(self.max_length, self.input_size)
-            else:
-                self.max_length = None
+        self._init_pos_embed(max_length, pos_embed)
         self.more_residuals = more_residuals
         self.dropout = nn.Dropout(0.5)
         self.layer_norm = nn.LayerNorm(self.input_size, epsilon)
@@ -59,39 +46,7 @@ class Transformer(nn.Module):
                     fn(self.transformer_encoder.layers[i].linear1.weight)
                     fn(self.transformer_encoder.layers[i].linear2.weight)
                 fn(self.k1.weight); fn(self.k2.weight)
-        self._pos_rows_cache = {}
         self._seed_counter = 0
-
-    def _pos(self, T, B, device):
-        if self.max_length is None:
-            return None, None
-        assert self.max_length >= T, "input sequence has higher length than max_length"
-        key = (T, B, str(device))
-        rows = self._pos_rows_cache.get(key)
-        if rows is None:
-            r = np.arange(B * T)
-            idx = (r % T) if self.pos_embed_type == "simple" else (r // B)
-            rows = self._pos_rows_cache[key] = torch.from_numpy(idx.astype(np.int32)).to(device)
-        if self.pos_embed_type == "simple":
-            return self.pos_embed.weight, rows
-        if self.pos_embed.device != device:
-            self.pos_embed = self.pos_embed.to(device)
-        return self.pos_embed, rows
-
-    def forward(self, x):
-        """x: (seq_len, batch_size, input_size) -> (seq_len, batch_size, 1)"""
-        seq_len, batch_size, input_size = x.shape
-        kernels._require_gpu(x, "Transformer.forward")
-        if batch_size == 1 and x.is_contiguous():
-            xp = x.view(seq_len, input_size)
-        else:
-            xp = x.permute(1, 0, 2).contiguous().view(batch_size * seq_len, input_size)
-        table, rows = self._pos(seq_len, batch_size, x.device)
-        s = self._score(xp, kernels.SeqBatch.get([seq_len] * batch_size, x.device), table, rows)
-        if table is not None and xp.data_ptr() != x.data_ptr():
-            with torch.no_grad():
-                x.copy_(xp.view(batch_size, seq_len, input_size).permute(1, 0, 2))
-        return s.view(batch_size, seq_len, 1).permute(1, 0, 2)
 
     def score_packed(self, x_packed, lens):
         """x_packed: (sum(lens), D) frames of several videos back to back -> (sum(lens),) scores.  With `max_length`, frame t of every
@@ -103,10 +58,6 @@ class Transformer(nn.Module):
         # (the split-bf16 encoder splits its layer inputs itself: the fp32 sum is all it takes)
         xp, _ = packed_pos_input(self, x_packed, sb, getattr(self, "precision", "fp32"), 0)
         return self._score(xp, sb, None, None)
-
-    def load_state_dict(self, *args, **kwargs):
-        self._pos_gen = getattr(self, "_pos_gen", 0) + 1      # (packed_pos_input's cached sums)
-        return super().load_state_dict(*args, **kwargs)
 
     def _score(self, xp, sb, table, rows):
         p = dict(self.named_parameters())
@@ -129,20 +80,11 @@ class Transformer(nn.Module):
         return scores
 
     def _wplanes(self, p, precision):
-        """Cached weight-plane block (kernels.transformer_wplanes) of the current weights.  Keyed like VASNet's: storage addresses and
-        tensor versions (what torch can see), kernels.WEIGHTS_EPOCH (optimiser steps through the C ABI), precision and stream."""
+        """Cached weight-plane block (kernels.transformer_wplanes) of the current weights."""
         names = kernels.transformer_param_names(self.encoder_layers)
-        ps = [p[n] for n in names]
-        key = tuple(q.data_ptr() for q in ps) + tuple(q._version for q in ps) + (
-            kernels.WEIGHTS_EPOCH[0], precision, torch.cuda.current_stream(ps[0].device).cuda_stream if ps[0].is_cuda else 0)
-        if getattr(self, "_wpl", None) is None or self._wpl_key != key:
-            same_stream = getattr(self, "_wpl_stream", None) == key[-1]      # (VASNet._wplanes: no re-use across streams)
-            with torch.no_grad():
-                self._wpl = kernels.transformer_wplanes({n: q.detach() for n, q in zip(names, ps)}, self.input_size, self.input_size,
-                                                        self.encoder_layers, kernels.PLANES_OF[precision], out=getattr(self, "_wpl_buf", None) if same_stream else None)
-            self._wpl_buf = getattr(self._wpl, "_sumk_keep", None) if self._wpl is not None else None
-            self._wpl_key, self._wpl_stream = key, key[-1]
-        return self._wpl
+        key = kernels.weights_key([p[n] for n in names], precision)
+        return kernels.cached_block(self, "_wpl", key, lambda out: kernels.transformer_wplanes(
+            {n: p[n].detach() for n in names}, self.input_size, self.input_size, self.encoder_layers, kernels.PLANES_OF[precision], out=out))
 
 
 class TransformerTrainer(Trainer):
@@ -187,22 +129,16 @@ class TransformerTrainer(Trainer):
                 keys = my_keys[step * bv:(step + 1) * bv]
                 self.optimizer.zero_grad()
                 if keys:
-                    vids = [self._video_on_device(k, dev, want_target=True) for k in keys]
+                    x, target, lens_b, sb = self._packed_batch(keys, dev)
                     # (a model with max_pos takes this packed route too: score_packed adds the positions out of place)
-                    lens_b = [v[0].shape[0] for v in vids]
-                    x = vids[0][0] if len(vids) == 1 else torch.cat([v[0] for v in vids])
-                    target = vids[0][1] if len(vids) == 1 else torch.cat([v[1] for v in vids])
                     scores = self.model.score_packed(x, lens_b)
                     n_total = len(lens_b) if world == 1 else step_video_total(sizes, bv, step)
-                    loss = SegmentMseMeanFunction.apply(scores, target, kernels.SeqBatch.get(lens_b, dev), 1.0 / n_total)   # mean over videos of the MSE per video (transformer.py:161)
-                    for k, piece in zip(keys, torch.split(scores.detach(), lens_b)):
-                        dist_scores[k] = piece.view(-1, 1, 1)
-                    loss.backward(gradient=_k_one(loss))
+                    loss = SegmentMseMeanFunction.apply(scores, target, sb, 1.0 / n_total)   # mean over videos of the MSE per video (transformer.py:161)
+                    self._keep_scores(dist_scores, keys, scores, lens_b)
+                    loss.backward(gradient=kernels.one_for(loss))
                     losses.append(loss.detach())
                 self.optimizer.step(grad_scale=self.optimizer.all_reduce_grads(average=False))
-            train_avg_loss = float(torch.stack(losses).mean()) if losses else float("nan")
-            self.log.info(f"Epoch: {f'{epoch+1}/{self.hps.epochs}':6}   Loss: {train_avg_loss:.05f}")
-            self.hps.writer.add_scalar(f"{self.dataset_name}/Fold_{fold+1}/Train/Loss", train_avg_loss, epoch)
+            self._log_epoch(fold, epoch, Loss=float(torch.stack(losses).mean()) if losses else float("nan"))
             self._evaluate_epoch(fold, epoch, best)
         self.draw_scores(fold, dist_scores)
         return best[0], best[1], best[2]

@@ -19,14 +19,11 @@ import torch.nn.init as init
 from .. import kernels
 from ..autograd import SegmentMseMeanFunction
 from . import Trainer
-from ..training import FlatAdam, dist_info, plan_shards, step_video_total
+from ._positional import PositionalInput, _sinusoid_table, packed_pos_input      # noqa: F401  (re-exported: earlier home of both functions)
+from ..training import FlatAdam, dist_info, plan_shards, resolve_batch_videos, step_video_total
 
 
-def _k_one(loss):
-    return kernels.one(loss.device) if loss.is_cuda and loss.dim() == 0 and loss.dtype == torch.float32 else None
-
-
-class VASNet(nn.Module):
+class VASNet(PositionalInput, nn.Module):
     def __init__(self, input_size=1024, max_length=None, pos_embed="simple", ignore_self=False,
                  attention_aperture=None, scale=None, epsilon=1e-6, weight_init="xavier", precision="fp32", fold_vo=False):
         super().__init__()
@@ -43,15 +40,7 @@ class VASNet(nn.Module):
         self.epsilon = epsilon
 
         # module creation order follows vasnet.py:42-66 so that a given torch seed yields the same weights
-        self.max_length = max_length
-        if self.max_length:
-            self.pos_embed_type = pos_embed
-            if pos_embed == "simple":
-                self.pos_embed = nn.Embedding(self.max_length, self.input_size)
-            elif pos_embed == "attention":
-                self.pos_embed = _sinusoid_table(self.max_length, self.input_size)   # plain tensor, like the reference
-            else:
-                self.max_length = None
+        self._init_pos_embed(max_length, pos_embed)
         self.dropout = nn.Dropout(0.5)
         self.layer_norm = nn.LayerNorm(self.input_size, epsilon)
         self.K = nn.Linear(self.input_size, self.input_size, bias=False)
@@ -69,7 +58,6 @@ class VASNet(nn.Module):
                 init.xavier_uniform_(m.weight, gain=np.sqrt(2.0))
         init.constant_(self.k1.bias, 0.1)
         init.constant_(self.k2.bias, 0.1)
-        self._pos_rows_cache = {}
         self._seed_counter = 0
 
     # ------------------------------------------------------------------ helpers
@@ -92,42 +80,12 @@ class VASNet(nn.Module):
             o["tail_grads_ready_event"] = self.tail_grads_ready_event     # data-parallel trainers: see VASNetTrainer.train
         return o
 
-    def _pos(self, T, B, device):
-        """(table, rows) for the in-place positional add over batch-major packed rows r = b*T + t."""
-        if self.max_length is None:
-            return None, None
-        assert self.max_length >= T, "input sequence has higher length than max_length"     # vasnet.py:107
-        key = (T, B, str(device))
-        rows = self._pos_rows_cache.get(key)
-        if rows is None:
-            r = np.arange(B * T)
-            idx = (r % T) if self.pos_embed_type == "simple" else (r // B)     # vasnet.py:108 vs :111 (re-view quirk)
-            rows = self._pos_rows_cache[key] = torch.from_numpy(idx.astype(np.int32)).to(device)
-        if self.pos_embed_type == "simple":
-            table = self.pos_embed.weight
-        else:
-            if self.pos_embed.device != device:
-                self.pos_embed = self.pos_embed.to(device)
-            table = self.pos_embed
-        return table, rows
-
     # ------------------------------------------------------------------ reference interface
     def forward(self, x):
         """x: (seq_len, batch_size, input_size) -> (seq_len, batch_size, 1)"""
         seq_len, batch_size, input_size = x.shape
         assert self.input_size == input_size                                   # vasnet.py:104
-        kernels._require_gpu(x, "VASNet.forward")
-        if batch_size == 1 and x.is_contiguous():
-            xp = x.view(seq_len, input_size)                                   # zero-copy; pos add lands in caller's x
-        else:
-            xp = x.permute(1, 0, 2).contiguous().view(batch_size * seq_len, input_size)
-        table, rows = self._pos(seq_len, batch_size, x.device)
-        sb = kernels.SeqBatch.get([seq_len] * batch_size, x.device)
-        s = self._score(xp, sb, table, rows)
-        if table is not None and xp.data_ptr() != x.data_ptr():
-            with torch.no_grad():                                              # mirror the caller-visible mutation
-                x.copy_(xp.view(batch_size, seq_len, input_size).permute(1, 0, 2))
-        return s.view(batch_size, seq_len, 1).permute(1, 0, 2)
+        return super().forward(x)
 
     # ------------------------------------------------------------------ batched extension
     def score_packed(self, x_packed, lens):
@@ -160,27 +118,12 @@ class VASNet(nn.Module):
         scores, _ = kernels.vasnet_forward_packed(xp, sb, self._params(), opts, table, rows, training=False, wvo=wvo)
         return scores
 
-    def _weights_key(self):
-        """What a cache derived from the weights must be keyed by: storage addresses and tensor versions (what torch can see) plus
-        kernels.WEIGHTS_EPOCH (bumped by every optimiser step through the C ABI, invisible to torch)."""
-        ps = [p for _, p in sorted(self._params().items())]
-        # (+ the current stream: the block is built by kernels on it, a call on another stream builds its own)
-        return tuple(p.data_ptr() for p in ps) + tuple(p._version for p in ps) + (kernels.WEIGHTS_EPOCH[0], self.precision, bool(self.fold_vo),
-                                                                                  torch.cuda.current_stream(ps[0].device).cuda_stream if ps[0].is_cuda else 0)
-
     def _wplanes(self, wvo):
-        """Cached weight-plane block (kernels.vasnet_wplanes) of the current weights; rebuilt on any weight change (same rules as
-        _folded; invalidate_folded() drops it too)."""
-        key = self._weights_key()
-        if getattr(self, "_wpl", None) is None or self._wpl_key != key:
-            # the backing block is re-used only by the stream that built it: kernels another stream has queued may still read the old planes
-            same_stream = getattr(self, "_wpl_stream", None) == key[-1]
-            with torch.no_grad():
-                self._wpl = kernels.vasnet_wplanes({k: v.detach() for k, v in self._params().items()}, self.input_size,
-                                                   kernels.PLANES_OF[self.precision], wvo=wvo, out=getattr(self, "_wpl_buf", None) if same_stream else None)
-            self._wpl_buf = getattr(self._wpl, "_sumk_keep", None) if self._wpl is not None else None
-            self._wpl_key, self._wpl_stream = key, key[-1]
-        return self._wpl
+        """Cached weight-plane block (kernels.vasnet_wplanes) of the current weights; _drop_weight_caches() drops it too."""
+        p = self._params()
+        key = kernels.weights_key([v for _, v in sorted(p.items())], self.precision, bool(self.fold_vo))
+        return kernels.cached_block(self, "_wpl", key, lambda out: kernels.vasnet_wplanes(
+            {k: v.detach() for k, v in p.items()}, self.input_size, kernels.PLANES_OF[self.precision], wvo=wvo, out=out))
 
     def _folded(self):
         """Cached Wvo = Wo.Wv.  The key holds what torch can see (storage addresses and tensor versions) plus
@@ -189,6 +132,7 @@ class VASNet(nn.Module):
         drop the cache as well.  (Replays of a HIP-graph-captured training step bypass the Python wrappers: call
         invalidate_folded() after them.)"""
         wo, wv = self.attention_head_projection.weight, self.V.weight
+        # (no stream in this key, unlike kernels.weights_key: a rebuild per stream would put the fold's GEMM into captured scoring graphs)
         key = (wo.data_ptr(), wv.data_ptr(), wo._version, wv._version, kernels.WEIGHTS_EPOCH[0])
         if self._wvo is None or self._wvo_key != key:
             with torch.no_grad():
@@ -196,67 +140,20 @@ class VASNet(nn.Module):
             self._wvo_key = key
         return self._wvo
 
-    def invalidate_folded(self):
+    def _drop_weight_caches(self):
         self._wvo_key = None
         self._wpl_key = None
 
+    def invalidate_folded(self):
+        self._drop_weight_caches()
+
     def train(self, mode=True):
-        self._wvo_key = None
-        self._wpl_key = None
+        self._drop_weight_caches()
         return super().train(mode)
 
     def load_state_dict(self, *args, **kwargs):
-        self._wvo_key = None
-        self._wpl_key = None
-        self._pos_gen = getattr(self, "_pos_gen", 0) + 1      # (packed_pos_input's cached sums)
+        self._drop_weight_caches()
         return super().load_state_dict(*args, **kwargs)
-
-
-def _sinusoid_table(max_length, d):
-    """vasnet.py:44-48 (vectorised; same float64 -> float32 rounding as the reference's element-wise loop)."""
-    pos = np.arange(max_length, dtype=np.float64)[:, None]
-    i = np.arange(0, d, 2, dtype=np.float64)[None, :]
-    tab = np.zeros((max_length, d), dtype=np.float32)
-    tab[:, 0::2] = np.sin(pos / (10000 ** ((2 * i) / d)))
-    tab[:, 1::2] = np.cos(pos / (10000 ** ((2 * (i + 1)) / d)))
-    return torch.from_numpy(tab)
-
-
-def packed_pos_input(model, x, sb, precision, n_planes):
-    """(xp, extra options) for a packed batch of a model with `max_length` (VASNet and the Transformer scorer): xp = x + table[position]
-    from sumk_pos_add_packed, after which the packed pipeline runs as for a model without positions.
-    Under autograd (training, or any call that records a graph) the add is a PosAddPacked node and runs every call -- the learnable table
-    changes with each optimiser step; mixed-precision training takes bf16(xp) out of the same launch (options "x16").
-    Inference: n_planes > 0 (the caller's plane path will be taken) adds the KB planes of xp out of the same launch (options "xplanes");
-    the fp32 sum is still produced, the plane path reads it for the residual of the output projection.  The result is kept with the tensor
-    OBJECT x (kernels.pos_shadow, one entry per x) and rebuilt whenever x or the table may have changed: tensor versions, the table's
-    storage address, kernels.WEIGHTS_EPOCH (optimiser steps through the C ABI), load_state_dict, another stream."""
-    assert model.max_length >= max(sb.lens), "input sequence has higher length than max_length"     # vasnet.py:107 / transformer.py:83
-    kernels._require_gpu(x, f"{type(model).__name__}.score_packed")
-    if model.pos_embed_type == "simple":
-        table = model.pos_embed.weight
-    else:
-        if model.pos_embed.device != x.device:
-            model.pos_embed = model.pos_embed.to(x.device)
-        table = model.pos_embed
-    if torch.is_grad_enabled() and (model.training or any(p.requires_grad for p in model.parameters())):
-        from ..autograd import PosAddPacked
-        if model.training and precision == "bf16" and x.numel() % 4 == 0:
-            xp, x16 = PosAddPacked.apply(x, table, sb, True)
-            return xp, {"x16": x16}
-        return PosAddPacked.apply(x, table, sb, False), None
-
-    def build():
-        with torch.no_grad():
-            y32, _, planes = kernels.pos_add_packed(x, sb, table.detach(), want_f32=True, n_planes=n_planes)
-        return y32, planes
-    if torch.cuda.is_current_stream_capturing():
-        y32, planes = build()
-    else:
-        key = (x._version, id(model), getattr(model, "_pos_gen", 0), table.data_ptr(), table._version, kernels.WEIGHTS_EPOCH[0] if table.requires_grad or isinstance(table, nn.Parameter) else -1, id(sb), int(n_planes),
-               torch.cuda.current_stream(x.device).cuda_stream)
-        y32, planes = kernels.pos_shadow(x, key, build)
-    return y32, ({"xplanes": planes} if planes is not None else None)
 
 
 class _NotResident(RuntimeError):
@@ -298,16 +195,12 @@ class VASNetTrainer(Trainer):
             model.cuda()
         return model
 
-    def _load_video(self, key, dev):
-        return self._video_on_device(key, dev, want_target=True)
-
     def train(self, fold):
         self.model.train()
         train_keys, _ = self._get_train_test_keys(fold)
         self.draw_gtscores(fold, train_keys)
         dev = self._device()
         rank, world = dist_info()
-        from ..training import resolve_batch_videos
         bv = resolve_batch_videos(self.hps.extra_params, "vasnet", "bf16" if self.model.precision == "bf16" else "fp32", train_keys, self.log)
         # precision "bf16" = mixed-precision training (BASELINE config 2): bf16 matrix arithmetic with fp32 accumulation, fp32
         # master weights / moments in the flat bucket, and the gradient bucket crossing the all-reduce as bf16
@@ -354,20 +247,16 @@ class VASNetTrainer(Trainer):
                         continue
                 self.optimizer.zero_grad(zeroed_by_step=True)
                 if keys:
-                    vids = [self._load_video(k, dev) for k in keys]
+                    x, target, lens_b, sb = self._packed_batch(keys, dev)
                     # (a model with max_pos takes this packed route too: score_packed adds the positions out of place)
-                    lens_b = [v[0].shape[0] for v in vids]
-                    scores = self.model.score_packed(torch.cat([v[0] for v in vids]) if len(vids) > 1 else vids[0][0], lens_b)
-                    off = np.concatenate([[0], np.cumsum(lens_b)])
+                    scores = self.model.score_packed(x, lens_b)
                     # mean over videos of the per-video MSE (== nn.MSELoss per video, vasnet.py:209, when bv == 1)
-                    target = torch.cat([v[1] for v in vids]) if len(vids) > 1 else vids[0][1]
                     # world == 1: plain mean; data-parallel: every video of the GLOBAL step weighs 1/n_total (ranks whose
                     # shard has run out contribute nothing and the divisor shrinks with them)
                     n_total = len(lens_b) if world == 1 else step_video_total(sizes, bv, step)
-                    loss = SegmentMseMeanFunction.apply(scores, target, kernels.SeqBatch.get(lens_b, dev), 1.0 / n_total)
-                    for i, k in enumerate(keys):
-                        dist_scores[k] = scores[off[i]:off[i + 1]].detach().view(-1, 1, 1)
-                    loss.backward(gradient=_k_one(loss))
+                    loss = SegmentMseMeanFunction.apply(scores, target, sb, 1.0 / n_total)
+                    self._keep_scores(dist_scores, keys, scores, lens_b)
+                    loss.backward(gradient=kernels.one_for(loss))
                     losses.append(loss.detach())
                 if tail_from is not None:          # every rank issues the same two collectives, videos or not
                     if not keys:
@@ -376,9 +265,7 @@ class VASNetTrainer(Trainer):
                 scale = self.optimizer.all_reduce_grads(average=False)
                 self.optimizer.step(grad_scale=scale, zero_grad=True)
 
-            train_avg_loss = float(torch.stack(losses).mean()) if losses else float("nan")   # one D2H sync per epoch
-            self.log.info(f"Epoch: {f'{epoch+1}/{self.hps.epochs}':6}   Loss: {train_avg_loss:.05f}")
-            self.hps.writer.add_scalar(f"{self.dataset_name}/Fold_{fold+1}/Train/Loss", train_avg_loss, epoch)
+            self._log_epoch(fold, epoch, Loss=float(torch.stack(losses).mean()) if losses else float("nan"))   # one D2H sync per epoch
 
             self._evaluate_epoch(fold, epoch, best)
 
@@ -390,13 +277,13 @@ class VASNetTrainer(Trainer):
         """One optimiser step on one video (vasnet.py:193-212): (loss, scores) as detached tensors.  grads_are_zero: the captured
         form -- the previous step's Adam kernel left the gradient bucket zero and this one does the same, so no fill kernel runs.
         video: the (features, target) device tensors to use instead of loading `key` (a capture passes the tensors it keeps alive)."""
-        seq, target = video if video is not None else self._load_video(key, dev)
+        seq, target = video if video is not None else self._video_on_device(key, dev, want_target=True)
         lens_b = [seq.shape[0]]
         if not grads_are_zero:
             self.optimizer.zero_grad(zeroed_by_step=True)
         scores = self.model.score_packed(seq, lens_b)
         loss = SegmentMseMeanFunction.apply(scores, target, kernels.SeqBatch.get(lens_b, dev), 1.0)    # one video: the mean over videos is the value itself
-        loss.backward(gradient=_k_one(loss))
+        loss.backward(gradient=kernels.one_for(loss))
         self.optimizer.step(grad_scale=1.0, zero_grad=grads_are_zero)
         if self.model.graph_seed is not None:
             # next replay: other dropout masks.  The kernels add this word to the seed captured with the step, and the captured seeds of
@@ -412,7 +299,7 @@ class VASNetTrainer(Trainer):
         # trainer) and are ALSO kept in the graph entry -- a video the cache declined (over its byte limit) would be re-uploaded from a
         # pinned buffer INSIDE the capture and every replay would copy from recycled host memory: such a video stays eager.
         if (key, str(dev)) not in self._hbm:
-            self._load_video(key, dev)
+            self._video_on_device(key, dev, want_target=True)
         if (key, str(dev)) not in self._hbm:
             raise _NotResident(f"video {key} is not resident in the HBM cache")
         video = self._hbm[(key, str(dev))]

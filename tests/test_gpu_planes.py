@@ -279,20 +279,20 @@ def test_lstm_scorers_input_projection_on_planes(dev, kind):
         for prec, tol in (("bf16x6", 2e-6), ("bf16x3", 5e-5)):
             m.precision = prec
             got = m.score_packed(x, lens)
-            assert m.__dict__["_sumk_wpl"][1][0] is not None and f"planes{kernels.PLANES_OF[prec]}" in x._sumk_shadows      # the plane path ran
+            assert m._wpl[0] is not None and f"planes{kernels.PLANES_OF[prec]}" in x._sumk_shadows      # the plane path ran
             assert float((got - ref).abs().max()) < tol, (prec, float((got - ref).abs().max()))
             sb = kernels.SeqBatch.get(lens, dev)
             p = dict(m.named_parameters())
-            wpl = m.__dict__["_sumk_wpl"][1]
+            wpl = m._wpl
             h_pl, _ = kernels.bilstm_layer_forward(x, sb, p, prefix, 0, H, precision=prec, wplanes=wpl[0], dataset_input=True)
             h_old, _ = kernels.bilstm_layer_forward(x, sb, p, prefix, 0, H, precision=prec)
             # (both kinds run the plane GEMM in front of lstm_persist_kernel: the projection inside the recurrence,
             #  lstm_persist_proj_kernel, is opt-in -- SUMK_LSTM_PROJ=1 -- and tests/test_gpu_lstm.py holds it to the plane GEMM and the oracle)
             assert torch.equal(h_pl, h_old) if prec == "bf16x6" else float((h_pl - h_old).abs().max()) < 2e-6
-        key0 = m.__dict__["_sumk_wpl"][0]
+        key0 = m._wpl_key
         dict(m.named_parameters())[prefix + "weight_ih_l0"].mul_(1.1)
         got2 = m.score_packed(x, lens)
-        assert m.__dict__["_sumk_wpl"][0] != key0 and not torch.equal(got2, got)
+        assert m._wpl_key != key0 and not torch.equal(got2, got)
         m.precision = "fp32"
         assert float((m.score_packed(x, lens) - got2).abs().max()) < 5e-5
     kernels.health_check()
