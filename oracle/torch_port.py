@@ -1,6 +1,7 @@
 """Stock-PyTorch (CPU, fp32) functional port of the reference scorers.  TEST INFRASTRUCTURE ONLY.
 The SumGAN recurrences (lstm_stack_ref, dlstm_ref) and make_gru also run in float64: the high-precision oracles of
-tests/test_gpu_sumgan_full.py; transformer_ref likewise for tests/test_gpu_transformer_f64.py.
+tests/test_gpu_sumgan_full.py; transformer_ref likewise for tests/test_gpu_transformer_f64.py, bilstm_stack_ref for
+tests/test_gpu_lstm_f64.py (float64 reference and, in fp32 with the kernels' gate formulas, its yardstick).
 
 This is (1) a second, autograd-capable checker for the HIP path (forward AND gradients), and
 (2) the `cpu_baseline` ("kind": "port") that bench.py times on the GPU node's host cores: it issues the
@@ -243,6 +244,117 @@ def lstm_stack_ref(x_list, params, h0=None, c0=None):
         seq = torch.stack(outs)
         hn.append(h); cn.append(c)
     return [seq[:n, b] for b, n in enumerate(lens)], (torch.stack(hn), torch.stack(cn))
+
+
+GATE_MATH = {
+    # "exact": torch's own sigmoid / tanh.  "rcp_form": the formulas of the recurrence kernels (csrc/persist_common.h: fast_sigmoid,
+    # fast_tanh) in plain torch ops, so that autograd differentiates the same formula the kernels evaluate.
+    "exact": (torch.sigmoid, torch.tanh),
+    "rcp_form": (lambda v: 1.0 / (1.0 + torch.exp(-v)), lambda v: 1.0 - 2.0 / (1.0 + torch.exp(2.0 * v))),
+}
+
+
+def split_bf16(x):
+    """x ~= hi + lo, both bf16 values held in the dtype of x (the two operand planes of the bf16x3 arithmetic)."""
+    hi = x.to(torch.bfloat16).to(x.dtype)
+    return hi, (x - hi).to(torch.bfloat16).to(x.dtype)
+
+
+def mm3(a, b):
+    """a @ b as the bf16x3 MFMA path takes it: hi.hi + hi.lo + lo.hi on two-plane operands (lo.lo dropped), products exact and summed
+    in the dtype of the operands (tests/probes/bf16x3_emulation.py)."""
+    ah, al = split_bf16(a)
+    bh, bl = split_bf16(b)
+    return ah @ bh + (ah @ bl + al @ bh)
+
+
+class Linear3(torch.autograd.Function):
+    """y = x W^T (2-D x) in bf16x3, with the backward products the library runs for a layer of that precision: dW = dy^T x in bf16x3,
+    dx = dy W in bf16x3 -- or exactly (exact_dx: the BPTT multiplies dG by W_hh in fp32 whatever the layer's precision)."""
+
+    @staticmethod
+    def forward(ctx, x, w, exact_dx):
+        ctx.save_for_backward(x, w)
+        ctx.exact_dx = exact_dx
+        return mm3(x, w.t())
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        return (dy @ w if ctx.exact_dx else mm3(dy, w)), mm3(dy.t(), x), None
+
+
+def mm_chain(a, b):
+    """a (M, K) @ b (K, N) summed as ONE accumulator per output element walks k in the exact-fp32 MFMA GEMM (csrc/gemm_regstage.h:
+    v_mfma_f32_32x32x2_f32 adds two k into the accumulator per issue; within each block of 8 k the issues pair k with k + 4), in the
+    dtype of the operands.  A BLAS sums K terms in blocks and lanes, so its rounding error grows far slower with K than the
+    chain's: for a long K this, not a BLAS product, is what the fp32 yardstick of such a GEMM has to be."""
+    K = a.shape[1]
+    acc = a.new_zeros(a.shape[0], b.shape[1])
+    for k0 in range(0, K - K % 8, 8):
+        for j in range(4):
+            acc = torch.addmm(acc, a[:, [k0 + j, k0 + 4 + j]], b[[k0 + j, k0 + 4 + j]])
+    for k in range(K - K % 8, K):
+        acc = torch.addmm(acc, a[:, k:k + 1], b[k:k + 1])
+    return acc
+
+
+class LinearChainDx(torch.autograd.Function):
+    """y = x W^T (2-D x) whose backward takes dx = dy W with mm_chain: the dX GEMM of sumk_bilstm_layer_backward sums K = 4H gate
+    columns per direction in one accumulator chain (up to 4096 terms at H = 1024); the weight gradient stays a plain product (the
+    library sums it as split-K: many short chains)."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        ctx.save_for_backward(x, w)
+        return x @ w.t()
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        return mm_chain(dy, w), dy.t() @ x
+
+
+def bilstm_stack_ref(x_list, params, gate_math="exact", matmul=None):
+    """Stacked nn.LSTM(num_layers=L, bidirectional=True) over a ragged list of videos, written out step by step with plain torch
+    ops in the dtype of the inputs (float64: the reference of tests/test_gpu_lstm_f64.py; float32: its yardstick).
+    x_list: [(T_i, In)]; params: nn.LSTM state_dict names (weight_ih_l0, weight_ih_l0_reverse, ...).
+    gate_math: a key of GATE_MATH.  matmul: optional hook (a (n, K), w (N, K), site) -> a @ w.T with site "ih" (input projection) or
+    "hh" (recurrent product), e.g. Linear3 for the layers the library runs in bf16x3; None: a @ w.T in the dtype.
+    The videos run side by side in descending order of length, each direction over its own frames only (the reverse direction
+    starts at a video's LAST frame).  As in the kernels, the input projection of all frames comes first and carries both biases.
+    Returns [[h_i (T_i, 2H) = [h_fwd || h_rev] per video] per layer]; differentiable in inputs and parameters."""
+    sig, tanh = GATE_MATH[gate_math]
+    mm = matmul if matmul is not None else (lambda a, w, site: a @ w.t())
+    L = sum(1 for k in params if k.startswith("weight_ih_l") and not k.endswith("_reverse"))
+    H = params["weight_hh_l0"].shape[1]
+    lens = [int(x.shape[0]) for x in x_list]
+    order = sorted(range(len(lens)), key=lambda i: -lens[i])
+    n_act = [sum(1 for n in lens if n > t) for t in range(max(lens))]                # videos still running at step t: a prefix of `order`
+    layers, cur = [], list(x_list)
+    for l in range(L):
+        halves = []
+        for suf in ("", "_reverse"):
+            w_ih, w_hh = params[f"weight_ih_l{l}{suf}"], params[f"weight_hh_l{l}{suf}"]
+            bias = params[f"bias_ih_l{l}{suf}"] + params[f"bias_hh_l{l}{suf}"]
+            own = [torch.flip(cur[i], (0,)) if suf else cur[i] for i in order]       # each video in this direction's step order
+            seq = torch.nn.utils.rnn.pad_sequence(own)                               # (T_max, B, In)
+            gx = (mm(seq.reshape(-1, seq.shape[-1]), w_ih, "ih") + bias).reshape(seq.shape[0], seq.shape[1], 4 * H)
+            h = c = seq.new_zeros(len(lens), H)
+            outs = []
+            for t, nb in enumerate(n_act):
+                i, f, g, o = (gx[t, :nb] + mm(h[:nb], w_hh, "hh")).chunk(4, dim=-1)
+                c = sig(f) * c[:nb] + sig(i) * tanh(g)
+                h = sig(o) * tanh(c)
+                outs.append(torch.cat([h, h.new_zeros(len(lens) - nb, H)]) if nb < len(lens) else h)
+            out = torch.stack(outs)                                                  # (T_max, B, H), rows in `order`
+            per = [None] * len(lens)
+            for r, i in enumerate(order):
+                per[i] = torch.flip(out[:lens[i], r], (0,)) if suf else out[:lens[i], r]
+            halves.append(per)
+        cur = [torch.cat([a, b], dim=1) for a, b in zip(*halves)]
+        layers.append(cur)
+    return layers
 
 
 def dlstm_ref(params, recons, T, h0, c0):

@@ -279,6 +279,63 @@ def test_sumgan_lstm_refs_ragged_and_initial_state_vs_nn_lstm():
         torch.testing.assert_close(got[i], torch.flip(recons(steps), (0,)), rtol=1e-12, atol=1e-12)
 
 
+def test_bilstm_stack_ref_vs_nn_lstm_float64():
+    """bilstm_stack_ref (the float64 reference of tests/test_gpu_lstm_f64.py) against stock nn.LSTM(bidirectional=True).double()
+    through pack_sequence: a ragged batch with a one-frame video and a tie in length, two layers; hidden states of the top layer
+    (and of layer 0 against a one-layer module carrying the same weights), scores of a Linear(2H, 1) + sigmoid head, and the
+    gradient of a random-weighted sum of the scores w.r.t. every parameter and the inputs, all to 1e-12.  gate_math="rcp_form"
+    is the same function: 1e-12 in float64 too.  The bf16x3 hook (Linear3) differs from the plain product by 2^-16 relative, not
+    more, forward and backward; the one-accumulator dX product (mm_chain, LinearChainDx) is the plain product in another order."""
+    from torch.nn.utils.rnn import pack_sequence, pad_packed_sequence
+    torch.manual_seed(9)
+    D, H, L, lens = 12, 10, 2, [5, 1, 9, 5, 2]
+    lstm = torch.nn.LSTM(D, H, num_layers=L, bidirectional=True).double()
+    head = torch.nn.Linear(2 * H, 1).double()
+    p = dict(lstm.named_parameters())
+    xs = [torch.randn(T, D, dtype=torch.float64, requires_grad=True) for T in lens]
+    cw = [torch.randn(T, dtype=torch.float64) for T in lens]
+    leaves = xs + list(p.values()) + [head.weight, head.bias]
+    close = lambda a, b: torch.testing.assert_close(a, b, rtol=0, atol=1e-12)
+
+    out, _ = pad_packed_sequence(lstm(pack_sequence(xs, enforce_sorted=False))[0])            # (T_max, B, 2H)
+    want_h = [out[:T, i] for i, T in enumerate(lens)]
+    want_s = [torch.sigmoid(head(h))[:, 0] for h in want_h]
+    want_g = torch.autograd.grad(sum((s * w).sum() for s, w in zip(want_s, cw)), leaves)
+    l0 = torch.nn.LSTM(D, H, num_layers=1, bidirectional=True).double()
+    l0.load_state_dict({k: v for k, v in lstm.state_dict().items() if k.split("_reverse")[0].endswith("_l0")})
+    out0, _ = pad_packed_sequence(l0(pack_sequence(xs, enforce_sorted=False))[0])
+
+    for gate_math in ("exact", "rcp_form"):
+        layers = torch_port.bilstm_stack_ref(xs, p, gate_math=gate_math)
+        assert len(layers) == L and all(len(v) == len(lens) for v in layers)
+        got_s = [torch.sigmoid(head(h))[:, 0] for h in layers[-1]]
+        got_g = torch.autograd.grad(sum((s * w).sum() for s, w in zip(got_s, cw)), leaves)
+        for i, T in enumerate(lens):
+            assert tuple(layers[0][i].shape) == tuple(layers[1][i].shape) == (T, 2 * H)
+            close(layers[1][i], want_h[i]); close(layers[0][i], out0[:T, i]); close(got_s[i], want_s[i])
+        for a, b in zip(got_g, want_g):
+            close(a, b)
+
+    hook = lambda a, w, site: torch_port.Linear3.apply(a, w, site == "hh")
+    layers3 = torch_port.bilstm_stack_ref(xs, p, matmul=hook)
+    got3 = torch.autograd.grad(sum((torch.sigmoid(head(h))[:, 0] * w).sum() for h, w in zip(layers3[-1], cw)), leaves)
+    dh = max(float((a - b).detach().abs().max()) for a, b in zip(layers3[-1], want_h))
+    dg = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(got3, want_g))
+    assert 0 < dh < 1e-4 and 0 < dg < 1e-3, (dh, dg)                                          # the roundings happen, and stay at 2^-16
+
+    # the one-accumulator product of the fp32 yardstick's dX GEMM: the same product (K % 8 != 0 included), another order
+    a, b = torch.randn(7, 45, dtype=torch.float64), torch.randn(45, 6, dtype=torch.float64)
+    close(torch_port.mm_chain(a, b), a @ b)
+    a32, b32 = torch.randn(5, 4096), torch.randn(4096, 3)
+    e_chain = float((torch_port.mm_chain(a32, b32).double() - a32.double() @ b32.double()).abs().max())
+    assert 0 < e_chain < 4096 * 2.0 ** -24 * float((a32.abs() @ b32.abs()).max())              # fp32 roundings, within the chain's bound
+    chain = lambda x_, w_, site: torch_port.LinearChainDx.apply(x_, w_) if site == "ih" else x_ @ w_.t()
+    layers_c = torch_port.bilstm_stack_ref(xs, p, matmul=chain)
+    got_c = torch.autograd.grad(sum((torch.sigmoid(head(h))[:, 0] * w).sum() for h, w in zip(layers_c[-1], cw)), leaves)
+    for a, b in zip(got_c, want_g):
+        close(a, b)
+
+
 def test_make_gru_float64():
     torch.manual_seed(2)
     m = torch.nn.GRU(6, 5, num_layers=2, bidirectional=True)
