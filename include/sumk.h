@@ -617,6 +617,55 @@ size_t sumk_eval_device_kendall_scratch_bytes(int32_t n_videos, int64_t total_fr
 int sumk_eval_device_kendall(const float* scores_dev, const sumk_eval_dev_video* videos_dev, const sumk_eval_dev_kendall* kendall_dev,
                              int32_t n_videos, void* scratch_dev, double* corr_dev, int64_t* counts_dev, void* stream);
 
+/* DEVICE: key-shot selection, summary expansion and F-scores behind sumk_eval_device_segments (csrc/evalselect.hip) -- what
+ * sumk_eval_videos(seg_means given) does on the host, with the segment means where the device left them.  One launch, one workgroup per
+ * video, no atomics, no host synchronisation (capturable into a HIP graph).  Results equal the host's bit for bit: the values are
+ * (int64_t)((double)seg_mean * 1000.0) and the weights nfps[s]; method 0 selects exactly the set of sumk_knapsack_dp (its last-improver
+ * tie rule and its quirks: item 0 is taken when nothing improved the remaining capacity and it fits; nothing is taken when item 0 is too
+ * heavy), method 1 the set of the rank walk (descending score, the larger index first among equals, strict total + nfps < capacity); the
+ * summary holds nfps[s] entries of selected[s] per segment; F-scores follow evaluate_summary (float32, float64 when summary_len <
+ * n_frames) with the mean over annotators in numpy's pairwise order.
+ * Per video: seg_means (n_segs) float32 and nfps (n_segs) int32 on the device; capacity = floor((double)n_frames * proportion) and
+ * summary_len = sum(nfps), both computed by the caller; summary0 / sel0 = the video's offsets in machine_summary_dev / selected_dev;
+ * user_mask (n_users, n_frames) uint8 = the annotators' summaries binarised with > 0 (NULL or n_users 0: F-scores are NaN); method is
+ * one value per call.  Outputs (device): machine_summary (summary_total) float32 0 / 1, selected (selected_total) uint8, f_avg / f_max
+ * (n_videos) float64, status (n_videos) int32.
+ * Limits: 1 <= n_segs <= SUMK_SELECT_MAX_SEGS, 0 <= capacity <= SUMK_SELECT_MAX_CAPACITY (54 000 frames at proportion 0.15), n_users <=
+ * SUMK_SELECT_MAX_USERS, 1 <= n_frames <= 2^24.  The profit rows of the knapsack live in LDS up to capacity SUMK_SELECT_LDS_CAPACITY and in
+ * the workspace above it.  Everything the host can see -- these limits, null pointers, offsets outside the outputs, a short workspace --
+ * returns SUMK_ERR_ARG and launches nothing: the entry point reads videos_host, the host copy of the descriptor array videos_dev.
+ * status: 0 fine; 1 a segment mean is not finite or exceeds 1e12 in magnitude (the host's cast to int64 is undefined there); 2 the
+ * positive values that fit the capacity sum to 2^31 or more (the int32 profit rows would not hold the host's int64 result: means whose
+ * thousandfolds add up past 2.1e9); 3 a negative nfps, or nfps that do not sum to summary_len; 4 a device descriptor past the limits.
+ * A video with a nonzero status gets an all-zero summary and selection (status 4: neither is written) and NaN F-scores; the other videos
+ * of the call are unaffected and nothing is written out of bounds.
+ * workspace: sumk_eval_device_select_workspace_bytes(n_videos, largest n_segs, largest capacity) bytes, 8-byte aligned, contents
+ * irrelevant; pure host arithmetic, 0 = bad arguments. */
+#define SUMK_SELECT_MAX_SEGS 1024
+#define SUMK_SELECT_MAX_CAPACITY 8191
+#define SUMK_SELECT_LDS_CAPACITY 4095
+#define SUMK_SELECT_MAX_USERS 32
+typedef struct sumk_eval_dev_select {
+  const float* seg_means; const int32_t* nfps;
+  int32_t n_segs; int32_t n_frames; int32_t capacity; int32_t summary_len;
+  int64_t summary0; int64_t sel0;
+  const uint8_t* user_mask; int32_t n_users;
+  int32_t method;                              /* 0 = knapsack, 1 = rank                                                */
+} sumk_eval_dev_select;
+size_t sumk_eval_device_select_workspace_bytes(int32_t n_videos, int32_t max_n_segs, int32_t max_capacity);
+int sumk_eval_device_select(const sumk_eval_dev_select* videos_dev, const sumk_eval_dev_select* videos_host, int32_t n_videos,
+                            float* machine_summary_dev, int64_t summary_total, uint8_t* selected_dev, int64_t selected_total,
+                            double* f_avg_dev, double* f_max_dev, int32_t* status_dev, void* workspace, size_t workspace_bytes,
+                            void* stream);
+/* DEVICE: (n_cps, cps) of sumk_kts -> the change points the evaluation tail reads, at a fixed pitch of max_ncp + 1 segments per video, so
+ * that n_segs stays a host-known bound: change_points (n_seq, max_ncp + 1, 2) and nfps (n_seq, max_ncp + 1) int32.  Segment s <= n_cps[v]
+ * is [0 | frame(cps[s - 1]), frame(cps[s]) - 1 | n_frames[v] - 1] with frame(c) = picks_dev[v][c] (picks_dev, or an entry of it, NULL: c
+ * itself) and nfps = its length; the segments behind are EMPTY: (n_frames, n_frames - 1), nfps 0 -- mean 0 from the segments kernel, never
+ * an improvement of a knapsack capacity, no frames in rank mode: the summary equals the unpadded one. */
+int sumk_kts_segments(const int32_t* n_cps_dev, const int32_t* cps_dev, int32_t n_seq, int32_t max_ncp, const int32_t* seq_off_dev,
+                      const int32_t* const* picks_dev, const int32_t* n_frames_dev, int32_t* change_points_dev, int32_t* nfps_dev,
+                      void* stream);
+
 /* ------------------------------------------------------------------------------------------------ data-parallel exchange (RCCL)
  * The gradient all-reduce of data-parallel training as a library call: SUM, in place, over one flat bucket, on the caller's
  * HIP stream (one collective per optimiser step; the reference has no distributed code).  Bootstrap:

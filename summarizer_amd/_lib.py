@@ -84,6 +84,12 @@ class EvalDevKendall(C.Structure):    # sumk_eval_dev_kendall (device pointers),
     _fields_ = [("y_dense", C.c_void_p), ("ytie", C.c_void_p), ("counts0", C.c_int64)]
 
 
+class EvalDevSelect(C.Structure):     # sumk_eval_dev_select (device pointers), one per video
+    _fields_ = [("seg_means", C.c_void_p), ("nfps", C.c_void_p), ("n_segs", C.c_int32), ("n_frames", C.c_int32), ("capacity", C.c_int32),
+                ("summary_len", C.c_int32), ("summary0", C.c_int64), ("sel0", C.c_int64), ("user_mask", C.c_void_p), ("n_users", C.c_int32),
+                ("method", C.c_int32)]
+
+
 class LstmLayerWeights(C.Structure):
     _fields_ = [("w_ih", C.c_void_p * 2), ("w_hh", C.c_void_p * 2), ("b_ih", C.c_void_p * 2), ("b_hh", C.c_void_p * 2),
                 ("x_planes", C.c_void_p), ("w_planes", C.c_void_p)]
@@ -227,6 +233,10 @@ _SIGS = {
     "sumk_eval_device_spearman": (C.c_int, [c_f32p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sumk_eval_device_kendall_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "sumk_eval_device_kendall": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sumk_eval_device_select_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "sumk_eval_device_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_f32p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_kts_segments": (C.c_int, [c_i32p, c_i32p, C.c_int32, C.c_int32, c_i32p, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_void_p]),
     "sumk_pack_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), HOST_I32P, C.c_int32, C.c_int32, C.c_int32]),
     "sumk_pack_rows_bf16": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), HOST_I32P, C.c_int32, C.c_int32, C.c_int32]),
     "sumk_gemm_prec": (C.c_int, [C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

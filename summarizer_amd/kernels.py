@@ -729,6 +729,19 @@ def kts_gram_nonlin(K, sb, ncp, lmin=1, lmax=100000, want_scores=True):
     return _kts_call("sumk_kts_gram_nonlin", K, sb, 4, ncp, lmin, lmax, 1.0, want_scores)
 
 
+def kts_segments(n_cps, cps, sb, picks_ptrs, n_frames):
+    """(n_cps, cps) of `kts` -> (change_points (n_seq, max_ncp + 1, 2), n_frame_per_seg (n_seq, max_ncp + 1)) int32 device tensors, the
+    layout the evaluation tail reads, padded with empty segments behind n_cps[v] + 1 (sumk_kts_segments, include/sumk.h).
+    picks_ptrs: (n_seq,) int64 device tensor of device pointers to each video's int32 picks (0: the identity), or None; n_frames: (n_seq,)
+    int32 device tensor.  Only enqueues work on the current stream."""
+    max_ncp = int(cps.shape[1])
+    change_points = torch.empty(sb.n_seq, max_ncp + 1, 2, dtype=torch.int32, device=cps.device)
+    nfps = torch.empty(sb.n_seq, max_ncp + 1, dtype=torch.int32, device=cps.device)
+    _lib.check(_lib.load().sumk_kts_segments(_p(n_cps), _p(cps), sb.n_seq, max_ncp, sb.off_dev_p, _p(picks_ptrs), _p(n_frames), _p(change_points),
+                                             _p(nfps), _stream()), "sumk_kts_segments")
+    return change_points, nfps
+
+
 def dsn_policy_loss_forward(probs, sb, actions, rewards, base, beta, eps_target):
     """(loss_per_video (n_seq,), mean_probs (n_seq,)) of sumk_dsn_policy_loss_forward (include/sumk.h)."""
     lib = _lib.load()

@@ -239,8 +239,16 @@ class Trainer:
         else:
             packed, lens = hit
         scores = self.model.score_packed(packed, lens).detach().contiguous()
-        corr, f_avg, f_max, _ = eval_native.evaluate_batch_device(metas, scores, lens, self.hps.summary_proportion, self.hps.selection_algorithm,
-                                                                  metric=metric)
+        # opt-in (hps.selection_device = True): key shots, summaries and F-scores on the device too, when every video is within the limits
+        # of sumk_eval_device_select; the same numbers either way
+        on_device = getattr(self.hps, "selection_device", False) and all(eval_native.select_device_ready(m, self.hps.summary_proportion) for m in metas)
+        args = (metas, scores, lens, self.hps.summary_proportion, self.hps.selection_algorithm)
+        try:
+            corr, f_avg, f_max, _ = eval_native.evaluate_batch_device(*args, metric=metric, select="device" if on_device else "host")
+        except eval_native.SelectStatusError:
+            # something only the device sees (a non-finite segment mean, values past the kernel's int32 rows): the host tail defines the
+            # result there, as it does without the opt-in
+            corr, f_avg, f_max, _ = eval_native.evaluate_batch_device(*args, metric=metric, select="host")
         kernels.health_check()      # the D2H inside synchronised: fail loudly if a persistent recurrence kernel timed out
         return corr, f_avg, f_max
 

@@ -7,6 +7,7 @@ and the correlation equal to ~1e-15.  Both metrics of `evaluate_scores` run here
 tests/test_gpu_kendall.py).  This is what `Trainer.test` / `predict_dataset` call; the numpy functions stay the readable
 specification."""
 import ctypes as C
+import math
 import numpy as np
 
 from .. import _lib
@@ -14,6 +15,10 @@ from .. import _lib
 METHODS = {"knapsack": 0, "rank": 1}
 METRICS = ("spearmanr", "kendalltau")
 KENDALL_MAX_FRAMES = 16384      # KD_MAX_FRAMES of csrc/evaldev_common.h: frames per video the device Kendall kernel sorts in LDS
+# limits of sumk_eval_device_select (include/sumk.h SUMK_SELECT_*; csrc/evalselect.hip): segments, frame budget and annotators per video
+SELECT_MAX_SEGS, SELECT_MAX_CAPACITY, SELECT_MAX_USERS, SELECT_MAX_FRAMES = 1024, 8191, 32, 1 << 24
+SELECT_LDS_CAPACITY = 4095      # the knapsack's profit rows stay in LDS up to this budget and move to the workspace above it
+SELECTS = ("host", "device")
 
 
 def _check_metric(metric):
@@ -107,6 +112,44 @@ def device_ready(v):
     return r
 
 
+class SelectStatusError(_lib.SumkError):
+    """evaluate_batch_device(select="device"): sumk_eval_device_select gave a video up for something only the device sees (a nonzero
+    status: a non-finite or huge segment mean, segment values past the int32 profit rows).  The host tail takes such a batch."""
+
+
+def select_capacity(n_frames, proportion):
+    """The frame budget of a summary, as eval_one takes it: floor((double)n_frames * proportion)."""
+    return int(math.floor(float(int(n_frames)) * float(proportion)))
+
+
+def select_refusal(n_segs, n_frames, n_users, proportion):
+    """None when a video of this geometry is within the limits of sumk_eval_device_select, else the limit it is past, in words."""
+    cap = select_capacity(n_frames, proportion)
+    if not 1 <= n_segs <= SELECT_MAX_SEGS:
+        return f"{n_segs} segments (1 .. {SELECT_MAX_SEGS})"
+    if not 0 <= cap <= SELECT_MAX_CAPACITY:
+        return f"a budget of {cap} frames = floor({n_frames} x {proportion}) (0 .. {SELECT_MAX_CAPACITY})"
+    if not 0 <= n_users <= SELECT_MAX_USERS:
+        return f"{n_users} annotators (at most {SELECT_MAX_USERS})"
+    if not 1 <= n_frames <= SELECT_MAX_FRAMES:
+        return f"{n_frames} frames (1 .. {SELECT_MAX_FRAMES})"
+    return None
+
+
+def select_device_ready(v, proportion=0.15):
+    """Can this video's key-shot selection, summary and F-scores run on the device (sumk_eval_device_select)?  The one mirror of that
+    call's limits: change points present, <= 1024 segments of non-negative length, floor(n_frames * proportion) <= 8191, <= 32
+    annotators whose summaries span n_frames."""
+    if "cps" not in v:
+        return False
+    nfps, us = v["nfps"], v.get("user_summary")
+    if nfps.shape[0] != v["cps"].shape[0] or (nfps.shape[0] and (int(nfps.min()) < 0 or int(nfps.sum(dtype=np.int64)) >= 2 ** 31)):
+        return False
+    if us is not None and us.shape[1] != v["n_frames"]:
+        return False
+    return select_refusal(v["cps"].shape[0], v["n_frames"], 0 if us is None else us.shape[0], proportion) is None
+
+
 _DEV_BATCH_CACHE = {}      # (ids of the videos' dicts, lens, device) -> the batch's constant descriptors (device + host side); a few entries
 
 
@@ -132,12 +175,19 @@ def _kendall_meta(v):
     return m
 
 
-def _device_meta(v, device, kendall=False):
+def _device_meta(v, device, kendall=False, select=False):
     """The video's constant metadata as device tensors, uploaded once and cached inside the prepare_video dict
-    (kendall: with the annotators' dense ranks and tie counts, which only the Kendall launch reads)."""
+    (kendall: with the annotators' dense ranks and tie counts, which only the Kendall launch reads; select: with the frames per segment
+    and the annotators' summaries binarised to uint8, which only the select launch reads)."""
     import torch
     cache = v.setdefault("_dev", {})
     d = cache.get(str(device))
+    if select:
+        d = _device_meta(v, device) if d is None else d
+        if "nfps" not in d:
+            d["nfps"] = torch.from_numpy(v["nfps"]).to(device)
+            d["mask"] = torch.from_numpy((v["user_summary"] > 0).astype(np.uint8)).to(device) if "user_summary" in v else None
+        return d
     if kendall and d is not None and "ydense" not in d:
         dense, ytie = _kendall_meta(v)
         d["ydense"], d["ytie"] = torch.from_numpy(dense).to(device), torch.from_numpy(ytie).to(device)
@@ -154,16 +204,22 @@ def _device_meta(v, device, kendall=False):
 
 
 def evaluate_batch_device(videos, scores_dev, lens, proportion=0.15, method="knapsack", want_summaries=False, n_threads=0, metric="spearmanr",
-                          counts_out=None):
+                          counts_out=None, select="host"):
     """The same evaluation with the scores still in HBM: `scores_dev` = packed (sum(lens),) float32 device tensor, video i owning rows
     [sum(lens[:i]), sum(lens[:i + 1])).  One launch (a block per video) does upsample + float32 segment means + Spearman on the device
     (sumk_eval_device); one small D2H brings the segment means and correlations home; key-shot selection, summary expansion and
     F-scores finish in the native host threads (sumk_eval_videos with seg_means given).  Same return value as evaluate_batch.
     metric="kendalltau": sumk_eval_device_kendall (a workgroup per video and annotator) takes the Spearman launch's place; every video
-    must then pass kendall_device_ready.  counts_out: as in evaluate_batch."""
+    must then pass kendall_device_ready.  counts_out: as in evaluate_batch.
+    select="device": the selection, the summaries and the F-scores stay on the device too (sumk_eval_device_select, enqueued between the
+    segments kernel and the correlation); ONE D2H at the end carries corr, f_avg, f_max and the per-video status (plus the summaries
+    when asked for), no host thread runs.  Every video must pass select_device_ready(v, proportion); a nonzero status raises
+    SelectStatusError (a SumkError), after which select="host" on the same batch is the way to its numbers."""
     import torch
     if method not in METHODS:
         raise KeyError(f"Unknown method {method}")
+    if select not in SELECTS:
+        raise KeyError(f"Unknown select {select}")
     _check_metric(metric)
     kendall = metric == "kendalltau"
     lib = _lib.load()
@@ -239,25 +295,12 @@ def evaluate_batch_device(videos, scores_dev, lens, proportion=0.15, method="kna
                 seg_host=torch.empty(max(seg0, 1), dtype=torch.float32).pin_memory(), corr_host=torch.empty(n, dtype=torch.float64).pin_memory(),
                 ev_seg=torch.cuda.Event(), ev_corr=torch.cuda.Event())
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if select == "device":
+            return _select_on_device(lib, ent, buf, videos, scores_dev, n, dev, st, proportion, method, want_summaries, kendall, counts_out)
         _lib.check(lib.sumk_eval_device_segments(scores_dev.data_ptr(), descr_dev.data_ptr(), n, buf["scratch"].data_ptr(), buf["seg"].data_ptr(), st),
                    "sumk_eval_device_segments")
         buf["seg_host"].copy_(buf["seg"], non_blocking=True); buf["ev_seg"].record()
-        if kendall:
-            kent = ent["kendall"]
-            kbuf = kent.get("buffers")
-            if kbuf is None:
-                kbuf = kent["buffers"] = dict(
-                    tau=torch.empty(max(1, lib.sumk_eval_device_kendall_scratch_bytes(n, frame0) // 8), dtype=torch.float64, device=dev),
-                    counts=torch.empty(4 * max(kent["users"], 1), dtype=torch.int64, device=dev),
-                    counts_host=torch.empty(4 * max(kent["users"], 1), dtype=torch.int64).pin_memory())
-            _lib.check(lib.sumk_eval_device_kendall(scores_dev.data_ptr(), descr_dev.data_ptr(), kent["descr_dev"].data_ptr(), n, kbuf["tau"].data_ptr(),
-                                                    buf["corr"].data_ptr(), kbuf["counts"].data_ptr() if counts_out is not None else None, st),
-                       "sumk_eval_device_kendall")
-            if counts_out is not None:
-                kbuf["counts_host"].copy_(kbuf["counts"], non_blocking=True)
-        else:
-            _lib.check(lib.sumk_eval_device_spearman(scores_dev.data_ptr(), descr_dev.data_ptr(), n, buf["part"].data_ptr(), buf["corr"].data_ptr(), st),
-                       "sumk_eval_device_spearman")
+        _enqueue_corr(lib, ent, buf, scores_dev, n, dev, st, kendall, counts_out, buf["corr"].data_ptr())
         buf["corr_host"].copy_(buf["corr"], non_blocking=True); buf["ev_corr"].record()
         seg_means = buf["seg_host"].numpy()[:seg0]       # (a view of the pinned buffer: valid once ev_seg has passed)
         arr = (_lib.EvalVideo * n)()
@@ -285,3 +328,96 @@ def evaluate_batch_device(videos, scores_dev, lens, proportion=0.15, method="kna
             counts_out[:] = _split_counts(ent["kendall"]["buffers"]["counts_host"].numpy()[:4 * ent["kendall"]["users"]], ent["kendall"]["per_video"])
         f_avg = np.array([arr[i].f_avg for i in range(n)]); f_max = np.array([arr[i].f_max for i in range(n)])
     return corr, f_avg, f_max, (summaries if want_summaries else None)
+
+
+def _enqueue_corr(lib, ent, buf, scores_dev, n, dev, st, kendall, counts_out, corr_ptr):
+    """The correlation launch of a cached batch -- Spearman, or Kendall with its lazily built buffers and (counts_out given) the copy of
+    the pair counts into pinned memory -- writing the n float64 results at corr_ptr.  Shared by both select modes."""
+    import torch
+    descr_dev = ent["descr_dev"]
+    if kendall:
+        kent = ent["kendall"]
+        kbuf = kent.get("buffers")
+        if kbuf is None:
+            kbuf = kent["buffers"] = dict(
+                tau=torch.empty(max(1, lib.sumk_eval_device_kendall_scratch_bytes(n, ent["frames"]) // 8), dtype=torch.float64, device=dev),
+                counts=torch.empty(4 * max(kent["users"], 1), dtype=torch.int64, device=dev),
+                counts_host=torch.empty(4 * max(kent["users"], 1), dtype=torch.int64).pin_memory())
+        _lib.check(lib.sumk_eval_device_kendall(scores_dev.data_ptr(), descr_dev.data_ptr(), kent["descr_dev"].data_ptr(), n, kbuf["tau"].data_ptr(),
+                                                corr_ptr, kbuf["counts"].data_ptr() if counts_out is not None else None, st),
+                   "sumk_eval_device_kendall")
+        if counts_out is not None:
+            kbuf["counts_host"].copy_(kbuf["counts"], non_blocking=True)
+    else:
+        _lib.check(lib.sumk_eval_device_spearman(scores_dev.data_ptr(), descr_dev.data_ptr(), n, buf["part"].data_ptr(), corr_ptr, st),
+                   "sumk_eval_device_spearman")
+
+
+def _select_entry(lib, ent, buf, videos, n, dev, proportion, method):
+    """The select side of a cached batch for one (proportion, method): descriptors (host + device copy) and device buffers, built the
+    first time that pair is asked for.  `res` is the one block the call copies home: corr | f_avg | f_max | status (int32) per video."""
+    import torch
+    sel = ent.setdefault("select", {})
+    key = (float(proportion), METHODS[method])
+    se = sel.get(key)
+    if se is not None:
+        return se
+    for i, v in enumerate(videos):
+        if not select_device_ready(v, proportion):
+            raise _lib.SumkError(f"evaluate_batch_device: video {i} does not qualify for select=\"device\" (needs <= {SELECT_MAX_SEGS} segments, "
+                                 f"floor(n_frames x proportion) <= {SELECT_MAX_CAPACITY}, <= {SELECT_MAX_USERS} annotators over n_frames); "
+                                 "use select=\"host\"")
+    descr = (_lib.EvalDevSelect * n)()
+    metas, at, seg_at = [], 0, 0
+    for i, v in enumerate(videos):
+        m = _device_meta(v, dev, select=True); metas.append(m)
+        e = descr[i]
+        e.seg_means, e.nfps = buf["seg"].data_ptr() + 4 * seg_at, m["nfps"].data_ptr()
+        e.n_segs, e.n_frames, e.capacity = v["cps"].shape[0], v["n_frames"], select_capacity(v["n_frames"], proportion)
+        e.summary_len, e.summary0, e.sel0 = int(v["nfps"].sum(dtype=np.int64)), at, seg_at
+        if m["mask"] is not None:
+            e.user_mask, e.n_users = m["mask"].data_ptr(), m["mask"].shape[0]
+        e.method = METHODS[method]
+        at += e.summary_len; seg_at += e.n_segs
+    ws_bytes = lib.sumk_eval_device_select_workspace_bytes(n, max(e.n_segs for e in descr), max(e.capacity for e in descr))
+    if ws_bytes == 0:
+        raise _lib.SumkError("evaluate_batch_device: sumk_eval_device_select_workspace_bytes refused the batch")
+    if len(sel) >= 4:
+        sel.pop(next(iter(sel)))
+    se = sel[key] = dict(
+        metas=metas, descr=descr, descr_dev=torch.frombuffer(bytearray(bytes(descr)), dtype=torch.uint8).to(dev), summary_total=at,
+        summary_lens=[e.summary_len for e in descr], summary=torch.empty(max(at, 1), dtype=torch.float32, device=dev),
+        selected=torch.empty(max(seg_at, 1), dtype=torch.uint8, device=dev), res=torch.empty(4 * n, dtype=torch.float64, device=dev),
+        ws=torch.empty(ws_bytes, dtype=torch.uint8, device=dev), res_host=torch.empty(4 * n, dtype=torch.float64).pin_memory(),
+        summary_host=torch.empty(max(at, 1), dtype=torch.float32).pin_memory(), ev=torch.cuda.Event())
+    return se
+
+
+def _select_on_device(lib, ent, buf, videos, scores_dev, n, dev, st, proportion, method, want_summaries, kendall, counts_out):
+    """evaluate_batch_device(select="device") behind the argument checks, under the entry's lock: three enqueues, one D2H, one wait."""
+    se = _select_entry(lib, ent, buf, videos, n, dev, proportion, method)
+    descr_dev, res = ent["descr_dev"], se["res"]
+    _lib.check(lib.sumk_eval_device_segments(scores_dev.data_ptr(), descr_dev.data_ptr(), n, buf["scratch"].data_ptr(), buf["seg"].data_ptr(), st),
+               "sumk_eval_device_segments")
+    _lib.check(lib.sumk_eval_device_select(se["descr_dev"].data_ptr(), C.cast(se["descr"], C.c_void_p), n, se["summary"].data_ptr(), se["summary_total"],
+                                           se["selected"].data_ptr(), ent["segs"], res.data_ptr() + 8 * n, res.data_ptr() + 16 * n,
+                                           res.data_ptr() + 24 * n, se["ws"].data_ptr(), se["ws"].numel(), st), "sumk_eval_device_select")
+    _enqueue_corr(lib, ent, buf, scores_dev, n, dev, st, kendall, counts_out, res.data_ptr())
+    se["res_host"].copy_(res, non_blocking=True)
+    if want_summaries:
+        se["summary_host"].copy_(se["summary"], non_blocking=True)
+    se["ev"].record()
+    se["ev"].synchronize()
+    home = se["res_host"].numpy()
+    status = home[3 * n:].view(np.int32)[:n]
+    if status.any():
+        i = int(np.flatnonzero(status)[0])
+        raise SelectStatusError(f"evaluate_batch_device: video {i}: sumk_eval_device_select status {int(status[i])} (1: a segment mean is not finite "
+                             "or past 1e12; 2: segment values past the int32 profit rows; 3: n_frame_per_seg; 4: descriptor past the limits)")
+    if kendall and counts_out is not None:
+        counts_out[:] = _split_counts(ent["kendall"]["buffers"]["counts_host"].numpy()[:4 * ent["kendall"]["users"]], ent["kendall"]["per_video"])
+    summaries = None
+    if want_summaries:
+        flat = se["summary_host"].numpy()[:se["summary_total"]]
+        summaries = [a.copy() for a in np.split(flat, np.cumsum(se["summary_lens"])[:-1])]
+    return home[:n].copy(), home[n:2 * n].copy(), home[2 * n:3 * n].copy(), summaries

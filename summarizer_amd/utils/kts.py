@@ -65,6 +65,19 @@ def cps_to_segments(cps, picks, n_frames):
     return change_points, (ends - starts + 1).astype(np.int32)
 
 
+def cps_to_segments_padded(cps, picks, n_frames, n_segs):
+    """cps_to_segments at a fixed number of segments: the live ones first, then EMPTY segments -- change_points (n_frames, n_frames - 1),
+    n_frame_per_seg 0 -- up to n_segs.  An empty segment has mean 0, never improves a knapsack capacity and adds no frame in rank mode, so
+    utils.eval.generate_summary gives the summary of the unpadded segments.  The specification of sumk_kts_segments (csrc/evalselect.hip),
+    which builds this layout on the device so that the segment count of a video stays a host-known bound."""
+    change_points, nfps = cps_to_segments(cps, picks, n_frames)
+    pad = int(n_segs) - change_points.shape[0]
+    if pad < 0:
+        raise ValueError(f"cps_to_segments_padded: {change_points.shape[0]} segments do not fit n_segs={n_segs}")
+    empty = np.tile(np.array([[int(n_frames), int(n_frames) - 1]], dtype=np.int32), (pad, 1))
+    return np.concatenate([change_points, empty]), np.concatenate([nfps, np.zeros(pad, dtype=np.int32)])
+
+
 def default_max_ncp(n):
     return min(int(n) - 1, DEFAULT_MAX_NCP)
 
