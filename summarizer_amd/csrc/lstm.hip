@@ -3336,7 +3336,10 @@ extern "C" int sumk_frame_head_backward(const float* h, const float* scores, con
   hipStream_t stream = (hipStream_t)stream_;
   SUMK_ARG(h && scores && dscores && w && dh && dw && db && workspace, "frame_head_backward: null pointer");
   SUMK_ARG(n_rows > 0 && F > 0 && F % 4 == 0, "frame_head_backward: bad shape n_rows=%d F=%d", n_rows, F);
-  SUMK_ARG(workspace_bytes >= sumk_frame_head_workspace_bytes(F), "frame_head_backward: workspace too small");
+  if (workspace_bytes < sumk_frame_head_workspace_bytes(F)) {
+    set_error("frame_head_backward: workspace %zu < required %zu", workspace_bytes, sumk_frame_head_workspace_bytes(F));
+    return SUMK_ERR_WORKSPACE;
+  }
   int blocks = std::max(1, std::min((n_rows + 3) / 4, 256));
   float* part = (float*)workspace;
   hipLaunchKernelGGL(frame_head_bwd_kernel, dim3(blocks), dim3(256), 0, stream, h, scores, dscores, w, dh, part, n_rows, F);

@@ -287,3 +287,89 @@ def test_mfma_rate_probe_is_plausible_and_refuses_bad_arguments():
     t = C.c_double(0)
     assert lib.sumk_probe_mfma_rate(7, 10, C.byref(t), None, None) == -1
     assert lib.sumk_probe_mfma_rate(0, 0, C.byref(t), None, None) == -1
+
+
+def test_linear_and_frame_head_refusals():
+    """sumk_linear_forward / _backward and sumk_frame_head_forward / _backward: null pointers, shapes outside the domain and an unknown
+    precision are SUMK_ERR_ARG (-1), a workspace one byte short is SUMK_ERR_WORKSPACE (-2); every refusal leaves a message in
+    sumk_last_error() and launches nothing (the outputs keep their NaN fill)."""
+    from summarizer_amd import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    nan = float("nan")
+
+    def refused(rc, code, word):
+        msg = lib.sumk_last_error()
+        assert rc == code and word in msg, (rc, code, msg)
+
+    # ---- dense layer
+    M, N, K = 8, 8, 8
+    x = torch.ones(M, K, device=dev); w = torch.ones(N, K, device=dev); b = torch.ones(N, device=dev); dy = torch.ones(M, N, device=dev)
+    y = torch.full((M, N), nan, device=dev); dx = torch.full((M, K), nan, device=dev)
+    dw = torch.full((N, K), nan, device=dev); db = torch.full((N,), nan, device=dev)
+    nb = lib.sumk_linear_workspace_bytes(N, K)
+    assert nb > 0 and lib.sumk_linear_workspace_bytes(0, 8) == 0
+    ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
+    X, W, B, Y, DY, DX, DW, DB, WS = (t.data_ptr() for t in (x, w, b, y, dy, dx, dw, db, ws))
+
+    def fwd(x=X, w=W, b=B, y=Y, M=M, N=N, K=K, ws=WS, nb=nb, prec=0):
+        return lib.sumk_linear_forward(x, w, b, y, M, N, K, ws, nb, prec, st)
+
+    def bwd(x=X, w=W, dy=DY, M=M, N=N, K=K, dx=DX, dw=DW, db=DB, ws=WS, nb=nb, prec=0):
+        return lib.sumk_linear_backward(x, w, dy, M, N, K, dx, dw, db, ws, nb, prec, st)
+
+    for name in ("x", "w", "y", "ws"):
+        refused(fwd(**{name: None}), -1, b"null pointer")
+    for name in ("x", "w", "dy", "ws"):
+        refused(bwd(**{name: None}), -1, b"null pointer")
+    refused(fwd(K=6), -1, b"multiple of 4")
+    refused(bwd(K=6), -1, b"multiples of 4")
+    refused(bwd(N=6), -1, b"multiples of 4")
+    refused(fwd(M=0), -1, b"bad shape")
+    refused(fwd(prec=7), -1, b"precision 7")
+    refused(bwd(prec=7), -1, b"precision 7")
+    refused(fwd(nb=nb - 1), -2, b"workspace")
+    refused(bwd(nb=nb - 1), -2, b"workspace")
+    torch.cuda.synchronize()
+    for t in (y, dx, dw, db):
+        assert bool(torch.isnan(t).all()), "a refused call wrote an output"
+    assert fwd() == 0 and fwd(b=None) == 0                                   # the same arguments, nothing withheld: accepted
+    dw.zero_(); db.zero_()
+    assert bwd() == 0 and bwd(dx=None, dw=None, db=None) == 0                # every backward output is optional
+    torch.cuda.synchronize()
+    assert torch.equal(y, torch.full((M, N), float(K), device=dev)) and torch.equal(dx, torch.full((M, K), float(N), device=dev))
+    assert torch.equal(dw, torch.full((N, K), float(M), device=dev)) and torch.equal(db, torch.full((N,), float(M), device=dev))
+
+    # ---- frame head
+    R_, F_ = 8, 8
+    h = torch.ones(R_, F_, device=dev); hw = torch.ones(1, F_, device=dev); hb = torch.zeros(1, device=dev); ds = torch.ones(R_, device=dev)
+    s = torch.full((R_,), nan, device=dev); dh = torch.full((R_, F_), nan, device=dev)
+    hdw = torch.full((1, F_), nan, device=dev); hdb = torch.full((1,), nan, device=dev)
+    hnb = lib.sumk_frame_head_workspace_bytes(F_)
+    hws = torch.zeros(hnb, dtype=torch.uint8, device=dev)
+    H, HW, HB, S, DS, DH, HDW, HDB, HWS = (t.data_ptr() for t in (h, hw, hb, s, ds, dh, hdw, hdb, hws))
+
+    def hfwd(h=H, n=R_, F=F_, w=HW, b=HB, s=S):
+        return lib.sumk_frame_head_forward(h, n, F, w, b, s, st)
+
+    def hbwd(h=H, s=S, ds=DS, n=R_, F=F_, w=HW, dh=DH, dw=HDW, db=HDB, ws=HWS, nb=hnb):
+        return lib.sumk_frame_head_backward(h, s, ds, n, F, w, dh, dw, db, ws, nb, st)
+
+    for name in ("h", "w", "b", "s"):
+        refused(hfwd(**{name: None}), -1, b"null pointer")
+    for name in ("h", "s", "ds", "w", "dh", "dw", "db", "ws"):
+        refused(hbwd(**{name: None}), -1, b"null pointer")
+    refused(hfwd(F=6), -1, b"bad shape")
+    refused(hbwd(F=6), -1, b"bad shape")
+    refused(hfwd(n=0), -1, b"bad shape")
+    refused(hbwd(n=0), -1, b"bad shape")
+    refused(hbwd(nb=hnb - 1), -2, b"workspace")
+    torch.cuda.synchronize()
+    for t in (s, dh, hdw, hdb):
+        assert bool(torch.isnan(t).all()), "a refused call wrote an output"
+    assert hfwd() == 0
+    hdw.zero_(); hdb.zero_()
+    assert hbwd(s=S) == 0
+    torch.cuda.synchronize()
+    assert not bool(torch.isnan(s).any()) and not bool(torch.isnan(dh).any())

@@ -34,7 +34,12 @@ def _gemm(lib_fn, A, B, M, N, K, dev):
     return c.cpu().numpy()
 
 
-@pytest.mark.parametrize("M,N,K", [(1, 4, 4), (37, 64, 64), (130, 192, 100), (129, 128, 1024), (300, 3072, 1024), (64, 1000, 36), (257, 260, 8)])
+# (2052, 512, 64) and (2176, 1024, 36): tm = 17 tiles of 128 along M with tn = 4 and tn = 8 -- the XCD-aware tile map of the plain entry
+# points (launch_gemm: tn % 4 == 0 && tm >= 16), with an odd tm, so the launch walks 72 / 144 virtual tiles for 68 / 136 real ones
+XCD_SHAPES = [(2052, 512, 64), (2176, 1024, 36)]
+
+
+@pytest.mark.parametrize("M,N,K", [(1, 4, 4), (37, 64, 64), (130, 192, 100), (129, 128, 1024), (300, 3072, 1024), (64, 1000, 36), (257, 260, 8)] + XCD_SHAPES)
 def test_gemm_layouts_vs_float64(dev, M, N, K):
     from summarizer_amd import _lib
     lib = _lib.load()
@@ -54,7 +59,7 @@ def test_gemm_layouts_vs_float64(dev, M, N, K):
 
 
 @pytest.mark.parametrize("M,N,K", [(4, 4, 4), (36, 64, 64), (132, 192, 100), (128, 128, 1024), (300, 3072, 1024), (64, 1000, 36), (260, 260, 8),
-                                   (200, 1024, 260)])
+                                   (200, 1024, 260)] + XCD_SHAPES)
 def test_gemm_bf16x3_vs_float64(dev, M, N, K):
     """Opt-in bf16x3 arithmetic (hi+lo bf16 splits, 3 bf16 MFMAs, fp32 accumulate), all three layouts: each product carries
     ~2^-16 relative error (dropped lo*lo term and the rounding of lo), so the bound is 2^-15 * |A|.|B|^T -- far tighter
@@ -84,7 +89,7 @@ def test_gemm_bf16x3_vs_float64(dev, M, N, K):
                 assert (np.abs(got - ref) <= bound).all(), f"{name} bf16x3 max err {np.abs(got - ref).max()}"
 
 
-@pytest.mark.parametrize("M,N,K", [(4, 4, 4), (36, 64, 64), (132, 192, 100), (128, 128, 1024), (300, 3072, 1024), (64, 1000, 36), (200, 1024, 260)])
+@pytest.mark.parametrize("M,N,K", [(4, 4, 4), (36, 64, 64), (132, 192, 100), (128, 128, 1024), (300, 3072, 1024), (64, 1000, 36), (200, 1024, 260)] + XCD_SHAPES)
 def test_gemm_bf16x6_is_fp32_grade(dev, M, N, K):
     """bf16x6 (three bf16 planes = fp32's 24 significand bits, six bf16 MFMAs per product) must satisfy the SAME bound as the
     exact fp32 MFMA path in test_gemm_layouts_vs_float64, in all three layouts."""
