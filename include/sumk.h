@@ -666,6 +666,51 @@ int sumk_kts_segments(const int32_t* n_cps_dev, const int32_t* cps_dev, int32_t 
                       const int32_t* const* picks_dev, const int32_t* n_frames_dev, int32_t* change_points_dev, int32_t* nfps_dev,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------------ dataset records from raw annotations
+ * DEVICE: the frame-level arithmetic that turns a video's raw annotations into the fields a trainer reads (csrc/annotate.hip).  No
+ * reference counterpart: the reference READS gtscore / user_scores / user_summary / gtsummary that other projects' code prepared offline
+ * (summarizer/datasets/README.md:50-74); sumk_annotate is that step, in front of sumk_eval_device_segments and sumk_eval_device_select,
+ * which make the summaries from what it leaves in HBM (summarizer_amd/utils/annotate.py: annotate_batch).
+ * Per video: anno (n_users, n_frames) float32, picks (n_picks) int32 ascending inside 0 .. n_frames - 1, cps (n_segs, 2) int32 -- all
+ * DEVICE pointers.  All arithmetic is float32, in exactly this order (the unit is compiled without FMA contraction):
+ *   protocol SUMK_ANNOTATE_SCORES (TVSum style: grades in [lo, hi]):
+ *     user[u][f]   = (anno[u][f] - lo) / (hi - lo)                                                  -> the record's user_scores
+ *     consensus[f] = (((anno[0][f] + anno[1][f]) + ...) + anno[U-1][f]) / (float)U                  (sequential in u, from 0.f)
+ *     g[t]         = consensus[picks[t]];  gtscore[t] = (g[t] - min g) / (max g - min g), all 0 when max g == min g
+ *     seg_means[u][s] = pairwise_sum(user[u][start_s .. end_s]) / (float)count_s, 0 for an empty segment (numpy's float32 pairwise tree,
+ *                    the one of sumk_eval_device_segments): the knapsack / rank values of annotator u's own summary
+ *   protocol SUMK_ANNOTATE_SUMMARIES (SumMe style: any value > 0 means selected):
+ *     user[u][f]   = anno[u][f] > 0 ? 1 : 0                                                         -> the record's user_summary
+ *     consensus[f] = (float)count_u(anno[u][f] > 0) / (float)U;  gtscore[t] = consensus[picks[t]] (not normalised); no seg_means.
+ * Offsets (in elements) place the video in the caller's outputs: user0 its (n_users, n_frames) block in user_dev, frame0 its n_frames
+ * entries in consensus_dev, pick0 its n_picks entries in gtscore_dev (and in the gtsummary of sumk_annotate_gtsummary), seg0 its
+ * (n_users, n_segs) block in seg_means_dev, gtsum0 its n_frames entries in the frame summary sumk_annotate_gtsummary reads.
+ * summary_len = sum of the frames per segment, computed by the caller: the segments must tile the frames (summary_len == n_frames).
+ * Limits, those of the kernels this chains into: 1 <= n_users <= SUMK_SELECT_MAX_USERS, 1 <= n_picks <= 4095, 1 <= n_segs <=
+ * SUMK_SELECT_MAX_SEGS, 1 <= n_frames <= 2^24, hi > lo (both finite), n_videos <= 65535 and ceil(longest video / 256) x n_videos < 2^24 (one
+ * launch covers every frame of the batch), reserved == 0.  Everything the host can see -- these limits,
+ * null pointers, blocks outside the outputs -- returns SUMK_ERR_ARG and launches nothing: the entry reads videos_host, the host copy of
+ * videos_dev.  On the device every index read from picks or cps is clamped to the video, and a device descriptor past the limits is
+ * skipped: nothing is read or written out of bounds.  Two launches (one pass over the annotations; one workgroup per video for the
+ * reduction and one thread per (annotator, segment) mean), no atomics, no cooperative launch, no host synchronisation: capturable.
+ * sumk_annotate_gtsummary: gtsummary[pick0 + t] = frame_summary[gtsum0 + picks[t]] -- the key-shot summary of gtscore that
+ * sumk_eval_device_select expanded to frames, sampled back at the picks (the record's gtsummary).  Same descriptors, same checks. */
+#define SUMK_ANNOTATE_SCORES 0
+#define SUMK_ANNOTATE_SUMMARIES 1
+#define SUMK_ANNOTATE_MAX_PICKS 4095
+typedef struct sumk_annotate_video {
+  const float* anno; const int32_t* picks; const int32_t* cps;
+  int32_t n_users; int32_t n_frames; int32_t n_picks; int32_t n_segs;
+  int32_t summary_len; int32_t reserved;       /* reserved: 0                                                            */
+  int64_t user0; int64_t frame0; int64_t pick0; int64_t seg0; int64_t gtsum0;
+} sumk_annotate_video;
+int sumk_annotate(const sumk_annotate_video* videos_dev, const sumk_annotate_video* videos_host, int32_t n_videos, int32_t protocol,
+                  float lo, float hi, float* user_dev, int64_t user_total, float* consensus_dev, int64_t frame_total, float* gtscore_dev,
+                  int64_t pick_total, float* seg_means_dev, int64_t seg_total, void* stream);
+int sumk_annotate_gtsummary(const sumk_annotate_video* videos_dev, const sumk_annotate_video* videos_host, int32_t n_videos,
+                            const float* frame_summary_dev, int64_t frame_summary_total, float* gtsummary_dev, int64_t pick_total,
+                            void* stream);
+
 /* ------------------------------------------------------------------------------------------------ data-parallel exchange (RCCL)
  * The gradient all-reduce of data-parallel training as a library call: SUM, in place, over one flat bucket, on the caller's
  * HIP stream (one collective per optimiser step; the reference has no distributed code).  Bootstrap:

@@ -90,6 +90,12 @@ class EvalDevSelect(C.Structure):     # sumk_eval_dev_select (device pointers), 
                 ("method", C.c_int32)]
 
 
+class AnnotateVideo(C.Structure):     # sumk_annotate_video (device pointers), one per video
+    _fields_ = [("anno", C.c_void_p), ("picks", C.c_void_p), ("cps", C.c_void_p), ("n_users", C.c_int32), ("n_frames", C.c_int32),
+                ("n_picks", C.c_int32), ("n_segs", C.c_int32), ("summary_len", C.c_int32), ("reserved", C.c_int32), ("user0", C.c_int64),
+                ("frame0", C.c_int64), ("pick0", C.c_int64), ("seg0", C.c_int64), ("gtsum0", C.c_int64)]
+
+
 class LstmLayerWeights(C.Structure):
     _fields_ = [("w_ih", C.c_void_p * 2), ("w_hh", C.c_void_p * 2), ("b_ih", C.c_void_p * 2), ("b_hh", C.c_void_p * 2),
                 ("x_planes", C.c_void_p), ("w_planes", C.c_void_p)]
@@ -237,6 +243,9 @@ _SIGS = {
     "sumk_eval_device_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_f32p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sumk_kts_segments": (C.c_int, [c_i32p, c_i32p, C.c_int32, C.c_int32, c_i32p, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_void_p]),
+    "sumk_annotate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p,
+                                C.c_int64, c_f32p, C.c_int64, C.c_void_p]),
+    "sumk_annotate_gtsummary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_void_p]),
     "sumk_pack_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), HOST_I32P, C.c_int32, C.c_int32, C.c_int32]),
     "sumk_pack_rows_bf16": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), HOST_I32P, C.c_int32, C.c_int32, C.c_int32]),
     "sumk_gemm_prec": (C.c_int, [C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

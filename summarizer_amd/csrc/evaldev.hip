@@ -11,27 +11,7 @@
 
 namespace sumk {
 
-// numpy's pairwise summation (numpy/core/src/umath/loops_utils.h.src), float32 -- same tree as csrc/evaltail.hip
-__device__ float ed_pairwise_sum(const float* a, int n) {
-  if (n < 8) {
-    float r = 0.f;
-    for (int i = 0; i < n; ++i) r += a[i];
-    return r;
-  }
-  if (n <= 128) {
-    float r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-      for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-  }
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return ed_pairwise_sum(a, n2) + ed_pairwise_sum(a + n2, n - n2);
-}
+// (numpy's float32 pairwise summation, ed_pairwise_sum, is in evaldev_common.h: csrc/annotate.hip takes the same segment means)
 
 __global__ __launch_bounds__(256) void eval_device_kernel(const float* __restrict__ scores, const sumk_eval_dev_video* __restrict__ vids,
                                                           float* __restrict__ frame_scratch, float* __restrict__ seg_means,
