@@ -711,6 +711,52 @@ int sumk_annotate_gtsummary(const sumk_annotate_video* videos_dev, const sumk_an
                             const float* frame_summary_dev, int64_t frame_summary_total, float* gtsummary_dev, int64_t pick_total,
                             void* stream);
 
+/* ------------------------------------------------------------------------------------------------ inter-annotator agreement
+ * DEVICE: how well the annotators of a video agree with each other under the two metrics of the evaluation tail (csrc/agreement.hip;
+ * summarizer_amd/utils/agreement.py chains the three calls; the specification is tests/agreement_ref.py, bit for bit).
+ * Per video: user_summary (n_sum, n_frames) float32, > 0 = selected, and / or user_scores (n_sc, n_frames) float32, finite -- DEVICE
+ * pointers, NULL with a count of 0.  Offsets (in elements) place the video in the caller's buffers: rank0 its (n_sc, n_frames) block of
+ * ranks, row0 its n_sc per-row entries (ties, mean, ssq, corr_user), sum0 its n_sum entries of f_avg_user / f_max_user, f0 its
+ * (n_sum, n_sum) block of F, c0 its (n_sc, n_sc) block of C (and 4 x that in counts).
+ * sumk_rank_rows, one workgroup per row sorting kendall_float_key(x) in LDS (-0.0 and 0.0 are one value):
+ *   avg_ranks  float64, 1-based average ranks of -x = scipy.stats.rankdata(-x)
+ *   dense      int32, 0-based, ascending with the score, equal scores share one rank
+ *   ties       int64, sum t (t - 1) / 2 over the groups of equal scores
+ *   mean, ssq  float64 (n + 1) / 2 and sum (rank - mean)^2: multiples of 0.25 below 2^53, exact in any order
+ * sumk_agreement_f, one workgroup per video, float32 as evaluate_summary(user_summary[a], user_summary[b:b+1]) (eval.py:125-165):
+ *   F[a][b] = 2PR / (P + R), P = o / (sum_a + 1e-8), R = o / (sum_b + 1e-8), 0 when both are 0 -- the arithmetic of sumk_eval_device_select
+ *   f_avg_user[a] / f_max_user[a] = float32 mean (numpy's pairwise order) / maximum over b != a in index order
+ *   f_avg / f_max (per video) = float64 mean of those over a; all four NaN when n_sum < 2 (F is still written)
+ * sumk_agreement_corr on the outputs of sumk_rank_rows:
+ *   metric SUMK_AGREEMENT_SPEARMAN  C[a][b] = sum (r_a - mean)(r_b - mean) / sqrt(ssq_a ssq_b): NaN for a constant row
+ *   metric SUMK_AGREEMENT_KENDALL   C[a][b] = tau-b of sumk_eval_device_kendall from integer pair counts, x = annotator a, y = annotator b;
+ *                                   counts (optional) = {cmd, xtie, ytie, ntie} per entry of C
+ *                                   A pair whose rows hold few distinct values (their product <= 1024: TVSum grades give 5 x 5) takes its
+ *                                   counts from the rows' contingency table in LDS, every other pair from an LDS merge sort: the same integers.
+ *   corr_user[a] = float64 mean over b != a, corr (per video) = float64 mean over a, numpy's pairwise order, NaN propagates; NaN when n_sc < 2
+ * Limits: n_sum, n_sc <= SUMK_SELECT_MAX_USERS; 1 <= n_frames <= 2^24 for F and <= 16384 where n_sc > 0; n_videos <= 65535; reserved == 0.
+ * Everything the host can see -- these limits, null pointers, blocks outside the buffers -- returns SUMK_ERR_ARG and launches nothing: the
+ * entries read videos_host, the host copy of videos_dev.  A device descriptor past a limit gets NaN in its per-video results (NaN / -1 in
+ * the scalars of a rank row) and nothing else is touched.  No atomics, no cooperative launch, no host synchronisation: capturable. */
+#define SUMK_AGREEMENT_SPEARMAN 0
+#define SUMK_AGREEMENT_KENDALL 1
+#define SUMK_AGREEMENT_KENDALL_SORT 2          /* Kendall with every pair through the sort: what the tests hold the table path to     */
+typedef struct sumk_agreement_video {
+  const float* user_summary; const float* user_scores;
+  int32_t n_frames; int32_t n_sum; int32_t n_sc; int32_t reserved;       /* reserved: 0                                        */
+  int64_t rank0; int64_t row0; int64_t sum0; int64_t f0; int64_t c0;
+} sumk_agreement_video;
+int sumk_rank_rows(const sumk_agreement_video* videos_dev, const sumk_agreement_video* videos_host, int32_t n_videos, double* avg_ranks_dev,
+                   int32_t* dense_ranks_dev, int64_t rank_total, int64_t* ties_dev, double* mean_dev, double* ssq_dev, int64_t row_total,
+                   void* stream);
+int sumk_agreement_f(const sumk_agreement_video* videos_dev, const sumk_agreement_video* videos_host, int32_t n_videos, float* F_dev,
+                     int64_t f_total, float* f_avg_user_dev, float* f_max_user_dev, int64_t sum_total, double* f_avg_dev, double* f_max_dev,
+                     void* stream);
+int sumk_agreement_corr(const sumk_agreement_video* videos_dev, const sumk_agreement_video* videos_host, int32_t n_videos, int32_t metric,
+                        const double* avg_ranks_dev, const int32_t* dense_ranks_dev, int64_t rank_total, const int64_t* ties_dev,
+                        const double* ssq_dev, int64_t row_total, double* C_dev, int64_t c_total, int64_t* counts_dev,
+                        double* corr_user_dev, double* corr_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ data-parallel exchange (RCCL)
  * The gradient all-reduce of data-parallel training as a library call: SUM, in place, over one flat bucket, on the caller's
  * HIP stream (one collective per optimiser step; the reference has no distributed code).  Bootstrap:

@@ -96,6 +96,11 @@ class AnnotateVideo(C.Structure):     # sumk_annotate_video (device pointers), o
                 ("frame0", C.c_int64), ("pick0", C.c_int64), ("seg0", C.c_int64), ("gtsum0", C.c_int64)]
 
 
+class AgreementVideo(C.Structure):    # sumk_agreement_video (device pointers), one per video
+    _fields_ = [("user_summary", C.c_void_p), ("user_scores", C.c_void_p), ("n_frames", C.c_int32), ("n_sum", C.c_int32), ("n_sc", C.c_int32),
+                ("reserved", C.c_int32), ("rank0", C.c_int64), ("row0", C.c_int64), ("sum0", C.c_int64), ("f0", C.c_int64), ("c0", C.c_int64)]
+
+
 class LstmLayerWeights(C.Structure):
     _fields_ = [("w_ih", C.c_void_p * 2), ("w_hh", C.c_void_p * 2), ("b_ih", C.c_void_p * 2), ("b_hh", C.c_void_p * 2),
                 ("x_planes", C.c_void_p), ("w_planes", C.c_void_p)]
@@ -246,6 +251,12 @@ _SIGS = {
     "sumk_annotate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p,
                                 C.c_int64, c_f32p, C.c_int64, C.c_void_p]),
     "sumk_annotate_gtsummary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_void_p]),
+    "sumk_rank_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_void_p]),
+    "sumk_agreement_f": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "sumk_agreement_corr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sumk_pack_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), HOST_I32P, C.c_int32, C.c_int32, C.c_int32]),
     "sumk_pack_rows_bf16": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), HOST_I32P, C.c_int32, C.c_int32, C.c_int32]),
     "sumk_gemm_prec": (C.c_int, [C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

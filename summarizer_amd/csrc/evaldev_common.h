@@ -1,5 +1,6 @@
-// What the device-side evaluation kernels share (evaldev.hip: segment means + Spearman; evalkendall.hip: Kendall's tau-b): the limits of
-// the per-video LDS tables and the pick-interval tables themselves.
+// What the device-side evaluation kernels share (evaldev.hip: segment means + Spearman; evalkendall.hip: Kendall's tau-b; evalselect.hip:
+// key shots + F-scores; agreement.hip: inter-annotator agreement): the limits of the per-video LDS tables, the pick-interval tables
+// themselves, the LDS merge sort of the Kendall blocks and the F-score arithmetic.
 #pragma once
 #include "sumk_internal.h"
 #include <math.h>
@@ -63,6 +64,101 @@ __host__ __device__ inline double kendall_tau_b(int64_t cmd, int64_t tot, int64_
   if (xtie == tot || ytie == tot) return (double)NAN;          // a constant side (or fewer than two frames)
   const double tau = (double)cmd / sqrt((double)(tot - xtie)) / sqrt((double)(tot - ytie));
   return fmin(1.0, fmax(-1.0, tau));
+}
+
+// ---- what the Kendall blocks of evalkendall.hip and agreement.hip share: the block size, the binary searches and the LDS merge sort
+constexpr int KD_THREADS = 1024;
+
+// elements of the sorted run a[0..n) below v / not above v
+__device__ __forceinline__ int kd_lower(const uint32_t* a, int n, uint32_t v) {
+  int lo = 0, hi = n;
+  while (lo < hi) { const int m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1; else hi = m; }
+  return lo;
+}
+__device__ __forceinline__ int kd_upper(const uint32_t* a, int n, uint32_t v) {
+  int lo = 0, hi = n;
+  while (lo < hi) { const int m = (lo + hi) >> 1; if (a[m] <= v) lo = m + 1; else hi = m; }
+  return lo;
+}
+
+// Stable bottom-up merge sort of a[0..n) with b as the other buffer; returns the buffer that holds the result.  Every thread must call
+// it (barriers inside); a, b and n are block-uniform.  inv collects this thread's share of the inversions of the input.
+__device__ inline uint32_t* kd_merge_sort(uint32_t* a, uint32_t* b, int n, long long& inv) {
+  for (int w = 1; w < n; w <<= 1) {
+    for (int i = threadIdx.x; i < n; i += KD_THREADS) {
+      const int s = i & ~(2 * w - 1), mid = min(s + w, n), end = min(s + 2 * w, n);
+      const uint32_t v = a[i];
+      int dst;
+      if (i < mid) {
+        const int c = kd_lower(a + mid, end - mid, v);      // right-run elements below v: they overtake it
+        inv += c;
+        dst = i + c;
+      } else {
+        dst = s + (i - mid) + kd_upper(a + s, mid - s, v);   // left-run elements not above v stay in front
+      }
+      b[dst] = v;
+    }
+    __syncthreads();
+    uint32_t* t = a; a = b; b = t;
+  }
+  return a;
+}
+
+// numpy's pairwise summation for n <= 128 doubles (np.mean over the annotators; the same tree as pairwise_sum of evaltail.hip)
+__device__ inline double kd_pairwise_sum(const double* a, int n) {
+  if (n < 8) {
+    double r = 0.0;
+    for (int i = 0; i < n; ++i) r += a[i];
+    return r;
+  }
+  double r[8];
+  for (int j = 0; j < 8; ++j) r[j] = a[j];
+  int i = 8;
+  for (; i < n - (n % 8); i += 8)
+    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) res += a[i];
+  return res;
+}
+
+// ---- the F-score arithmetic evalselect.hip and agreement.hip share
+// numpy's pairwise summation for n <= 128 (csrc/evaltail.hip pairwise_sum; the annotators of a video are at most 32)
+template <typename T>
+__device__ T sel_pairwise(const T* a, int n) {
+  if (n < 8) {
+    T r = (T)0;
+    for (int i = 0; i < n; ++i) r += a[i];
+    return r;
+  }
+  T r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = a[j];
+  int i = 8;
+  for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+  }
+  T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) res += a[i];
+  return res;
+}
+
+// fscores<T> of csrc/evaltail.hip from the counts: msum = ones of the machine summary over the video's frames, ov[k] / gs[k] = the
+// overlap with annotator k and the annotator's own count
+template <typename T>
+__device__ void sel_fscores(int msum, const int* ov, const int* gs, int n_users, T eps, T* f, double* f_avg, double* f_max) {
+  const T m_sum = (T)msum;
+  T best = (T)0;
+  for (int k = 0; k < n_users; ++k) {
+    const T overlap = (T)ov[k];
+    const T precision = overlap / (T)(m_sum + eps);
+    const float gsum = (float)gs[k];
+    const T recall = overlap / (T)(float)(gsum + 1e-8f);
+    f[k] = (precision == (T)0 && recall == (T)0) ? (T)0 : (((T)2 * precision) * recall) / (precision + recall);
+    best = (k == 0 || best < f[k]) ? f[k] : best;
+  }
+  *f_avg = (double)(T)(sel_pairwise(f, n_users) / (T)n_users);
+  *f_max = (double)best;
 }
 
 }  // namespace sumk

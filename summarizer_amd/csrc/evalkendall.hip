@@ -18,48 +18,12 @@
 
 namespace sumk {
 
-constexpr int KD_THREADS = 1024;
 constexpr int KD_TABLE = ED_MAX_INT + 8;                                  // entries of one group table (4097 used), a multiple of 4
 constexpr size_t KD_BUF_BYTES = (size_t)KD_MAX_FRAMES * sizeof(uint32_t);
 constexpr size_t KD_LDS_BYTES = KD_BUF_BYTES + (4 * (size_t)KD_TABLE * 4 > KD_BUF_BYTES ? 4 * (size_t)KD_TABLE * 4 : KD_BUF_BYTES);
 static_assert(KD_LDS_BYTES <= 160 * 1024 - 1024, "the Kendall block must fit the CU's LDS");
 static_assert(2 * (ED_MAX_INT + 1) <= KD_MAX_FRAMES, "the group sort ping-pongs inside the first key buffer");
 static_assert(ED_MAX_INT + 1 < (1 << (32 - KD_Y_BITS)) && KD_MAX_FRAMES <= (1 << KD_Y_BITS), "key = x rank << KD_Y_BITS | y rank");
-
-// elements of the sorted run a[0..n) below v / not above v
-__device__ __forceinline__ int kd_lower(const uint32_t* a, int n, uint32_t v) {
-  int lo = 0, hi = n;
-  while (lo < hi) { const int m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1; else hi = m; }
-  return lo;
-}
-__device__ __forceinline__ int kd_upper(const uint32_t* a, int n, uint32_t v) {
-  int lo = 0, hi = n;
-  while (lo < hi) { const int m = (lo + hi) >> 1; if (a[m] <= v) lo = m + 1; else hi = m; }
-  return lo;
-}
-
-// Stable bottom-up merge sort of a[0..n) with b as the other buffer; returns the buffer that holds the result.  Every thread must call
-// it (barriers inside); a, b and n are block-uniform.  inv collects this thread's share of the inversions of the input.
-__device__ uint32_t* kd_merge_sort(uint32_t* a, uint32_t* b, int n, long long& inv) {
-  for (int w = 1; w < n; w <<= 1) {
-    for (int i = threadIdx.x; i < n; i += KD_THREADS) {
-      const int s = i & ~(2 * w - 1), mid = min(s + w, n), end = min(s + 2 * w, n);
-      const uint32_t v = a[i];
-      int dst;
-      if (i < mid) {
-        const int c = kd_lower(a + mid, end - mid, v);      // right-run elements below v: they overtake it
-        inv += c;
-        dst = i + c;
-      } else {
-        dst = s + (i - mid) + kd_upper(a + s, mid - s, v);   // left-run elements not above v stay in front
-      }
-      b[dst] = v;
-    }
-    __syncthreads();
-    uint32_t* t = a; a = b; b = t;
-  }
-  return a;
-}
 
 // grid (ED_MAX_USERS, n_videos); tau[video * ED_MAX_USERS + user]
 __global__ __launch_bounds__(KD_THREADS) void eval_kendall_kernel(const float* __restrict__ scores, const sumk_eval_dev_video* __restrict__ vids,
@@ -147,23 +111,6 @@ __global__ __launch_bounds__(KD_THREADS) void eval_kendall_kernel(const float* _
       c[0] = cmd; c[1] = xtie; c[2] = ytie; c[3] = ntie;
     }
   }
-}
-
-// numpy's pairwise summation for n <= 128 doubles (np.mean over the annotators; the same tree as pairwise_sum of evaltail.hip)
-__device__ double kd_pairwise_sum(const double* a, int n) {
-  if (n < 8) {
-    double r = 0.0;
-    for (int i = 0; i < n; ++i) r += a[i];
-    return r;
-  }
-  double r[8];
-  for (int j = 0; j < 8; ++j) r[j] = a[j];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8)
-    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += a[i];
-  return res;
 }
 
 // one thread per video: the mean over its annotators

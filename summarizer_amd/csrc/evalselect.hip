@@ -96,45 +96,6 @@ __device__ __forceinline__ void sel_dp(int* r0, int* r1, unsigned long long* __r
   }
 }
 
-// numpy's pairwise summation for n <= 128 (csrc/evaltail.hip pairwise_sum; the annotators of a video are at most 32)
-template <typename T>
-__device__ T sel_pairwise(const T* a, int n) {
-  if (n < 8) {
-    T r = (T)0;
-    for (int i = 0; i < n; ++i) r += a[i];
-    return r;
-  }
-  T r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = a[j];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-  }
-  T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += a[i];
-  return res;
-}
-
-// fscores<T> of csrc/evaltail.hip from the counts: msum = ones of the machine summary over the video's frames, ov[k] / gs[k] = the
-// overlap with annotator k and the annotator's own count
-template <typename T>
-__device__ void sel_fscores(int msum, const int* ov, const int* gs, int n_users, T eps, T* f, double* f_avg, double* f_max) {
-  const T m_sum = (T)msum;
-  T best = (T)0;
-  for (int k = 0; k < n_users; ++k) {
-    const T overlap = (T)ov[k];
-    const T precision = overlap / (T)(m_sum + eps);
-    const float gsum = (float)gs[k];
-    const T recall = overlap / (T)(float)(gsum + 1e-8f);
-    f[k] = (precision == (T)0 && recall == (T)0) ? (T)0 : (((T)2 * precision) * recall) / (precision + recall);
-    best = (k == 0 || best < f[k]) ? f[k] : best;
-  }
-  *f_avg = (double)(T)(sel_pairwise(f, n_users) / (T)n_users);
-  *f_max = (double)best;
-}
-
 // the segment that owns summary entry f: the last s with start[s] <= f (empty segments share their start with the next one)
 __device__ __forceinline__ int sel_segment_of(const int* s_start, int n, int f) {
   int lo = 0, hi = n;                        // start[lo] <= f < start[hi] (start[n] = summary_len > f)

@@ -209,6 +209,14 @@ class Trainer:
         corr, f_avg, f_max, _ = self._evaluate_native(activations, test_keys)
         return np.mean(corr), (np.mean(f_avg), np.mean(f_max))
 
+    def human_agreement(self, fold, metric=None):
+        """How well the annotators of the fold's test videos agree with each other, under the metrics `test` reports for the model: the
+        result of `utils.agreement.human_agreement` on those records -- `["result"]` is the (avg_corr, (avg_f, max_f)) of the "human" row.
+        metric: hps.correlation_metric unless given.  Reads the dataset and the split only: no trainer state changes."""
+        from ..utils import agreement
+        keys = list(self.hps.splits_of_file[self.splits_file][fold]["test_keys"])
+        return agreement.human_agreement({k: self.dataset[k] for k in keys}, self._correlation_metric() if metric is None else metric)
+
     def _test_on_device(self, keys, max_frames_per_launch=1 << 17):
         """Device-side evaluation tail: ONE packed scoring launch, then sumk_eval_device on the scores where they
         are; a single small D2H carries segment means + correlations to the host knapsack / F-score threads.  None when the batch does
