@@ -540,6 +540,27 @@ int sumk_kts_gram_nonlin(const double* K, int32_t n_seq, const int32_t* seq_off_
                          int32_t lmin, int32_t lmax, int32_t* n_cps, int32_t* cps, double* scores, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ change points, banded (long videos)
+ * sumk_kts for videos past its 16384 steps, or long enough that one workgroup per video is the wrong shape (csrc/kts_banded.hip).  The
+ * definition, the tie rules (smallest t, smallest k), the exclusive lmax of row 0 and the outputs (-1 behind n_cps[v], +inf where a score
+ * exceeds 1e99 and behind n_cps[v]) are those of sumk_kts above.  Two things differ:
+ *   storage  with B = min(lmax, n) only J[t, t .. t + B - 1] is built and kept per row t (pitch B), and the fp32 Gram only in 64-row strips
+ *            of at most B + 63 columns from their own diagonal: the workspace is O(n B), not O(n^2), every offset 64-bit, p int32;
+ *   the DP   row k is ONE launch over the end points l of all videos (lane = l, the window max(k lmin, l - lmax) <= t < l cut over the
+ *            waves of a block, partial minima joined by an explicit (value, index) compare), rows with (k + 1) lmin > n are not launched,
+ *            and one closing launch does penalty, arg-min, backtrack and scores.  Stream order is the only dependency between rows: no
+ *            grid barrier, no cooperative launch, no spin-wait, no float atomics.  The call enqueues 6 + rows launches and never waits.
+ * Inside the band every number comes from the arithmetic of the dense path in its order (same lean NT Gram launch and K loop, same
+ * descending-s column sums, same 64-wide scans with carry, c = I[k-1,t] + J[t,l-1] under a strict < on ascending t), so for every input
+ * both calls accept, n_cps, cps and the bits of scores EQUAL those of sumk_kts whatever lmax is; results are bit-deterministic.
+ * Limits: 1 <= n <= 1048576 per video, at most 65535 videos, D % 4 == 0, 1 <= lmin <= lmax, 0 <= max_ncp <= longest video - 1; anything
+ * else -- a short workspace included -- returns SUMK_ERR_ARG, sets sumk_last_error and launches nothing.
+ * sumk_kts_banded_workspace_bytes: pure host arithmetic (0 = bad arguments): about n (8 B + 4 (B + 63) + 4 max_ncp) bytes per video. */
+size_t sumk_kts_banded_workspace_bytes(int32_t D, int32_t n_seq, const int32_t* seq_off_host, int32_t max_ncp, int32_t lmax);
+int sumk_kts_banded(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, int32_t max_ncp,
+                    int32_t lmin, int32_t lmax, double vmax, int32_t* n_cps, int32_t* cps, double* scores, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ shot selection
  * HOST function (no GPU work).  Replaces knapsack_ortools (summarizer/utils/knapsack.py:5-23): maximise
  * sum(values[i]) subject to sum(weights[i]) <= capacity; selected[i] = 1 for chosen items.  values/weights are the

@@ -279,6 +279,9 @@ _SIGS = {
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sumk_kts_gram_nonlin": (C.c_int, [C.c_void_p, C.c_int32, HOST_I32P, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p,
                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_kts_banded_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, HOST_I32P, C.c_int32, C.c_int32]),
+    "sumk_kts_banded": (C.c_int, [c_f32p, C.c_int32, C.c_int32, HOST_I32P, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_double, c_i32p, c_i32p,
+                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sumk_knapsack_dp": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64,
                                    C.POINTER(C.c_uint8)]),
     "sumk_eval_videos": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32]),

@@ -710,6 +710,34 @@ def kts(x, sb, max_ncp, vmax=1.0, lmin=1, lmax=100000, want_scores=True):
     return _kts_call("sumk_kts", x, sb, x.shape[1], max_ncp, lmin, lmax, vmax, want_scores)
 
 
+KTS_BANDED_MAX_STEPS = 1048576      # per video: sumk_kts_banded (include/sumk.h)
+
+
+def kts_banded_workspace_bytes(D, sb, max_ncp, lmax=100000):
+    """Bytes sumk_kts_banded needs for this batch: pure host arithmetic, 0 for arguments it would refuse."""
+    return _lib.load().sumk_kts_banded_workspace_bytes(int(D), sb.n_seq, sb.off_host_p, int(max_ncp), int(min(lmax, 2 ** 31 - 1)))
+
+
+def kts_banded(x, sb, max_ncp, vmax=1.0, lmin=1, lmax=100000, want_scores=True):
+    """`kts` for long videos: only the band J[t, t .. t + min(lmax, n) - 1] is kept and every row of the dynamic programme is one launch
+    over the whole chip (sumk_kts_banded, include/sumk.h).  Same outputs, bit for bit, wherever `kts` accepts the input.  Only enqueues
+    work on the current stream."""
+    _require_gpu(x, "kts_banded features")
+    if x.dim() != 2 or x.shape[0] != sb.n_rows or not x.is_contiguous():
+        raise SumkError(f"kts_banded: features must be contiguous ({sb.n_rows}, D), got {tuple(x.shape)}")
+    lib = _lib.load()
+    D, max_ncp, lmin, lmax = int(x.shape[1]), int(max_ncp), int(min(lmin, 2 ** 31 - 1)), int(min(lmax, 2 ** 31 - 1))
+    nb = _nonzero(lib.sumk_kts_banded_workspace_bytes(D, sb.n_seq, sb.off_host_p, max_ncp, lmax), "sumk_kts_banded_workspace_bytes")
+    ws = workspace(nb, x.device)
+    n_cps = torch.empty(sb.n_seq, dtype=torch.int32, device=x.device)
+    cps = torch.empty(sb.n_seq, max(max_ncp, 1), dtype=torch.int32, device=x.device)[:, :max_ncp]
+    scores = torch.empty(sb.n_seq, max_ncp + 1, dtype=torch.float64, device=x.device) if want_scores else None
+    rc = lib.sumk_kts_banded(_p(x), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, max_ncp, lmin, lmax, float(vmax), _p(n_cps), _p(cps), _p(scores),
+                             _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "sumk_kts_banded")
+    return n_cps, cps, scores
+
+
 def _kts_gram_check(K, sb):
     want = sum(n * n for n in sb.lens)
     if not K.is_cuda or K.dtype != torch.float64 or K.dim() != 1 or K.numel() != want or not K.is_contiguous():

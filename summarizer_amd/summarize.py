@@ -22,15 +22,17 @@ from .utils import kts
 
 
 class Summarizer:
-    """Summarizer(model, proportion=0.15, method="knapsack", **kts_options)
+    """Summarizer(model, proportion=0.15, method="knapsack", device=False, kts="dense", **kts_options)
 
     model: any scorer of this package with `score_packed` (VASNet, DSN, sLSTM, Transformer, ...), on the GPU.
     proportion / method: the summary budget and the selection algorithm of `generate_summary` ("knapsack" | "rank").
     kts_options: max_ncp, vmax, lmin, lmax of `utils.kts.segment` (max_ncp=None: min(n - 1, 1023)).
+    kts: "dense" (the default: `sumk_kts`, videos up to 16384 steps) | "banded" (`sumk_kts_banded`: long videos, see `utils.kts.segment_packed`;
+    the same change points wherever both apply, and the same output layout, so it goes with device=True as well).
     device: False (the default) returns numpy arrays after one D2H; True returns device tensors and never synchronises (see
     `summarize_batch`)."""
 
-    def __init__(self, model, proportion=0.15, method="knapsack", device=False, **kts_options):
+    def __init__(self, model, proportion=0.15, method="knapsack", device=False, kts="dense", **kts_options):
         if not hasattr(model, "score_packed"):
             raise SumkError(f"Summarizer: {type(model).__name__} has no score_packed")
         unknown = sorted(set(kts_options) - {"max_ncp", "vmax", "lmin", "lmax"})
@@ -38,6 +40,9 @@ class Summarizer:
             raise TypeError(f"Summarizer: unknown KTS options {unknown}")
         if method not in ("knapsack", "rank"):
             raise KeyError(f"Unknown method {method}")
+        if kts not in ("dense", "banded"):
+            raise KeyError(f"Unknown kts {kts}")
+        self.kts = kts
         self.model, self.proportion, self.method, self.kts_options, self.device = model, proportion, method, kts_options, bool(device)
 
     def summarize(self, features, picks=None, n_frames=None):
@@ -71,7 +76,7 @@ class Summarizer:
         try:
             with torch.no_grad():
                 scores = self.model.score_packed(packed, lens).detach().reshape(-1)
-                n_cps, cps = kts.segment_packed(packed, lens, **self.kts_options)
+                n_cps, cps = kts.segment_packed(packed, lens, banded=self.kts == "banded", **self.kts_options)
         finally:
             if was_training:
                 self.model.train()

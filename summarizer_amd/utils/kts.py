@@ -12,6 +12,7 @@ from .. import kernels
 from .._lib import SumkError
 
 DEFAULT_MAX_NCP = 1023
+DEFAULT_MAX_WORKSPACE_BYTES = 8 << 30      # banded path: refuse, before anything is enqueued, a workspace a shared card should not be asked for
 
 
 def _gram_on_device(K):
@@ -82,13 +83,24 @@ def default_max_ncp(n):
     return min(int(n) - 1, DEFAULT_MAX_NCP)
 
 
-def segment_packed(x, lens, max_ncp=None, vmax=1.0, lmin=1, lmax=100000):
-    """Device half of `segment`: (n_cps, cps) device tensors for a packed batch; only enqueues work."""
+def segment_packed(x, lens, max_ncp=None, vmax=1.0, lmin=1, lmax=100000, banded=False, max_workspace_bytes=DEFAULT_MAX_WORKSPACE_BYTES):
+    """Device half of `segment`: (n_cps, cps) device tensors for a packed batch; only enqueues work.
+    banded=True: the long-video path (sumk_kts_banded: up to 1 048 576 steps per video, memory O(n min(lmax, n)), a DP row per launch);
+    the same change points as the default wherever both accept the input.  It raises SumkError before anything is enqueued when its
+    workspace would pass max_workspace_bytes -- a safety condition for shared cards, not a tuning value."""
     sb = kernels.SeqBatch.get(lens, x.device)
     if max_ncp is None:
         max_ncp = default_max_ncp(max(sb.lens))
     max_ncp = min(int(max_ncp), max(sb.lens) - 1)
-    n_cps, cps, _ = kernels.kts(x, sb, max_ncp, vmax, lmin, lmax, want_scores=False)
+    if not banded:
+        n_cps, cps, _ = kernels.kts(x, sb, max_ncp, vmax, lmin, lmax, want_scores=False)
+        return n_cps, cps
+    need = kernels.kts_banded_workspace_bytes(x.shape[-1], sb, max_ncp, lmax)
+    if need > int(max_workspace_bytes):
+        n = max(sb.lens)
+        raise SumkError(f"kts banded: n={n} steps with a band of B=min(lmax, n)={min(int(lmax), n)} need a workspace of {need} bytes, over "
+                        f"max_workspace_bytes={int(max_workspace_bytes)}: use a smaller lmax (the workspace grows as n * B)")
+    n_cps, cps, _ = kernels.kts_banded(x, sb, max_ncp, vmax, lmin, lmax, want_scores=False)
     return n_cps, cps
 
 
@@ -105,17 +117,19 @@ def segments_from_device(n_cps, cps, lens, picks=None, n_frames=None):
     return out
 
 
-def segment(features, lens=None, picks=None, n_frames=None, max_ncp=None, vmax=1.0, lmin=1, lmax=100000):
+def segment(features, lens=None, picks=None, n_frames=None, max_ncp=None, vmax=1.0, lmin=1, lmax=100000, banded=False,
+            max_workspace_bytes=DEFAULT_MAX_WORKSPACE_BYTES):
     """KTS change points of one video or of a packed batch, in frames.
 
     features: one (T, D) float32 CUDA tensor, or the rows of several videos packed back to back with their `lens`.
     picks / n_frames: positions of the steps in the original video and its frame count (per video: lists when `lens` is given);
     None means picks = arange(n) and n_frames = n.  max_ncp=None means min(n - 1, 1023) change points at most (n = the longest video
     of the call); a video shorter than max_ncp + 1 steps is searched up to n - 1.
+    banded / max_workspace_bytes: the long-video path of `segment_packed` (set lmax to the longest segment worth looking for).
     Returns (change_points (S, 2) int32, n_frame_per_seg (S,) int32) -- a list of such pairs when `lens` is given."""
     single = lens is None
     if single:
         lens, picks, n_frames = [features.shape[0]], [picks], [n_frames]
-    n_cps, cps = segment_packed(features, lens, max_ncp, vmax, lmin, lmax)
+    n_cps, cps = segment_packed(features, lens, max_ncp, vmax, lmin, lmax, banded, max_workspace_bytes)
     out = segments_from_device(n_cps, cps, [int(v) for v in lens], picks, n_frames)
     return out[0] if single else out
