@@ -231,8 +231,8 @@ __global__ __launch_bounds__(AG_F_THREADS) void agreement_f_kernel(FArgs a) {
   }
   __syncthreads();
   if (tid == 0) {
-    a.f_avg[vi] = U >= 2 ? kd_pairwise_sum(s_avg, U) / (double)U : nan("");
-    a.f_max[vi] = U >= 2 ? kd_pairwise_sum(s_max, U) / (double)U : nan("");
+    a.f_avg[vi] = U >= 2 ? np_pairwise_leaf(s_avg, U) / (double)U : nan("");
+    a.f_max[vi] = U >= 2 ? np_pairwise_leaf(s_max, U) / (double)U : nan("");
   }
 }
 
@@ -386,12 +386,12 @@ __global__ __launch_bounds__(64) void agreement_final_kernel(CorrArgs a) {
     int m = 0;
     for (int k = 0; k < U; ++k)
       if (k != r) s_row[r][m++] = Cv[(size_t)r * U + k];
-    const double c = U >= 2 ? kd_pairwise_sum(s_row[r], U - 1) / (double)(U - 1) : nan("");
+    const double c = U >= 2 ? np_pairwise_leaf(s_row[r], U - 1) / (double)(U - 1) : nan("");
     a.corr_user[v.row0 + r] = c;
     s_corr[r] = c;
   }
   __syncthreads();
-  if (tid == 0) a.corr[vi] = U >= 2 ? kd_pairwise_sum(s_corr, U) / (double)U : nan("");
+  if (tid == 0) a.corr[vi] = U >= 2 ? np_pairwise_leaf(s_corr, U) / (double)U : nan("");
 }
 
 namespace {

@@ -6,7 +6,7 @@
 //   annotate_frames_kernel   one thread per frame, the annotators of that frame in order: user rows, consensus.  One pass over the
 //                            U x n_frames floats, coalesced along the frames; the sum over annotators is sequential by definition.
 //   annotate_video_kernel    one workgroup per video: min / max of the consensus at the picks (exact in any order), gtscore, then one
-//                            thread per (annotator, segment) mean on the rows the first kernel wrote (ed_pairwise_sum, the tree of
+//                            thread per (annotator, segment) mean on the rows the first kernel wrote (np_pairwise_sum, the tree of
 //                            evaldev.hip).  Stream order is the only dependency between the two: no atomics, no cooperative launch.
 //   annotate_gtsummary_kernel  gtsummary[t] = frame summary of gtscore at picks[t].
 // The specification is tests/annotate_ref.py, bit for bit: float32 operations in the stated order, compiled without FMA contraction.
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(AN_THREADS) void annotate_video_kernel(const sumk_a
     const int u = i / n_segs, s = i - u * n_segs;
     const int lo = max(0, min(n_frames, v.cps[2 * s])), hi = max(lo, min(n_frames, v.cps[2 * s + 1] + 1));
     const float* row = user + v.user0 + (size_t)u * n_frames;
-    seg_means[v.seg0 + i] = hi > lo ? ed_pairwise_sum(row + lo, hi - lo) / (float)(hi - lo) : 0.f;
+    seg_means[v.seg0 + i] = hi > lo ? np_pairwise_sum(row + lo, hi - lo) / (float)(hi - lo) : 0.f;
   }
 }
 

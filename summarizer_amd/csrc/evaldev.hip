@@ -11,7 +11,7 @@
 
 namespace sumk {
 
-// (numpy's float32 pairwise summation, ed_pairwise_sum, is in evaldev_common.h: csrc/annotate.hip takes the same segment means)
+// (numpy's float32 pairwise summation, np_pairwise_sum, is in evaldev_common.h: csrc/annotate.hip takes the same segment means)
 
 __global__ __launch_bounds__(256) void eval_device_kernel(const float* __restrict__ scores, const sumk_eval_dev_video* __restrict__ vids,
                                                           float* __restrict__ frame_scratch, float* __restrict__ seg_means,
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void eval_device_kernel(const float* __restric
   // ---- float32 segment means (eval.py:91-94), one thread per segment
   for (int s = tid; s < v.n_segs; s += 256) {
     const int lo = max(0, min(n_frames, v.cps[2 * s])), hi = max(lo, min(n_frames, v.cps[2 * s + 1] + 1));
-    seg_means[v.seg0 + s] = hi > lo ? ed_pairwise_sum(fs + lo, hi - lo) / (float)(hi - lo) : 0.f;
+    seg_means[v.seg0 + s] = hi > lo ? np_pairwise_sum(fs + lo, hi - lo) / (float)(hi - lo) : 0.f;
   }
   // ---- Spearman (eval.py:49-72): average ranks of -frame_scores.  Frames of one interval share their value, so ranks are taken per
   // interval with the interval's frame count as multiplicity (picks are ascending: checked by the host wrapper).
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void eval_segments_kernel(const float* __restr
   __syncthreads();
   for (int s = tid; s < v.n_segs; s += 256) {
     const int lo = max(0, min(n_frames, v.cps[2 * s])), hi = max(lo, min(n_frames, v.cps[2 * s + 1] + 1));
-    seg_means[v.seg0 + s] = hi > lo ? ed_pairwise_sum(fs + lo, hi - lo) / (float)(hi - lo) : 0.f;
+    seg_means[v.seg0 + s] = hi > lo ? np_pairwise_sum(fs + lo, hi - lo) / (float)(hi - lo) : 0.f;
   }
 }
 

@@ -10,27 +10,39 @@ namespace sumk {
 constexpr int ED_MAX_INT = 4096;     // pick intervals per video the block keeps in LDS (T <= 4095 steps)
 constexpr int ED_MAX_USERS = 32;
 
-// numpy's pairwise summation (numpy/core/src/umath/loops_utils.h.src), float32 -- same tree as csrc/evaltail.hip.  Shared by the segment
-// means of evaldev.hip (upsampled scores) and annotate.hip (annotator rows): additions only, in one order.
-__device__ inline float ed_pairwise_sum(const float* a, int n) {
+// numpy's pairwise summation (numpy/core/src/umath/loops_utils.h.src), the one copy every bit-exact mean of the library goes through, host
+// (evaltail.hip) and device, T = float or double.  Additions only, in one order: there is nothing for FMA contraction to fuse, so the
+// contraction setting of the including unit (-ffp-contract=off, #pragma clang fp contract(off)) cannot change a result.
+// np_pairwise_leaf: the unrolled block of n <= 128 values (below 8 a running sum; numpy starts that one from -0.0, which differs from +0
+// only for an all -0.0 input).  Callers that know n <= 128 (the annotators of a video: at most ED_MAX_USERS) take it directly and stay
+// free of device recursion.
+template <class T>
+__host__ __device__ inline T np_pairwise_leaf(const T* a, int n) {
   if (n < 8) {
-    float r = 0.f;
+    T r = (T)0;
     for (int i = 0; i < n; ++i) r += a[i];
     return r;
   }
-  if (n <= 128) {
-    float r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-      for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
+  T r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = a[j];
+  int i = 8;
+  for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
   }
-  int n2 = n / 2;
+  T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) res += a[i];
+  return res;
+}
+// any n: the leaf up to 128, above that the halves split at a multiple of 8.  N = the caller's own length type (int in the kernels, whose
+// recursion then keeps 32-bit lengths on its call stack; int64_t on the host).
+template <class T, class N>
+__host__ __device__ inline T np_pairwise_sum(const T* a, N n) {
+  if (n <= 128) return np_pairwise_leaf(a, (int)n);
+  N n2 = n / 2;
   n2 -= n2 % 8;
-  return ed_pairwise_sum(a, n2) + ed_pairwise_sum(a + n2, n - n2);
+  return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
 }
 
 // the interval tables of a video: interval i = frames [s_lo[i], s_hi[i]) takes score i (0 past the scores) -- eval.py:24-34.
@@ -104,45 +116,7 @@ __device__ inline uint32_t* kd_merge_sort(uint32_t* a, uint32_t* b, int n, long 
   return a;
 }
 
-// numpy's pairwise summation for n <= 128 doubles (np.mean over the annotators; the same tree as pairwise_sum of evaltail.hip)
-__device__ inline double kd_pairwise_sum(const double* a, int n) {
-  if (n < 8) {
-    double r = 0.0;
-    for (int i = 0; i < n; ++i) r += a[i];
-    return r;
-  }
-  double r[8];
-  for (int j = 0; j < 8; ++j) r[j] = a[j];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8)
-    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += a[i];
-  return res;
-}
-
 // ---- the F-score arithmetic evalselect.hip and agreement.hip share
-// numpy's pairwise summation for n <= 128 (csrc/evaltail.hip pairwise_sum; the annotators of a video are at most 32)
-template <typename T>
-__device__ T sel_pairwise(const T* a, int n) {
-  if (n < 8) {
-    T r = (T)0;
-    for (int i = 0; i < n; ++i) r += a[i];
-    return r;
-  }
-  T r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = a[j];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-  }
-  T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += a[i];
-  return res;
-}
-
 // fscores<T> of csrc/evaltail.hip from the counts: msum = ones of the machine summary over the video's frames, ov[k] / gs[k] = the
 // overlap with annotator k and the annotator's own count
 template <typename T>
@@ -157,7 +131,7 @@ __device__ void sel_fscores(int msum, const int* ov, const int* gs, int n_users,
     f[k] = (precision == (T)0 && recall == (T)0) ? (T)0 : (((T)2 * precision) * recall) / (precision + recall);
     best = (k == 0 || best < f[k]) ? f[k] : best;
   }
-  *f_avg = (double)(T)(sel_pairwise(f, n_users) / (T)n_users);
+  *f_avg = (double)(T)(np_pairwise_leaf(f, n_users) / (T)n_users);      // n_users <= ED_MAX_USERS
   *f_max = (double)best;
 }
 

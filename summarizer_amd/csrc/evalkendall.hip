@@ -119,7 +119,7 @@ __global__ __launch_bounds__(64) void eval_kendall_final_kernel(const sumk_eval_
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= n_videos) return;
   const int nu = vids[i].n_users;
-  corr[i] = nu > 0 && nu <= ED_MAX_USERS ? kd_pairwise_sum(tau + (size_t)i * ED_MAX_USERS, nu) / (double)nu : nan("");
+  corr[i] = nu > 0 && nu <= ED_MAX_USERS ? np_pairwise_leaf(tau + (size_t)i * ED_MAX_USERS, nu) / (double)nu : nan("");
 }
 
 }  // namespace sumk

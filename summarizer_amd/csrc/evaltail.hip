@@ -25,28 +25,7 @@
 
 namespace {
 
-// numpy's pairwise summation (numpy/core/src/umath/loops_utils.h.src), for T = float or double
-template <typename T>
-T pairwise_sum(const T* a, int64_t n) {
-  if (n < 8) {
-    T r = (T)0;   // numpy starts from -0.0 for floats; +0 vs -0 only differs for an all -0.0 input
-    for (int64_t i = 0; i < n; ++i) r += a[i];
-    return r;
-  }
-  if (n <= 128) {
-    T r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int64_t i = 8;
-    for (; i < n - (n % 8); i += 8)
-      for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-  }
-  int64_t n2 = n / 2;
-  n2 -= n2 % 8;
-  return pairwise_sum(a, n2) + pairwise_sum(a + n2, n - n2);
-}
+using sumk::np_pairwise_sum;      // numpy's pairwise summation (evaldev_common.h), for T = float or double
 
 struct Scratch {
   std::vector<float> frame_scores, summary;
@@ -75,13 +54,13 @@ void rank_desc(const float* x, int n, Scratch& S) {
 
 template <typename T>
 void fscores(const T* m, const float* user_summary, int n_users, int n_frames, T eps, double* f_avg, double* f_max, std::vector<T>& f) {
-  T m_sum = pairwise_sum(m, (int64_t)n_frames);
+  T m_sum = np_pairwise_sum(m, (int64_t)n_frames);
   f.resize(n_users);
   std::vector<T> prod(n_frames), u(n_frames);
   for (int k = 0; k < n_users; ++k) {
     const float* us = user_summary + (int64_t)k * n_frames;
     for (int i = 0; i < n_frames; ++i) { u[i] = us[i] > 0.f ? (T)1 : (T)0; prod[i] = m[i] * u[i]; }
-    const T overlap = pairwise_sum(prod.data(), (int64_t)n_frames);
+    const T overlap = np_pairwise_sum(prod.data(), (int64_t)n_frames);
     const T precision = overlap / (T)(m_sum + eps);
     // the annotator's sum stays float32 in numpy (a float32 array summed, + a python float under NEP 50) even when the
     // machine summary was promoted to float64 by its zero padding
@@ -90,7 +69,7 @@ void fscores(const T* m, const float* user_summary, int n_users, int n_frames, T
     const T recall = overlap / (T)(float)(gsum + 1e-8f);
     f[k] = (precision == (T)0 && recall == (T)0) ? (T)0 : (((T)2 * precision) * recall) / (precision + recall);
   }
-  *f_avg = (double)(T)(pairwise_sum(f.data(), (int64_t)n_users) / (T)n_users);
+  *f_avg = (double)(T)(np_pairwise_sum(f.data(), (int64_t)n_users) / (T)n_users);
   *f_max = (double)*std::max_element(f.begin(), f.end());
 }
 
@@ -120,14 +99,14 @@ int eval_one(sumk_eval_video& v, double proportion, int method, Scratch& S) {
   v.corr = std::nan("");
   if (v.user_ranks != nullptr && v.n_users > 0) {
     rank_desc(S.frame_scores.data(), n_frames, S);
-    double mean = pairwise_sum(S.rank.data(), (int64_t)n_frames) / (double)n_frames;
+    double mean = np_pairwise_sum(S.rank.data(), (int64_t)n_frames) / (double)n_frames;
     S.dsum.resize(n_frames);
     double smm = 0.0;
     for (int i = 0; i < n_frames; ++i) { S.dsum[i] = S.rank[i] - mean; smm += S.dsum[i] * S.dsum[i]; }
     double acc = 0.0;
     for (int k = 0; k < v.n_users; ++k) {
       const double* ru = v.user_ranks + (int64_t)k * n_frames;
-      const double mu = pairwise_sum(ru, (int64_t)n_frames) / (double)n_frames;
+      const double mu = np_pairwise_sum(ru, (int64_t)n_frames) / (double)n_frames;
       double sxy = 0.0, suu = 0.0;
       for (int i = 0; i < n_frames; ++i) { const double d = ru[i] - mu; sxy += d * S.dsum[i]; suu += d * d; }
       acc += sxy / std::sqrt(suu * smm);
@@ -144,7 +123,7 @@ int eval_one(sumk_eval_video& v, double proportion, int method, Scratch& S) {
   for (int s = 0; s < S_; ++s) {
     const int lo = std::max(0, std::min(n_frames, v.cps[2 * s])), hi = std::max(lo, std::min(n_frames, v.cps[2 * s + 1] + 1));
     const float mean = from_device ? v.seg_means[s]
-                     : hi > lo ? pairwise_sum(S.frame_scores.data() + lo, (int64_t)(hi - lo)) / (float)(hi - lo) : 0.f;   // float32 mean (numpy gives NaN for an empty segment)
+                     : hi > lo ? np_pairwise_sum(S.frame_scores.data() + lo, (int64_t)(hi - lo)) / (float)(hi - lo) : 0.f;   // float32 mean (numpy gives NaN for an empty segment)
     seg[s] = (double)mean;
     S.values[s] = (int64_t)(seg[s] * 1000.0);   // np.int truncation, knapsack.py:13
     S.weights[s] = v.nfps[s];
@@ -336,7 +315,7 @@ int kendall_one(sumk_eval_video& v, int64_t* counts, Scratch& S, KendallScratch&
     K.tau[u] = sumk::kendall_tau_b(cmd, tot, xtie, ytie);
     if (counts != nullptr) { counts[4 * u] = cmd; counts[4 * u + 1] = xtie; counts[4 * u + 2] = ytie; counts[4 * u + 3] = ntie; }
   }
-  v.corr = pairwise_sum(K.tau.data(), (int64_t)v.n_users) / (double)v.n_users;      // np.mean over the annotators (a NaN annotator: NaN)
+  v.corr = np_pairwise_sum(K.tau.data(), (int64_t)v.n_users) / (double)v.n_users;      // np.mean over the annotators (a NaN annotator: NaN)
   return 0;
 }
 

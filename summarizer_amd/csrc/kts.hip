@@ -21,18 +21,15 @@
 // DP: one workgroup per video, threads strided over the end point l, two rows of I double-buffered in LDS when they fit (n <= 4062),
 // in the workspace otherwise; p in uint8 (n <= 255) or uint16; one barrier per k.  `<` on ascending t / k keeps the smallest index at
 // ties (wave and block reductions compare the index explicitly); no atomics: bit-deterministic.  Penalty, argmin and backtrack run at
-// the end of the same launch: no host synchronisation anywhere in the call.
-#include "sumk_internal.h"
-#include <math.h>
+// the end of the same launch: no host synchronisation anywhere in the call.  The row scans, that tail, the markers and the per-video
+// sizes are in kts_common.h, shared with the banded path (kts_banded.hip), which must return the same bits.
+#include "kts_common.h"
 
 namespace sumk {
 
 namespace {
 constexpr int KTS_MAX_N = 16384;
-constexpr int KTS_THREADS = 1024;
-constexpr int KTS_RED_BYTES = 512;                          // block-reduction scratch behind the two I rows
-constexpr int KTS_LDS_LIMIT = 65536;
-constexpr double KTS_BIG = 1e101, KTS_INF_ABOVE = 1e99;     // "no segmentation" marker of the original code and its reporting threshold
+constexpr int KTS_THREADS = KTS_TAIL_THREADS;               // one block runs the DP rows and then the shared tail
 
 struct KSeq {
   int64_t goff;    // fp32 Gram: element offset of the video's (n x ldg) block
@@ -43,9 +40,6 @@ struct KSeq {
 };
 
 struct KtsWs { size_t gram, J, diag, p, irows, sc, seq, prob, total; int32_t n_max, tiles, nprob, lds; };
-
-inline int kts_p_bytes(int n) { return n <= 255 ? 1 : 2; }
-inline bool kts_in_lds(int n) { return 2 * ((size_t)n + 1) * 8 + KTS_RED_BYTES <= (size_t)KTS_LDS_LIMIT; }
 
 int kts_carve(int D, int n_seq, const int32_t* off, int max_ncp, bool want_gram, KtsWs* w) {
   SUMK_ARG(D > 0 && D % 4 == 0, "kts: D=%d must be a positive multiple of 4", D);
@@ -58,12 +52,10 @@ int kts_carve(int D, int n_seq, const int32_t* off, int max_ncp, bool want_gram,
   }
   SUMK_ARG(max_ncp >= 0 && max_ncp <= n_max - 1, "kts: max_ncp=%d outside 0 .. %d (longest video - 1)", max_ncp, n_max - 1);
   for (int s = 0; s < n_seq; ++s) {
-    const int n = off[s + 1] - off[s], tm = (n + 63) / 64, m = max_ncp < n - 1 ? max_ncp : n - 1;
-    g += (size_t)n * ((n + 3) & ~3); j += (size_t)n * n;
-    pb += align_up((size_t)m * (n + 1) * kts_p_bytes(n), 16);
-    if (kts_in_lds(n)) { const int b = 2 * (n + 1) * 8 + KTS_RED_BYTES; lds = b > lds ? b : lds; }
-    else ir += 2 * ((size_t)n + 1);
-    tiles += tm * (tm + 1) / 2; nprob += tm;
+    const KtsSizes z = kts_sizes(off[s + 1] - off[s], max_ncp);
+    g += z.gram; j += z.J; pb += z.p; ir += z.irows;
+    lds = z.lds > lds ? z.lds : lds;
+    tiles += z.tiles; nprob += z.probs;
   }
   size_t p = 0;
   auto take = [&](size_t bytes) { size_t at = p; p += align_up(bytes, 256); return at; };
@@ -80,34 +72,26 @@ int kts_carve(int D, int n_seq, const int32_t* off, int max_ncp, bool want_gram,
 }
 }  // namespace
 
-// One thread per video: its offsets, and (features path) one GEMM problem per 64-row strip of its Gram matrix that covers the tiles from
-// the diagonal to the right edge -- the tiles below the diagonal are never read and never computed.
+// One thread per video: its offsets (the sums of kts_sizes over the videos before it, as kts_carve adds them), and (features path) one
+// GEMM problem per 64-row strip of its Gram matrix that covers the tiles from the diagonal to the right edge -- the tiles below the
+// diagonal are never read and never computed.
 __global__ void kts_setup_kernel(const int32_t* off, int n_seq, int D, int max_ncp, KSeq* seq, GemmProb* prob) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n_seq) return;
   int64_t goff = 0, joff = 0, poff = 0, ioff = 0; int ts = 0, pi = 0;
   for (int q = 0; q < s; ++q) {
-    const int n = off[q + 1] - off[q], tm = (n + 63) / 64, m = max_ncp < n - 1 ? max_ncp : n - 1;
-    goff += (int64_t)n * ((n + 3) & ~3); joff += (int64_t)n * n;
-    poff += ((int64_t)m * (n + 1) * (n <= 255 ? 1 : 2) + 15) / 16 * 16;
-    if (2 * ((int64_t)n + 1) * 8 + KTS_RED_BYTES > KTS_LDS_LIMIT) ioff += 2 * ((int64_t)n + 1);
-    ts += tm * (tm + 1) / 2; pi += tm;
+    const KtsSizes z = kts_sizes(off[q + 1] - off[q], max_ncp);
+    goff += z.gram; joff += z.J; poff += z.p; ioff += z.irows;
+    ts += z.tiles; pi += z.probs;
   }
-  const int row0 = off[s], n = off[s + 1] - row0, ld = (n + 3) & ~3, tm = (n + 63) / 64;
-  KSeq k; k.goff = goff; k.joff = joff; k.poff = poff;
-  k.ioff = 2 * ((int64_t)n + 1) * 8 + KTS_RED_BYTES > KTS_LDS_LIMIT ? ioff : -1;
-  k.row0 = row0; k.n = n; k.ldg = ld; k.m = max_ncp < n - 1 ? max_ncp : n - 1;
+  const int row0 = off[s], n = off[s + 1] - row0;
+  const KtsSizes z = kts_sizes(n, max_ncp);
+  KSeq k; k.goff = goff; k.joff = joff; k.poff = poff; k.ioff = z.irows ? ioff : -1;
+  k.row0 = row0; k.n = n; k.ldg = z.ldg; k.m = z.m;
   seq[s] = k;
   if (!prob) return;
-  for (int r = 0; r < tm; ++r) {
-    GemmProb q;
-    q.a_off = (int64_t)(row0 + 64 * r) * D; q.b_off = q.a_off; q.c_off = goff + (int64_t)64 * r * ld + 64 * r; q.r_off = 0;
-    q.M = n - 64 * r < 64 ? n - 64 * r : 64; q.N = n - 64 * r; q.K = D; q.lda = D; q.ldb = D; q.ldc = ld; q.ldr = 0;
-    q.tile_start = ts; q.tiles_n = tm - r;
-    for (int i = 0; i < 7; ++i) q.pad_[i] = 0;
-    prob[pi + r] = q;
-    ts += tm - r;
-  }
+  for (int r = 0; r < z.probs; ++r)
+    ts += kts_strip_prob(prob + pi + r, row0, n, r, D, n - 64 * r, goff + (int64_t)64 * r * z.ldg + 64 * r, z.ldg, ts);
 }
 
 // Column pass: thread = column j, s descending from the diagonal.  FROM_F32: the symmetric fp32 Gram (upper triangle); otherwise the
@@ -131,26 +115,12 @@ __global__ __launch_bounds__(256) void kts_col_kernel(const float* __restrict__ 
   }
 }
 
-// Row pass: one wave per row i; inclusive scans of W[i][t] and K[t][t] over t = i .. n - 1 in chunks of 64 with a carry; J over W.
+// Row pass: one wave per row i; kts_row_scan over t = i .. n - 1, J over W.
 __global__ __launch_bounds__(256) void kts_row_kernel(const KSeq* __restrict__ seq, double* __restrict__ W, const double* __restrict__ diag) {
   const KSeq si = seq[blockIdx.y];
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, n = si.n;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), n = si.n;
   if (i >= n) return;
-  double* w = W + si.joff + (int64_t)i * n;
-  const double* dg = diag + si.row0;
-  double cs = 0.0, cd = 0.0;
-  for (int base = i; base < n; base += 64) {
-    const int t = base + lane;
-    double a = t < n ? w[t] : 0.0, d = t < n ? dg[t] : 0.0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double ua = __shfl_up(a, o), ud = __shfl_up(d, o);
-      if (lane >= o) { a += ua; d += ud; }
-    }
-    a += cs; d += cd;
-    if (t < n) w[t] = d - a / (double)(t - i + 1);
-    cs = __shfl(a, 63); cd = __shfl(d, 63);
-  }
+  kts_row_scan(W + si.joff + (int64_t)i * n + i, diag + si.row0 + i, n - i, threadIdx.x & 63);
 }
 
 struct KtsArgs {
@@ -199,10 +169,10 @@ __device__ __forceinline__ void kts_dp_rows(double* I0, double* I1, const double
 
 __global__ __launch_bounds__(KTS_THREADS) void kts_dp_kernel(KtsArgs a) {
   extern __shared__ __attribute__((aligned(16))) double kts_lds[];
-  const int v = blockIdx.x, tid = threadIdx.x;
+  const int v = blockIdx.x;
   const KSeq si = a.seq[v];
   const int n = si.n, m = si.m;
-  const bool narrow = n <= 255;
+  const bool narrow = kts_p_narrow(n);
   const double* J = a.J + si.joff;
   void* p = (char*)a.p + si.poff;
   double* sc = a.sc + (int64_t)v * (a.max_ncp + 1);
@@ -215,61 +185,14 @@ __global__ __launch_bounds__(KTS_THREADS) void kts_dp_kernel(KtsArgs a) {
     kts_dp_rows(I0, I0 + (n + 1), J, p, narrow, sc, n, m, a.lmin, a.lmax);
     red = kts_lds;
   }
-  // penalty + argmin over k (the smallest k at a tie; an infinite score never wins: +inf < x is false and k = 0 is the start value)
-  int* redk = (int*)(red + 16);
-  int mb = m;
-  if (!a.fixed_m) {
-    double best = INFINITY; int bk = 0;
-    for (int k = tid; k <= m; k += KTS_THREADS) {
-      double s = sc[k];
-      if (s > KTS_INF_ABOVE) s = INFINITY;
-      double c = s / (double)n;
-      if (k > 0) c += (a.vmax * (double)k / (2.0 * (double)n)) * (log((double)n / (double)k) + 1.0);
-      if (c < best) { best = c; bk = k; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double ob = __shfl_xor(best, o); const int ok = __shfl_xor(bk, o);
-      if (ob < best || (ob == best && ok < bk)) { best = ob; bk = ok; }
-    }
-    if ((tid & 63) == 0) { red[tid >> 6] = best; redk[tid >> 6] = bk; }
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < KTS_THREADS / 64; ++w)
-        if (red[w] < best || (red[w] == best && redk[w] < bk)) { best = red[w]; bk = redk[w]; }
-      redk[0] = best < INFINITY ? bk : 0;
-    }
-    __syncthreads();
-    mb = redk[0];
-  }
-  if (tid == 0) {
-    a.n_cps[v] = mb;
-    int32_t* out = a.cps + (int64_t)v * a.max_ncp;
-    int cur = n;
-    for (int k = mb; k >= 1; --k) {
-      // an entry the DP never wrote (no feasible end point there) reads as 0, as in the zero-initialised table of the original
-      cur = cur >= (int64_t)(k + 1) * a.lmin ? kts_p_load(p, narrow, (int64_t)(k - 1) * (n + 1) + cur) : 0;
-      out[k - 1] = cur;
-    }
-    for (int k = mb; k < a.max_ncp; ++k) out[k] = -1;
-  }
-  if (a.scores) {
-    double* so = a.scores + (int64_t)v * (a.max_ncp + 1);
-    for (int k = tid; k <= a.max_ncp; k += KTS_THREADS) {
-      double s = INFINITY;
-      if (k <= mb) { s = sc[k]; if (s > KTS_INF_ABOVE) s = INFINITY; }
-      so[k] = s;
-    }
-  }
+  const KtsTail t = {a.max_ncp, a.lmin, a.fixed_m, a.vmax, a.n_cps, a.cps, a.scores};
+  kts_tail(t, v, n, m, sc, red, (int*)(red + 16), [&](int64_t idx) { return kts_p_load(p, narrow, idx); });
 }
 
 static int kts_run(const float* x, const double* K, int D, int n_seq, const int32_t* off_host, const int32_t* off_dev, int max_ncp, int lmin,
                    int lmax, double vmax, int fixed_m, int32_t* n_cps, int32_t* cps, double* scores, void* workspace, size_t workspace_bytes,
                    hipStream_t stream, const char* who) {
-  SUMK_ARG((x || K) && off_dev && n_cps && workspace, "%s: null pointer", who);
-  SUMK_ARG(cps || max_ncp == 0, "%s: null cps", who);
-  SUMK_ARG(lmin >= 1 && lmax >= lmin, "%s: need 1 <= lmin <= lmax, got lmin=%d lmax=%d", who, lmin, lmax);
-  SUMK_ARG(vmax == vmax, "%s: vmax is NaN", who);
+  SUMK_TRY(kts_check_args(who, x ? (const void*)x : (const void*)K, off_dev, n_cps, cps, workspace, max_ncp, lmin, lmax, vmax));
   KtsWs L;
   SUMK_TRY(kts_carve(D, n_seq, off_host, max_ncp, x != nullptr, &L));
   SUMK_ARG(workspace_bytes >= L.total, "%s: workspace %zu < required %zu", who, workspace_bytes, L.total);

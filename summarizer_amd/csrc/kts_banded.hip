@@ -12,26 +12,24 @@
 //      column pass  W[s][j] = K[j][j] + sum_{s <= s' < j} 2 K[s'][j], s descending from the diagonal and stopping at j - s = B - 1.  One wave per
 //                   64 columns walks s down TOGETHER (lane j joins at s = j and leaves after s = j - B + 1): the lanes of one step then read
 //                   one Gram row and write one band row, both contiguous -- the per-lane order of additions is the dense one.
-//      row pass     the two inclusive scans from t = i in chunks of 64 with the carry, as kts_row_kernel, over the min(B, n - i) entries of row i.
+//      row pass     the two inclusive scans from t = i in chunks of 64 with the carry (kts_row_scan, kts_common.h), over the min(B, n - i) entries of row i.
 // 2. A DP row is a launch.  Row k depends on the whole of row k - 1, and the only chip-wide ordering that needs no barrier, no cooperative
 //    launch, no spin-wait and no atomics is the stream: k launches, each over all end points l of all videos.  A block owns 64 consecutive end
 //    points (lane = l: the reads of J[t][l - 1 - t] at a fixed t are 64 consecutive doubles) and its 16 waves cut the window
 //    max(k lmin, l - lmax) <= t < l into 16 ascending pieces; the partial minima meet in LDS under an explicit (value, index) compare, so the
 //    smallest t still wins a tie.  A row streams every band entry it needs exactly once: at most n B doubles (n^2 / 2 when B = n), spread
 //    over ceil(n / 64) blocks instead of one.  Rows with (k + 1) lmin > n are not launched (the host knows n).  p is int32 for every n.
-//    The closing launch (one block per video) is the dense path's tail: penalty, arg-min over k, backtrack, score row.
+//    The closing launch (one block per video) runs the tail both paths share (kts_tail, kts_common.h): penalty, arg-min over k, backtrack,
+//    score row.
 // Nothing waits on the host: the call enqueues 6 + (number of DP rows) launches.
-#include "sumk_internal.h"
-#include <math.h>
+#include "kts_common.h"
 
 namespace sumk {
 
 namespace {
 constexpr int KB_MAX_N = 1048576;
 constexpr int KB_DP_THREADS = 1024, KB_DP_WAVES = KB_DP_THREADS / 64;
-constexpr int KB_TAIL_THREADS = 1024;
 constexpr int KB_J_PAD = 64;                                // doubles behind the last band: lanes outside their window read (and drop) up to 63 past a row
-constexpr double KB_BIG = 1e101, KB_INF_ABOVE = 1e99;       // as kts.hip: the original's "no segmentation" marker and its reporting threshold
 
 struct BSeq {
   int64_t goff;    // fp32 Gram strips: element offset
@@ -42,9 +40,6 @@ struct BSeq {
 };
 
 struct KbWs { size_t gram, J, diag, p, irows, sc, seq, prob, total; int32_t n_max, tiles, nprob; };
-
-inline int kb_band(int n, int lmax) { return lmax < n ? lmax : n; }
-inline int kb_ldg(int n, int B) { const int64_t w = (int64_t)B + 63 < n ? (int64_t)B + 63 : n; return (int)((w + 3) & ~(int64_t)3); }
 
 int kb_carve(int D, int n_seq, const int32_t* off, int max_ncp, int lmax, KbWs* w) {
   SUMK_ARG(D > 0 && D % 4 == 0, "kts_banded: D=%d must be a positive multiple of 4", D);
@@ -59,12 +54,9 @@ int kb_carve(int D, int n_seq, const int32_t* off, int max_ncp, int lmax, KbWs* 
   SUMK_ARG(max_ncp >= 0 && max_ncp <= n_max - 1, "kts_banded: max_ncp=%d outside 0 .. %d (longest video - 1)", max_ncp, n_max - 1);
   size_t g = 0, j = 0, pe = 0, ir = 0; int64_t tiles = 0, nprob = 0;
   for (int s = 0; s < n_seq; ++s) {
-    const int n = off[s + 1] - off[s], B = kb_band(n, lmax), tm = (n + 63) / 64, m = max_ncp < n - 1 ? max_ncp : n - 1;
-    g += (size_t)n * kb_ldg(n, B); j += (size_t)n * B;
-    pe += align_up((size_t)m * ((size_t)n + 1), 4);
-    ir += 2 * ((size_t)n + 1);
-    for (int r = 0; r < tm; ++r) { const int64_t N = n - 64 * r < B + 63 ? n - 64 * r : B + 63; tiles += (N + 63) / 64; }
-    nprob += tm;
+    const KtsBandSizes z = kts_band_sizes(off[s + 1] - off[s], max_ncp, lmax);
+    g += z.gram; j += z.J; pe += z.p; ir += z.irows;
+    tiles += z.tiles; nprob += z.probs;
   }
   SUMK_ARG(tiles < ((int64_t)1 << 31), "kts_banded: %lld Gram tiles do not fit one launch: use a smaller lmax", (long long)tiles);
   size_t p = 0;
@@ -83,37 +75,24 @@ int kb_carve(int D, int n_seq, const int32_t* off, int max_ncp, int lmax, KbWs* 
 }
 }  // namespace
 
-// One thread per video: its offsets and one GEMM problem per 64-row strip of its Gram band.
+// One thread per video: its offsets (the sums of kts_band_sizes over the videos before it, as kb_carve adds them) and one GEMM problem
+// per 64-row strip of its Gram band.
 __global__ void kts_banded_setup_kernel(const int32_t* off, int n_seq, int D, int max_ncp, int lmax, BSeq* seq, GemmProb* prob) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n_seq) return;
   int64_t goff = 0, joff = 0, poff = 0, ioff = 0; int ts = 0, pi = 0;
-  for (int q = 0; q <= s; ++q) {
-    const int n = off[q + 1] - off[q], B = lmax < n ? lmax : n, tm = (n + 63) / 64, m = max_ncp < n - 1 ? max_ncp : n - 1;
-    const int64_t wd = (int64_t)B + 63 < n ? (int64_t)B + 63 : n;
-    const int ld = (int)((wd + 3) & ~(int64_t)3);
-    if (q == s) {
-      BSeq k; k.goff = goff; k.joff = joff; k.poff = poff; k.ioff = ioff;
-      k.row0 = off[q]; k.n = n; k.ldg = ld; k.m = m; k.B = B; k.pad_[0] = k.pad_[1] = k.pad_[2] = 0;
-      seq[s] = k;
-      for (int r = 0; r < tm; ++r) {
-        GemmProb g;
-        g.a_off = (int64_t)(k.row0 + 64 * r) * D; g.b_off = g.a_off; g.c_off = goff + (int64_t)64 * r * ld; g.r_off = 0;
-        g.M = n - 64 * r < 64 ? n - 64 * r : 64; g.N = n - 64 * r < B + 63 ? n - 64 * r : B + 63; g.K = D;
-        g.lda = D; g.ldb = D; g.ldc = ld; g.ldr = 0;
-        g.tile_start = ts; g.tiles_n = (g.N + 63) / 64;
-        for (int i = 0; i < 7; ++i) g.pad_[i] = 0;
-        prob[pi + r] = g;
-        ts += g.tiles_n;
-      }
-      return;
-    }
-    goff += (int64_t)n * ld; joff += (int64_t)n * B;
-    poff += ((int64_t)m * ((int64_t)n + 1) + 3) / 4 * 4;
-    ioff += 2 * ((int64_t)n + 1);
-    for (int r = 0; r < tm; ++r) { const int N = n - 64 * r < B + 63 ? n - 64 * r : B + 63; ts += (N + 63) / 64; }
-    pi += tm;
+  for (int q = 0; q < s; ++q) {
+    const KtsBandSizes z = kts_band_sizes(off[q + 1] - off[q], max_ncp, lmax);
+    goff += z.gram; joff += z.J; poff += z.p; ioff += z.irows;
+    ts += z.tiles; pi += z.probs;
   }
+  const int row0 = off[s], n = off[s + 1] - row0;
+  const KtsBandSizes z = kts_band_sizes(n, max_ncp, lmax);
+  BSeq k; k.goff = goff; k.joff = joff; k.poff = poff; k.ioff = ioff;
+  k.row0 = row0; k.n = n; k.ldg = z.ldg; k.m = z.m; k.B = z.B; k.pad_[0] = k.pad_[1] = k.pad_[2] = 0;
+  seq[s] = k;
+  for (int r = 0; r < z.probs; ++r)
+    ts += kts_strip_prob(prob + pi + r, row0, n, r, D, kts_band_strip_n(n, z.B, r), goff + (int64_t)64 * r * z.ldg, z.ldg, ts);
 }
 
 // Column pass.  One wave per 64 columns; the wave walks s down from its last column, lane j takes part while j - B < s <= j.
@@ -140,27 +119,12 @@ __global__ __launch_bounds__(256) void kts_banded_col_kernel(const float* __rest
   }
 }
 
-// Row pass: one wave per row i; inclusive scans of W[i][t] and K[t][t] over the band entries of the row, J over W (kts_row_kernel's scans).
+// Row pass: one wave per row i; kts_row_scan over the min(B, n - i) band entries of the row, J over W.
 __global__ __launch_bounds__(256) void kts_banded_row_kernel(const BSeq* __restrict__ seq, double* __restrict__ W, const double* __restrict__ diag) {
   const BSeq si = seq[blockIdx.y];
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, n = si.n;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), n = si.n;
   if (i >= n) return;
-  const int len = n - i < si.B ? n - i : si.B;
-  double* w = W + si.joff + (int64_t)i * si.B;
-  const double* dg = diag + si.row0 + i;
-  double cs = 0.0, cd = 0.0;
-  for (int base = 0; base < len; base += 64) {
-    const int c = base + lane;
-    double a = c < len ? w[c] : 0.0, d = c < len ? dg[c] : 0.0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double ua = __shfl_up(a, o), ud = __shfl_up(d, o);
-      if (lane >= o) { a += ua; d += ud; }
-    }
-    a += cs; d += cd;
-    if (c < len) w[c] = d - a / (double)(c + 1);
-    cs = __shfl(a, 63); cd = __shfl(d, 63);
-  }
+  kts_row_scan(W + si.joff + (int64_t)i * si.B, diag + si.row0 + i, n - i < si.B ? n - i : si.B, threadIdx.x & 63);
 }
 
 struct KbArgs {
@@ -169,12 +133,12 @@ struct KbArgs {
   int32_t* n_cps; int32_t* cps; double* scores;
 };
 
-// DP row 0: I[0][l] = J[0][l - 1] for lmin <= l < lmax (EXCLUSIVE: the kept quirk), 1e101 elsewhere; l - 1 <= B - 1 there.
+// DP row 0: I[0][l] = J[0][l - 1] for lmin <= l < lmax (EXCLUSIVE: the kept quirk), KTS_BIG elsewhere; l - 1 <= B - 1 there.
 __global__ __launch_bounds__(256) void kts_banded_row0_kernel(KbArgs a) {
   const BSeq si = a.seq[blockIdx.y];
   const int l = blockIdx.x * 256 + threadIdx.x, n = si.n;
   if (l > n) return;
-  const double v = (l >= a.lmin && l < a.lmax) ? a.J[si.joff + (l - 1)] : KB_BIG;
+  const double v = (l >= a.lmin && l < a.lmax) ? a.J[si.joff + (l - 1)] : KTS_BIG;
   a.irows[si.ioff + l] = v;
   if (l == n) a.sc[(int64_t)blockIdx.y * (a.max_ncp + 1)] = v;
 }
@@ -236,11 +200,11 @@ __global__ __launch_bounds__(KB_DP_THREADS) void kts_banded_dp_kernel(KbArgs a) 
   }
 }
 
-// Closing launch, one block per video: the rows that were not run read 1e101, then the tail of kts_dp_kernel (penalty + arg-min over k
-// with the smallest k at a tie, backtrack, score row).
-__global__ __launch_bounds__(KB_TAIL_THREADS) void kts_banded_tail_kernel(KbArgs a) {
-  __shared__ double red[KB_TAIL_THREADS / 64];
-  __shared__ int redk[KB_TAIL_THREADS / 64];
+// Closing launch, one block per video: the rows that were not run read KTS_BIG, then kts_tail (penalty + arg-min over k with the
+// smallest k at a tie, backtrack, score row).
+__global__ __launch_bounds__(KTS_TAIL_THREADS) void kts_banded_tail_kernel(KbArgs a) {
+  __shared__ double red[KTS_TAIL_THREADS / 64];
+  __shared__ int redk[KTS_TAIL_THREADS / 64];
   const int v = blockIdx.x, tid = threadIdx.x;
   const BSeq si = a.seq[v];
   const int n = si.n, m = si.m;
@@ -248,49 +212,10 @@ __global__ __launch_bounds__(KB_TAIL_THREADS) void kts_banded_tail_kernel(KbArgs
   double* sc = a.sc + (int64_t)v * (a.max_ncp + 1);
   const int64_t kfeas = (int64_t)n / a.lmin;                  // rows 1 .. kfeas - 1 have (k + 1) lmin <= n
   const int krun = kfeas - 1 < m ? (int)(kfeas - 1 > 0 ? kfeas - 1 : 0) : m;
-  for (int q = krun + 1 + tid; q <= m; q += KB_TAIL_THREADS) sc[q] = KB_BIG;
+  for (int q = krun + 1 + tid; q <= m; q += KTS_TAIL_THREADS) sc[q] = KTS_BIG;
   __syncthreads();
-  double best = INFINITY; int bk = 0;
-  for (int k = tid; k <= m; k += KB_TAIL_THREADS) {
-    double s = sc[k];
-    if (s > KB_INF_ABOVE) s = INFINITY;
-    double c = s / (double)n;
-    if (k > 0) c += (a.vmax * (double)k / (2.0 * (double)n)) * (log((double)n / (double)k) + 1.0);
-    if (c < best) { best = c; bk = k; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ob = __shfl_xor(best, o); const int ok = __shfl_xor(bk, o);
-    if (ob < best || (ob == best && ok < bk)) { best = ob; bk = ok; }
-  }
-  if ((tid & 63) == 0) { red[tid >> 6] = best; redk[tid >> 6] = bk; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < KB_TAIL_THREADS / 64; ++w)
-      if (red[w] < best || (red[w] == best && redk[w] < bk)) { best = red[w]; bk = redk[w]; }
-    redk[0] = best < INFINITY ? bk : 0;
-  }
-  __syncthreads();
-  const int mb = redk[0];
-  if (tid == 0) {
-    a.n_cps[v] = mb;
-    int32_t* out = a.cps + (int64_t)v * a.max_ncp;
-    int cur = n;
-    for (int k = mb; k >= 1; --k) {
-      // an entry the DP never wrote (no feasible end point there) reads as 0, as in the zero-initialised table of the original
-      cur = cur >= (int64_t)(k + 1) * a.lmin ? p[(int64_t)(k - 1) * (n + 1) + cur] : 0;
-      out[k - 1] = cur;
-    }
-    for (int k = mb; k < a.max_ncp; ++k) out[k] = -1;
-  }
-  if (a.scores) {
-    double* so = a.scores + (int64_t)v * (a.max_ncp + 1);
-    for (int k = tid; k <= a.max_ncp; k += KB_TAIL_THREADS) {
-      double s = INFINITY;
-      if (k <= mb) { s = sc[k]; if (s > KB_INF_ABOVE) s = INFINITY; }
-      so[k] = s;
-    }
-  }
+  const KtsTail t = {a.max_ncp, a.lmin, 0, a.vmax, a.n_cps, a.cps, a.scores};
+  kts_tail(t, v, n, m, sc, red, redk, [&](int64_t idx) { return p[idx]; });
 }
 
 }  // namespace sumk
@@ -307,10 +232,7 @@ extern "C" int sumk_kts_banded(const float* x, int32_t D, int32_t n_seq, const i
                                int32_t max_ncp, int32_t lmin, int32_t lmax, double vmax, int32_t* n_cps, int32_t* cps, double* scores,
                                void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  SUMK_ARG(x && seq_off_dev && n_cps && workspace, "kts_banded: null pointer");
-  SUMK_ARG(cps || max_ncp == 0, "kts_banded: null cps");
-  SUMK_ARG(lmin >= 1 && lmax >= lmin, "kts_banded: need 1 <= lmin <= lmax, got lmin=%d lmax=%d", lmin, lmax);
-  SUMK_ARG(vmax == vmax, "kts_banded: vmax is NaN");
+  SUMK_TRY(kts_check_args("kts_banded", x, seq_off_dev, n_cps, cps, workspace, max_ncp, lmin, lmax, vmax));
   KbWs L;
   SUMK_TRY(kb_carve(D, n_seq, seq_off_host, max_ncp, lmax, &L));
   SUMK_ARG(workspace_bytes >= L.total, "kts_banded: workspace %zu < required %zu", workspace_bytes, L.total);
@@ -339,7 +261,7 @@ extern "C" int sumk_kts_banded(const float* x, int32_t D, int32_t n_seq, const i
     const int64_t lstart = (int64_t)(k + 1) * lmin;
     hipLaunchKernelGGL(kts_banded_dp_kernel, dim3((unsigned)((L.n_max - lstart) / 64 + 1), n_seq), dim3(KB_DP_THREADS), 0, stream, a);
   }
-  hipLaunchKernelGGL(kts_banded_tail_kernel, dim3(n_seq), dim3(KB_TAIL_THREADS), 0, stream, a);
+  hipLaunchKernelGGL(kts_banded_tail_kernel, dim3(n_seq), dim3(KTS_TAIL_THREADS), 0, stream, a);
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
 }

@@ -683,15 +683,18 @@ def kts_workspace_bytes(D, sb, max_ncp):
 
 def _kts_call(name, src, sb, D, max_ncp, lmin, lmax, vmax, want_scores):
     lib = _lib.load()
-    max_ncp, lmin, lmax = int(max_ncp), int(min(lmin, 2 ** 31 - 1)), int(min(lmax, 2 ** 31 - 1))
-    nb = _nonzero(lib.sumk_kts_workspace_bytes(D, sb.n_seq, sb.off_host_p, max_ncp), "sumk_kts_workspace_bytes")
+    D, max_ncp, lmin, lmax = int(D), int(max_ncp), int(min(lmin, 2 ** 31 - 1)), int(min(lmax, 2 ** 31 - 1))
+    if name == "sumk_kts_banded":
+        nb = _nonzero(lib.sumk_kts_banded_workspace_bytes(D, sb.n_seq, sb.off_host_p, max_ncp, lmax), "sumk_kts_banded_workspace_bytes")
+    else:
+        nb = _nonzero(lib.sumk_kts_workspace_bytes(D, sb.n_seq, sb.off_host_p, max_ncp), "sumk_kts_workspace_bytes")
     ws = workspace(nb, src.device)
     n_cps = torch.empty(sb.n_seq, dtype=torch.int32, device=src.device)
     cps = torch.empty(sb.n_seq, max(max_ncp, 1), dtype=torch.int32, device=src.device)[:, :max_ncp]
     scores = torch.empty(sb.n_seq, max_ncp + 1, dtype=torch.float64, device=src.device) if want_scores else None
     tail = (_p(n_cps), _p(cps), _p(scores), _p(ws), ws.numel(), _stream())
-    if name == "sumk_kts":
-        rc = lib.sumk_kts(_p(src), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, max_ncp, lmin, lmax, float(vmax), *tail)
+    if name in ("sumk_kts", "sumk_kts_banded"):
+        rc = getattr(lib, name)(_p(src), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, max_ncp, lmin, lmax, float(vmax), *tail)
     elif name == "sumk_kts_gram":
         rc = lib.sumk_kts_gram(_p(src), sb.n_seq, sb.off_host_p, sb.off_dev_p, max_ncp, lmin, lmax, float(vmax), *tail)
     else:
@@ -725,17 +728,7 @@ def kts_banded(x, sb, max_ncp, vmax=1.0, lmin=1, lmax=100000, want_scores=True):
     _require_gpu(x, "kts_banded features")
     if x.dim() != 2 or x.shape[0] != sb.n_rows or not x.is_contiguous():
         raise SumkError(f"kts_banded: features must be contiguous ({sb.n_rows}, D), got {tuple(x.shape)}")
-    lib = _lib.load()
-    D, max_ncp, lmin, lmax = int(x.shape[1]), int(max_ncp), int(min(lmin, 2 ** 31 - 1)), int(min(lmax, 2 ** 31 - 1))
-    nb = _nonzero(lib.sumk_kts_banded_workspace_bytes(D, sb.n_seq, sb.off_host_p, max_ncp, lmax), "sumk_kts_banded_workspace_bytes")
-    ws = workspace(nb, x.device)
-    n_cps = torch.empty(sb.n_seq, dtype=torch.int32, device=x.device)
-    cps = torch.empty(sb.n_seq, max(max_ncp, 1), dtype=torch.int32, device=x.device)[:, :max_ncp]
-    scores = torch.empty(sb.n_seq, max_ncp + 1, dtype=torch.float64, device=x.device) if want_scores else None
-    rc = lib.sumk_kts_banded(_p(x), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, max_ncp, lmin, lmax, float(vmax), _p(n_cps), _p(cps), _p(scores),
-                             _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "sumk_kts_banded")
-    return n_cps, cps, scores
+    return _kts_call("sumk_kts_banded", x, sb, x.shape[1], max_ncp, lmin, lmax, vmax, want_scores)
 
 
 def _kts_gram_check(K, sb):

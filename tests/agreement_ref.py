@@ -21,7 +21,7 @@ F32, F64 = np.float32, np.float64
 
 
 def pairwise_sum64(a):
-    """numpy's pairwise summation of at most 128 float64 values written out (kd_pairwise_sum of csrc/evaldev_common.h)."""
+    """numpy's pairwise summation of at most 128 float64 values written out (np_pairwise_leaf of csrc/evaldev_common.h)."""
     a = np.asarray(a, dtype=F64)
     n = a.shape[0]
     assert n <= 128
