@@ -33,7 +33,6 @@ prof vasnet_score_folded_bf16x6 --precision bf16x6 --fold-vo
 for args in "" "--precision bf16x6" "--precision bf16x3" "--mode train" "--mode train --precision bf16" "--model dsn" "--model dsn --precision bf16x6" "--model dsn --precision bf16x3" "--model dsn --mode train" "--model dsn --mode reinforce" "--model dsn --mode reinforce --precision bf16x6" "--model dsn --mode train --precision bf16x6" "--mode train --precision bf16x6" "--model slstm" "--model slstm --precision bf16x6" "--model slstm --precision bf16x3" "--model slstm --mode train --steps 5 --warmup 2" "--model transformer" "--model transformer --precision bf16x6" "--model transformer --precision bf16x3" "--precision bf16x6 --fold-vo" "--precision bf16x3 --fold-vo" "--workload stress --steps 3 --warmup 1" "--workload stress --precision bf16x6 --steps 3 --warmup 1" "--workload stress --precision bf16x3 --steps 3 --warmup 1" "--mode stream"; do
   timeout 300 python3 bench.py --full --no-cpu-baseline --headline-only --steps 30 --warmup 5 $args 2>/dev/null | tail -1 | grep '^{' >> $OUT/bench_lines.jsonl
 done
-python3 scripts/probes/wide2_probe.py > $OUT/wide2_probe.txt 2>&1
 python3 scripts/probes/dsn_probe.py > $OUT/dsn_probe.txt 2>&1
 python3 scripts/probes/dsn_train_probe.py > $OUT/dsn_train_probe.txt 2>&1
 python3 scripts/probes/slstm_train_probe.py > $OUT/slstm_train_probe.txt 2>&1

@@ -25,5 +25,5 @@ for _ in range(2): step()
 torch.cuda.synchronize(); t0 = time.perf_counter()
 for _ in range(5): step()
 torch.cuda.synchronize()
-print(f"sLSTM training step R6={os.environ.get('SUMK_LSTM_BWD_R6', '1')} WIDE2={os.environ.get('SUMK_LSTM_WIDE2', '1')}: {(time.perf_counter() - t0) / 5 * 1e3:.2f} ms", flush=True)
+print(f"sLSTM training step R6={os.environ.get('SUMK_LSTM_BWD_R6', '1')}: {(time.perf_counter() - t0) / 5 * 1e3:.2f} ms", flush=True)
 kernels.health_check()

@@ -36,7 +36,6 @@ struct LstmWs {
   size_t g, cstate, prob, pstate, gates, call, hprev, dg, slab, dhrec, dcstate, prob_sk, colpart, pstate_b, xchg, partial, total;
   size_t xchg_bytes;
   size_t ll, ll_bytes;     // forward recurrence hand-off buffer (H <= 256): directly behind pstate, zeroed with it
-  size_t llb, llb_bytes;   // backward recurrence hand-off buffer (H <= 256): directly behind pstate_b, zeroed with it
   size_t wx, wx_bytes;     // forward recurrence exchange of lstm_wide2_kernel (256 < H <= 1024): [group][step parity 2][direction 2][k/4 256][row 64][4 floats]
   size_t slab_elems;
   int32_t n_rows, t_max;
@@ -84,7 +83,7 @@ static int lstm_carve(int In, int H, int n_seq, const int32_t* off, int training
   w->wx_bytes = (H > 256 && H <= 1024) ? (size_t)((n_seq + 63) / 64) * 4 * 256 * 64 * 16 : 0;
   w->wx = take(w->wx_bytes);
   w->gates = w->call = w->hprev = w->dg = w->slab = w->dhrec = w->dcstate = w->prob_sk = w->colpart = 0;
-  w->pstate_b = w->xchg = 0; w->xchg_bytes = 0; w->llb = 0; w->llb_bytes = 0;
+  w->pstate_b = w->xchg = 0; w->xchg_bytes = 0;
   w->slab_elems = 0;
   if (training) {
     w->gates = take(R * 8 * H * 4);                 // post-nonlinearity i,f,g,o per row and direction
@@ -98,13 +97,6 @@ static int lstm_carve(int In, int H, int n_seq, const int32_t* off, int training
     w->prob_sk = take(64 * sizeof(GemmProb));
     w->colpart = take((size_t)128 * 8 * H * 4);
     w->pstate_b = take(PSTATE_WORDS * 4);
-    {  // flag-in-data exchange of the H <= 256 BPTT: [step parity 2][item][member 32][video < gsize][H] x {float partial, uint32 step tag}
-      const int gsz = std::min(32, std::max(1, (2 * n_seq + 7) / 8));
-      const int items = 2 * ((n_seq + gsz - 1) / gsz);
-      static const bool ll_bwd = getenv("SUMK_LSTM_LL_BWD") && getenv("SUMK_LSTM_LL_BWD")[0] == '1';   // (opt-in variant: no buffer otherwise)
-      w->llb_bytes = (ll_bwd && H <= 256) ? (size_t)2 * items * 32 * gsz * H * 8 : 0;
-      w->llb = take(w->llb_bytes);
-    }
     {  // persistent BPTT exchange: [parity 2][item][member 32][video 32][H] partial sums of dh (H <= 256 only)
       int gsize = std::min(32, std::max(1, (2 * n_seq + 7) / 8));
       int items = 2 * ((n_seq + gsize - 1) / gsize);
@@ -564,10 +556,10 @@ __global__ void zero_words_kernel(unsigned* p, int n) {
 __device__ unsigned g_sumk_health = 0u;
 
 
-// CPW = 8-wide k chunks per wave: the block's 8 waves cover K = 64 * CPW >= H (4 for DSN's H = 256, 16 for sLSTM's 1024).
+// CPW = 4 k chunks of 8 per wave: the block's 8 waves cover K = 64 * CPW = 256 >= H.
 // The member's W_hh fragments (32 gate rows x its wave's k range) live in REGISTERS for the whole work item -- exactly the
 // MFMA B operands every step needs -- so LDS holds only the split-K partial tiles.  The A fragments (h_{t-1}[video li][k..k+3]) go
-// straight from the sc1 buffer loads into the MFMAs, as in lstm_wide_kernel below (staging h through an LDS panel measured slower).
+// straight from the sc1 buffer loads into the MFMAs, as in lstm_wide2_kernel below (staging h through an LDS panel measured slower).
 // LL ("flag in the data", the low-latency protocol of collective libraries): h_t is published as ONE 8-byte {value, step tag} store per
 // element into a double-buffered exchange array, and the consumers' OWN loads of h_{t-1} are the poll -- reloaded until every tag
 // they need says t.  An aligned 8-byte store is single-copy atomic, so a matching tag proves its value; no other ordering is needed.
@@ -580,9 +572,10 @@ __device__ unsigned g_sumk_health = 0u;
 // upper half would multiply zeros: half the matrix-pipe time of a step.  Lane group g = lane / 16 takes the CONTIGUOUS k range
 // [32 wave + 8 g, + 8) of both operands (the sum over k does not care which lane group carries which k), so a lane's eight h values are
 // four 16-byte loads.
-template <int CPW, bool LL = false, bool M16 = false>
+template <bool LL = false, bool M16 = false>
 __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a) {
-  static_assert(!M16 || (LL && CPW == 4), "the 16-row form exists for the flag-in-data kernel with 32 k per wave");
+  static_assert(!M16 || LL, "the 16-row form exists for the flag-in-data kernel");
+  constexpr int CPW = 4;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int H = a.H, P = H + 4;
   // [8 waves][32 rows][PP] split-K partial tiles; PP = 32: the epilogue's float4 read (a 16-lane group = 2 videos x 8 units x 16 B)
@@ -841,479 +834,21 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_kernel(PersistArgs a)
   }
 }
 
-// ------------------------------------------------------------------------------------------- persistent recurrence with the input projection inside (round 6)
-// Inference in the split-bf16 modes: the hoisted projection GEMM G = X W_ih^T + b (215 us in front of an 836-us recurrence on the S-TVSum
-// batch) disappears INTO the recurrence.  A member's slice of it -- the group's <= 16 videos x its 32 gate columns x In = 1024 -- does not
-// depend on h, and a step of the flag-in-data kernel spends two thirds of its ~4 700 cycles waiting (hand-off latency, arrival skew).
-// Each wave multiplies its k range (128) of the NEXT step's x rows with its W_ih fragments (registers / LDS for the whole item: 2 column
-// tiles x 4 k32 steps x NP planes of 16-byte chunks -- exactly the lane fragment of v_mfma_f32_16x16x32_bf16 in the "KB planes" format of
-// the weight-plane block) while it would otherwise wait: the waves without a cell-update role right behind the step's barrier, the others
-// behind their publish.  The products START the next step's accumulators; the recurrent MFMAs add on top and the existing cross-wave sum
-// delivers  x W_ih^T + h W_hh^T  in one piece; the epilogue adds the two biases.  G (R x 8H fp32, 98 MB here) is never written or read.
-// x comes from the fp32 feature matrix itself: a lane's k range of a k32 step is 32 contiguous bytes, the four lanes of a row cover one
-// 128-byte line (the x PLANES would be a gather here: one 16-byte chunk per 128-byte line, eight frames of a video to a line -- measured
-// 8.4 us per step, 786 KB per member and step through L2); it is split into the planes in registers (the roundings of split_planes).
-// The partial tiles are double-buffered by step parity, so the step has ONE workgroup barrier.  Same hand-off (flag in the data), same
-// 16-row MFMAs, same gate arithmetic as lstm_persist_kernel<4, true, true>; term order of the split products as gemm_regstage.h.
-#ifndef SUMK_PROJ_KA
-#define SUMK_PROJ_KA 4
-#endif
-constexpr int PROJ_KA = SUMK_PROJ_KA;
-constexpr int PROJ_RF = 12;     // W_ih fragments a lane keeps in registers; the rest of its 8 / 16 / 24 are read from LDS every step
-struct PersistProjArgs {
-  const float* x; const char* wpl; const float* bias;     // x (n_rows x In, fp32); KB planes of [w_ih[0]; w_ih[1]] (8H x In); b_ih + b_hh (8H)
-  const float* whh[2]; float* Hout;
-  const int32_t* off; unsigned* state;
-  unsigned long long* ll; int32_t ll_bytes;
-  int32_t n_seq, H, In, gsize, n_groups, upm, n_active, n_teams;
-  uint32_t w_rp16;                                         // bytes of one (k16 block, plane, half) sub-array of the weight planes
-};
-
-// KA: k32 steps of the projection per wave 0..3 (the waves with the cell update); waves 4..7 take KB = 8 - KA each (4 KA + 4 KB = 32 steps
-// = In = 1024): the cell-update waves have the step's critical chain and only the hand-off latency behind their publish to work in, the
-// others idle from the step's barrier on.  (Measured: the symmetric 4 : 4 is the fastest -- 3 : 5, 2 : 6 and 5 : 3 all lose 0.1-0.5 us per step,
-// profiles/r06_dsn_fused_projection_probe.txt -- so PROJ_KA = 4; the parameter stays as the record of that sweep.)  A wave holds its first RF = 12 W_ih fragments (in (k32 step, tile, plane) order) in registers,
-// the rest in LDS.
-template <int NP, int KA>
-__global__ __launch_bounds__(PK_THREADS) void lstm_persist_proj_kernel(PersistProjArgs a) {
-  constexpr int KB = 8 - KA, KMAX = KB > KA ? KB : KA;
-  constexpr int RF = PROJ_RF;       // W_ih fragments per lane in registers (4 VGPRs each)
-  constexpr int FA = KA * 2 * NP;                                            // fragments per wave of role A (role B: KB * 2 * NP)
-  constexpr int LA = FA > RF ? FA - RF : 0;                                  // of them in LDS (role A's come first)
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int H = a.H;
-  constexpr int PP = 32;
-  float* part = smem;               // [step parity 2][8 waves][16 rows][PP] split-K partial tiles
-  int* sR0 = reinterpret_cast<int*>(part + 2 * 8 * 16 * PP);
-  int* sT = sR0 + 32;
-  int* sTg = sT + 32;
-  bf16x8* wlds = reinterpret_cast<bf16x8*>(sTg + 32);      // [(LA | LB) fragments][256 threads of the role] x 16 B: waves 0..3 first
-
-  const int team = blockIdx.x % a.n_teams, slot = blockIdx.x / a.n_teams;
-  if (slot >= a.n_active) return;
-  const __amdgpu_buffer_rsrc_t lrsrc = __builtin_amdgcn_make_buffer_rsrc(a.ll, (short)0, a.ll_bytes, 0x00020000);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int u0 = slot * a.upm, nu = min(a.upm, H - u0);
-  const int n_items = 2 * a.n_groups;
-  const int vl = lane & 15, kq = lane >> 4;     // this lane's MFMA row (video of the group) / column, and its k quarter
-  int loaded_dir = -1;
-  bool dead = false;
-  if (wave < 4) __builtin_amdgcn_s_setprio(1);  // the waves with the cell update (the step's critical chain) win the SIMD's issue arbitration
-
-  float4 wreg[4];                   // W_hh fragments (fp32 16x16x4 form): column n = 16 tile + lane % 16; k = 32 wave + 8 kq + 0..7
-  bf16x8 wih[RF];                   // W_ih fragments f = (s 2 + tile) NP + plane < RF: column n = 16 tile + lane % 16, k = 32 (ks0 + s) + 8 kq + 0..7
-  const bool roleA = wave < 4;
-  const int ks0 = roleA ? KA * wave : 4 * KA + KB * (wave - 4);               // the wave's first k32 step
-  bf16x8* wl = wlds + (roleA ? 0 : LA * 256) + (tid & 255);                  // this thread's LDS fragments: wl[f' * 256]
-  for (int item = team; item < n_items; item += a.n_teams) {
-    const int g = item >> 1, d = item & 1;
-    const int v0 = g * a.gsize, nv = min(a.gsize, a.n_seq - v0);
-    __syncthreads();   // previous item fully done with LDS
-    if (loaded_dir != d) {
-#pragma unroll
-      for (int tile = 0; tile < 2; ++tile) {
-        const int n = 16 * tile + vl;
-        const int wr = (n & 3) * H + min(u0 + (n >> 2), H - 1);
-        const float* wrow = a.whh[d] + (int64_t)wr * H;
-        const int k = wave * 32 + 8 * kq;
-        wreg[2 * tile] = k < H ? *reinterpret_cast<const float4*>(wrow + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        wreg[2 * tile + 1] = k + 4 < H ? *reinterpret_cast<const float4*>(wrow + k + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      auto load_w = [&](auto nk_) {
-        constexpr int NK = decltype(nk_)::value;
-#pragma unroll
-        for (int sl = 0; sl < NK; ++sl)
-#pragma unroll
-          for (int tile = 0; tile < 2; ++tile) {
-            const int n = 16 * tile + vl;
-            const char* wp = a.wpl + (size_t)(d * 4 * H + (n & 3) * H + min(u0 + (n >> 2), H - 1)) * 16;
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) {
-              const unsigned sub = (unsigned)((((2 * (ks0 + sl) + (kq >> 1)) * NP + pl) * 2) + (kq & 1));
-              const bf16x8 wv = *reinterpret_cast<const bf16x8*>(wp + (size_t)sub * a.w_rp16);
-              const int f = (sl * 2 + tile) * NP + pl;
-              if (f < RF) wih[f < RF ? f : 0] = wv; else wl[(f - RF) * 256] = wv;
-            }
-          }
-      };
-      if (roleA) load_w(std::integral_constant<int, KA>{}); else load_w(std::integral_constant<int, KB>{});
-      loaded_dir = d;
-    }
-    if (tid == 0) *sTg = 0;
-    __syncthreads();
-    if (tid < 32) {
-      int r0 = 0, T = 0;
-      if (tid < nv) { r0 = a.off[v0 + tid]; T = a.off[v0 + tid + 1] - r0; atomicMax(sTg, T); }
-      sR0[tid] = r0; sT[tid] = T;
-    }
-    __syncthreads();
-    const int Tg = *sTg;
-
-    // epilogue role: thread (video i, unit u) for tid < 256; cell state lives in a register for the whole item
-    const int ei = tid >> 3, eu = tid & 7;
-    const bool erole = tid < 256 && ei < nv && eu < nu;
-    const int er0 = erole ? sR0[ei] : 0, eT = erole ? sT[ei] : 0;
-    const int j = u0 + eu;
-    float c = 0.f;
-    float bsum[4] = {0.f, 0.f, 0.f, 0.f};
-    if (erole) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) bsum[q] = a.bias[d * 4 * H + q * H + j];
-    }
-    const int r0l = sR0[vl], Tl = sT[vl];
-    // x of a step: row (r0 + t | r0 + T - 1 - t), the wave's k32 steps, 8 floats per lane and step (32 contiguous bytes)
-    f32x4 xr[KMAX][2], xn[KMAX][2];     // two steps of x rows in flight / in use; the step loop alternates their roles
-    auto load_x = [&](int t, f32x4 (&xr)[KMAX][2]) {
-      const bool on = t < Tl;
-      const float* xp = a.x + (size_t)(d == 0 ? r0l + t : r0l + Tl - 1 - t) * a.In + 32 * ks0 + 8 * kq;
-#pragma unroll
-      for (int sl = 0; sl < KMAX; ++sl) {
-        f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = {0.f, 0.f, 0.f, 0.f};
-        if (on && (sl < KA || !roleA)) { v0 = *reinterpret_cast<const f32x4*>(xp + 32 * sl); v1 = *reinterpret_cast<const f32x4*>(xp + 32 * sl + 4); }
-        xr[sl][0] = v0; xr[sl][1] = v1;
-      }
-    };
-    // the slice of the input projection of one step -> accn (i + j descending, as gemm_regstage.h)
-    f32x4 accn[2];
-    auto project_n = [&](auto nk_, f32x4 (&xr)[KMAX][2]) {
-      constexpr int NK = decltype(nk_)::value;
-#pragma unroll
-      for (int sl = 0; sl < NK; ++sl) {
-        bf16x8 xp[3];
-        if constexpr (NP == 3) split8x3(xr[sl][0], xr[sl][1], xp[0], xp[1], xp[2]);
-        else { split8(xr[sl][0], xr[sl][1], xp[0], xp[1]); xp[2] = xp[1]; }
-#pragma unroll
-        for (int tile = 0; tile < 2; ++tile)
-#pragma unroll
-          for (int sum = NP - 1; sum >= 0; --sum)
-#pragma unroll
-            for (int i = NP - 1; i >= 0; --i) {
-              const int jj = sum - i;
-              if (jj < 0 || jj >= NP) continue;
-              const int f = (sl * 2 + tile) * NP + jj;
-              const bf16x8 wv = f < RF ? wih[f < RF ? f : 0] : wl[(f - RF) * 256];
-              accn[tile] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xp[i], wv, accn[tile], 0, 0, 0);
-            }
-      }
-    };
-    auto project = [&](f32x4 (&xb)[KMAX][2]) {
-      accn[0] = f32x4{0.f, 0.f, 0.f, 0.f}; accn[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (roleA) project_n(std::integral_constant<int, KA>{}, xb); else project_n(std::integral_constant<int, KB>{}, xb);
-    };
-    load_x(0, xn);
-    load_x(1, xr);
-    project(xn);
-
-    // one step: xa holds the x rows of step t + 1 (projected behind this step's publish), xb receives those of step t + 2
-    auto step = [&](const int t, f32x4 (&xa)[KMAX][2], f32x4 (&xb)[KMAX][2]) {
-      const bool need_row = t < Tl;
-      const unsigned want = (unsigned)t;
-      const int k0 = wave * 32 + 8 * kq;
-      const unsigned rowb = (unsigned)((((unsigned)((t - 1) & 1) * 2u + (unsigned)d) * (unsigned)a.n_seq + (unsigned)(v0 + vl)) * (unsigned)H) * 8u;
-      f32x4 acc16[2] = {accn[0], accn[1]};
-      if (t > 0) {
-        u32x4 va[4];
-        unsigned spins = 0;
-        unsigned long long ll_t0 = 0;
-        while (true) {
-          asm volatile("" ::: "memory");   // the loads below are a poll: they must be re-issued every turn
-#pragma unroll
-          for (int p = 0; p < 4; ++p) {
-            const unsigned o = (need_row && k0 + 2 * p < H) ? rowb + 8u * (unsigned)(k0 + 2 * p) : 0x7ffffff0u;     // beyond num_records: zeros
-            va[p] = __builtin_amdgcn_raw_buffer_load_b128(lrsrc, o, 0, 16 /* sc1 */);
-          }
-          bool ok = true;
-#pragma unroll
-          for (int p = 0; p < 4; ++p)
-            ok = ok & (((va[p][1] == want) & (va[p][3] == want)) | !(need_row && k0 + 2 * p < H));      // (branch-free tag checks: lstm_persist_kernel)
-          if (__all(ok) || dead) break;
-          if (pk_ll_timed_out(spins, ll_t0)) {     // never hang the GPU: flag the failure and stop waiting
-            if (lane == 0) { atomicOr(a.state, 1u); atomicOr(&g_sumk_health, 1u); }
-            dead = true;
-          }
-        }
-        f32x4 hv[4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) hv[p] = __builtin_bit_cast(f32x4, va[p]);     // {h_k, tag, h_k+1, tag}
-#pragma unroll
-        for (int tile = 0; tile < 2; ++tile) {
-          const float4 w0 = wreg[2 * tile], w1 = wreg[2 * tile + 1];
-          acc16[tile] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[0][0], w0.x, acc16[tile], 0, 0, 0);
-          acc16[tile] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[0][2], w0.y, acc16[tile], 0, 0, 0);
-          acc16[tile] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[1][0], w0.z, acc16[tile], 0, 0, 0);
-          acc16[tile] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[1][2], w0.w, acc16[tile], 0, 0, 0);
-          acc16[tile] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[2][0], w1.x, acc16[tile], 0, 0, 0);
-          acc16[tile] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[2][2], w1.y, acc16[tile], 0, 0, 0);
-          acc16[tile] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[3][0], w1.z, acc16[tile], 0, 0, 0);
-          acc16[tile] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[3][2], w1.w, acc16[tile], 0, 0, 0);
-        }
-      }
-      if (t + 2 < Tg) load_x(t + 2, xb);     // the x rows of the step after next: a whole step in flight (8 waves x 8 KB per step queue for ~1 000 cycles in the CU's load path)
-      // C/D map of the 16x16 MFMAs: row = 4 (lane / 16) + r, column = lane % 16
-      float* pt = part + (t & 1) * (8 * 16 * PP);
-#pragma unroll
-      for (int tile = 0; tile < 2; ++tile)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pt[(wave * 16 + 4 * kq + r) * PP + 16 * tile + vl] = acc16[tile][r];
-      __syncthreads();
-      if (erole && t < eT) {
-        const int64_t row = d == 0 ? er0 + t : er0 + eT - 1 - t;
-        float4 ps = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int w8 = 0; w8 < 8; ++w8) {     // fixed order: wave 0 .. 7
-          const float4 pw = *reinterpret_cast<const float4*>(&pt[(w8 * 16 + ei) * PP + 4 * eu]);
-          ps.x += pw.x; ps.y += pw.y; ps.z += pw.z; ps.w += pw.w;
-        }
-        const float ig = fast_sigmoid(ps.x + bsum[0]), fg = fast_sigmoid(ps.y + bsum[1]), gg = fast_tanh(ps.z + bsum[2]), og = fast_sigmoid(ps.w + bsum[3]);
-        c = fg * c + ig * gg;
-        const float h = og * fast_tanh(c);
-        const unsigned long long pkt = ((unsigned long long)(unsigned)(t + 1) << 32) | (unsigned long long)__builtin_bit_cast(unsigned, h);
-        __hip_atomic_store(a.ll + ((int64_t)((t & 1) * 2 + d) * a.n_seq + (v0 + ei)) * H + j, pkt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a.Hout[row * (2 * H) + d * H + j] = h;
-      }
-      // (no second barrier: the next step writes the OTHER parity of the partial tiles, and the step after that comes behind the next barrier)
-      if (t + 1 < Tg) project(xa);        // the next step's projection: under the hand-off latency of the publish above
-    };
-    for (int t = 0; t < Tg; t += 2) {
-      step(t, xr, xn);
-      if (t + 1 < Tg) step(t + 1, xn, xr);
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------- wide persistent recurrence
 // The same one-launch recurrence for 256 < H <= 1024 (sLSTM: H = 1024, W_hh = 16 MB per direction -- the launch chain
 // re-reads it from the Infinity Cache every step, 28 us per step).  Here W_hh never moves: the 256 CUs split into TWO teams
 // of 128 (team = direction; XCDs 0-3 / 4-7 under the observed round-robin dispatch -- speed only, as above), member m keeps
 // the 32 gate rows of its 8 hidden units as MFMA B fragments in registers (64 VGPRs per lane: 32 rows x the wave's 128 k),
 // and a work item is a group of up to 64 videos = two 32-row MFMA tiles.  A 64 x 1024 fp32 panel of h_{t-1} (256 KB) does
-// not fit in LDS, so the A fragments are loaded straight into registers (sc1 16-B buffer loads, 32 in flight per lane; a
-// lane pair covers 32 contiguous bytes of one video's row, L2-served after the first CU of the XCD has pulled the line).
+// not fit in LDS, so the A fragments are loaded straight into registers (sc1 16-B buffer loads).
 // Hand-off protocol, bounded spins and error word are exactly those of lstm_persist_kernel (Guideline 16 R1).
 // Per step and CU: 2 x 16 x 4 fp32 MFMAs per wave = 6.8 us of MFMA time at 2 waves per SIMD -- the fp32 floor of this
 // shape -- plus the panel load and one hand-off.
-struct WideArgs {
-  const float* G; const float* whh[2]; float* Hout;
-  float* gates; float* c_all; float* hprev;   // training-mode saves (nullptr in inference)
-  const int32_t* off; unsigned* state;
-  int32_t n_seq, H, n_groups, upm, n_active, hout_bytes;
-};
-constexpr int WK_GROUP = 64;    // videos per work item
-constexpr int WK_CPW = 16;      // 8-wide k chunks per wave: 8 waves x 16 x 8 = 1024 >= H
-
-
-// X3: the recurrent product in bf16x3 arithmetic (3 v_mfma_f32_32x32x16_bf16 per 16 k instead of 8 fp32 MFMAs): W_hh is
-// split once into hi/lo bf16 fragments (the same 64 VGPRs), h_{t-1} is split in registers after the load.
-template <bool X3>
-__global__ __launch_bounds__(PK_THREADS) void lstm_wide_kernel(WideArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int H = a.H;
-  // [8 waves][64 videos][PP] split-K partial tiles; gate columns ordered n = 4 unit + gate and PP = 32, so that the cell update reads
-  // ONE conflict-free float4 per wave partial (as in lstm_persist_kernel: the pitch-33 scalar reads of the first version were 8-way)
-  constexpr int PP = 32;
-  float* part = smem;
-  int* sR0 = reinterpret_cast<int*>(part + 8 * 64 * PP);  // [64] first row of each video
-  int* sT = sR0 + 64;                                     // [64] length of each video (0 past the group)
-  int* sTg = sT + 64;                                     // [1]  longest video of the group
-
-  const int d = (blockIdx.x & 7) >> 2;                    // team = direction
-  const int slot = (blockIdx.x >> 3) * 4 + (blockIdx.x & 3);
-  if (slot >= a.n_active) return;
-  const __amdgpu_buffer_rsrc_t hrsrc = __builtin_amdgcn_make_buffer_rsrc(a.Hout, (short)0, a.hout_bytes, 0x00020000);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  const int u0 = slot * a.upm, nu = min(a.upm, H - u0);
-  bool dead = false;   // (thread 0 only) a wait timed out: results are invalid, state[0] says so
-
-  // this lane's W_hh fragments -> registers for the whole launch (plain loads: weights are never written here)
-  // fp32: chunk c of 8 k, this lane holds k = 8c + 4 lh .. +3.  X3: k16-step s, this lane holds k = 16s + 8 lh .. +7.
-  constexpr int NS = WK_CPW / 2;    // k16 steps per wave
-  float4 wreg[X3 ? 1 : WK_CPW];
-  bf16x8 whi[X3 ? NS : 1], wlo[X3 ? NS : 1];
-  {
-    const float* wrow = a.whh[d] + (int64_t)((li & 3) * H + min(u0 + (li >> 2), H - 1)) * H;     // column li = 4 unit + gate
-    if constexpr (X3) {
-#pragma unroll
-      for (int sidx = 0; sidx < NS; ++sidx) {
-        const int k = (wave * NS + sidx) * 16 + 8 * lh;
-        const float4 w0 = k < H ? *reinterpret_cast<const float4*>(wrow + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 w1 = k + 4 < H ? *reinterpret_cast<const float4*>(wrow + k + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        split8(f32x4{w0.x, w0.y, w0.z, w0.w}, f32x4{w1.x, w1.y, w1.z, w1.w}, whi[sidx], wlo[sidx]);
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < WK_CPW; ++c) {
-        const int k = (wave * WK_CPW + c) * 8 + 4 * lh;
-        wreg[c] = k < H ? *reinterpret_cast<const float4*>(wrow + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
-  }
-  constexpr unsigned OOB = 0x7ffffff0u;   // beyond num_records: the buffer load returns zeros
-
-  for (int g = 0; g < a.n_groups; ++g) {
-    const int item = 2 * g + d;
-    const int v0 = g * WK_GROUP, nv = min(WK_GROUP, a.n_seq - v0);
-    unsigned* bar = a.state + 16 + item;
-    __syncthreads();   // previous item fully done with LDS
-    if (tid == 0) *sTg = 0;
-    __syncthreads();
-    if (tid < 64) {
-      int r0 = 0, T = 0;
-      if (tid < nv) { r0 = a.off[v0 + tid]; T = a.off[v0 + tid + 1] - r0; atomicMax(sTg, T); }
-      sR0[tid] = r0; sT[tid] = T;
-    }
-    __syncthreads();
-    const int Tg = *sTg;
-    const int r0a = sR0[li], Ta = sT[li], r0b = sR0[32 + li], Tb = sT[32 + li];   // the two videos this lane feeds to the MFMAs
-
-    // epilogue role: thread (video ei, unit eu); cell state and last h live in registers for the whole item
-    const int ei = tid >> 3, eu = tid & 7;
-    const bool erole = ei < nv && eu < nu;
-    const int er0 = erole ? sR0[ei] : 0, eT = erole ? sT[ei] : 0;
-    const int j = u0 + eu;
-    float c = 0.f, hlast = 0.f;
-    float gcur[4] = {0.f, 0.f, 0.f, 0.f};
-    if (erole && eT > 0) {
-      const int64_t row = d == 0 ? er0 : er0 + eT - 1;
-      const float* gp = a.G + row * (8 * H) + d * 4 * H;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) gcur[q] = gp[q * H + j];
-    }
-
-    for (int t = 0; t < Tg; ++t) {
-      if (t > 0) {
-        if (tid == 0 && !dead) {   // wait until every member published step t-1
-          const unsigned want = (unsigned)t * (unsigned)a.n_active;
-          unsigned spins = 0;
-          while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > PK_SPIN_LIMIT || ((spins & 1023) == 0 &&
-                 __hip_atomic_load(a.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-              atomicOr(a.state, 1u); atomicOr(&g_sumk_health, 1u); dead = true; break;   // never hang the GPU: flag the failure and stop waiting
-            }
-          }
-        }
-        __syncthreads();
-        // A fragments: h_{t-1}[video][k..k+3], sc1 (L1-bypassing) 16-B buffer loads ONLY; finished videos read zeros
-        const unsigned basea = t < Ta ? (unsigned)(((int64_t)(d == 0 ? r0a + t - 1 : r0a + Ta - t) * (2 * H) + d * H) * 4) : OOB;
-        const unsigned baseb = t < Tb ? (unsigned)(((int64_t)(d == 0 ? r0b + t - 1 : r0b + Tb - t) * (2 * H) + d * H) * 4) : OOB;
-        f32x16 acc0, acc1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
-        u32x4 va[WK_CPW], vb[WK_CPW];
-        if constexpr (X3) {
-#pragma unroll
-          for (int cc = 0; cc < WK_CPW; ++cc) {     // [2 sidx + half]: 32 contiguous bytes per lane, 64 per lane pair
-            const int k = (wave * NS + (cc >> 1)) * 16 + 8 * lh + 4 * (cc & 1);
-            va[cc] = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, k < H ? basea + 4u * k : OOB, 0, 16 /* sc1 */);
-          }
-#pragma unroll
-          for (int cc = 0; cc < WK_CPW; ++cc) {
-            const int k = (wave * NS + (cc >> 1)) * 16 + 8 * lh + 4 * (cc & 1);
-            vb[cc] = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, k < H ? baseb + 4u * k : OOB, 0, 16 /* sc1 */);
-          }
-#pragma unroll
-          for (int sidx = 0; sidx < NS; ++sidx) {
-            bf16x8 ah, al;
-            split8(__builtin_bit_cast(f32x4, va[2 * sidx]), __builtin_bit_cast(f32x4, va[2 * sidx + 1]), ah, al);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, whi[sidx], acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wlo[sidx], acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, whi[sidx], acc0, 0, 0, 0);
-          }
-          if (nv > 32)      // second MFMA tile only when the group has more than 32 videos (uniform)
-#pragma unroll
-          for (int sidx = 0; sidx < NS; ++sidx) {
-            bf16x8 bh, bl;
-            split8(__builtin_bit_cast(f32x4, vb[2 * sidx]), __builtin_bit_cast(f32x4, vb[2 * sidx + 1]), bh, bl);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl, whi[sidx], acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, wlo[sidx], acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, whi[sidx], acc1, 0, 0, 0);
-          }
-        } else {
-#pragma unroll
-          for (int cc = 0; cc < WK_CPW; ++cc) {
-            const int k = (wave * WK_CPW + cc) * 8 + 4 * lh;
-            va[cc] = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, k < H ? basea + 4u * k : OOB, 0, 16 /* sc1 */);
-          }
-#pragma unroll
-          for (int cc = 0; cc < WK_CPW; ++cc) {
-            const int k = (wave * WK_CPW + cc) * 8 + 4 * lh;
-            vb[cc] = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, k < H ? baseb + 4u * k : OOB, 0, 16 /* sc1 */);
-          }
-          // (the whole vector is bit-cast before its elements are taken: bit-casting va[cc][j] element-wise made hipcc narrow
-          //  the load to one dword and feed element 0 to all four MFMAs)
-#pragma unroll
-          for (int cc = 0; cc < WK_CPW; ++cc) {
-            const float4 bv = wreg[cc];
-            const f32x4 av = __builtin_bit_cast(f32x4, va[cc]);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], bv.x, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], bv.y, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], bv.z, acc0, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], bv.w, acc0, 0, 0, 0);
-          }
-          if (nv > 32)      // second MFMA tile only when the group has more than 32 videos (uniform)
-#pragma unroll
-          for (int cc = 0; cc < WK_CPW; ++cc) {
-            const float4 bv = wreg[cc];
-            const f32x4 av = __builtin_bit_cast(f32x4, vb[cc]);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], bv.x, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], bv.y, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], bv.z, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], bv.w, acc1, 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-          part[(wave * 64 + row) * PP + li] = acc0[r];
-          part[(wave * 64 + 32 + row) * PP + li] = acc1[r];
-        }
-        __syncthreads();
-      }
-      if (erole && t < eT) {
-        const int64_t row = d == 0 ? er0 + t : er0 + eT - 1 - t;
-        float pre[4] = {gcur[0], gcur[1], gcur[2], gcur[3]};
-        if (t > 0) {
-          float4 ps = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-          for (int w8 = 0; w8 < 8; ++w8) {     // fixed order: wave 0 .. 7
-            const float4 pw = *reinterpret_cast<const float4*>(&part[(w8 * 64 + ei) * PP + 4 * eu]);
-            ps.x += pw.x; ps.y += pw.y; ps.z += pw.z; ps.w += pw.w;
-          }
-          pre[0] += ps.x; pre[1] += ps.y; pre[2] += ps.z; pre[3] += ps.w;
-        }
-        const float ig = fast_sigmoid(pre[0]), fg = fast_sigmoid(pre[1]), gg = fast_tanh(pre[2]), og = fast_sigmoid(pre[3]);
-        c = fg * c + ig * gg;
-        const float h = og * fast_tanh(c);
-        st_sc1(a.Hout + row * (2 * H) + d * H + j, h);
-        if (a.gates) {
-          float* gs = a.gates + row * (8 * H) + d * 4 * H;
-          gs[j] = ig; gs[H + j] = fg; gs[2 * H + j] = gg; gs[3 * H + j] = og;
-          a.c_all[row * (2 * H) + d * H + j] = c;
-          a.hprev[row * (2 * H) + d * H + j] = hlast;
-        }
-        hlast = h;
-        if (t + 1 < eT) {   // next step's input-projection slice, one step ahead
-          const int64_t nrow = d == 0 ? row + 1 : row - 1;
-          const float* gp = a.G + nrow * (8 * H) + d * 4 * H;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) gcur[q] = gp[q * H + j];
-        }
-      }
-      // publish step t: every storing wave drains its stores, then one lane signals
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------- wide persistent recurrence, round 6
-// The same team structure as lstm_wide_kernel (two teams of 128, W_hh slices in registers, counter hand-off R1), re-partitioned around
-// what that kernel's step consisted of ("Round 6: the wide recurrence"):
+// The step is partitioned as follows ("Round 6: the wide recurrence"; the round-2 kernel it replaced read h_{t-1} from the
+// output matrix and kept one counter word per item):
 //  * h_{t-1} travels through an EXCHANGE buffer laid out for the consumers, [step parity][direction][k / 4][video row 64][4 floats],
-//    not through the output matrix: one A-fragment load instruction of a wave is two contiguous 512-byte runs (the old form touched 32
-//    rows x 32 bytes -- 32 half-used 64-byte requests per instruction, twice the bytes through L2), and a member's publish is two
+//    not through the output matrix: one A-fragment load instruction of a wave is two contiguous 512-byte runs (reading the output rows
+//    touched 32 rows x 32 bytes -- 32 half-used 64-byte requests per instruction, twice the bytes through L2), and a member's publish is two
 //    contiguous 1-KB runs of 16-byte sc1 stores (was 512 dword stores, one fabric write each).  Parity by step: a member can publish
 //    step t + 1 only after every member published step t, i.e. after all of them finished reading step t - 1 -- the slot it overwrites.
 //    Each group of 64 videos has its own exchange region (a short group could otherwise be overrun by the next one's step 0).
@@ -1336,6 +871,8 @@ struct Wide2Args {
   const int32_t* off; unsigned* state; float* xchg;
   int32_t n_seq, H, n_groups, upm, n_active, pack16;
 };
+constexpr int WK_GROUP = 64;    // videos per work item
+constexpr int WK_CPW = 16;      // 8-wide k chunks per wave: 8 waves x 16 x 8 = 1024 >= H
 constexpr int W2_SLICE_FLOATS = 256 * 64 * 4;   // one (parity, direction) slice of the exchange: [k4 256][row 64][4 floats] = 256 KB
 constexpr int W2_ITEM_WORDS = 128;              // state words per work item: four counter shards, 32 words (128 B) apart
 
@@ -1470,7 +1007,8 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_wide2_kernel(Wide2Args a) {
           const unsigned vob = (t < Tb ? (unsigned)(32 + li) * 16u : OOB) + (unsigned)lh * 1024u;
 #pragma unroll
           for (int cc = 0; cc < WK_CPW; ++cc) va[cc] = __builtin_amdgcn_raw_buffer_load_b128(xr, voa, (wave * WK_CPW + cc) * 2048, 16 /* sc1 */);
-          // (the whole vector is bit-cast before its elements are taken: see lstm_wide_kernel)
+          // (the whole vector is bit-cast before its elements are taken: bit-casting va[cc][j] element-wise made hipcc narrow
+          //  the load to one dword and feed element 0 to all four MFMAs)
 #pragma unroll
           for (int cc = 0; cc < WK_CPW; ++cc) {
             const float4 bv = wreg[cc];
@@ -1730,14 +1268,11 @@ struct PersistBwdArgs {
   // (members own 8 aligned units): [parity][item][reader c = column / 8][producer m][video < gsize][8 columns], so the 32 partials a cell-update
   // thread sums are 32 loads of ONE contiguous 13-KB block per member instead of 32 B out of every producer's 1-KB rows
   int32_t item_words, n_shards, coal;
-  unsigned long long* ll;     // LL instances: {partial, step tag} packets [parity 2][item][member 32][video < gsize][H]
 };
 
-// LL / M16: as in lstm_persist_kernel -- the partial products travel as 8-byte {value, step tag} packets and the consumers' loads
-// are the poll (no counter, no vmcnt(0) drain, no atomic); groups of <= 16 videos multiply on v_mfma_f32_16x16x4_f32 with the W_hh
-// fragments of the wave's 32 output columns held in REGISTERS for the whole item (the 32-row form re-reads them from LDS every step).
-// Tag of the partials of step s (s = Tg-1 .. 1): Tg - s >= 1; the buffer is zeroed before the launch (0 matches no step).
-template <bool LL = false, bool M16 = false>
+// M16: as in lstm_persist_kernel -- groups of <= 16 videos multiply on v_mfma_f32_16x16x4_f32 with the W_hh fragments of the
+// wave's 32 output columns held in REGISTERS for the whole item (the 32-row form re-reads them from LDS every step).
+template <bool M16>
 __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int H = a.H, P = H + 4;
@@ -1821,7 +1356,7 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwd
       if (have_next) fetch(t - 1);
       // zero this step's A tile (rows of inactive videos and columns of absent units must contribute nothing)
       for (int idx = tid; idx < 32 * 36; idx += PK_THREADS) sA[idx] = 0.f;
-      if (!LL && t < Tg - 1) {
+      if (t < Tg - 1) {
         if (wave == 0 && !dead) {   // wait until every member published step t+1: lanes 0 .. n_shards-1 poll one shard each
           const unsigned cnt = (lane < a.n_shards && lane < a.n_active) ? (unsigned)((a.n_active - lane + a.n_shards - 1) / a.n_shards) : 0u;
           const unsigned want = (unsigned)(Tg - 1 - t) * cnt;
@@ -1839,57 +1374,8 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwd
         }
       }
       __syncthreads();
-      float rec_ll = 0.f;
-      if constexpr (LL) {   // the 32 members' partials of step t+1: the loads are the poll (every wave of the epilogue role spins for itself)
-        if (tid < 256) {
-          const bool need = erole && t + 1 < eT;
-          const unsigned want = (unsigned)(Tg - 1 - t);
-          const unsigned long long* xp = a.ll + ((((int64_t)((t + 1) & 1) * a.n_items + item) * 32) * a.gsize + (need ? ei : 0)) * H + (need ? j : 0);
-          unsigned spins = 0;
-          unsigned long long ll_t0 = 0;
-          const unsigned long long* xb64 = a.ll + (((int64_t)((t + 1) & 1) * a.n_items + item) * 32) * a.gsize * H;
-          while (true) {
-            unsigned long long pv[32];
-            bool ok = true;
-            float rec = 0.f;
-            if (a.n_active == 32) {     // all members present: 32-bit buffer offsets walked in a VGPR, no per-member predicate (see the counter form below)
-              typedef unsigned int u32x2_ __attribute__((ext_vector_type(2)));
-              const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(xb64), (short)0, 0x7FFFFFFF, 0x00020000);
-              unsigned vo = (unsigned)(xp - xb64) * 8u;
-              const unsigned st = (unsigned)(a.gsize * H) * 8u;
-#pragma unroll
-              for (int m = 0; m < 32; ++m) { pv[m] = __builtin_bit_cast(unsigned long long, (u32x2_)__builtin_amdgcn_raw_buffer_load_b64(xr, vo, 0, 16 /* sc1 */)); vo += st; }
-#pragma unroll
-              for (int m = 0; m < 32; ++m) {
-                ok = ok & ((unsigned)(pv[m] >> 32) == want);
-                rec += __builtin_bit_cast(float, (unsigned)pv[m]);
-              }
-              ok = ok | !need;
-              if (!need) rec = 0.f;
-            } else {
-#pragma unroll
-            for (int m = 0; m < 32; ++m)
-              pv[m] = (need && m < a.n_active) ? __hip_atomic_load(xp + (int64_t)m * a.gsize * H, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-#pragma unroll
-            for (int m = 0; m < 32; ++m) {
-              if (need && m < a.n_active) ok = ok && (unsigned)(pv[m] >> 32) == want;
-              rec += __builtin_bit_cast(float, (unsigned)pv[m]);       // fixed order m = 0 .. 31 (absent members add +0)
-            }
-            }
-            rec_ll = rec;
-            if (__all(ok) || dead) break;
-            if (pk_ll_timed_out(spins, ll_t0)) {
-              if (lane == 0) { atomicOr(a.state, 1u); atomicOr(&g_sumk_health, 1u); }
-              dead = true;
-            }
-          }
-        }
-      }
       if (erole && t < eT) {
         float dh = sv_dh;
-        if (LL) {
-          if (t + 1 < eT) dh += rec_ll;
-        } else
         if (t + 1 < eT) {   // recurrent part: fixed-order sum of the 32 members' partials of step t+1 (sc1 loads)
           const float* xb = a.xchg + (((int64_t)((t + 1) & 1) * a.n_items + item) * 32) * 32 * H;
           const float* xp = a.coal ? xb + ((int64_t)slot * 32 * a.gsize + ei) * 8 + eu : xb + (int64_t)ei * H + j;
@@ -1933,67 +1419,34 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwd
           const int i16 = lane & 15, g4 = lane >> 4;
           const float4 a0 = *reinterpret_cast<const float4*>(&sA[i16 * 36 + 8 * g4]);
           const float4 a1 = *reinterpret_cast<const float4*>(&sA[i16 * 36 + 8 * g4 + 4]);
-          const unsigned tag = (unsigned)(Tg - t);
-          unsigned long long* xo = a.ll + ((((int64_t)(t & 1) * a.n_items + item) * 32 + slot) * a.gsize) * H;
-          float* xf = a.xchg + ((((int64_t)(t & 1) * a.n_items + item) * 32 + slot) * 32) * H;        // counter hand-off: fp32 partials
-          if constexpr (!LL) {
-            // Counter hand-off: the operands SWAPPED (W as "A", dG as "B") -- the tile comes out transposed, D^T[n][i], so a lane holds
-            // FOUR CONSECUTIVE COLUMNS n = 4 (lane / 16) + r of video i = lane % 16 and the publish is ONE 16-byte sc1 store per tile
-            // instead of four dword ones (dword sc1 stores cost ~6x per byte: the stamps of profiles/r04_lstm_bptt_phase_stamps.txt
-            // had 2 700 of a step's 11 250 cycles in this block, 512 of them MFMA).  Same products, same k order: the same bits.
-#pragma unroll
-            for (int tile = 0; tile < 2; ++tile) {
-              f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][0], a0.x, acc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][1], a0.y, acc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][2], a0.z, acc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][3], a0.w, acc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][4], a1.x, acc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][5], a1.y, acc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][6], a1.z, acc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][7], a1.w, acc, 0, 0, 0);
-              const int n4 = wave * 32 + 16 * tile + 4 * g4;           // first of this lane's four columns (H % 4 == 0: all four inside or outside)
-              if (n4 < H && i16 < nv && t < sT[i16]) {
-                typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
-                // coal: the reader of columns n4 .. n4 + 3 is member n4 / 8; its block of THIS producer is [video < gsize][8 columns]
-                float* xw = a.coal ? a.xchg + (((int64_t)(t & 1) * a.n_items + item) * 32) * 32 * H : xf;
-                const unsigned xo4 = a.coal ? (unsigned)(((((n4 >> 3) * 32 + slot) * a.gsize + i16) * 8 + (n4 & 7)) * 4) : (unsigned)((i16 * H + n4) * 4);
-                const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(xw, (short)0, 0x7FFFFFFF, 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, acc), xr, xo4, 0, 16 /* sc1 */);
-              }
-            }
-          } else
+          float* xf = a.xchg + ((((int64_t)(t & 1) * a.n_items + item) * 32 + slot) * 32) * H;
+          // The operands SWAPPED (W as "A", dG as "B") -- the tile comes out transposed, D^T[n][i], so a lane holds
+          // FOUR CONSECUTIVE COLUMNS n = 4 (lane / 16) + r of video i = lane % 16 and the publish is ONE 16-byte sc1 store per tile
+          // instead of four dword ones (dword sc1 stores cost ~6x per byte: the stamps of profiles/r04_lstm_bptt_phase_stamps.txt
+          // had 2 700 of a step's 11 250 cycles in this block, 512 of them MFMA).  Same products, same k order: the same bits.
 #pragma unroll
           for (int tile = 0; tile < 2; ++tile) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, wB[tile][0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, wB[tile][1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, wB[tile][2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, wB[tile][3], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, wB[tile][4], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, wB[tile][5], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, wB[tile][6], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, wB[tile][7], acc, 0, 0, 0);
-            const int n = wave * 32 + 16 * tile + i16;
-            if (n < H) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const int i = 4 * g4 + r;      // C/D map of the 16x16 MFMA: row = 4 (lane / 16) + r, column = lane % 16
-                const float pv_ = acc[r];     // (a scalar copy: __builtin_bit_cast applied to a vector ELEMENT read element 0 with this compiler)
-                if (i < nv && t < sT[i]) {
-                  if constexpr (LL)
-                    __hip_atomic_store(xo + (int64_t)i * H + n, ((unsigned long long)tag << 32) | (unsigned long long)__builtin_bit_cast(unsigned, pv_),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                  else
-                    st_sc1(a.coal ? a.xchg + (((int64_t)(t & 1) * a.n_items + item) * 32) * 32 * H + ((((int64_t)(n >> 3) * 32 + slot) * a.gsize + i) * 8 + (n & 7)) : xf + (int64_t)i * H + n, pv_);
-                }
-              }
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][0], a0.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][1], a0.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][2], a0.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][3], a0.w, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][4], a1.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][5], a1.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][6], a1.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wB[tile][7], a1.w, acc, 0, 0, 0);
+            const int n4 = wave * 32 + 16 * tile + 4 * g4;           // first of this lane's four columns (H % 4 == 0: all four inside or outside)
+            if (n4 < H && i16 < nv && t < sT[i16]) {
+              typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
+              // coal: the reader of columns n4 .. n4 + 3 is member n4 / 8; its block of THIS producer is [video < gsize][8 columns]
+              float* xw = a.coal ? a.xchg + (((int64_t)(t & 1) * a.n_items + item) * 32) * 32 * H : xf;
+              const unsigned xo4 = a.coal ? (unsigned)(((((n4 >> 3) * 32 + slot) * a.gsize + i16) * 8 + (n4 & 7)) * 4) : (unsigned)((i16 * H + n4) * 4);
+              const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(xw, (short)0, 0x7FFFFFFF, 0x00020000);
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, acc), xr, xo4, 0, 16 /* sc1 */);
             }
           }
         } else {
         float* xo = a.xchg + ((((int64_t)(t & 1) * a.n_items + item) * 32 + slot) * 32) * H;
-        unsigned long long* xl = a.ll + ((((int64_t)(t & 1) * a.n_items + item) * 32 + slot) * a.gsize) * H;
-        const unsigned tag = (unsigned)(Tg - t);
         const int ntile = (H + 31) >> 5;
         for (int nt = wave; nt < ntile; nt += 8) {
           const int n = nt * 32 + li, nc = min(n, H - 1);
@@ -2014,26 +1467,17 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwd
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int i = (r & 3) + 8 * (r >> 2) + 4 * lh;
-              if (i < nv && t < sT[i]) {
-                if constexpr (LL) {
-                  const float pv_ = acc[r];   // (scalar copy: see the 16-row form)
-                  __hip_atomic_store(xl + (int64_t)i * H + n, ((unsigned long long)tag << 32) | (unsigned long long)__builtin_bit_cast(unsigned, pv_),
-                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else
-                  st_sc1(a.coal ? a.xchg + (((int64_t)(t & 1) * a.n_items + item) * 32) * 32 * H + ((((int64_t)(n >> 3) * 32 + slot) * a.gsize + i) * 8 + (n & 7)) : xo + (int64_t)i * H + n, acc[r]);
-              }
+              if (i < nv && t < sT[i])
+                st_sc1(a.coal ? a.xchg + (((int64_t)(t & 1) * a.n_items + item) * 32) * 32 * H + ((((int64_t)(n >> 3) * 32 + slot) * a.gsize + i) * 8 + (n & 7)) : xo + (int64_t)i * H + n, acc[r]);
             }
           }
         }
         }
       }
-      if constexpr (LL) {
-        __syncthreads();   // the A tile in LDS is free again (the published partials need no further signal)
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) __hip_atomic_fetch_add(bar + 32 * (slot % a.n_shards), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      // publish step t: every storing wave drains its stores, then one lane signals
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (tid == 0) __hip_atomic_fetch_add(bar + 32 * (slot % a.n_shards), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 }
@@ -2041,7 +1485,7 @@ __global__ __launch_bounds__(PK_THREADS) void lstm_persist_bwd_kernel(PersistBwd
 // ------------------------------------------------------------------------------------------- wide persistent BPTT
 // One launch runs the whole backward recurrence for 256 < H <= 1024 (sLSTM: H = 1024; the launch chain above re-reads the
 // 16 MB W_hh per direction from the Infinity Cache every step: 74 us per step measured, 60 % of an sLSTM training step).
-// Two teams of up to 128 CUs, team = direction (as lstm_wide_kernel).  The contraction of step t,
+// Two teams of up to 128 CUs, team = direction (as lstm_wide2_kernel).  The contraction of step t,
 //     dh_rec[i][j] = sum_k dG_t[i][k] W_hh[k][j]        (i < 64 videos, k < 4H, j < H),
 // is tiled K x N over the team: member (kg, ng) keeps W_hh[4 gates x units 32kg..32kg+31][columns 256ng..256ng+255] -- a
 // 128 x 256 slice, 128 KB -- as MFMA B fragments in REGISTERS for the whole launch (64 VGPRs per lane; wave w owns the 32
@@ -2284,9 +1728,21 @@ using namespace sumk;
 
 // The persistent recurrences are written for the full chip: 256 co-resident blocks, one per CU.  On a partitioned device
 // (CPX / fewer CUs) or with SUMK_LSTM_PERSIST=0 the launch-per-step kernels run instead -- same arithmetic.
+// The four recurrence switches of the environment ("Environment switches"), read once.  All default to on; "0" forces
+// the other form that the default dispatch also reaches for some shape: the launch chain, the counter hand-off of the forward
+// recurrence, the 32-row MFMA forms, the unsharded counter and uncoalesced exchange of the BPTTs (A/B tests: tests/test_gpu_lstm.py).
+struct LstmSwitches { bool persist, ll, m16, bwd_r6; };
+static const LstmSwitches& lstm_switches() {
+  static const LstmSwitches s = [] {
+    auto on = [](const char* name) { const char* v = getenv(name); return !(v && v[0] == '0'); };
+    return LstmSwitches{on("SUMK_LSTM_PERSIST"), on("SUMK_LSTM_LL"), on("SUMK_LSTM_M16"), on("SUMK_LSTM_BWD_R6")};
+  }();
+  return s;
+}
+
 bool sumk::persistent_kernels_usable() {
   static const bool ok = [] {
-    if (getenv("SUMK_LSTM_PERSIST") && getenv("SUMK_LSTM_PERSIST")[0] == '0') return false;
+    if (!lstm_switches().persist) return false;
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess) return false;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
@@ -2364,47 +1820,8 @@ extern "C" int sumk_bilstm_layer_forward(const float* x, int32_t In, int32_t H, 
   const int small = gemm_tiles(R, 8 * H, 0) >= 512 ? 0 : 1;
   const int np_in = precision == SUMK_PRECISION_BF16X6 ? 3 : precision == SUMK_PRECISION_BF16X3 ? 2 : 0;
   static const bool persist_ok = persistent_kernels_usable();
+  const LstmSwitches& sw = lstm_switches();
   const bool planes_in = !training && np_in && w->x_planes && w->w_planes && bilstm_wplanes_ok(In, H, np_in) && R >= 1024 && pw_ok(R, 8 * (int64_t)H, In, R, 8 * (int64_t)H, np_in);
-  // round 6: with operand planes at hand and the H <= 256 persistent recurrence on 16-row MFMAs, the projection CAN run inside the recurrence
-  // (lstm_persist_proj_kernel): no G, no GEMM launch.  It was the default while the plain recurrence cost 2.55 us per step (1.065 against 1.09 ms at three
-  // planes); with the branch-free tag checks the plain step is 2.05 us and the plane GEMM in front of it wins (DSN scoring bf16x6 0.94-0.96 against 1.04-1.05
-  // ms, bf16x3 0.84-0.88 against 0.88-0.89: the projection costs 1.07 us per step inside, 0.23 ms as a launch) -- SUMK_LSTM_PROJ=1 selects the fused form
-  // (A/B: tests/test_gpu_lstm.py)
-  {
-    static const bool proj_on = getenv("SUMK_LSTM_PROJ") && getenv("SUMK_LSTM_PROJ")[0] == '1';
-    static const bool ll_on = !(getenv("SUMK_LSTM_LL") && getenv("SUMK_LSTM_LL")[0] == '0');
-    static const bool m16_on = !(getenv("SUMK_LSTM_M16") && getenv("SUMK_LSTM_M16")[0] == '0');
-    const int gsize = std::min(32, std::max(1, (2 * n_seq + PK_TEAMS - 1) / PK_TEAMS));
-    const int n_groups = (n_seq + gsize - 1) / gsize;
-    if (planes_in && proj_on && ll_on && m16_on && persist_ok && H <= 256 && In == 1024 && gsize <= 16 && (size_t)R * 2 * H * 4 < 0x7fffffff &&
-        L.ll_bytes > 0 && L.ll_bytes < 0x7fffffe0 && 2 * n_groups <= PSTATE_WORDS - 16 && 16 * (uint64_t)pw_rows_pitch(R) < 0xffffffffull) {
-      const size_t words = (L.ll + L.ll_bytes - L.pstate) / 4;
-      hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)std::min<size_t>(64, (words + 255) / 256)), dim3(256), 0, stream, (unsigned*)(ws + L.pstate), (int)words);
-      PersistProjArgs pa;
-      pa.x = x; pa.In = In; pa.wpl = (const char*)w->w_planes;
-      pa.bias = (const float*)((const char*)w->w_planes + align_up(pw_planes_bytes(8 * (int64_t)H, In, np_in), 256));
-      pa.whh[0] = w->w_hh[0]; pa.whh[1] = w->w_hh[1]; pa.Hout = h_out;
-      pa.off = seq_off_dev; pa.state = (unsigned*)(ws + L.pstate);
-      pa.ll = (unsigned long long*)(ws + L.ll); pa.ll_bytes = (int32_t)L.ll_bytes;
-      pa.n_seq = n_seq; pa.H = H; pa.gsize = gsize; pa.n_groups = n_groups; pa.n_teams = PK_TEAMS;
-      pa.upm = std::min(8, (H + 31) / 32); pa.n_active = (H + pa.upm - 1) / pa.upm;
-      pa.w_rp16 = (uint32_t)(16 * pw_rows_pitch(8 * (int64_t)H));
-      const void* fn = np_in == 3 ? (const void*)lstm_persist_proj_kernel<3, PROJ_KA> : (const void*)lstm_persist_proj_kernel<2, PROJ_KA>;
-      static bool pp_attr_set[2] = {false, false};
-      if (!pp_attr_set[np_in - 2]) {
-        SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        pp_attr_set[np_in - 2] = true;
-      }
-      void* kargs[] = {&pa};
-      prof_begin(SUMK_PROF_LSTM_REC, stream);
-      // LDS: 33 KB of partial tiles and video tables + the W_ih fragments beyond the PROJ_RF a lane keeps in registers; > 80 KB keeps one block per CU
-      const int frag_a = PROJ_KA * 2 * np_in, frag_b = (8 - PROJ_KA) * 2 * np_in;
-      const size_t shmem = std::max<size_t>(96 * 1024, 34 * 1024 + (size_t)(std::max(frag_a - PROJ_RF, 0) + std::max(frag_b - PROJ_RF, 0)) * 256 * 16);
-      SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(256), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
-      prof_end(SUMK_PROF_LSTM_REC, stream);
-      return SUMK_OK;
-    }
-  }
   if (planes_in) {
     // operand planes (x per dataset / per call, weights per weight change): the plane-aware wide GEMM, no split in the k-loop
     PwLaunch g; g.A = w->x_planes; g.a_rows = R; g.B = w->w_planes; g.b_rows = 8 * (int64_t)H; g.M = R; g.N = 8 * H; g.K = In; g.np = np_in;
@@ -2437,24 +1854,21 @@ extern "C" int sumk_bilstm_layer_forward(const float* x, int32_t In, int32_t H, 
     pa.off = seq_off_dev; pa.state = (unsigned*)(ws + L.pstate);
     pa.n_seq = n_seq; pa.H = H; pa.hout_bytes = (int32_t)std::min<size_t>((size_t)R * 2 * H * 4, 0x7fffffff);
     pa.ll = (unsigned long long*)(ws + L.ll); pa.ll_bytes = (int32_t)std::min<size_t>(L.ll_bytes, 0x7fffffe0);
-    // H <= 256: 8 teams of 32 CUs (one XCD each); larger H: 2 teams of 128 CUs so every member still owns only 8 units
-    pa.n_teams = H <= 256 ? PK_TEAMS : 2;
+    pa.n_teams = PK_TEAMS;                     // 8 teams of 32 CUs (one XCD each)
     const int team_size = 256 / pa.n_teams;
     pa.upm = std::min(8, (H + team_size - 1) / team_size); pa.n_active = (H + pa.upm - 1) / pa.upm;
-    const int gmax = H <= 256 ? 32 : 24;       // videos per work item (the LDS map keeps gsize x (H+4) floats in front of the partial tiles)
-    int gsize = std::min(gmax, std::max(1, (2 * n_seq + pa.n_teams - 1) / pa.n_teams));
+    // videos per work item: at most 32 (the LDS map keeps gsize x (H+4) floats in front of the partial tiles)
+    const int gsize = std::min(32, std::max(1, (2 * n_seq + pa.n_teams - 1) / pa.n_teams));
     pa.gsize = gsize; pa.n_groups = (n_seq + gsize - 1) / gsize;
     if (2 * pa.n_groups <= PSTATE_WORDS - 16 && pa.n_active <= team_size) {
       const size_t shmem = std::max<size_t>(((size_t)gsize * (H + 4) + 8 * 32 * 32 + 96) * sizeof(float), 96 * 1024);  // >80 KB: one block per CU
       // SUMK_LSTM_LL=0: the counter hand-off (A/B switch); the flag-in-data one needs the exchange buffer's byte offsets in 31 bits
-      static const bool ll_on = !(getenv("SUMK_LSTM_LL") && getenv("SUMK_LSTM_LL")[0] == '0');
-      const bool ll = ll_on && L.ll_bytes > 0 && L.ll_bytes < 0x7fffffe0;
-      static const bool m16_on = !(getenv("SUMK_LSTM_M16") && getenv("SUMK_LSTM_M16")[0] == '0');
-      const bool m16 = ll && m16_on && gsize <= 16;
+      const bool ll = sw.ll && L.ll_bytes > 0 && L.ll_bytes < 0x7fffffe0;
+      const bool m16 = ll && sw.m16 && gsize <= 16;
       const int which = m16 ? 2 : ll ? 1 : 0;
-      const void* fn = m16 ? (const void*)lstm_persist_kernel<4, true, true>
-                     : ll ? (const void*)lstm_persist_kernel<4, true>
-                          : (const void*)lstm_persist_kernel<4>;
+      const void* fn = m16 ? (const void*)lstm_persist_kernel<true, true>
+                     : ll ? (const void*)lstm_persist_kernel<true>
+                          : (const void*)lstm_persist_kernel<>;
       static bool attr_set[3] = {false, false, false};
       if (!attr_set[which]) {
         SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -2467,52 +1881,32 @@ extern "C" int sumk_bilstm_layer_forward(const float* x, int32_t In, int32_t H, 
       return SUMK_OK;
     }
   }
-  if (persist_ok && H > 256 && H <= 64 * WK_CPW && (size_t)R * 2 * H * 4 < 0x7fffffe0 &&
-      2 * ((n_seq + WK_GROUP - 1) / WK_GROUP) <= PSTATE_WORDS - 16) {
-    WideArgs wa;
-    wa.G = G; wa.whh[0] = w->w_hh[0]; wa.whh[1] = w->w_hh[1]; wa.Hout = h_out;
-    wa.gates = training ? (float*)(ws + L.gates) : nullptr;
-    wa.c_all = training ? (float*)(ws + L.call) : nullptr;
-    wa.hprev = training ? (float*)(ws + L.hprev) : nullptr;
-    wa.off = seq_off_dev; wa.state = (unsigned*)(ws + L.pstate);
-    wa.n_seq = n_seq; wa.H = H; wa.hout_bytes = (int32_t)((size_t)R * 2 * H * 4);
-    wa.n_groups = (n_seq + WK_GROUP - 1) / WK_GROUP;
-    wa.upm = (H + 127) / 128; wa.n_active = (H + wa.upm - 1) / wa.upm;     // <= 8 units per member, <= 128 members per team
-    // round 6: the re-partitioned form (exchange buffer laid out for the consumers, rows sorted by length, sharded counter, bf16x6 mode);
-    // SUMK_LSTM_WIDE2=0 keeps lstm_wide_kernel (A/B switch: tests/test_gpu_lstm.py::test_wide_recurrence_forms_agree)
-    static const bool wide2_on = !(getenv("SUMK_LSTM_WIDE2") && getenv("SUMK_LSTM_WIDE2")[0] == '0');
-    if (wide2_on && L.wx_bytes > 0 && 2 * wa.n_groups * W2_ITEM_WORDS <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS) {
-      Wide2Args w2;
-      w2.G = wa.G; w2.whh[0] = wa.whh[0]; w2.whh[1] = wa.whh[1]; w2.Hout = h_out;
-      w2.gates = wa.gates; w2.c_all = wa.c_all; w2.hprev = wa.hprev; w2.off = wa.off; w2.state = wa.state;
-      w2.xchg = (float*)(ws + L.wx);
-      w2.n_seq = n_seq; w2.H = H; w2.n_groups = wa.n_groups; w2.upm = wa.upm; w2.n_active = wa.n_active;
-      w2.pack16 = (wa.upm == 8 && wa.n_active * 8 == H) ? 1 : 0;
-      // the recurrent product follows the layer's arithmetic: exact fp32 MFMA, bf16x3 (hi / lo) or the fp32-grade bf16x6 (three planes);
-      // training keeps exact fp32 in the bf16x6 mode (the BPTT multiplies in fp32)
-      const int mode = precision == SUMK_PRECISION_BF16X3 ? 1 : (precision == SUMK_PRECISION_BF16X6 && !training) ? 2 : 0;
-      const void* fn2 = mode == 2 ? (const void*)lstm_wide2_kernel<2> : mode == 1 ? (const void*)lstm_wide2_kernel<1> : (const void*)lstm_wide2_kernel<0>;
-      static bool w2_attr_set[3] = {false, false, false};
-      if (!w2_attr_set[mode]) {
-        SUMK_HIP(hipFuncSetAttribute(fn2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        w2_attr_set[mode] = true;
-      }
-      const size_t shmem2 = mode == 2 ? (size_t)(64 + 1 + 64) * 1024 : (size_t)96 * 1024;   // 65 KB (+ 64 KB of W_hh plane 3); > 80 KB keeps one block per CU
-      void* kargs2[] = {&w2};
-      prof_begin(SUMK_PROF_LSTM_REC, stream);
-      SUMK_HIP(hipLaunchCooperativeKernel(fn2, dim3(256), dim3(PK_THREADS), kargs2, (unsigned)shmem2, stream));
-      prof_end(SUMK_PROF_LSTM_REC, stream);
-      return SUMK_OK;
-    }
-    const size_t shmem = 96 * 1024;   // 68 KB used; > 80 KB keeps one block per CU
-    const bool x3 = precision == SUMK_PRECISION_BF16X3;
-    const void* fn = x3 ? (const void*)lstm_wide_kernel<true> : (const void*)lstm_wide_kernel<false>;
-    static bool wide_attr_set[2] = {false, false};
-    if (!wide_attr_set[x3]) {
+  // (the exchange buffer exists for 256 < H <= 64 WK_CPW; four counter shards per item fit the state block up to 62 groups = 3 968
+  //  videos -- a larger batch takes the launch chain below)
+  const int n_wgroups = (n_seq + WK_GROUP - 1) / WK_GROUP;
+  if (persist_ok && L.wx_bytes > 0 && (size_t)R * 2 * H * 4 < 0x7fffffe0 &&
+      2 * n_wgroups * W2_ITEM_WORDS <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS) {
+    Wide2Args w2;
+    w2.G = G; w2.whh[0] = w->w_hh[0]; w2.whh[1] = w->w_hh[1]; w2.Hout = h_out;
+    w2.gates = training ? (float*)(ws + L.gates) : nullptr;
+    w2.c_all = training ? (float*)(ws + L.call) : nullptr;
+    w2.hprev = training ? (float*)(ws + L.hprev) : nullptr;
+    w2.off = seq_off_dev; w2.state = (unsigned*)(ws + L.pstate);
+    w2.xchg = (float*)(ws + L.wx);
+    w2.n_seq = n_seq; w2.H = H; w2.n_groups = n_wgroups;
+    w2.upm = (H + 127) / 128; w2.n_active = (H + w2.upm - 1) / w2.upm;     // <= 8 units per member, <= 128 members per team
+    w2.pack16 = (w2.upm == 8 && w2.n_active * 8 == H) ? 1 : 0;
+    // the recurrent product follows the layer's arithmetic: exact fp32 MFMA, bf16x3 (hi / lo) or the fp32-grade bf16x6 (three planes);
+    // training keeps exact fp32 in the bf16x6 mode (the BPTT multiplies in fp32)
+    const int mode = precision == SUMK_PRECISION_BF16X3 ? 1 : (precision == SUMK_PRECISION_BF16X6 && !training) ? 2 : 0;
+    const void* fn = mode == 2 ? (const void*)lstm_wide2_kernel<2> : mode == 1 ? (const void*)lstm_wide2_kernel<1> : (const void*)lstm_wide2_kernel<0>;
+    static bool w2_attr_set[3] = {false, false, false};
+    if (!w2_attr_set[mode]) {
       SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      wide_attr_set[x3] = true;
+      w2_attr_set[mode] = true;
     }
-    void* kargs[] = {&wa};
+    const size_t shmem = mode == 2 ? (size_t)(64 + 1 + 64) * 1024 : (size_t)96 * 1024;   // 65 KB (+ 64 KB of W_hh plane 3); > 80 KB keeps one block per CU
+    void* kargs[] = {&w2};
     prof_begin(SUMK_PROF_LSTM_REC, stream);
     SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(256), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
     prof_end(SUMK_PROF_LSTM_REC, stream);
@@ -2573,11 +1967,8 @@ extern "C" int sumk_bilstm_layer_backward(const float* x, const float* h_out, co
   GemmProb* psk = (GemmProb*)(ws + L.prob_sk);
 
   static const bool persist_ok = persistent_kernels_usable();
-  {   // state words + (flag-in-data hand-off only: directly behind them) the exchange buffer: a tag of 0 matches no step
-    static const bool ll_bwd = getenv("SUMK_LSTM_LL_BWD") && getenv("SUMK_LSTM_LL_BWD")[0] == '1';
-    const size_t words = ll_bwd ? (L.llb + L.llb_bytes - L.pstate_b) / 4 : (size_t)PSTATE_WORDS;
-    hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)std::min<size_t>(256, (words + 255) / 256)), dim3(256), 0, stream, (unsigned*)(ws + L.pstate_b), (int)words);
-  }
+  const LstmSwitches& sw = lstm_switches();
+  hipLaunchKernelGGL(zero_words_kernel, dim3((PSTATE_WORDS + 255) / 256), dim3(256), 0, stream, (unsigned*)(ws + L.pstate_b), PSTATE_WORDS);
   bool done = false;
   if (persist_ok && H <= 256 && L.xchg_bytes > 0) {
     PersistBwdArgs pa;
@@ -2590,26 +1981,20 @@ extern "C" int sumk_bilstm_layer_backward(const float* x, const float* h_out, co
     pa.gsize = gsize; pa.n_groups = (n_seq + gsize - 1) / gsize; pa.n_items = 2 * pa.n_groups;
     // round 6: sharded step counter (while the items fit the state block, short of its spare words) and the reader-shaped
     // exchange (members own 8 aligned units); SUMK_LSTM_BWD_R6=0 keeps the round-5 forms (A/B: tests/test_gpu_lstm.py)
-    static const bool r6_on = !(getenv("SUMK_LSTM_BWD_R6") && getenv("SUMK_LSTM_BWD_R6")[0] == '0');
-    const bool shard = r6_on && pa.n_items * 128 <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS;
+    const bool shard = sw.bwd_r6 && pa.n_items * 128 <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS;
     pa.item_words = shard ? 128 : 1; pa.n_shards = shard ? 4 : 1;
-    pa.coal = (r6_on && pa.upm == 8 && pa.n_active * 8 == H) ? 1 : 0;
+    pa.coal = (sw.bwd_r6 && pa.upm == 8 && pa.n_active * 8 == H) ? 1 : 0;
     if (pa.n_items <= PSTATE_WORDS - 16) {
       const size_t shmem = std::max<size_t>(((size_t)32 * (H + 4) + 32 * 36 + 96) * sizeof(float), 96 * 1024);  // >80 KB: one block per CU
-      pa.ll = (unsigned long long*)(ws + L.llb);
-      // The BPTT keeps the COUNTER hand-off by default: its exchange is a reduce-scatter of 32 partials per element (each epilogue thread
-      // polls 32 packets, the exchange bytes double), and the flag-in-data form measured SLOWER here (DSN training step 3.93 vs 3.76 ms);
-      // SUMK_LSTM_LL_BWD=1 selects it.  The 16-row MFMA form (groups of <= 16 videos) is independent of the hand-off.
-      static const bool ll_on = getenv("SUMK_LSTM_LL_BWD") && getenv("SUMK_LSTM_LL_BWD")[0] == '1';
-      static const bool m16_on = !(getenv("SUMK_LSTM_M16") && getenv("SUMK_LSTM_M16")[0] == '0');
-      const bool ll = ll_on && L.llb_bytes > 0, m16 = m16_on && gsize <= 16;
-      const int which = (ll ? 2 : 0) + (m16 ? 1 : 0);
-      const void* fn = ll ? (m16 ? (const void*)lstm_persist_bwd_kernel<true, true> : (const void*)lstm_persist_bwd_kernel<true, false>)
-                          : (m16 ? (const void*)lstm_persist_bwd_kernel<false, true> : (const void*)lstm_persist_bwd_kernel<false, false>);
-      static bool attr_set[4] = {false, false, false, false};
-      if (!attr_set[which]) {
+      // The BPTT hands off through the step COUNTER: its exchange is a reduce-scatter of 32 partials per element, and a flag-in-data
+      // form (each epilogue thread polls 32 packets, the exchange bytes double) measured slower.  The 16-row MFMA form
+      // serves groups of <= 16 videos.
+      const bool m16 = sw.m16 && gsize <= 16;
+      const void* fn = m16 ? (const void*)lstm_persist_bwd_kernel<true> : (const void*)lstm_persist_bwd_kernel<false>;
+      static bool attr_set[2] = {false, false};
+      if (!attr_set[m16]) {
         SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[which] = true;
+        attr_set[m16] = true;
       }
       void* kargs[] = {&pa};
       SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(PK_TEAMS * 32), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
@@ -2626,8 +2011,7 @@ extern "C" int sumk_bilstm_layer_backward(const float* x, const float* h_out, co
     wa.KG = H / 32; wa.NG = (H + 255) / 256; wa.n_active = wa.KG * wa.NG;
     wa.xchg_dir_bytes = (int32_t)(L.xchg_bytes / 2);
     {   // round 6: sharded step counter while the items fit the state block (SUMK_LSTM_BWD_R6=0: one word per item, as round 5)
-      static const bool r6_on = !(getenv("SUMK_LSTM_BWD_R6") && getenv("SUMK_LSTM_BWD_R6")[0] == '0');
-      const bool shard = r6_on && 2 * wa.n_groups * 128 <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS;
+      const bool shard = sw.bwd_r6 && 2 * wa.n_groups * 128 <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS;
       wa.item_words = shard ? 128 : 1; wa.n_shards = shard ? 4 : 1;
     }
     static bool wb_attr_set = false;

@@ -26,8 +26,7 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Environment switches the library reads: the A/B switches that have a test comparing both settings (SUMK_SK, SUMK_LEAN,
 // SUMK_FUSED_HEAD, SUMK_FUSED_LN, SUMK_BF16_SRC, SUMK_B16_WIDE, SUMK_ATTN_FUSED, SUMK_ATTN_WIDE, SUMK_ATTN_NT, SUMK_PW_LONG,
-// SUMK_LSTM_PERSIST, SUMK_LSTM_LL, SUMK_LSTM_LL_BWD, SUMK_LSTM_M16, SUMK_LSTM_WIDE2, SUMK_LSTM_PROJ, SUMK_LSTM_BWD_R6; DESIGN.md
-// section 7).  Every tile shape and schedule is otherwise fixed at its measured-best setting.
+// SUMK_LSTM_PERSIST, SUMK_LSTM_LL, SUMK_LSTM_M16, SUMK_LSTM_BWD_R6).  Every tile shape and schedule is otherwise fixed at its measured-best setting.
 
 // ------------------------------------------------------------------------------------------- GEMM
 // One sub-problem of a grouped launch.  Offsets are in elements from the launch's base pointers.

@@ -43,6 +43,9 @@ Cases (H, D, videos; what the dispatch gives them):
   j 1028,  64,  10 (<= 12)         H > 1024: lstm_step_kernel and lstm_bwd_step_kernel
   k  256,  64,   1 of 1000 frames  forward only: error growth over a long chain of hand-offs
   l  case d in a child process with SUMK_LSTM_PERSIST=0: the launch-per-step kernels at H <= 256 ("same arithmetic")
+  m  384,  64, 3969 (<= 3)         one video past what lstm_wide2_kernel's sharded counters hold (62 groups of 64): lstm_step_kernel at a
+                                   wide H, inference; in training mode its saves feed lstm_wide_bwd_kernel (63 groups, one counter word
+                                   per item) -- training-mode scores of every video, dx of the first and the last 64 videos
 
 The dX GEMM of the backward (dx = dG_fwd W_ih_fwd + dG_rev W_ih_rev) sums its K = 4H gate columns per direction in ONE fp32 MFMA accumulator
 (csrc/gemm_regstage.h); a BLAS product sums in blocks and lanes and its error grows far slower with K.  With a BLAS product in the yardstick
@@ -67,6 +70,8 @@ Figures, measured on MI355X (worst HIP error / yardstick per kind, 4 is the limi
   j fp32          0.26    0.74  1.20       0.50       0.40  0.48  0.19     9.4e-8 / 7.0e-8 / 1.3e-6
   k fp32          1.10    1.00                                             1.2e-7 / 7.3e-8 (forward only)
   l (d, steps)    0.84    0.73  1.23       0.44       0.57  1.25  0.33     (case d's)
+  m fp32          0.44    0.71                                             1.1e-7 / 8.6e-8 (inference)
+  m fp32 training         0.71  1.32                                       8.6e-8 / 1.3e-6 (scores / dx; dx of 128 videos)
   Parameter-gradient yardsticks lie between 3.8e-7 and 2.4e-6 (fp32) and 4.4e-6 and 8.1e-6 (bf16x3).  No kernel exceeded the gate.
 
 What these gates see and the earlier ones (scores 1e-4, hidden states 2e-5, whole-tensor relative L2 3e-4) do not, shown on the CPU with the
@@ -110,7 +115,9 @@ CASES = {
     "i": dict(H=1024, D=64, L=1, lens=[40, 1, 2]),
     "j": dict(H=1028, D=64, L=1, lens=[12, 1, 2, 7, 12, 5, 9, 3, 7, 11]),
     "k": dict(H=256, D=64, L=1, lens=[1000], forward_only=True),
+    "m": dict(H=384, D=64, L=1, lens=[3, 1, 2] + [(i % 3) + 1 for i in range(3966)], forward_only=True),
 }
+M_DX_VIDEOS = tuple(range(64)) + tuple(range(3969 - 64, 3969))     # case m in training mode: the videos whose dx is judged
 SEED = {c: 4100 + 100 * i for i, c in enumerate(sorted(CASES))}
 LSTM_TENSORS = (("weight_ih", "dweight_ih"), ("weight_hh", "dweight_hh"), ("bias_ih", "dbias"), ("bias_hh", "dbias"))
 
@@ -142,7 +149,7 @@ def _inputs(case):
     lens, seed = c["lens"], SEED[case]
     if len(lens) > 3:
         assert 1 in lens and 2 in lens and len(set(lens)) < len(lens), case
-    assert max(lens) <= {"a": 64, "b": 40, "c": 24, "d": 50, "e": 30, "f": 70, "g": 40, "h": 40, "i": 40, "j": 12, "k": 1000}[case]
+    assert max(lens) <= {"a": 64, "b": 40, "c": 24, "d": 50, "e": 30, "f": 70, "g": 40, "h": 40, "i": 40, "j": 12, "k": 1000, "m": 3}[case]
     w = R.lstm_weights("rnn.", c["D"], c["H"], c["L"], seed, "out.0.")
     xs = [R.features(T, 1, c["D"], seed + 1 + i)[:, 0, :] - 0.2 for i, T in enumerate(lens)]
     cw = np.random.default_rng(seed + 99).standard_normal(sum(lens)).astype(np.float32)
@@ -150,14 +157,18 @@ def _inputs(case):
 
 
 @functools.lru_cache(maxsize=None)
-def _oracle(case, mode, grads):
+def _oracle(case, mode, grads, videos=None):
     """bilstm_stack_ref + head + the gradients of sum(scores * cw).  mode "f64": float64, exact gate functions (the reference);
     "fp32": float32 with the kernels' gate formulas (the yardstick); "x3": the fp32 yardstick with the bf16x3 products where the
-    library runs them.  Returns {name: float64 array}: h<l> (R, 2H), scores (R,), dx (R, D), the state_dict names.  Never modified."""
+    library runs them.  videos: a tuple of video indices -- the batch of those videos alone, with their rows of cw (scores and dx of a
+    video depend on that video alone).  Returns {name: float64 array}: h<l> (R, 2H), scores (R,), dx (R, D), the state_dict names.
+    Never modified."""
     c, inp = CASES[case], _inputs(case)
     dt = F64 if mode == "f64" else torch.float32
     p = {k: torch.from_numpy(v).to(dt).requires_grad_(grads) for k, v in inp["w"].items()}
-    xs = [torch.from_numpy(x).to(dt).requires_grad_(grads) for x in inp["xs"]]
+    vids = range(len(inp["xs"])) if videos is None else videos
+    xs = [torch.from_numpy(inp["xs"][v]).to(dt).requires_grad_(grads) for v in vids]
+    cw = np.concatenate([inp["cw"][inp["off"][v]:inp["off"][v + 1]] for v in vids])
     hook = None
     if mode == "fp32" and grads:     # the dX GEMM's one accumulator chain over 4H columns per direction (torch_port.mm_chain says why)
         hook = lambda a, w, site: torch_port.LinearChainDx.apply(a, w) if site == "ih" else a @ w.t()
@@ -173,7 +184,7 @@ def _oracle(case, mode, grads):
         out["scores"] = scores
         if grads:
             names = list(p)
-            g = torch.autograd.grad((scores * torch.from_numpy(inp["cw"]).to(dt)).sum(), xs + [p[n] for n in names])
+            g = torch.autograd.grad((scores * torch.from_numpy(cw).to(dt)).sum(), xs + [p[n] for n in names])
             out["dx"] = torch.cat(g[:len(xs)])
             out.update(zip(names, g[len(xs):]))
     return {k: v.detach().to(F64).numpy() for k, v in out.items()}
@@ -251,10 +262,11 @@ def _slices(case, grads):
     return sl
 
 
-def _judge(tag, case, got, ref, yard, grads):
-    """Every slice of the case against float64; prints and records yardsticks and worst ratios; fails listing what is over the gate."""
+def _judge(tag, case, got, ref, yard, grads, slices=None):
+    """Every slice of the case (or the given ones) against float64; prints and records yardsticks and worst ratios; fails listing what is
+    over the gate."""
     rows, ys = [], {}
-    for kind, name, gk, rk, idx, rel in _slices(case, grads):
+    for kind, name, gk, rk, idx, rel in (_slices(case, grads) if slices is None else slices):
         r = ref[rk][idx]
         scale = float(np.abs(r).max())
         assert scale > 0 and got[gk].shape == ref[rk].shape, (tag, name, scale, got[gk].shape, ref[rk].shape)
@@ -287,7 +299,7 @@ def _refs(case, precision, grads):
 
 # ------------------------------------------------------------------------------------------------ the cases
 TRAIN_RUNS = [(c, "fp32") for c in "abcdefghij"] + [("f", "bf16x3")]
-INFER_RUNS = [("c", "bf16x6"), ("c", "bf16x3"), ("f", "bf16x6"), ("k", "fp32")]
+INFER_RUNS = [("c", "bf16x6"), ("c", "bf16x3"), ("f", "bf16x6"), ("k", "fp32"), ("m", "fp32")]
 
 
 @pytest.mark.parametrize("case,precision", TRAIN_RUNS, ids=[f"{c}-{p}" for c, p in TRAIN_RUNS])
@@ -300,11 +312,38 @@ def test_bilstm_forward_and_gradients_vs_float64(monkeypatch, case, precision):
 @pytest.mark.parametrize("case,precision", INFER_RUNS, ids=[f"{c}-{p}" for c, p in INFER_RUNS])
 def test_bilstm_inference_vs_float64(monkeypatch, case, precision):
     """Inference only: the split-bf16 arithmetics of cases c (projection on operand planes) and f (the wide recurrence's bf16x6 recurrent
-    product; bf16x6 training keeps the exact-fp32 recurrence, so there is nothing else to run in that mode), and the 1000-frame chain."""
+    product; bf16x6 training keeps the exact-fp32 recurrence, so there is nothing else to run in that mode), the 1000-frame chain, and
+    the 3 969-video batch of case m on the launch chain."""
     if case == "c":
         assert sum(CASES[case]["lens"]) >= 1024                          # (below that the planes are not taken)
     ref, yard = _refs(case, precision, False)
     _judge(f"{case}/{precision}/inference", case, _hip(case, precision, False, monkeypatch), ref, yard, False)
+
+
+def test_launch_chain_saves_feed_wide_bptt_case_m_vs_float64(monkeypatch):
+    """Case m in training mode: lstm_step_kernel writes the saves (gates, cell states, h_{t-1}) that lstm_wide_bwd_kernel reads.  Training-mode
+    scores of all 3 969 videos, and dx of the first 64 and the last 64 videos (first and last group of 64, the last one a single video), under
+    the gates of the other cases.  The float64 / fp32 gradient oracles run on those 128 videos alone: dx of a video depends on that video and its
+    rows of cw only (the full-batch gradient oracles take most of a minute on the CPU)."""
+    from summarizer_amd.models.dsn import DSN
+    c, inp = CASES["m"], _inputs("m")
+    lens, off = c["lens"], inp["off"]
+    dev = torch.device("cuda:0")
+    m = DSN(c["D"], c["H"], c["L"])
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in inp["w"].items()})
+    m = m.to(dev)
+    with Poison(monkeypatch):
+        xg = torch.from_numpy(np.concatenate(inp["xs"])).to(dev).requires_grad_(True)
+        s = m.score_packed(xg, lens)
+        (s * torch.from_numpy(inp["cw"]).to(dev)).sum().backward()
+        dx = xg.grad.cpu().numpy().astype(np.float64)
+        got = dict(train_scores=s.detach().cpu().numpy().astype(np.float64),
+                   dx=np.concatenate([dx[off[v]:off[v + 1]] for v in M_DX_VIDEOS]))
+    ref, yard = ({"scores": _oracle("m", mode, False)["scores"], "dx": _oracle("m", mode, True, M_DX_VIDEOS)["dx"]} for mode in ("f64", "fp32"))
+    sub = np.concatenate([[0], np.cumsum([lens[v] for v in M_DX_VIDEOS])])
+    sl = [("scores", f"train_scores[video {v}, T={lens[v]}]", "train_scores", "scores", (slice(off[v], off[v + 1]),), False) for v in range(len(lens))]
+    sl += [("dx", f"dx[video {v}, T={lens[v]}]", "dx", "dx", (slice(sub[i], sub[i + 1]),), True) for i, v in enumerate(M_DX_VIDEOS)]
+    _judge("m/fp32/training", "m", got, ref, yard, True, sl)
 
 
 _CHILD = r'''

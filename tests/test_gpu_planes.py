@@ -286,8 +286,7 @@ def test_lstm_scorers_input_projection_on_planes(dev, kind):
             wpl = m._wpl
             h_pl, _ = kernels.bilstm_layer_forward(x, sb, p, prefix, 0, H, precision=prec, wplanes=wpl[0], dataset_input=True)
             h_old, _ = kernels.bilstm_layer_forward(x, sb, p, prefix, 0, H, precision=prec)
-            # (both kinds run the plane GEMM in front of lstm_persist_kernel: the projection inside the recurrence,
-            #  lstm_persist_proj_kernel, is opt-in -- SUMK_LSTM_PROJ=1 -- and tests/test_gpu_lstm.py holds it to the plane GEMM and the oracle)
+            # (both kinds run the plane GEMM in front of the recurrence: lstm_persist_kernel for DSN, lstm_wide2_kernel for sLSTM)
             assert torch.equal(h_pl, h_old) if prec == "bf16x6" else float((h_pl - h_old).abs().max()) < 2e-6
         key0 = m._wpl_key
         dict(m.named_parameters())[prefix + "weight_ih_l0"].mul_(1.1)
