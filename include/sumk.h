@@ -676,6 +676,46 @@ int sumk_eval_device_select(const sumk_eval_dev_select* videos_dev, const sumk_e
                             float* machine_summary_dev, int64_t summary_total, uint8_t* selected_dev, int64_t selected_total,
                             double* f_avg_dev, double* f_max_dev, int32_t* status_dev, void* workspace, size_t workspace_bytes,
                             void* stream);
+
+/* DEVICE, long videos (csrc/evallong.hip): the same two steps without the per-video LDS tables of the calls above, for what
+ * sumk_kts_banded segments.  Neither uses a cooperative launch or a flag polled across workgroups: every launch ends by itself, the
+ * work of a video is spread over the chip, and both can be captured into a HIP graph.
+ *
+ * sumk_eval_device_segments_long: sumk_eval_device_segments on the same descriptors, results equal bit for bit wherever both accept the
+ * input.  Upsampling is frame-centric on a grid over (frame chunks, videos): frame f takes the score of the last pick interval i with
+ * picks[i] <= f by binary search (0 for i >= n_steps and for frames in front of the first pick) -- for ascending picks, duplicates
+ * allowed, the array the in-order interval loop writes.  A segment mean is one workgroup per (video, segment): numpy's float32 sum -- up to 8192 frames one
+ * pairwise tree, cut at depth 8, a subtree per thread, joined in tree order; past that the trees of 8192-frame blocks added in order --
+ * then one division; empty segments give 0.
+ * Limits: 1 <= n_picks <= SUMK_SEGMENTS_LONG_MAX_PICKS (the cap of sumk_kts_banded), 1 <= n_frames <= SUMK_SEGMENTS_LONG_MAX_FRAMES,
+ * n_segs >= 0, n_videos <= 65535; user_* are not read.  videos_host is the host copy of videos_dev: a video past a limit returns
+ * SUMK_ERR_ARG and launches nothing.  A device descriptor that disagrees with it and is past a limit gets NaN segment means. */
+#define SUMK_SEGMENTS_LONG_MAX_PICKS 1048576
+#define SUMK_SEGMENTS_LONG_MAX_FRAMES 16777216
+int sumk_eval_device_segments_long(const float* scores_dev, const sumk_eval_dev_video* videos_dev, const sumk_eval_dev_video* videos_host,
+                                   int32_t n_videos, float* frame_scratch_dev, float* seg_means_dev, void* stream);
+/* sumk_eval_device_select_long: sumk_eval_device_select on the same descriptors, outputs and status codes, for any frame budget:
+ * 1 <= n_segs <= SUMK_SELECT_MAX_SEGS, 0 <= capacity <= SUMK_SELECT_LONG_MAX_CAPACITY, n_users <= SUMK_SELECT_MAX_USERS, 1 <= n_frames <=
+ * 2^24.  Results equal sumk_eval_device_select's and the host tail's bit for bit.  Launches: a prologue (one workgroup per video: the
+ * integers, the items of the knapsack's pass, the status); method 0: one launch per item position j = 0 .. largest n_segs of the call
+ * - 1 on a grid over (SUMK_SELECT_LONG_CHUNK capacities, videos), each reading one int32 profit row of the workspace and writing the
+ * other plus one 64-bit word of improvement bits per wave -- a block whose video has fewer items in its pass, a nonzero status or
+ * capacity 0 exits at once; the backtrack (method 1: the rank walk) per video; summary expansion and the annotators' int32 counts over
+ * (frame chunks, videos); a last launch that adds the counts and takes the F-scores.
+ * A device descriptor past the limits, past the call's largest n_segs / capacity / n_frames as the host copy has them, or with offsets
+ * outside the outputs gets status 4 and nothing else of it is written.
+ * workspace: sumk_eval_device_select_long_workspace_bytes(n_videos, largest n_segs, largest capacity) bytes, 8-byte aligned, contents
+ * irrelevant; pure host arithmetic, 0 = bad arguments.  Per video, each part rounded up to 256 bytes: n_segs x ceil((capacity + 1) / 64)
+ * 64-bit words of improvement bits; two rows of capacity + 1 int32; 5 n_segs + 9 int32 of item tables; SUMK_SELECT_LONG_FRAME_CHUNKS x
+ * (2 SUMK_SELECT_MAX_USERS + 1) int32 of partial counts.  The bits are what grows: n_segs x capacity / 8 bytes. */
+#define SUMK_SELECT_LONG_MAX_CAPACITY 16777216
+#define SUMK_SELECT_LONG_CHUNK 2048
+#define SUMK_SELECT_LONG_FRAME_CHUNKS 64
+size_t sumk_eval_device_select_long_workspace_bytes(int32_t n_videos, int32_t max_n_segs, int32_t max_capacity);
+int sumk_eval_device_select_long(const sumk_eval_dev_select* videos_dev, const sumk_eval_dev_select* videos_host, int32_t n_videos,
+                                 float* machine_summary_dev, int64_t summary_total, uint8_t* selected_dev, int64_t selected_total,
+                                 double* f_avg_dev, double* f_max_dev, int32_t* status_dev, void* workspace, size_t workspace_bytes,
+                                 void* stream);
 /* DEVICE: (n_cps, cps) of sumk_kts -> the change points the evaluation tail reads, at a fixed pitch of max_ncp + 1 segments per video, so
  * that n_segs stays a host-known bound: change_points (n_seq, max_ncp + 1, 2) and nfps (n_seq, max_ncp + 1) int32.  Segment s <= n_cps[v]
  * is [0 | frame(cps[s - 1]), frame(cps[s]) - 1 | n_frames[v] - 1] with frame(c) = picks_dev[v][c] (picks_dev, or an entry of it, NULL: c

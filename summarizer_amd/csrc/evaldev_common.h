@@ -1,6 +1,7 @@
 // What the device-side evaluation kernels share (evaldev.hip: segment means + Spearman; evalkendall.hip: Kendall's tau-b; evalselect.hip:
-// key shots + F-scores; agreement.hip: inter-annotator agreement): the limits of the per-video LDS tables, the pick-interval tables
-// themselves, the LDS merge sort of the Kendall blocks and the F-score arithmetic.
+// key shots + F-scores; evallong.hip: both for long videos; agreement.hip: inter-annotator agreement): the limits of the per-video LDS
+// tables, numpy's pairwise sum, the pick-interval tables themselves, the LDS merge sort of the Kendall blocks, the steps of the key-shot
+// selection and the F-score arithmetic.
 #pragma once
 #include "sumk_internal.h"
 #include <math.h>
@@ -35,14 +36,69 @@ __host__ __device__ inline T np_pairwise_leaf(const T* a, int n) {
   for (; i < n; ++i) res += a[i];
   return res;
 }
-// any n: the leaf up to 128, above that the halves split at a multiple of 8.  N = the caller's own length type (int in the kernels, whose
-// recursion then keeps 32-bit lengths on its call stack; int64_t on the host).
+// the tree: the leaf up to 128 values, above that the halves split at a multiple of 8.  N = the caller's own length type (int in the
+// kernels, whose recursion then keeps 32-bit lengths on its call stack; int64_t on the host).
 template <class T, class N>
-__host__ __device__ inline T np_pairwise_sum(const T* a, N n) {
+__host__ __device__ inline T np_pairwise_tree(const T* a, N n) {
   if (n <= 128) return np_pairwise_leaf(a, (int)n);
   N n2 = n / 2;
   n2 -= n2 % 8;
-  return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
+  return np_pairwise_tree(a, n2) + np_pairwise_tree(a + n2, n - n2);
+}
+// any n, what `a.sum()` of a contiguous array gives: numpy hands its reduction loop at most one buffer of the array at a time --
+// NP_BUFSIZE = 8192 elements, numpy.getbufsize()'s default, of either type -- so the tree spans one such block and the blocks' sums are
+// added one after the other, in order.  Up to 8192 values this is the tree itself.
+constexpr int NP_BUFSIZE = 8192;
+template <class T, class N>
+__host__ __device__ inline T np_pairwise_sum(const T* a, N n) {
+  if (n <= (N)NP_BUFSIZE) return np_pairwise_tree(a, n);
+  T r = np_pairwise_tree(a, (N)NP_BUFSIZE);
+  for (N i = NP_BUFSIZE; i < n; i += NP_BUFSIZE) r += np_pairwise_tree(a + i, n - i < (N)NP_BUFSIZE ? n - i : (N)NP_BUFSIZE);
+  return r;
+}
+
+// The tree of n <= NP_BUFSIZE values by a block of 1 << DEPTH threads (evallong.hip: a workgroup per segment).  The block walks the split
+// rule above DEPTH levels down, thread t taking the turns its bits spell (the most significant first), each thread sums the subtree it
+// arrives at with np_pairwise_tree, and the partial sums are joined in LDS, deepest level first, left + right: the additions of the
+// one-thread tree, each once, on the same operands in the same order -- the same bits.  A node of 128 values or fewer above the cut is a
+// leaf of the tree: the thread on its leftmost path sums it, the others below it hold nothing.  Every thread of the block calls it
+// (barriers inside; a, n block-uniform); s_sum / s_has: 1 << DEPTH LDS entries each.  The result is thread 0's.
+template <int DEPTH>
+__device__ inline float np_pairwise_tree_block(const float* a, int n, float* s_sum, uint8_t* s_has) {
+  constexpr int NT = 1 << DEPTH;
+  const int tid = threadIdx.x;
+  int off = 0, len = n;
+  bool has = true;
+  for (int level = 0; level < DEPTH; ++level) {
+    if (len <= 128) { has = (tid & ((1 << (DEPTH - level)) - 1)) == 0; break; }
+    int n2 = len / 2;
+    n2 -= n2 % 8;
+    if ((tid >> (DEPTH - 1 - level)) & 1) { off += n2; len -= n2; } else len = n2;
+  }
+  s_sum[tid] = has ? np_pairwise_tree(a + off, len) : 0.f;
+  s_has[tid] = has ? 1 : 0;
+  __syncthreads();
+  // at stride st the node on whose leftmost path thread t lies takes its right child, if the tree split there
+  for (int st = 1; st < NT; st <<= 1) {
+    if ((tid & (2 * st - 1)) == 0 && s_has[tid + st]) s_sum[tid] = s_sum[tid] + s_sum[tid + st];
+    __syncthreads();
+  }
+  return s_sum[0];
+}
+// np_pairwise_sum of n > NP_BUFSIZE values by a block of NT threads: a buffer block per thread (thread t takes blocks t, t + NT, ...), the
+// blocks' sums in LDS, then thread 0 adds them in order.  s_part: ceil(n / NP_BUFSIZE) LDS entries.  Every thread of the block calls it
+// (one barrier inside); the result is thread 0's.
+template <int NT>
+__device__ inline float np_pairwise_sum_blocks(const float* a, int n, float* s_part) {
+  const int n_blocks = (n + NP_BUFSIZE - 1) / NP_BUFSIZE;
+  for (int b = threadIdx.x; b < n_blocks; b += NT) s_part[b] = np_pairwise_tree(a + b * NP_BUFSIZE, min(NP_BUFSIZE, n - b * NP_BUFSIZE));
+  __syncthreads();
+  float r = 0.f;
+  if (threadIdx.x == 0) {
+    r = s_part[0];
+    for (int b = 1; b < n_blocks; ++b) r += s_part[b];
+  }
+  return r;
 }
 
 // the interval tables of a video: interval i = frames [s_lo[i], s_hi[i]) takes score i (0 past the scores) -- eval.py:24-34.
@@ -116,7 +172,132 @@ __device__ inline uint32_t* kd_merge_sort(uint32_t* a, uint32_t* b, int n, long 
   return a;
 }
 
-// ---- the F-score arithmetic evalselect.hip and agreement.hip share
+// ---- what the two key-shot selections share (evalselect.hip: one workgroup per video; evallong.hip: the chip-wide form)
+constexpr int SEL_THREADS = 1024;                            // one segment per thread in the scans
+constexpr int SEL_WAVES = SEL_THREADS / 64;
+constexpr int SEL_MAX_SEGS = SUMK_SELECT_MAX_SEGS;
+constexpr int SEL_MAX_USERS = SUMK_SELECT_MAX_USERS;
+constexpr int SEL_MAX_FRAMES = 1 << 24;                      // counts of frames stay exact in float32
+static_assert(SEL_MAX_SEGS == SEL_THREADS && SEL_MAX_USERS == ED_MAX_USERS, "limits of the select kernels");
+
+// exclusive prefix sum over the block of one value per thread, *total = the block's sum; s_wsum: SEL_WAVES entries
+__device__ __forceinline__ long long sel_scan(long long x, long long* s_wsum, long long* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  long long incl = x;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long u = __shfl_up(incl, o);
+    if (lane >= o) incl += u;
+  }
+  __syncthreads();                           // (the previous scan's readers are done with s_wsum)
+  if (lane == 63) s_wsum[wave] = incl;
+  __syncthreads();
+  long long base = 0, tot = 0;
+  for (int q = 0; q < SEL_WAVES; ++q) { const long long c = s_wsum[q]; base += q < wave ? c : 0; tot += c; }
+  *total = tot;
+  return base + incl - x;
+}
+
+// The integers of a video's selection, one thread per segment (a block of SEL_THREADS; every thread calls it: barriers inside).
+//   by segment:  w_all[s] = nfps[s] (0 for a negative one), start[s] = the prefix sum of the weights, clamped to len; start[n] = len
+//   by position in the knapsack's pass (method 0; items with val > 0 and w <= cap, in segment order): live[pos] = the segment,
+//                sv[pos] = its value (int64_t)((double)mean * 1000.0), swl[pos] = its weight
+// The tables may be LDS or global memory; s_flag (2 ints) and s_wsum (SEL_WAVES) are LDS.  *m = items in the pass (0 when their values
+// sum to 2^31 or more), *x = this thread's segment mean as a double.  Returns the video's status: 0, or 1 (a segment mean is not
+// finite or past 1e12), 3 (a negative nfps, or nfps that do not sum to len), 2 (values past the int32 profit rows), in this precedence.
+template <class LiveT>
+__device__ __forceinline__ int sel_prepare(const sumk_eval_dev_select& v, int n, int cap, int len, int* s_flag, long long* s_wsum, int* w_all,
+                                           int* start_tab, LiveT* live_tab, int* sv, int* swl, int* m_out, double* x_out) {
+  const int tid = threadIdx.x;
+  if (tid < 2) s_flag[tid] = 0;
+  __syncthreads();
+  // ---- values and weights (eval_one: int64 truncation of the double product)
+  long long val = 0; int w = 0; double x = 0.0;
+  if (tid < n) {
+    const float mean = v.seg_means[tid];
+    w = v.nfps[tid];
+    x = (double)mean;
+    if (!(fabs(x) <= 1e12)) { s_flag[0] = 1; x = 0.0; }          // NaN, infinite, or past what the cast to int64 defines
+    if (w < 0) { s_flag[1] = 1; w = 0; }
+    val = (long long)(x * 1000.0);
+    w_all[tid] = w;
+  }
+  long long total;
+  const long long start = sel_scan((long long)w, s_wsum, &total);
+  if (tid < n) start_tab[tid] = (int)(start < (long long)len ? start : (long long)len);
+  if (tid == 0) { start_tab[n] = len; if (total != (long long)len) s_flag[1] = 1; }
+  int m = 0;
+  if (v.method == 0) {
+    const bool live = tid < n && val > 0 && w <= cap;
+    long long possum, cnt;
+    sel_scan(live ? val : 0, s_wsum, &possum);
+    const long long pos = sel_scan(live ? 1 : 0, s_wsum, &cnt);
+    if (possum >= ((long long)1 << 31) && tid == 0) s_flag[0] = s_flag[0] ? 1 : 2;
+    m = possum < ((long long)1 << 31) ? (int)cnt : 0;
+    if (live && m > 0) { live_tab[pos] = (LiveT)tid; sv[pos] = (int)val; swl[pos] = w; }
+  }
+  __syncthreads();
+  *m_out = m; *x_out = x;
+  return s_flag[0] == 1 ? 1 : s_flag[1] ? 3 : s_flag[0];          // 1: segment mean; 3: nfps; 2: values past int32 rows
+}
+
+// the segment that owns summary entry f: the last s with start[s] <= f (empty segments share their start with the next one)
+__device__ __forceinline__ int sel_segment_of(const int* s_start, int n, int f) {
+  int lo = 0, hi = n;                        // start[lo] <= f < start[hi] (start[n] = summary_len > f)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (s_start[mid] <= f) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// Backtrack of the one-pass knapsack on one wave (every lane of it calls this): bit (j, c) of `bits` = the item at position j improved
+// capacity c, `words` 64-bit words per item.  From (k = n, rem = cap): s = the segment of the largest position < kpos whose bit is set
+// at rem, segment 0 if there is none; rem -= its weight; s is selected if rem >= 0; repeat while rem > 0 and k > 0.  The scan for the
+// largest set bit only ever moves down.  kpos = items in the pass (0 when no pass ran); w0 = the weight of segment 0.
+template <class LiveT>
+__device__ __forceinline__ void sel_backtrack(const unsigned long long* bits, int words, int n, int cap, int kpos, const LiveT* live_tab, const int* swl,
+                                              int w0, uint8_t* sel) {
+  const int lane = threadIdx.x & 63;
+  int rem = cap, k = n;
+  while (rem > 0 && k > 0) {
+    int found = -1;
+    for (int hi = kpos; hi > 0 && found < 0; hi -= 64) {
+      const int j = hi - 1 - lane;
+      const bool b = j >= 0 && ((bits[(size_t)j * words + (rem >> 6)] >> (rem & 63)) & 1ull) != 0;
+      const unsigned long long mask = __ballot(b);
+      if (mask) found = hi - __ffsll((long long)mask);
+    }
+    const int s = found >= 0 ? (int)live_tab[found] : 0;
+    rem -= found >= 0 ? swl[found] : w0;
+    k = s; kpos = found > 0 ? found : 0;
+    if (rem >= 0 && lane == 0) sel[s] = 1;
+  }
+}
+
+// eval_one's rank walk: stable_sort by ascending double score walked from the back = descending score, the larger index first among
+// equals; the sorted position by counting, the greedy walk (strict total + nfps < capacity) on one thread.  s_x (SEL_MAX_SEGS doubles)
+// and s_order (SEL_MAX_SEGS ints) are LDS; x = this thread's score; every thread of the block calls it (barriers inside).
+__device__ __forceinline__ void sel_rank_walk(double x, int n, int cap, const int* w_all, double* s_x, int* s_order, uint8_t* sel) {
+  const int tid = threadIdx.x;
+  if (tid < n) s_x[tid] = x;
+  __syncthreads();
+  if (tid < n) {
+    int pos = 0;
+    for (int j = 0; j < n; ++j) { const double y = s_x[j]; pos += (y < x || (y == x && j < tid)) ? 1 : 0; }
+    s_order[pos] = tid;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    long long used = 0;
+    for (int q = n - 1; q >= 0; --q) {
+      const int i = s_order[q];
+      if (used + w_all[i] < (long long)cap) { sel[i] = 1; used += w_all[i]; }
+    }
+  }
+}
+
+// ---- the F-score arithmetic evalselect.hip, evallong.hip and agreement.hip share
 // fscores<T> of csrc/evaltail.hip from the counts: msum = ones of the machine summary over the video's frames, ov[k] / gs[k] = the
 // overlap with annotator k and the annotator's own count
 template <typename T>

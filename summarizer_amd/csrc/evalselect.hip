@@ -28,14 +28,9 @@
 namespace sumk {
 
 namespace {
-constexpr int SEL_THREADS = 1024;
-constexpr int SEL_WAVES = SEL_THREADS / 64;
-constexpr int SEL_MAX_SEGS = SUMK_SELECT_MAX_SEGS;           // one segment per thread in the scans
 constexpr int SEL_MAX_CAP = SUMK_SELECT_MAX_CAPACITY;
 constexpr int SEL_LDS_CAP = SUMK_SELECT_LDS_CAPACITY;        // two int32 rows of SEL_LDS_CAP + 1 entries: 32 KiB
-constexpr int SEL_MAX_USERS = SUMK_SELECT_MAX_USERS;
-constexpr int SEL_MAX_FRAMES = 1 << 24;                      // counts of frames stay exact in float32 (and 16 bits hold a thread's share)
-static_assert(SEL_MAX_SEGS == SEL_THREADS && SEL_MAX_USERS == ED_MAX_USERS, "limits of the select kernel");
+// (SEL_THREADS, SEL_MAX_SEGS, SEL_MAX_USERS and SEL_MAX_FRAMES -- 16 bits hold a thread's share of 2^24 frames -- are in evaldev_common.h)
 
 inline size_t sel_words(int64_t capacity) { return (size_t)((capacity + 1 + 63) / 64); }
 inline size_t sel_bits_bytes(int max_segs, int max_cap) { return align_up((size_t)max_segs * sel_words(max_cap) * 8, 256); }
@@ -50,23 +45,7 @@ struct SelArgs {
   char* ws; size_t pitch, bits_bytes;      // per video: improvement bits, then (capacity > SEL_LDS_CAP) the two profit rows
 };
 
-// exclusive prefix sum over the block of one value per thread, *total = the block's sum; s_wsum: SEL_WAVES entries
-__device__ __forceinline__ long long sel_scan(long long x, long long* s_wsum, long long* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long incl = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long u = __shfl_up(incl, o);
-    if (lane >= o) incl += u;
-  }
-  __syncthreads();                           // (the previous scan's readers are done with s_wsum)
-  if (lane == 63) s_wsum[wave] = incl;
-  __syncthreads();
-  long long base = 0, tot = 0;
-  for (int q = 0; q < SEL_WAVES; ++q) { const long long c = s_wsum[q]; base += q < wave ? c : 0; tot += c; }
-  *total = tot;
-  return base + incl - x;
-}
+// (sel_scan, sel_prepare, sel_segment_of, sel_backtrack and sel_rank_walk are in evaldev_common.h: evallong.hip takes the same steps)
 
 // The one pass of the DP over the m items it keeps (values sv, weights swl, by position), rows r0 / r1 both in LDS or both in the
 // workspace (one inlined copy per address space); bit (j, c) of `bits` = item j improved capacity c.  Ends on a barrier.
@@ -96,16 +75,6 @@ __device__ __forceinline__ void sel_dp(int* r0, int* r1, unsigned long long* __r
   }
 }
 
-// the segment that owns summary entry f: the last s with start[s] <= f (empty segments share their start with the next one)
-__device__ __forceinline__ int sel_segment_of(const int* s_start, int n, int f) {
-  int lo = 0, hi = n;                        // start[lo] <= f < start[hi] (start[n] = summary_len > f)
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (s_start[mid] <= f) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(SEL_THREADS) void eval_select_kernel(SelArgs a) {
   __shared__ __attribute__((aligned(16))) int s_rows[2 * (SEL_LDS_CAP + 1)];      // knapsack: two profit rows; rank: scores + order
   __shared__ int s_v[SEL_MAX_SEGS], s_wl[SEL_MAX_SEGS];                           // value / weight of the items in the pass, by position
@@ -127,36 +96,9 @@ __global__ __launch_bounds__(SEL_THREADS) void eval_select_kernel(SelArgs a) {
     if (tid == 0) { a.status[vi] = 4; a.f_avg[vi] = nan(""); a.f_max[vi] = nan(""); }
     return;
   }
-  if (tid < 2) s_flag[tid] = 0;
   s_sel[tid] = 0;
-  __syncthreads();
-  // ---- values and weights (eval_one: int64 truncation of the double product)
-  long long val = 0; int w = 0; double x = 0.0;
-  if (tid < n) {
-    const float mean = v.seg_means[tid];
-    w = v.nfps[tid];
-    x = (double)mean;
-    if (!(fabs(x) <= 1e12)) { s_flag[0] = 1; x = 0.0; }          // NaN, infinite, or past what the cast to int64 defines
-    if (w < 0) { s_flag[1] = 1; w = 0; }
-    val = (long long)(x * 1000.0);
-    s_w[tid] = w;
-  }
-  long long total;
-  const long long start = sel_scan((long long)w, s_wsum, &total);
-  if (tid < n) s_start[tid] = (int)(start < (long long)len ? start : (long long)len);
-  if (tid == 0) { s_start[n] = len; if (total != (long long)len) s_flag[1] = 1; }
-  int m = 0;
-  if (v.method == 0) {
-    const bool live = tid < n && val > 0 && w <= cap;
-    long long possum, cnt;
-    sel_scan(live ? val : 0, s_wsum, &possum);
-    const long long pos = sel_scan(live ? 1 : 0, s_wsum, &cnt);
-    if (possum >= ((long long)1 << 31) && tid == 0) s_flag[0] = s_flag[0] ? 1 : 2;
-    m = possum < ((long long)1 << 31) ? (int)cnt : 0;
-    if (live && m > 0) { s_live[pos] = (uint16_t)tid; s_v[pos] = (int)val; s_wl[pos] = w; }
-  }
-  __syncthreads();
-  const int bad = s_flag[0] == 1 ? 1 : s_flag[1] ? 3 : s_flag[0];          // 1: segment mean; 3: nfps; 2: values past int32 rows
+  int m; double x;
+  const int bad = sel_prepare(v, n, cap, len, s_flag, s_wsum, s_w, s_start, s_live, s_v, s_wl, &m, &x);
   if (!bad) {
     if (v.method == 0) {
       unsigned long long* bits = (unsigned long long*)(a.ws + (size_t)vi * a.pitch);
@@ -169,41 +111,11 @@ __global__ __launch_bounds__(SEL_THREADS) void eval_select_kernel(SelArgs a) {
           sel_dp(r0, r0 + (cap + 1), bits, s_v, s_wl, m, cap, words);
         }
       }
-      // backtrack on one wave: the scan for the largest set bit only ever moves down
-      if (wave == 0) {
-        int rem = cap, k = n, kpos = (cap > 0) ? m : 0;
-        while (rem > 0 && k > 0) {
-          int found = -1;
-          for (int hi = kpos; hi > 0 && found < 0; hi -= 64) {
-            const int j = hi - 1 - lane;
-            const bool b = j >= 0 && ((bits[(size_t)j * words + (rem >> 6)] >> (rem & 63)) & 1ull) != 0;
-            const unsigned long long mask = __ballot(b);
-            if (mask) found = hi - __ffsll((long long)mask);
-          }
-          const int s = found >= 0 ? (int)s_live[found] : 0;
-          rem -= found >= 0 ? s_wl[found] : s_w[0];
-          k = s; kpos = found > 0 ? found : 0;
-          if (rem >= 0 && lane == 0) s_sel[s] = 1;
-        }
-      }
+      if (wave == 0) sel_backtrack(bits, words, n, cap, cap > 0 ? m : 0, s_live, s_wl, s_w[0], s_sel);
     } else {
       double* s_x = (double*)s_rows;
       int* s_order = (int*)(s_x + SEL_MAX_SEGS);
-      if (tid < n) s_x[tid] = x;
-      __syncthreads();
-      if (tid < n) {
-        int pos = 0;
-        for (int j = 0; j < n; ++j) { const double y = s_x[j]; pos += (y < x || (y == x && j < tid)) ? 1 : 0; }
-        s_order[pos] = tid;
-      }
-      __syncthreads();
-      if (tid == 0) {
-        long long used = 0;
-        for (int q = n - 1; q >= 0; --q) {
-          const int i = s_order[q];
-          if (used + s_w[i] < (long long)cap) { s_sel[i] = 1; used += s_w[i]; }
-        }
-      }
+      sel_rank_walk(x, n, cap, s_w, s_x, s_order, s_sel);
     }
   }
   __syncthreads();

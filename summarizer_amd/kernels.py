@@ -763,6 +763,26 @@ def kts_segments(n_cps, cps, sb, picks_ptrs, n_frames):
     return change_points, nfps
 
 
+def eval_segments_long(scores, descr_dev, descr_host, frame_scratch, seg_means):
+    """Upsample + float32 segment means for videos past the 4096 picks of the one-workgroup tail (sumk_eval_device_segments_long,
+    include/sumk.h).  descr_host: a ctypes array of _lib.EvalDevVideo, descr_dev: its bytes as a device tensor.  Only enqueues work."""
+    _lib.check(_lib.load().sumk_eval_device_segments_long(_p(scores), _p(descr_dev), C.cast(descr_host, C.c_void_p), len(descr_host), _p(frame_scratch),
+                                                          _p(seg_means), _stream()), "sumk_eval_device_segments_long")
+
+
+def eval_select_long_workspace_bytes(n_videos, max_n_segs, max_capacity):
+    return _nonzero(_lib.load().sumk_eval_device_select_long_workspace_bytes(int(n_videos), int(max_n_segs), int(max_capacity)),
+                    "sumk_eval_device_select_long_workspace_bytes")
+
+
+def eval_select_long(descr_dev, descr_host, summary, selected, f_avg, f_max, status, ws):
+    """Key shots, expanded summaries and F-scores at any frame budget (sumk_eval_device_select_long, include/sumk.h).  descr_host: a ctypes
+    array of _lib.EvalDevSelect, descr_dev: its bytes as a device tensor; ws: eval_select_long_workspace_bytes(...) bytes.  Only enqueues work."""
+    _lib.check(_lib.load().sumk_eval_device_select_long(_p(descr_dev), C.cast(descr_host, C.c_void_p), len(descr_host), _p(summary), summary.numel(),
+                                                        _p(selected), selected.numel(), _p(f_avg), _p(f_max), _p(status), _p(ws), ws.numel(), _stream()),
+               "sumk_eval_device_select_long")
+
+
 def dsn_policy_loss_forward(probs, sb, actions, rewards, base, beta, eps_target):
     """(loss_per_video (n_seq,), mean_probs (n_seq,)) of sumk_dsn_policy_loss_forward (include/sumk.h)."""
     lib = _lib.load()

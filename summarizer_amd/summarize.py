@@ -7,7 +7,9 @@ selection of `utils.eval.generate_summary` (knapsack or rank under the frame bud
 
 `Summarizer(..., device=True)` keeps the whole chain on the device instead: scoring, `sumk_kts`, `sumk_kts_segments` (change points ->
 padded segments), `sumk_eval_device_segments` (upsample + segment means) and `sumk_eval_device_select` (key shots + expansion) are
-enqueued back to back, nothing is copied home and nothing waits: the results are device tensors."""
+enqueued back to back, nothing is copied home and nothing waits: the results are device tensors.  `tail="long"` puts
+`sumk_eval_device_segments_long` and `sumk_eval_device_select_long` (csrc/evallong.hip) in the place of the last two: the same results
+without their limits of 4096 steps and a budget of 8191 frames, for the videos `kts="banded"` segments."""
 import ctypes as C
 
 import numpy as np
@@ -22,17 +24,21 @@ from .utils import kts
 
 
 class Summarizer:
-    """Summarizer(model, proportion=0.15, method="knapsack", device=False, kts="dense", **kts_options)
+    """Summarizer(model, proportion=0.15, method="knapsack", device=False, kts="dense", tail="block", max_workspace_bytes=None, **kts_options)
 
     model: any scorer of this package with `score_packed` (VASNet, DSN, sLSTM, Transformer, ...), on the GPU.
     proportion / method: the summary budget and the selection algorithm of `generate_summary` ("knapsack" | "rank").
     kts_options: max_ncp, vmax, lmin, lmax of `utils.kts.segment` (max_ncp=None: min(n - 1, 1023)).
     kts: "dense" (the default: `sumk_kts`, videos up to 16384 steps) | "banded" (`sumk_kts_banded`: long videos, see `utils.kts.segment_packed`;
-    the same change points wherever both apply, and the same output layout, so it goes with device=True as well).
+    the same change points wherever both apply, and the same output layout, so it goes with device=True as well -- past 4096 steps with
+    tail="long").
     device: False (the default) returns numpy arrays after one D2H; True returns device tensors and never synchronises (see
-    `summarize_batch`)."""
+    `summarize_batch`).
+    tail (device=True only): "block" (the default: one workgroup per video, at most 4096 steps and a budget of 8191 frames) | "long" (the
+    chip-wide kernels: up to 1 048 576 steps, 2^24 frames and any budget; the same results bit for bit).
+    max_workspace_bytes: None = `utils.kts.DEFAULT_MAX_WORKSPACE_BYTES`; what the banded KTS and the long tail's selection may ask for."""
 
-    def __init__(self, model, proportion=0.15, method="knapsack", device=False, kts="dense", **kts_options):
+    def __init__(self, model, proportion=0.15, method="knapsack", device=False, kts="dense", tail="block", max_workspace_bytes=None, **kts_options):
         if not hasattr(model, "score_packed"):
             raise SumkError(f"Summarizer: {type(model).__name__} has no score_packed")
         unknown = sorted(set(kts_options) - {"max_ncp", "vmax", "lmin", "lmax"})
@@ -42,7 +48,11 @@ class Summarizer:
             raise KeyError(f"Unknown method {method}")
         if kts not in ("dense", "banded"):
             raise KeyError(f"Unknown kts {kts}")
-        self.kts = kts
+        if tail not in ("block", "long"):
+            raise KeyError(f"Unknown tail {tail}")
+        if tail == "long" and not device:
+            raise SumkError('Summarizer: tail="long" needs device=True (the host tail has no limits to lift)')
+        self.kts, self.tail, self.max_workspace_bytes = kts, tail, max_workspace_bytes
         self.model, self.proportion, self.method, self.kts_options, self.device = model, proportion, method, kts_options, bool(device)
 
     def summarize(self, features, picks=None, n_frames=None):
@@ -68,7 +78,7 @@ class Summarizer:
         picks = [None] * len(feats) if picks is None else list(picks)
         n_frames = [None] * len(feats) if n_frames is None else list(n_frames)
         if self.device:
-            n_frames, picks = self._check_device_limits(lens, picks, n_frames)
+            n_frames, picks = (self._check_long_limits if self.tail == "long" else self._check_device_limits)(lens, picks, n_frames)
         packed = (feats[0] if len(feats) == 1 else torch.cat(feats)).contiguous()
         was_training = getattr(self.model, "training", False)
         if was_training:
@@ -76,7 +86,7 @@ class Summarizer:
         try:
             with torch.no_grad():
                 scores = self.model.score_packed(packed, lens).detach().reshape(-1)
-                n_cps, cps = kts.segment_packed(packed, lens, banded=self.kts == "banded", **self.kts_options)
+                n_cps, cps = kts.segment_packed(packed, lens, banded=self.kts == "banded", max_workspace_bytes=self._max_ws(), **self.kts_options)
         finally:
             if was_training:
                 self.model.train()
@@ -97,8 +107,7 @@ class Summarizer:
         """device=True, before anything is enqueued: the videos against the limits of the device tail (ascending picks within the video,
         at most 4096 of them) and of sumk_eval_device_select at the padded segment count.  Returns (n_frames per video, picks per video
         as contiguous int32 arrays or None for the identity)."""
-        max_ncp = self.kts_options.get("max_ncp")
-        P = min(kts.default_max_ncp(max(lens)) if max_ncp is None else int(max_ncp), max(lens) - 1) + 1
+        P = self._padded_segments(lens)
         nf = [int(T) if f is None else int(f) for T, f in zip(lens, n_frames)]
         out = []
         for v, (T, pk) in enumerate(zip(lens, picks)):
@@ -107,13 +116,46 @@ class Summarizer:
             why = eval_native.select_refusal(P, nf[v], 0, self.proportion)
             if why is not None:
                 raise SumkError(f"Summarizer(device=True): video {v} has {why}: past the limits of sumk_eval_device_select")
-            if pk is not None:
-                pk = np.ascontiguousarray(np.asarray(pk), dtype=np.int32).reshape(-1)
-                if pk.shape[0] != T:
-                    raise ValueError(f"Summarizer: video {v} has {T} steps but {pk.shape[0]} picks")
-                if np.any(np.diff(pk) < 0) or (T and (pk[0] < 0 or pk[-1] > nf[v])):
-                    raise SumkError(f"Summarizer(device=True): video {v}: picks must ascend within 0 .. n_frames (the device tail's limit)")
-            out.append(pk)
+            out.append(self._checked_picks(v, T, pk, nf[v]))
+        return nf, out
+
+    @staticmethod
+    def _checked_picks(v, T, pk, n_frames):
+        """The picks of video v as a contiguous int32 array (None: the identity), ascending within 0 .. n_frames as both device tails need."""
+        if pk is not None:
+            pk = np.ascontiguousarray(np.asarray(pk), dtype=np.int32).reshape(-1)
+            if pk.shape[0] != T:
+                raise ValueError(f"Summarizer: video {v} has {T} steps but {pk.shape[0]} picks")
+            if np.any(np.diff(pk) < 0) or (T and (pk[0] < 0 or pk[-1] > n_frames)):
+                raise SumkError(f"Summarizer(device=True): video {v}: picks must ascend within 0 .. n_frames (the device tail's limit)")
+        return pk
+
+    def _max_ws(self):
+        return kts.DEFAULT_MAX_WORKSPACE_BYTES if self.max_workspace_bytes is None else int(self.max_workspace_bytes)
+
+    def _padded_segments(self, lens):
+        max_ncp = self.kts_options.get("max_ncp")
+        return min(kts.default_max_ncp(max(lens)) if max_ncp is None else int(max_ncp), max(lens) - 1) + 1
+
+    def _check_long_limits(self, lens, picks, n_frames):
+        """device=True, tail="long", before anything is enqueued: the videos against the limits of sumk_eval_device_segments_long (ascending
+        picks within the video, at most 1 048 576 of them, at most 2^24 frames) and of sumk_eval_device_select_long at the padded segment
+        count, and that call's workspace against max_workspace_bytes.  Returns what _check_device_limits returns."""
+        P = self._padded_segments(lens)
+        nf = [int(T) if f is None else int(f) for T, f in zip(lens, n_frames)]
+        out = []
+        for v, (T, pk) in enumerate(zip(lens, picks)):
+            if T > eval_native.SEGMENTS_LONG_MAX_PICKS:
+                raise SumkError(f'Summarizer(tail="long"): video {v} has {T} picks, the long device tail takes {eval_native.SEGMENTS_LONG_MAX_PICKS}')
+            why = eval_native.select_long_refusal(P, nf[v], 0, self.proportion)
+            if why is not None:
+                raise SumkError(f'Summarizer(tail="long"): video {v} has {why}: past the limits of sumk_eval_device_select_long')
+            out.append(self._checked_picks(v, T, pk, nf[v]))
+        cap = max(eval_native.select_capacity(f, self.proportion) for f in nf)
+        need = eval_native.select_long_workspace_bytes(len(lens), P, cap)
+        if need > self._max_ws():
+            raise SumkError(f'Summarizer(tail="long"): {len(lens)} videos of {P} padded segments with a budget of {cap} frames need a workspace of {need} '
+                            f"bytes, over max_workspace_bytes={self._max_ws()}: use a smaller max_ncp (the workspace grows as segments x budget / 8)")
         return nf, out
 
     def _finish_on_device(self, scores, n_cps, cps, lens, picks, nf, dev):
@@ -148,13 +190,18 @@ class Summarizer:
         selected = torch.empty(n * P, dtype=torch.uint8, device=dev)
         f = torch.empty(2 * n, dtype=torch.float64, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
-        ws = kernels.workspace(lib.sumk_eval_device_select_workspace_bytes(n, P, max(q.capacity for q in sd)), dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.sumk_eval_device_segments(scores.data_ptr(), vd_dev.data_ptr(), n, scratch.data_ptr(), seg.data_ptr(), st),
-                   "sumk_eval_device_segments")
-        _lib.check(lib.sumk_eval_device_select(sd_dev.data_ptr(), C.cast(sd, C.c_void_p), n, summary.data_ptr(), frame0, selected.data_ptr(), n * P,
-                                               f.data_ptr(), f.data_ptr() + 8 * n, status.data_ptr(), ws.data_ptr(), ws.numel(), st),
-                   "sumk_eval_device_select")
+        if self.tail == "long":
+            ws = kernels.workspace(kernels.eval_select_long_workspace_bytes(n, P, max(q.capacity for q in sd)), dev)
+            kernels.eval_segments_long(scores, vd_dev, vd, scratch, seg)
+            kernels.eval_select_long(sd_dev, sd, summary, selected, f[:n], f[n:], status, ws)
+        else:
+            ws = kernels.workspace(lib.sumk_eval_device_select_workspace_bytes(n, P, max(q.capacity for q in sd)), dev)
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.sumk_eval_device_segments(scores.data_ptr(), vd_dev.data_ptr(), n, scratch.data_ptr(), seg.data_ptr(), st),
+                       "sumk_eval_device_segments")
+            _lib.check(lib.sumk_eval_device_select(sd_dev.data_ptr(), C.cast(sd, C.c_void_p), n, summary.data_ptr(), frame0, selected.data_ptr(), n * P,
+                                                   f.data_ptr(), f.data_ptr() + 8 * n, status.data_ptr(), ws.data_ptr(), ws.numel(), st),
+                       "sumk_eval_device_select")
         out, at = [], 0
         for v, T in enumerate(lens):
             r0 = int(sb.off_host[v])

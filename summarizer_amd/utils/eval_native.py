@@ -19,6 +19,10 @@ KENDALL_MAX_FRAMES = 16384      # KD_MAX_FRAMES of csrc/evaldev_common.h: frames
 SELECT_MAX_SEGS, SELECT_MAX_CAPACITY, SELECT_MAX_USERS, SELECT_MAX_FRAMES = 1024, 8191, 32, 1 << 24
 SELECT_LDS_CAPACITY = 4095      # the knapsack's profit rows stay in LDS up to this budget and move to the workspace above it
 SELECTS = ("host", "device")
+# limits of the long-video tail (include/sumk.h SUMK_SEGMENTS_LONG_* / SUMK_SELECT_LONG_*; csrc/evallong.hip): picks and frames per video of
+# sumk_eval_device_segments_long; frame budget, capacities per DP block and frame chunks per video of sumk_eval_device_select_long
+SEGMENTS_LONG_MAX_PICKS, SEGMENTS_LONG_MAX_FRAMES = 1 << 20, 1 << 24
+SELECT_LONG_MAX_CAPACITY, SELECT_LONG_CHUNK, SELECT_LONG_FRAME_CHUNKS = 1 << 24, 2048, 64
 
 
 def _check_metric(metric):
@@ -134,6 +138,33 @@ def select_refusal(n_segs, n_frames, n_users, proportion):
     if not 1 <= n_frames <= SELECT_MAX_FRAMES:
         return f"{n_frames} frames (1 .. {SELECT_MAX_FRAMES})"
     return None
+
+
+def select_long_refusal(n_segs, n_frames, n_users, proportion):
+    """select_refusal for sumk_eval_device_select_long: the same limits but for the frame budget, which may reach SELECT_LONG_MAX_CAPACITY."""
+    cap = select_capacity(n_frames, proportion)
+    if not 1 <= n_segs <= SELECT_MAX_SEGS:
+        return f"{n_segs} segments (1 .. {SELECT_MAX_SEGS})"
+    if not 0 <= cap <= SELECT_LONG_MAX_CAPACITY:
+        return f"a budget of {cap} frames = floor({n_frames} x {proportion}) (0 .. {SELECT_LONG_MAX_CAPACITY})"
+    if not 0 <= n_users <= SELECT_MAX_USERS:
+        return f"{n_users} annotators (at most {SELECT_MAX_USERS})"
+    if not 1 <= n_frames <= SELECT_MAX_FRAMES:
+        return f"{n_frames} frames (1 .. {SELECT_MAX_FRAMES})"
+    return None
+
+
+def select_long_workspace_bytes(n_videos, max_n_segs, max_capacity):
+    """The formula of sumk_eval_device_select_long_workspace_bytes (include/sumk.h), for a caller that wants the size before it loads the
+    library's answer: per video, each part rounded up to 256 bytes, the improvement bits, two int32 profit rows, the item tables and the
+    partial counts of the frame chunks.  The bits are what grows: n_segs x capacity / 8 bytes."""
+    def up(b):
+        return (b + 255) // 256 * 256
+    bits = up(max_n_segs * ((max_capacity + 1 + 63) // 64) * 8)
+    rows = up(2 * (max_capacity + 1) * 4)
+    items = up((5 * max_n_segs + 9) * 4)
+    counts = up(SELECT_LONG_FRAME_CHUNKS * (2 * SELECT_MAX_USERS + 1) * 4)
+    return n_videos * (bits + rows + items + counts)
 
 
 def select_device_ready(v, proportion=0.15):
