@@ -716,6 +716,38 @@ int sumk_eval_device_select_long(const sumk_eval_dev_select* videos_dev, const s
                                  float* machine_summary_dev, int64_t summary_total, uint8_t* selected_dev, int64_t selected_total,
                                  double* f_avg_dev, double* f_max_dev, int32_t* status_dev, void* workspace, size_t workspace_bytes,
                                  void* stream);
+/* Rank correlation for long videos (csrc/evalcorr_long.hip): sumk_eval_device_spearman_long and sumk_eval_device_kendall_long take the
+ * place of sumk_eval_device_spearman / sumk_eval_device_kendall behind sumk_eval_device_segments_long, on the same descriptors
+ * (sumk_eval_dev_video, plus one sumk_eval_dev_kendall per video for Kendall) and with the same results: Kendall's tau, its mean and the
+ * counts {cmd, xtie, ytie, ntie} bit for bit (integers, then kendall_tau_b and numpy's summation order); Spearman to float64
+ * re-association (the ranks are the same values; the sum of squared rank deviations is taken over the groups, the cross terms over
+ * min(256, ceil(n_frames / 4096)) chunks of the video's frames, added in chunk order -- a video's result does not depend on the other
+ * videos of the call).  NaN where the block kernels give NaN: no annotators, Spearman without user_ranks, a constant side.
+ * Limits: 1 <= n_picks <= SUMK_SEGMENTS_LONG_MAX_PICKS, 1 <= n_frames <= SUMK_SEGMENTS_LONG_MAX_FRAMES, n_users <= 32, n_videos <= 65535;
+ * picks ascend.  Everything the host can see -- these limits in videos_host (the host copy of videos_dev), a null pointer, a short
+ * workspace -- returns SUMK_ERR_ARG and launches nothing.  A device descriptor that disagrees with the host copy and is past a limit, or
+ * past the call's largest n_picks / n_frames / n_users as the host copy has them, gets NaN (Kendall: and -1 in its counts); nothing is
+ * written out of bounds and the other videos are unaffected.
+ * How: the groups of a video (its pick intervals plus the frames no interval covers) are sorted by value with a chip-wide stable merge
+ * sort -- tiles of SUMK_CORR_LONG_TILE keys in LDS, then one launch per merge level over two buffers, every element placed by one binary
+ * search in the sibling run; prefix sums over the sorted groups give every rank and tie count as integers.  Kendall sorts the 64-bit
+ * frame keys (dense x rank << 24 | y_dense) of every (video, annotator) with the same sort, then their y parts with its inversion count
+ * on.  No cooperative launch, no flag polled across workgroups, no float atomics; the launches depend on videos_host only, so a call
+ * captures into a HIP graph.
+ * workspace: sumk_eval_device_{spearman,kendall}_long_workspace_bytes(videos_host, n_videos) bytes, 8-byte aligned, contents irrelevant;
+ * pure host arithmetic, 0 = bad arguments.  With G = sum(n_picks + 1), B = sum(ceil((n_picks + 1) / 1024)), U = sum(max(n_users, 0)),
+ * UF = sum(max(n_users, 0) x n_frames) and C = sum(min(256, ceil(n_frames / 4096))) over the videos, each part rounded up to 256 bytes:
+ *   both      72 n_videos (headers) + 8 G + 8 G (group keys, two buffers) + 4 G + 4 G (prefix sums) + 8 B (scan blocks)
+ *   Spearman  + 8 G (ranks) + 8 x 33 C (partial sums)
+ *   Kendall   + 4 G (dense x ranks) + 8 UF + 8 UF (frame keys, two buffers: 16 bytes per annotator and frame) + 8 (2 U + n_videos) (counters) */
+#define SUMK_CORR_LONG_TILE 2048   /* keys one workgroup sorts in LDS before the global merge levels; exported so tests can sit on its edges */
+size_t sumk_eval_device_spearman_long_workspace_bytes(const sumk_eval_dev_video* videos_host, int32_t n_videos);
+int sumk_eval_device_spearman_long(const float* scores_dev, const sumk_eval_dev_video* videos_dev, const sumk_eval_dev_video* videos_host,
+                                   int32_t n_videos, void* workspace, size_t workspace_bytes, double* corr_dev, void* stream);
+size_t sumk_eval_device_kendall_long_workspace_bytes(const sumk_eval_dev_video* videos_host, int32_t n_videos);
+int sumk_eval_device_kendall_long(const float* scores_dev, const sumk_eval_dev_video* videos_dev, const sumk_eval_dev_video* videos_host,
+                                  const sumk_eval_dev_kendall* kendall_dev, int32_t n_videos, void* workspace, size_t workspace_bytes,
+                                  double* corr_dev, int64_t* counts_dev, void* stream);
 /* DEVICE: (n_cps, cps) of sumk_kts -> the change points the evaluation tail reads, at a fixed pitch of max_ncp + 1 segments per video, so
  * that n_segs stays a host-known bound: change_points (n_seq, max_ncp + 1, 2) and nfps (n_seq, max_ncp + 1) int32.  Segment s <= n_cps[v]
  * is [0 | frame(cps[s - 1]), frame(cps[s]) - 1 | n_frames[v] - 1] with frame(c) = picks_dev[v][c] (picks_dev, or an entry of it, NULL: c

@@ -251,6 +251,11 @@ _SIGS = {
     "sumk_eval_device_select_long_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "sumk_eval_device_select_long": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_f32p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_eval_device_spearman_long_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32]),
+    "sumk_eval_device_spearman_long": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "sumk_eval_device_kendall_long_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32]),
+    "sumk_eval_device_kendall_long": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
     "sumk_kts_segments": (C.c_int, [c_i32p, c_i32p, C.c_int32, C.c_int32, c_i32p, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_void_p]),
     "sumk_annotate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p,
                                 C.c_int64, c_f32p, C.c_int64, C.c_void_p]),

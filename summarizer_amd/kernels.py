@@ -783,6 +783,33 @@ def eval_select_long(descr_dev, descr_host, summary, selected, f_avg, f_max, sta
                "sumk_eval_device_select_long")
 
 
+def eval_spearman_long_workspace_bytes(descr_host):
+    """Workspace of eval_spearman_long for these videos (a ctypes array of _lib.EvalDevVideo); pure host arithmetic."""
+    return _nonzero(_lib.load().sumk_eval_device_spearman_long_workspace_bytes(C.cast(descr_host, C.c_void_p), len(descr_host)),
+                    "sumk_eval_device_spearman_long_workspace_bytes")
+
+
+def eval_spearman_long(scores, descr_dev, descr_host, ws, corr):
+    """Mean Spearman correlation per video for any number of picks and frames the long tail accepts (sumk_eval_device_spearman_long,
+    include/sumk.h), into corr (n_videos,) float64.  ws: eval_spearman_long_workspace_bytes(descr_host) bytes.  Only enqueues work."""
+    _lib.check(_lib.load().sumk_eval_device_spearman_long(_p(scores), _p(descr_dev), C.cast(descr_host, C.c_void_p), len(descr_host), _p(ws), ws.numel(),
+                                                          _p(corr), _stream()), "sumk_eval_device_spearman_long")
+
+
+def eval_kendall_long_workspace_bytes(descr_host):
+    """Workspace of eval_kendall_long for these videos (a ctypes array of _lib.EvalDevVideo); pure host arithmetic."""
+    return _nonzero(_lib.load().sumk_eval_device_kendall_long_workspace_bytes(C.cast(descr_host, C.c_void_p), len(descr_host)),
+                    "sumk_eval_device_kendall_long_workspace_bytes")
+
+
+def eval_kendall_long(scores, descr_dev, descr_host, kendall_dev, ws, corr, counts=None):
+    """Mean Kendall tau-b per video, and (counts given: (sum n_users, 4) int64) the pair counts {cmd, xtie, ytie, ntie}, for any number of
+    picks and frames the long tail accepts (sumk_eval_device_kendall_long, include/sumk.h).  kendall_dev: the bytes of a ctypes array of
+    _lib.EvalDevKendall as a device tensor; ws: eval_kendall_long_workspace_bytes(descr_host) bytes.  Only enqueues work."""
+    _lib.check(_lib.load().sumk_eval_device_kendall_long(_p(scores), _p(descr_dev), C.cast(descr_host, C.c_void_p), _p(kendall_dev), len(descr_host),
+                                                         _p(ws), ws.numel(), _p(corr), _p(counts), _stream()), "sumk_eval_device_kendall_long")
+
+
 def dsn_policy_loss_forward(probs, sb, actions, rewards, base, beta, eps_target):
     """(loss_per_video (n_seq,), mean_probs (n_seq,)) of sumk_dsn_policy_loss_forward (include/sumk.h)."""
     lib = _lib.load()

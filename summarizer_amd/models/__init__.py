@@ -229,6 +229,11 @@ class Trainer:
             return None
         metas = [self._native_meta(k) for k in keys]
         metric = self._correlation_metric()
+        tail = getattr(self.hps, "eval_tail", "block")
+        if tail not in eval_native.TAILS:
+            raise KeyError(f"Unknown tail {tail}")
+        if tail == "long":
+            return self._test_on_device_long(keys, metas, metric, dev, max_frames_per_launch)
         if not all((eval_native.kendall_device_ready if metric == "kendalltau" else eval_native.device_ready)(m) for m in metas):
             return None
         # the fold's test set packed once and kept in HBM (a second copy of its features: 49 MB for 50 TVSum videos of 288 GB): every later
@@ -258,6 +263,38 @@ class Trainer:
             # result there, as it does without the opt-in
             corr, f_avg, f_max, _ = eval_native.evaluate_batch_device(*args, metric=metric, select="host")
         kernels.health_check()      # the D2H inside synchronised: fail loudly if a persistent recurrence kernel timed out
+        return corr, f_avg, f_max
+
+    def _test_on_device_long(self, keys, metas, metric, dev, max_frames_per_launch):
+        """_test_on_device with hps.eval_tail = "long": videos past the one-workgroup limits of the block tail stay on the device
+        (utils/eval_native.py, tail="long").  The fold is scored in groups of at most max_frames_per_launch steps, as _score_keys groups
+        them, and the scores are concatenated on the device.  None when a video is past the long tail's limits or the workspace budget:
+        the host tail then takes over."""
+        if not all(eval_native.device_ready_long(m) for m in metas):
+            return None
+        feats = [self._video_on_device(k, dev)[0] for k in keys]
+        lens = [f.shape[0] for f in feats]
+        groups, cur, frames = [], [], 0
+        for i, T in enumerate(lens):
+            if cur and frames + T > max_frames_per_launch:
+                groups.append(cur); cur, frames = [], 0
+            cur.append(i); frames += T
+        groups.append(cur)
+        pieces = []
+        for grp in groups:
+            packed = feats[grp[0]] if len(grp) == 1 else torch.cat([feats[i] for i in grp])
+            pieces.append(self.model.score_packed(packed, [lens[i] for i in grp]).detach().reshape(-1))
+        scores = (pieces[0] if len(pieces) == 1 else torch.cat(pieces)).contiguous()
+        on_device = getattr(self.hps, "selection_device", False) and all(eval_native.select_long_device_ready(m, self.hps.summary_proportion) for m in metas)
+        args = (metas, scores, lens, self.hps.summary_proportion, self.hps.selection_algorithm)
+        try:
+            try:
+                corr, f_avg, f_max, _ = eval_native.evaluate_batch_device(*args, metric=metric, select="device" if on_device else "host", tail="long")
+            except eval_native.SelectStatusError:
+                corr, f_avg, f_max, _ = eval_native.evaluate_batch_device(*args, metric=metric, select="host", tail="long")
+        except kernels.SumkError:
+            return None          # a limit or the workspace budget: the host tail computes the same numbers
+        kernels.health_check()
         return corr, f_avg, f_max
 
     def _correlation_metric(self):
