@@ -104,6 +104,39 @@ size_t sumk_vasnet_workspace_bytes(int32_t D, int32_t n_seq, const int32_t* seq_
  * (SUMK_ERR_WORKSPACE), so a forward and a backward pass cannot end up on different paths. */
 size_t sumk_vasnet_workspace_bytes_for(int32_t D, int32_t n_seq, const int32_t* seq_off_host, int32_t training, int32_t precision);
 
+/* ------------------------------------------------------------------------------------------------ local attention on the band (long videos)
+ * VASNet's `local` option (sumk_vasnet_opts::aperture = w >= 0, vasnet.py:124-127) for videos the dense path cannot hold: there the logits
+ * are a full (T x T) block per video with the mask applied afterwards, so workspace and FLOPs grow with T^2 whatever w is
+ * (csrc/attn_band.hip).  Here, per video of a packed batch, ctx = softmax(mask(Q K^T * scale)) V over the keys [i - w, i + w] of every
+ * query row i only.  The definition -- scale, ignore_self, the tril * triu == 0 rule that also masks in-band logits whose square is 0, NaN
+ * for a row with every key masked -- is that of the dense path.  What differs:
+ *   storage  a video is cut into strips of 64 query rows; strip r keeps a rectangle of 64 x (k_hi - k_lo) fp32 logits for the keys
+ *            k_lo = max(0, 64 r - w) .. k_hi = min(T, 64 r + 64 + w), pitch = min(T, 2 w + 64) rounded up to 4, all strips of all videos
+ *            back to back, every offset 64-bit: the workspace is O(T w), nothing of size T x T exists;
+ *   launches one setup launch, then three: the logits of every strip (ONE grouped exact-fp32 NT launch, a problem per strip, the kernel and
+ *            k order of the dense path's per-video launch), the band softmax in place (one wave per row), the context of every strip
+ *            (ONE grouped NN launch contracting over exactly the strip's k_hi - k_lo keys: V rows of the next video, or scratch behind
+ *            the last one, are never multiplied -- 0 x NaN would be NaN).  No atomics, no cooperative launch, no flag polled across
+ *            workgroups; bit-deterministic; only enqueues work (captures into a HIP graph).
+ * sumk_attn_band: Q, K, V (rows x D, leading dimensions ldq / ldk / ldv) -> ctx (rows x D, ldc).  alpha: NULL, or (rows x (2 w + 1)) floats
+ * that receive the attention weights, entry c of row i = key i - w + c, zeros for keys outside the video (a test entry; w <= 1048576).
+ * sumk_vasnet_forward_band: inference of vasnet.py:114-145 with steps 118-131 on the band -- QKV projection, the launches above, output
+ * projection + residual, LayerNorm, k1 + ReLU, LayerNorm + k2 + sigmoid.  x is NOT modified (a caller with positions adds them beforehand);
+ * opts->tables / x16 / xplanes / wplanes are ignored.
+ * Limits: aperture >= 0 (any value: the key range is clipped to the video), D % 4 == 0, 1 <= T <= 1048576 per video, at most 65535
+ * videos, leading dimensions >= D and % 4 == 0; the forward also needs opts->precision == SUMK_PRECISION_FP32 and dropout_p == 0.
+ * Anything else returns SUMK_ERR_ARG (a short workspace: SUMK_ERR_WORKSPACE), sets sumk_last_error and launches nothing.
+ * The *_workspace_bytes functions are pure host arithmetic (0 = bad arguments): about 4 T (2 w + 64) bytes per video for the band, plus
+ * 20 T D bytes of activations for the forward. */
+size_t sumk_attn_band_workspace_bytes(int32_t D, int32_t n_seq, const int32_t* seq_off_host, int32_t aperture);
+int sumk_attn_band(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, int32_t D, int32_t n_seq,
+                   const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale, int32_t ignore_self, int32_t aperture, float* ctx,
+                   int32_t ldc, float* alpha, void* workspace, size_t workspace_bytes, void* stream);
+size_t sumk_vasnet_band_workspace_bytes(int32_t D, int32_t n_seq, const int32_t* seq_off_host, int32_t aperture);
+int sumk_vasnet_forward_band(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                             const sumk_vasnet_weights* w, const sumk_vasnet_opts* opts, float* scores, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* Weight-plane block of sumk_vasnet_opts::wplanes: bytes (0 = D or n_planes not eligible: D % 256, n_planes 2 or 3), and the build --
  * planes of [Wq; Wk; Wv] (Wvo != NULL: [Wq; Wk; Wvo], the folded path of sumk_vasnet_forward_folded), of Wo, of k1's weight with the
  * LayerNorm gain folded in (W1 diag(ln_w)), and the three per-column vectors of the fused tail.  256-byte aligned device buffer; redo
@@ -879,6 +912,7 @@ int sumk_pack_rows_bf16(uint16_t* dst_bf16, const float* const* srcs, const int3
 #define SUMK_PROF_GEMM_PV 4      /* per-video alpha.V launches                                          */
 #define SUMK_PROF_GEMM_OPROJ 5   /* output projection (+ residual)                                      */
 #define SUMK_PROF_GEMM_K1 6      /* k1 (+ bias, ReLU)                                                   */
+#define SUMK_PROF_BAND_SOFTMAX 7 /* band softmax launch of sumk_attn_band (its two products: QKT and PV above) */
 #define SUMK_PROF_NTAGS 8
 /* The small-batch GEMM form by itself (tests, probes): C = epilogue(A . B) for ONE exact-fp32 problem on 64x64 tiles whose K is cut
  * into `slices` (1 .. 8) slices INSIDE the launch -- every (tile, slice) block stores a partial tile, the last one to arrive adds

@@ -1,0 +1,109 @@
+"""VASNet local attention on the band (sumk_vasnet_forward_band, csrc/attn_band.hip) beside the dense masked path on one long video.
+
+One video at D = 1024, exact fp32, `score_packed` of VASNet(attention_aperture=w) with local_attention="band" and with "dense":
+  * T = 4096 and 16384 at w = 64 and 256: both paths, their ratio, and the largest score difference between them;
+  * T = 65536 at w = 64 and 256: the band alone.  The dense run is skipped there -- its workspace query answers more than DENSE_MAX_WS
+    (the (T x T) logits alone are 16 GiB) -- and the record says so with the bytes it asked for;
+  * per run the three band launches separately (logits, softmax, context: event pairs of the library's profiler around each launch).
+The expectation nobody has measured before is the FLOP ratio of the two per-video products, T / (2 w + 64); it is recorded beside each measured
+ratio.  No time is gated.  Per run: the median over 5 calls of one call's stream time (HIP events around the call, 2 warm-up calls first).
+Every GPU step is a fresh child of this script under its own time limit; after a step that fails or runs out of time nothing more is started.
+    python scripts/attn_band_timing.py [OUT.json]      (writes profiles/attn_band_timing.json by default)"""
+import json, os, subprocess, sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+D = 1024
+STEP_LIMIT_S = 240
+DENSE_MAX_WS = 8 * 2 ** 30
+RUNS = [(4096, 64), (4096, 256), (16384, 64), (16384, 256), (65536, 64), (65536, 256)]
+TAGS = {"logits_ms": 3, "context_ms": 4, "softmax_ms": 7}      # SUMK_PROF_GEMM_QKT / _PV / _BAND_SOFTMAX (include/sumk.h)
+
+
+def worker(spec):
+    import ctypes as C
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    from summarizer_amd import _lib, kernels
+    from summarizer_amd.models.vasnet import VASNet
+    dev = torch.device("cuda:0")
+    T, w, reps, warm = spec["T"], spec["w"], spec["reps"], spec["warmup"]
+    lib = _lib.load()
+    torch.manual_seed(1)
+    band = VASNet(input_size=D, attention_aperture=w, local_attention="band").eval()
+    dense = VASNet(input_size=D, attention_aperture=w).eval()
+    dense.load_state_dict(band.state_dict())
+    band, dense = band.to(dev), dense.to(dev)
+    x = (0.5 * torch.randn(T, D, generator=torch.Generator().manual_seed(T + w)).abs()).to(dev)      # pool5-like non-negative features
+    sb = kernels.SeqBatch.get([T], dev)
+    out = {"T": T, "w": w, "reps": reps, "warmup": warm, "flop_ratio_T_over_2w_plus_64": T / (2 * w + 64),
+           "band_workspace_bytes": int(kernels.vasnet_band_workspace_bytes(D, sb, w)),
+           "dense_workspace_bytes": int(lib.sumk_vasnet_workspace_bytes(D, 1, sb.off_host_p, 0))}
+
+    def timed(fn):
+        with torch.no_grad():
+            for _ in range(warm):
+                fn()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(reps):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(); res = fn(); b.record()
+                b.synchronize()
+                ts.append(a.elapsed_time(b))
+        return float(np.median(ts)), [round(t, 3) for t in ts], res
+
+    out["band_ms"], out["band_ms_all"], sband = timed(lambda: band.score_packed(x, [T]))
+    assert bool(torch.isfinite(sband).all())
+    # the three launches, on calls of their own (the event pairs serialise nothing, but they are not part of the timed calls above)
+    lib.sumk_prof_enable(sum(1 << t for t in TAGS.values()))
+    for t in TAGS.values():
+        lib.sumk_prof_read(t, None, None, 1)
+    with torch.no_grad():
+        for _ in range(reps):
+            band.score_packed(x, [T])
+    torch.cuda.synchronize()
+    for name, t in TAGS.items():
+        ms, n = C.c_double(0.0), C.c_int64(0)
+        lib.sumk_prof_read(t, C.byref(ms), C.byref(n), 1)
+        out[name] = ms.value / max(n.value, 1)
+    lib.sumk_prof_enable(0)
+    if out["dense_workspace_bytes"] == 0 or out["dense_workspace_bytes"] > DENSE_MAX_WS:
+        out["dense_skipped"] = (f"the dense path asks for {out['dense_workspace_bytes']} bytes of workspace (the (T x T) logits alone are {4 * T * T}), "
+                                f"past this script's cap of {DENSE_MAX_WS}: not run, not estimated")
+    else:
+        out["dense_ms"], out["dense_ms_all"], sdense = timed(lambda: dense.score_packed(x, [T]))
+        out["dense_over_band"] = out["dense_ms"] / out["band_ms"]
+        out["max_abs_score_difference"] = float((sband - sdense).abs().max())
+    print("RESULT " + json.dumps(out))
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    out_path = args[0] if args else os.path.join(ROOT, "profiles", "attn_band_timing.json")
+    res = {"box": "1x MI355X", "D": D, "precision": "fp32", "runs": {}}
+    for T, w in RUNS:
+        spec = {"T": T, "w": w, "reps": 5, "warmup": 2}
+        try:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", json.dumps(spec)], capture_output=True, text=True,
+                               timeout=STEP_LIMIT_S, cwd=ROOT)
+        except subprocess.TimeoutExpired:
+            res["stopped"] = f"T={T} w={w}: no result within {STEP_LIMIT_S} s; nothing more was started"
+            break
+        line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
+        if r.returncode != 0 or not line:
+            res["stopped"] = f"T={T} w={w}: exit code {r.returncode}; nothing more was started: {r.stderr[-600:]}"
+            break
+        res["runs"][f"T{T}_w{w}"] = json.loads(line[-1][7:])
+        print(f"T={T} w={w}: " + line[-1][7:], flush=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", out_path)
+    return 1 if "stopped" in res else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 2 and sys.argv[1] == "--worker":
+        worker(json.loads(sys.argv[2]))
+    else:
+        sys.exit(main())

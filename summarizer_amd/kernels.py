@@ -404,6 +404,63 @@ def vasnet_forward_packed(x, sb, params, opts, pos_table=None, pos_rows=None, tr
     return scores, (ws if training else None)
 
 
+# ------------------------------------------------------------------------------------------------ local attention on the band
+ATTN_BAND_MAX_STEPS = 1048576      # per video: sumk_attn_band / sumk_vasnet_forward_band (include/sumk.h)
+
+
+def _band_aperture(aperture, what):
+    if not isinstance(aperture, (int, np.integer)) or isinstance(aperture, bool) or aperture < 0:
+        raise SumkError(f"{what}: the band needs an int aperture >= 0, got {aperture!r}")
+    return int(min(aperture, 2 ** 31 - 1))
+
+
+def attn_band_workspace_bytes(D, sb, aperture):
+    """Bytes sumk_attn_band needs for this batch: pure host arithmetic, 0 for arguments it would refuse."""
+    return _lib.load().sumk_attn_band_workspace_bytes(int(D), sb.n_seq, sb.off_host_p, int(aperture))
+
+
+def vasnet_band_workspace_bytes(D, sb, aperture):
+    """Bytes sumk_vasnet_forward_band needs for this batch: pure host arithmetic, 0 for arguments it would refuse."""
+    return _lib.load().sumk_vasnet_band_workspace_bytes(int(D), sb.n_seq, sb.off_host_p, int(aperture))
+
+
+def attn_band(q, k, v, sb, aperture, scale, ignore_self=False, want_alpha=False):
+    """Per video of the packed batch, ctx = softmax(mask(q k^T * scale)) v over the keys [i - aperture, i + aperture] of every query row i
+    (sumk_attn_band, include/sumk.h): O(T aperture) workspace and work.  q, k, v: (n_rows, D) views with unit column stride (e.g. column
+    blocks of one (n_rows, 3 D) projection).  Returns (ctx (n_rows, D), alpha (n_rows, 2 aperture + 1) or None); alpha[i, c] is the weight
+    of key i - aperture + c, zero outside the video.  Only enqueues work on the current stream."""
+    lib = _lib.load()
+    w = _band_aperture(aperture, "attn_band")
+    D = q.shape[1] if q.dim() == 2 else -1
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _require_gpu(t, f"attn_band {name}")
+        if t.dim() != 2 or t.shape != (sb.n_rows, D) or t.stride(1) != 1:
+            raise SumkError(f"attn_band: {name} must be ({sb.n_rows}, D) with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
+    nb = _nonzero(lib.sumk_attn_band_workspace_bytes(D, sb.n_seq, sb.off_host_p, w), "sumk_attn_band_workspace_bytes")
+    ws = workspace(nb, q.device)
+    ctx = torch.empty(sb.n_rows, D, dtype=torch.float32, device=q.device)
+    alpha = torch.empty(sb.n_rows, 2 * w + 1, dtype=torch.float32, device=q.device) if want_alpha else None
+    _lib.check(lib.sumk_attn_band(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, sb.n_seq, sb.off_host_p, sb.off_dev_p,
+                                  float(scale), int(bool(ignore_self)), w, _p(ctx), D, _p(alpha), _p(ws), ws.numel(), _stream()), "sumk_attn_band")
+    return ctx, alpha
+
+
+def vasnet_forward_band(x, sb, params, opts):
+    """VASNet inference with the attention on the band (sumk_vasnet_forward_band): x (n_rows, D) packed -> scores (n_rows,).  opts as for
+    vasnet_forward_packed; needs an int aperture >= 0, exact fp32 and no dropout.  x is not modified.  Only enqueues work."""
+    lib = _lib.load()
+    _check_rows(x, sb, "vasnet input")
+    D = x.shape[1]
+    w = _band_aperture(opts.get("aperture"), "vasnet_forward_band")
+    wts, o = _vasnet_structs(params, dict({k: v for k, v in opts.items() if k not in ("tables", "x16", "xplanes", "wplanes")}, aperture=w))
+    nb = _nonzero(lib.sumk_vasnet_band_workspace_bytes(D, sb.n_seq, sb.off_host_p, w), "sumk_vasnet_band_workspace_bytes")
+    ws = workspace(nb, x.device)
+    scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
+    _lib.check(lib.sumk_vasnet_forward_band(_p(x), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, C.byref(wts), C.byref(o), _p(scores), _p(ws),
+                                            ws.numel(), _stream()), "sumk_vasnet_forward_band")
+    return scores
+
+
 # ------------------------------------------------------------------------------------------------ BiLSTM scorers
 # SUMK_CHECK=1 (set by the test-suite): synchronise after every recurrent layer and verify that the persistent kernel's
 # bounded waits did not time out.  Off by default (it costs a host sync per layer).

@@ -25,8 +25,25 @@ from ..training import FlatAdam, dist_info, plan_shards, resolve_batch_videos, s
 
 class VASNet(PositionalInput, nn.Module):
     def __init__(self, input_size=1024, max_length=None, pos_embed="simple", ignore_self=False,
-                 attention_aperture=None, scale=None, epsilon=1e-6, weight_init="xavier", precision="fp32", fold_vo=False):
+                 attention_aperture=None, scale=None, epsilon=1e-6, weight_init="xavier", precision="fp32", fold_vo=False,
+                 local_attention="dense"):
         super().__init__()
+        # local_attention (not in the reference, opt-in): where the `attention_aperture` mask is computed when SCORING (no-grad calls).
+        #   "dense"  the full (T x T) logits of every video with the mask applied afterwards: workspace and FLOPs grow with T^2 whatever
+        #            the aperture is (today's path, every precision);
+        #   "band"   only the keys [i - w, i + w] of every query row (kernels.vasnet_forward_band, csrc/attn_band.hip): O(T w), videos up
+        #            to 1 048 576 steps -- the scorer in front of Summarizer(kts="banded", tail="long").  Needs an int
+        #            attention_aperture >= 0, precision "fp32" and fold_vo=False.  It adds no parameter (same state_dict).
+        # TRAINING on the band is out of scope: a call that records a graph (the autograd branch of _score) stays on the dense masked path.
+        if local_attention not in ("dense", "band"):
+            raise kernels.SumkError(f"VASNet: local_attention must be 'dense' or 'band', got {local_attention!r}")
+        if local_attention == "band":
+            if not isinstance(attention_aperture, (int, np.integer)) or isinstance(attention_aperture, bool) or attention_aperture < 0:
+                raise kernels.SumkError(f"VASNet(local_attention='band') needs an int attention_aperture >= 0, got {attention_aperture!r}")
+            if precision != "fp32" or fold_vo:
+                raise kernels.SumkError(f"VASNet(local_attention='band') runs in exact fp32 without fold_vo, got precision={precision!r} fold_vo={fold_vo!r}")
+            attention_aperture = int(attention_aperture)
+        self.local_attention = local_attention
         self.precision = precision      # GEMM arithmetic: "fp32" (exact) | "bf16x6" | "bf16x3" | "bf16" (kernels.precision_code); not in the reference
         # fold_vo (not in the reference, opt-in): inference folds the value and output projections into ONE matrix Wvo = Wo.Wv
         # (recomputed whenever the weights may have changed), which removes the out-projection GEMM: 18 % fewer FLOPs per frame,
@@ -101,7 +118,9 @@ class VASNet(PositionalInput, nn.Module):
 
     def _score(self, xp, sb, table, rows, extra=None):
         """extra: entries for the call's options that the caller derived from xp itself (score_packed: the bf16 shadow / the planes that
-        came out of the positional add's launch)."""
+        came out of the positional add's launch).
+        local_attention="band": the no-grad branch scores through kernels.vasnet_forward_band; the autograd branch stays on the dense masked
+        path -- training on the band is out of scope."""
         training = self.training and torch.is_grad_enabled()
         if training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             from ..autograd import VasnetFunction
@@ -112,6 +131,10 @@ class VASNet(PositionalInput, nn.Module):
             return VasnetFunction.apply(xp, sb, opts, table, rows, names, *[p[n] for n in names])
         opts = self._opts(False)
         opts.update(extra or {})
+        if self.local_attention == "band":
+            if self.precision != "fp32" or self.fold_vo or table is not None:
+                raise kernels.SumkError("VASNet(local_attention='band') scores in exact fp32, without fold_vo, through score_packed")
+            return kernels.vasnet_forward_band(xp, sb, self._params(), opts)
         wvo = self._folded() if self.fold_vo else None
         if self.precision in kernels.PLANES_OF and table is None and self.input_size % 256 == 0 and sb.n_rows >= 256:
             opts["wplanes"] = self._wplanes(wvo)          # split-bf16 scoring on operand planes (csrc/gemm_pw.hip)
@@ -188,6 +211,7 @@ class VASNetTrainer(Trainer):
             weight_init=ep.get("weight_init", "xavier"),
             precision=ep.get("precision", "fp32"),
             fold_vo=bool(ep.get("fold_vo", False)),
+            local_attention=ep.get("local_attention", "dense"),
             **({"input_size": int(ep["input_size"])} if "input_size" in ep else {}))
         if self.hps.use_cuda:
             self.log.info(f"Setting CUDA device: {self.hps.cuda_device}")
