@@ -137,6 +137,50 @@ int sumk_vasnet_forward_band(const float* x, int32_t D, int32_t n_seq, const int
                              const sumk_vasnet_weights* w, const sumk_vasnet_opts* opts, float* scores, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ TRAINING on the band
+ * The attention above with what its backward needs kept, and that backward, in O(T w) per video (csrc/attn_band_bwd.hip).  A training
+ * workspace holds THREE rectangle buffers of the scoring layout: E (alpha), E2 (dropout(alpha) forward; dAlphaD, then dLogits, backward) and
+ * ET (transposed rectangles).  The band is symmetric -- key strip c is seen by exactly the query rows ab_k_lo(w, c) .. ab_k_hi(T, w, c), the
+ * count, pitch and offset of strip c's own rectangle -- so with a rectangle transposed into ET, dV = alphaD^T dCTX and dK = dLogits^T Q are the
+ * scoring path's context launch again: ONE grouped NN launch, a problem per key strip contracting over exactly its query rows.
+ * Backward launches, given dCTX: setup; transpose(alphaD); dV; dAlphaD = dCTX V^T (the logits launch); softmax backward in place
+ * (dLogits = scale * alpha * (drop'(dAlphaD) - sum_j drop'(dAlphaD)_j alpha_j)); dQ = dLogits K; transpose(dLogits); dK.  No atomics, no
+ * cooperative launch, no flag polled across workgroups; bit-deterministic; every call only enqueues work (captures into a HIP graph).
+ * Dropout of alpha (site 0) draws entry (packed row r, key j of the video) at index (r << 20) | j -- the dense path's index, so one seed
+ * gives a dense and a band model the same masks; the 20 key bits are exactly the limit of 1048576 steps.  seed_dev: NULL, or a device word
+ * the kernels add to `seed` when they run (sumk_vasnet_opts::seed_dev).
+ * NaN: an all-masked query row i has NaN weights; its dQ row is NaN and NaN reaches dK / dV only at the keys [i - w, i + w] (the dense path
+ * spreads it over the whole video).  A NaN video never reaches another video's gradients.
+ * sumk_attn_band_forward_train: as sumk_attn_band (no alpha output), leaving alpha / dropout(alpha) in the workspace.
+ * sumk_attn_band_backward: reads the workspace the forward left (same batch, aperture, dropout_p and seed) -> dQ, dK, dV (rows x D).
+ * sumk_vasnet_forward_band_train: vasnet.py:114-145 in training mode -- the three dropout sites, sites 1 and 2 (before either LayerNorm)
+ * indexed as the dense path -- keeping [Q | K | V], the context, both LayerNorm inputs, their statistics and the scores in the workspace.
+ * sumk_vasnet_backward_band: the stage order of sumk_vasnet_backward's large-batch path; weight gradients ACCUMULATE into `grads`;
+ * dx (NULL, or rows x D) = dY0 + dQ Wq + dK Wk + dV Wv; tail_grads_ready_event (NULL, or a hipEvent_t) is recorded once the gradients of
+ * Wo, W1, b1, w2, b2 are final.  x is NOT modified; opts->tables / x16 / xplanes / wplanes are ignored.
+ * Limits and status codes are those of the band forward; exact fp32 only; 0 <= dropout_p < 1; the VASNet pair also needs D <= 2048.
+ * A short workspace returns SUMK_ERR_WORKSPACE; nothing is launched on any error.  Workspace: about 12 T (2 w + 64) bytes per video for the
+ * band, plus 56 T D bytes of activations and gradients and 128 D^2 bytes of split-K slab for the VASNet pair. */
+size_t sumk_attn_band_train_workspace_bytes(int32_t D, int32_t n_seq, const int32_t* seq_off_host, int32_t aperture);
+int sumk_attn_band_forward_train(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, int32_t D,
+                                 int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale, int32_t ignore_self,
+                                 int32_t aperture, float dropout_p, uint64_t seed, const uint64_t* seed_dev, float* ctx, int32_t ldc,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+int sumk_attn_band_backward(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, const float* dctx,
+                            int32_t lddc, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale,
+                            int32_t ignore_self, int32_t aperture, float dropout_p, uint64_t seed, const uint64_t* seed_dev, float* dQ,
+                            int32_t lddq, float* dK, int32_t lddk, float* dV, int32_t lddv, void* workspace, size_t workspace_bytes,
+                            void* stream);
+size_t sumk_vasnet_band_train_workspace_bytes(int32_t D, int32_t n_seq, const int32_t* seq_off_host, int32_t aperture);
+int sumk_vasnet_forward_band_train(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                   const sumk_vasnet_weights* w, const sumk_vasnet_opts* opts, float* scores, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+struct sumk_vasnet_grads;
+int sumk_vasnet_backward_band(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                              const sumk_vasnet_weights* w, const sumk_vasnet_opts* opts, const float* dscores,
+                              const struct sumk_vasnet_grads* grads, float* dx, void* workspace, size_t workspace_bytes, void* stream,
+                              void* tail_grads_ready_event);
+
 /* Weight-plane block of sumk_vasnet_opts::wplanes: bytes (0 = D or n_planes not eligible: D % 256, n_planes 2 or 3), and the build --
  * planes of [Wq; Wk; Wv] (Wvo != NULL: [Wq; Wk; Wvo], the folded path of sumk_vasnet_forward_folded), of Wo, of k1's weight with the
  * LayerNorm gain folded in (W1 diag(ln_w)), and the three per-column vectors of the fused tail.  256-byte aligned device buffer; redo
@@ -913,7 +957,15 @@ int sumk_pack_rows_bf16(uint16_t* dst_bf16, const float* const* srcs, const int3
 #define SUMK_PROF_GEMM_OPROJ 5   /* output projection (+ residual)                                      */
 #define SUMK_PROF_GEMM_K1 6      /* k1 (+ bias, ReLU)                                                   */
 #define SUMK_PROF_BAND_SOFTMAX 7 /* band softmax launch of sumk_attn_band (its two products: QKT and PV above) */
-#define SUMK_PROF_NTAGS 8
+/* the seven launches of the attention backward on the band (sumk_attn_band_backward), in launch order */
+#define SUMK_PROF_BAND_BWD_TRANSPOSE_P 8   /* transpose(dropout(alpha))   */
+#define SUMK_PROF_BAND_BWD_DV 9            /* dV = alphaD^T dCTX          */
+#define SUMK_PROF_BAND_BWD_DP 10           /* dAlphaD = dCTX V^T          */
+#define SUMK_PROF_BAND_BWD_SOFTMAX 11      /* softmax backward            */
+#define SUMK_PROF_BAND_BWD_DQ 12           /* dQ = dLogits K              */
+#define SUMK_PROF_BAND_BWD_TRANSPOSE_S 13  /* transpose(dLogits)          */
+#define SUMK_PROF_BAND_BWD_DK 14           /* dK = dLogits^T Q            */
+#define SUMK_PROF_NTAGS 15
 /* The small-batch GEMM form by itself (tests, probes): C = epilogue(A . B) for ONE exact-fp32 problem on 64x64 tiles whose K is cut
  * into `slices` (1 .. 8) slices INSIDE the launch -- every (tile, slice) block stores a partial tile, the last one to arrive adds
  * them in slice order and runs the epilogue (csrc/gemm_lean.hip, SK instances; what sumk_vasnet_forward / _backward launch for batches

@@ -141,6 +141,18 @@ _SIGS = {
     "sumk_vasnet_band_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, HOST_I32P, C.c_int32]),
     "sumk_vasnet_forward_band": (C.c_int, [c_f32p, C.c_int32, C.c_int32, HOST_I32P, c_i32p, C.POINTER(VasnetWeights), C.POINTER(VasnetOpts),
                                            c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_attn_band_train_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, HOST_I32P, C.c_int32]),
+    "sumk_attn_band_forward_train": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
+                                               C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_void_p, c_f32p, C.c_int32, C.c_void_p,
+                                               C.c_size_t, C.c_void_p]),
+    "sumk_attn_band_backward": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32,
+                                          HOST_I32P, c_i32p, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_void_p, c_f32p, C.c_int32,
+                                          c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_vasnet_band_train_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, HOST_I32P, C.c_int32]),
+    "sumk_vasnet_forward_band_train": (C.c_int, [c_f32p, C.c_int32, C.c_int32, HOST_I32P, c_i32p, C.POINTER(VasnetWeights), C.POINTER(VasnetOpts),
+                                                 c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_vasnet_backward_band": (C.c_int, [c_f32p, C.c_int32, C.c_int32, HOST_I32P, c_i32p, C.POINTER(VasnetWeights), C.POINTER(VasnetOpts),
+                                            c_f32p, C.POINTER(VasnetGrads), c_f32p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "sumk_vasnet_backward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, HOST_I32P, c_i32p, C.POINTER(VasnetWeights),
                                        C.POINTER(VasnetOpts), c_f32p, C.POINTER(VasnetGrads), c_f32p, C.c_void_p,
                                        C.c_size_t, C.c_void_p, C.c_void_p]),

@@ -90,6 +90,31 @@ class VasnetFunction(torch.autograd.Function):
         return (gx, None, None, None, None, None) + tuple(ret)
 
 
+class VasnetBandFunction(torch.autograd.Function):
+    """VasnetFunction with the attention on the band, forward and backward (VASNet(local_attention_train="band"), csrc/attn_band_bwd.hip):
+    nothing of size T x T is kept.  inputs: x (positions already added), SeqBatch, opts, param names, *params.  A learnable positional table
+    reaches its gradient through PosAddPacked in front of this function (packed_pos_input)."""
+
+    @staticmethod
+    def forward(ctx, xp, sb, opts, names, *params):
+        p = dict(zip(names, params))
+        scores, ws = kernels.vasnet_forward_band_train(xp, sb, p, opts)
+        ctx.sb, ctx.opts, ctx.names, ctx.ws = sb, dict(opts), names, ws
+        ctx.params = params          # the Parameter objects themselves (their .grad may be a bucket view)
+        ctx.save_for_backward(xp)
+        return scores
+
+    @staticmethod
+    def backward(ctx, dscores):
+        (xp,) = ctx.saved_tensors
+        params = ctx.params
+        p = dict(zip(ctx.names, params))
+        grads, ret = _grad_targets(ctx.names, params)
+        dx = kernels.vasnet_backward_band(xp, ctx.sb, p, ctx.opts, dscores, ctx.ws, grads, want_dx=ctx.needs_input_grad[0])
+        ctx.ws = ctx.params = None
+        return (dx, None, None, None) + tuple(ret)
+
+
 class BiLstmScorerFunction(torch.autograd.Function):
     """scores = sigmoid(Linear(BiLSTM_stack(x))) for a packed batch (DSN: dsn.py:45-46, sLSTM: sumgan.py:43-45)."""
 

@@ -19,53 +19,11 @@
 //            the next video, or poisoned scratch behind the last one, never reach a multiplier (0 x NaN = NaN: zero alpha is not enough).
 // The grouped kernel takes these tables as they are -- no strip kernel of its own was needed.
 // No atomics, no cooperative launch, no flag polled across workgroups; every element is produced by one thread in a fixed order.
-#include "sumk_internal.h"
-#include <math.h>
+#include "attn_band_common.h"
 
 namespace sumk {
 
-namespace {
-constexpr int AB_MAX_T = 1048576;
-
-// ---- sizes of one video; host and device must agree byte for byte, so both call these
-struct ABandSizes { int64_t e, tiles_s; int32_t strips, pitch; };     // floats of logits, 64x64 logits tiles, strips, rectangle pitch
-
-__host__ __device__ inline int ab_k_lo(int w, int r) { const int64_t v = (int64_t)64 * r - w; return v > 0 ? (int)v : 0; }
-__host__ __device__ inline int ab_k_hi(int T, int w, int r) { const int64_t v = (int64_t)64 * r + 64 + w; return v < T ? (int)v : T; }
-__host__ __device__ inline int ab_strip_tiles(int T, int w, int r) { return (ab_k_hi(T, w, r) - ab_k_lo(w, r) + 63) / 64; }
-// logits tiles of strips 0 .. r - 1.  Strips that touch neither end of the video have 2 w + 64 keys each; only the (at most ~ w / 32 + 3)
-// strips at the two ends are walked.
-__host__ __device__ inline int64_t ab_tiles_before(int T, int w, int r) {
-  const int64_t strips = ((int64_t)T + 63) / 64;
-  int64_t i0 = ((int64_t)w + 63) / 64;                                  // first strip with 64 r - w >= 0
-  int64_t i1 = (int64_t)T - 64 - w >= 0 ? ((int64_t)T - 64 - w) / 64 + 1 : 0;      // one past the last strip with 64 r + 64 + w <= T
-  i0 = i0 < strips ? i0 : strips; i1 = i1 < strips ? i1 : strips; i1 = i1 > i0 ? i1 : i0;
-  int64_t s = 0;
-  const int64_t a = r < i0 ? r : i0;
-  for (int64_t q = 0; q < a; ++q) s += ab_strip_tiles(T, w, (int)q);
-  if (r > i0) s += ((r < i1 ? r : i1) - i0) * (((int64_t)2 * w + 64 + 63) / 64);
-  for (int64_t q = i1; q < r; ++q) s += ab_strip_tiles(T, w, (int)q);
-  return s;
-}
-__host__ __device__ inline ABandSizes aband_sizes(int T, int w) {
-  ABandSizes z;
-  const int64_t full = (int64_t)2 * w + 64;
-  z.pitch = (int)(((T < full ? T : full) + 3) & ~(int64_t)3);
-  z.strips = (T + 63) / 64;
-  z.e = (int64_t)z.strips * 64 * z.pitch;
-  z.tiles_s = ab_tiles_before(T, w, z.strips);
-  return z;
-}
-
-struct ABSeq { int64_t e_off, tile_s0; int32_t row0, T, strip0, pitch; };               // one video
-struct ABStrip { int64_t e_off; int32_t row0, rows, i0, k_lo, n_keys, pitch; };         // one strip: row0 = its first PACKED row, i0 = that row inside the video
-
-struct ABandWs { size_t e, seq, strip, prob_s, prob_c, total; int64_t strips, tiles_s, tiles_c; int32_t w, keys_max, rows; };
-
-// `w` of the geometry: an aperture past the longest possible video sees every key, as AB_MAX_T does (and stays clear of int32 overflow)
-inline int ab_clamp_w(int aperture) { return aperture < AB_MAX_T ? aperture : AB_MAX_T; }
-
-int ab_carve(const char* who, int D, int n_seq, const int32_t* off, int aperture, size_t base, ABandWs* L) {
+int ab_carve(const char* who, int D, int n_seq, const int32_t* off, int aperture, size_t base, int n_e, int n_tab, ABandWs* L) {
   SUMK_ARG(D > 0 && D % 4 == 0, "%s: D=%d must be a positive multiple of 4", who, D);
   SUMK_ARG(n_seq > 0 && n_seq <= 65535 && off && off[0] == 0, "%s: empty batch (or more than 65535 videos)", who);
   SUMK_ARG(aperture >= 0, "%s: the band needs an aperture >= 0, got %d", who, aperture);
@@ -83,26 +41,30 @@ int ab_carve(const char* who, int D, int n_seq, const int32_t* off, int aperture
            who, (long long)tiles, (long long)tiles_c);
   size_t p = base;
   auto take = [&](size_t bytes) { size_t at = p; p += align_up(bytes, 256); return at; };
-  L->e = take((size_t)e * 4);
+  L->e = p; L->e_stride = align_up((size_t)e * 4, 256);
+  for (int k = 0; k < n_e; ++k) take((size_t)e * 4);
   L->seq = take((size_t)n_seq * sizeof(ABSeq));
   L->strip = take((size_t)strips * sizeof(ABStrip));
-  L->prob_s = take((size_t)strips * sizeof(GemmProb));
-  L->prob_c = take((size_t)strips * sizeof(GemmProb));
-  L->total = p; L->strips = strips; L->tiles_s = tiles; L->tiles_c = tiles_c; L->w = w; L->keys_max = keys_max; L->rows = off[n_seq];
+  L->prob = p; L->prob_stride = align_up((size_t)strips * sizeof(GemmProb), 256);
+  for (int k = 0; k < n_tab; ++k) take((size_t)strips * sizeof(GemmProb));
+  L->total = p; L->e_elems = e; L->strips = strips; L->tiles_s = tiles; L->tiles_c = tiles_c; L->w = w; L->keys_max = keys_max; L->rows = off[n_seq];
   return SUMK_OK;
 }
 
-__device__ __forceinline__ float ab_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
+int ab_t_max(int n_seq, const int32_t* off) {
+  int t = 0;
+  for (int s = 0; s < n_seq; ++s) t = off[s + 1] - off[s] > t ? off[s + 1] - off[s] : t;
+  return t;
 }
-__device__ __forceinline__ float ab_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
+
+int ab_check_operands(const char* who, int D, const void* const ptrs[], const int32_t lds[], int n) {
+  const int ld_max = 1 << 22;      // (a 64-row tile of an operand stays far below the 2^31 bytes the GEMM's 32-bit row offsets span)
+  for (int k = 0; k < n; ++k) {
+    SUMK_ARG(lds[k] >= D && lds[k] % 4 == 0 && lds[k] <= ld_max, "%s: leading dimensions must be multiples of 4 in D .. %d, got %d", who, ld_max, lds[k]);
+    SUMK_ARG((uintptr_t)ptrs[k] % 16 == 0, "%s: pointers must be 16-byte aligned", who);
+  }
+  return SUMK_OK;
 }
-}  // namespace
 
 // One thread per video: where its rectangles, strips and logits tiles start.
 __global__ void attn_band_seq_kernel(const int32_t* off, int n_seq, int w, ABSeq* seq) {
@@ -118,9 +80,7 @@ __global__ void attn_band_seq_kernel(const int32_t* off, int n_seq, int w, ABSeq
   seq[s] = k;
 }
 
-struct ABSetup { const ABSeq* seq; ABStrip* strip; GemmProb* prob_s; GemmProb* prob_c; int32_t w, D, ldq, ldk, ldv, ldc; };
-
-// One thread per (video, strip): the strip's record and its two GEMM problems.
+// One thread per (video, strip): the strip's record and its GEMM problems (ABTab, attn_band_common.h).
 __global__ void attn_band_strip_kernel(ABSetup a) {
   const ABSeq v = a.seq[blockIdx.y];
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -135,16 +95,30 @@ __global__ void attn_band_strip_kernel(ABSetup a) {
   GemmProb q;
   for (int i = 0; i < 7; ++i) q.pad_[i] = 0;
   q.r_off = 0; q.ldr = 0;
-  // logits: C(rows, n_keys) = Q[row0 ..] K[k_lo ..]^T
-  q.a_off = (int64_t)t.row0 * a.ldq; q.b_off = (int64_t)(v.row0 + k_lo) * a.ldk; q.c_off = e_off;
-  q.M = rows; q.N = n_keys; q.K = a.D; q.lda = a.ldq; q.ldb = a.ldk; q.ldc = v.pitch;
-  q.tiles_n = (n_keys + 63) / 64; q.tile_start = (int32_t)(v.tile_s0 + ab_tiles_before(v.T, a.w, r));
-  a.prob_s[idx] = q;
-  // context: C(rows, D) = alpha(rows, n_keys) V[k_lo .. k_lo + n_keys)
-  q.a_off = e_off; q.b_off = (int64_t)(v.row0 + k_lo) * a.ldv; q.c_off = (int64_t)t.row0 * a.ldc;
-  q.M = rows; q.N = a.D; q.K = n_keys; q.lda = v.pitch; q.ldb = a.ldv; q.ldc = a.ldc;
-  q.tiles_n = (a.D + 63) / 64; q.tile_start = idx * q.tiles_n;
-  a.prob_c[idx] = q;
+  for (int k = 0; k < a.n_tab; ++k) {
+    const ABTab tb = a.tab[k];
+    if (tb.rect_out) {      // C(rows, n_keys) = A[row0 ..] B[k_lo ..]^T into the rectangle
+      q.a_off = (int64_t)t.row0 * tb.lda; q.b_off = (int64_t)(v.row0 + k_lo) * tb.ldb; q.c_off = e_off;
+      q.M = rows; q.N = n_keys; q.K = a.D; q.lda = tb.lda; q.ldb = tb.ldb; q.ldc = v.pitch;
+      q.tiles_n = (n_keys + 63) / 64; q.tile_start = (int32_t)(v.tile_s0 + ab_tiles_before(v.T, a.w, r));
+    } else {                // C(rows, D) = rect(rows, n_keys) B[k_lo .. k_lo + n_keys)
+      q.a_off = e_off; q.b_off = (int64_t)(v.row0 + k_lo) * tb.ldb; q.c_off = (int64_t)t.row0 * tb.ldc;
+      q.M = rows; q.N = a.D; q.K = n_keys; q.lda = v.pitch; q.ldb = tb.ldb; q.ldc = tb.ldc;
+      q.tiles_n = (a.D + 63) / 64; q.tile_start = idx * q.tiles_n;
+    }
+    tb.prob[idx] = q;
+  }
+}
+
+int ab_launch_setup(const ABandWs& L, char* ws, const int32_t* off_dev, int n_seq, int t_max, int D, const ABTab* tabs, int n_tab, hipStream_t stream) {
+  ABSeq* seq = (ABSeq*)(ws + L.seq);
+  hipLaunchKernelGGL(attn_band_seq_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, stream, off_dev, n_seq, L.w, seq);
+  ABSetup su;
+  su.seq = seq; su.strip = (ABStrip*)(ws + L.strip); su.n_tab = n_tab; su.w = L.w; su.D = D;
+  for (int k = 0; k < 6; ++k) su.tab[k] = k < n_tab ? tabs[k] : ABTab{nullptr, 0, 0, 0, 0};
+  hipLaunchKernelGGL(attn_band_strip_kernel, dim3(((t_max + 63) / 64 + 63) / 64, n_seq), dim3(64), 0, stream, su);
+  SUMK_HIP(hipGetLastError());
+  return SUMK_OK;
 }
 
 // Band softmax, in place.  One wave per query row, four rows per block, 16 blocks per strip.  NR > 0: the row (n_keys <= 64 NR) lives in
@@ -212,25 +186,14 @@ __global__ __launch_bounds__(256) void attn_band_softmax_kernel(float* __restric
   }
 }
 
-namespace {
-struct ABandCall {
-  const float* Q; const float* K; const float* V; float* ctx; float* alpha;
-  int32_t ldq, ldk, ldv, ldc, D, n_seq; const int32_t* off_dev; float scale; int32_t ignore_self, aperture;
-};
-
 // the four launches + setup; every argument has been checked
 int attn_band_launch(const ABandCall& c, const ABandWs& L, char* ws, int t_max, hipStream_t stream) {
   float* E = (float*)(ws + L.e);
-  ABSeq* seq = (ABSeq*)(ws + L.seq);
   ABStrip* strip = (ABStrip*)(ws + L.strip);
-  GemmProb* prob_s = (GemmProb*)(ws + L.prob_s);
-  GemmProb* prob_c = (GemmProb*)(ws + L.prob_c);
-  hipLaunchKernelGGL(attn_band_seq_kernel, dim3((c.n_seq + 63) / 64), dim3(64), 0, stream, c.off_dev, c.n_seq, L.w, seq);
-  ABSetup su;
-  su.seq = seq; su.strip = strip; su.prob_s = prob_s; su.prob_c = prob_c; su.w = L.w; su.D = c.D;
-  su.ldq = c.ldq; su.ldk = c.ldk; su.ldv = c.ldv; su.ldc = c.ldc;
-  hipLaunchKernelGGL(attn_band_strip_kernel, dim3(((t_max + 63) / 64 + 63) / 64, c.n_seq), dim3(64), 0, stream, su);
-  SUMK_HIP(hipGetLastError());
+  GemmProb* prob_s = (GemmProb*)(ws + L.prob);
+  GemmProb* prob_c = (GemmProb*)(ws + L.prob + L.prob_stride);
+  const ABTab tabs[2] = {{prob_s, 1, c.ldq, c.ldk, 0}, {prob_c, 0, 0, c.ldv, c.ldc}};
+  SUMK_TRY(ab_launch_setup(L, ws, c.off_dev, c.n_seq, t_max, c.D, tabs, 2, stream));
   {
     GemmLaunch g;
     g.A = c.Q; g.B[0] = c.K; g.C = E; g.probs = prob_s; g.nprob = (int32_t)L.strips; g.small_tile = 1; g.total_tiles = (int32_t)L.tiles_s;
@@ -257,21 +220,16 @@ int attn_band_launch(const ABandCall& c, const ABandWs& L, char* ws, int t_max, 
   return SUMK_OK;
 }
 
-int ab_t_max(int n_seq, const int32_t* off) {
-  int t = 0;
-  for (int s = 0; s < n_seq; ++s) t = off[s + 1] - off[s] > t ? off[s + 1] - off[s] : t;
-  return t;
-}
-
+namespace {
 // workspace of the forward: [Q | K | V] (rows x 3 D; the first LayerNorm's output takes its place once the context exists), the context (later
 // k1's output), the residual sum, three one-entry problem tables, then the band
 struct VBandWs { size_t qkv, ctx, y0, prow; ABandWs band; };
 int vb_carve(int D, int n_seq, const int32_t* off, int aperture, VBandWs* L) {
   ABandWs probe;
-  SUMK_TRY(ab_carve("vasnet_forward_band", D, n_seq, off, aperture, 0, &probe));      // (checks the batch before off[n_seq] is used)
+  SUMK_TRY(ab_carve("vasnet_forward_band", D, n_seq, off, aperture, 0, 1, 2, &probe));      // (checks the batch before off[n_seq] is used)
   const size_t rd = align_up((size_t)off[n_seq] * D * 4, 256);
   L->qkv = 0; L->ctx = 3 * rd; L->y0 = 4 * rd; L->prow = 5 * rd;
-  return ab_carve("vasnet_forward_band", D, n_seq, off, aperture, 5 * rd + align_up(3 * sizeof(GemmProb), 256), &L->band);
+  return ab_carve("vasnet_forward_band", D, n_seq, off, aperture, 5 * rd + align_up(3 * sizeof(GemmProb), 256), 1, 2, &L->band);
 }
 }  // namespace
 
@@ -281,7 +239,7 @@ using namespace sumk;
 
 extern "C" size_t sumk_attn_band_workspace_bytes(int32_t D, int32_t n_seq, const int32_t* seq_off_host, int32_t aperture) {
   ABandWs L;
-  if (ab_carve("attn_band", D, n_seq, seq_off_host, aperture, 0, &L) != SUMK_OK) return 0;
+  if (ab_carve("attn_band", D, n_seq, seq_off_host, aperture, 0, 1, 2, &L) != SUMK_OK) return 0;
   return L.total;
 }
 
@@ -291,7 +249,7 @@ extern "C" int sumk_attn_band(const float* Q, int32_t ldq, const float* K, int32
   hipStream_t stream = (hipStream_t)stream_;
   SUMK_ARG(Q && K && V && ctx && seq_off_dev && workspace, "attn_band: null pointer");
   ABandWs L;
-  SUMK_TRY(ab_carve("attn_band", D, n_seq, seq_off_host, aperture, 0, &L));
+  SUMK_TRY(ab_carve("attn_band", D, n_seq, seq_off_host, aperture, 0, 1, 2, &L));
   const int ld_max = 1 << 22;      // (a 64-row tile of an operand stays far below the 2^31 bytes the GEMM's 32-bit row offsets span)
   SUMK_ARG(ldq >= D && ldk >= D && ldv >= D && ldc >= D && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldc % 4 == 0 && ldq <= ld_max &&
            ldk <= ld_max && ldv <= ld_max && ldc <= ld_max, "attn_band: leading dimensions must be multiples of 4 in D .. %d, got %d %d %d %d",

@@ -461,6 +461,111 @@ def vasnet_forward_band(x, sb, params, opts):
     return scores
 
 
+def attn_band_train_workspace_bytes(D, sb, aperture):
+    """Bytes a training call of the band attention needs (three rectangle buffers): pure host arithmetic, 0 for arguments it would refuse."""
+    return _lib.load().sumk_attn_band_train_workspace_bytes(int(D), sb.n_seq, sb.off_host_p, int(aperture))
+
+
+def vasnet_band_train_workspace_bytes(D, sb, aperture):
+    """Bytes sumk_vasnet_forward_band_train / _backward_band need for this batch: pure host arithmetic, 0 for arguments they would refuse."""
+    return _lib.load().sumk_vasnet_band_train_workspace_bytes(int(D), sb.n_seq, sb.off_host_p, int(aperture))
+
+
+def _band_rows(what, sb, D, **tensors):
+    for name, t in tensors.items():
+        _require_gpu(t, f"{what} {name}")
+        if t.dim() != 2 or t.shape != (sb.n_rows, D) or t.stride(1) != 1:
+            raise SumkError(f"{what}: {name} must be ({sb.n_rows}, D) with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
+
+
+def _seed_dev_p(seed_dev):
+    return C.c_void_p(seed_dev.data_ptr()) if seed_dev is not None else C.c_void_p(0)
+
+
+def attn_band_train(q, k, v, sb, aperture, scale, ignore_self=False, dropout_p=0.0, seed=0, seed_dev=None, ctx=None, ws=None):
+    """`attn_band` in training mode (sumk_attn_band_forward_train): dropout of the weights at site 0 with the dense path's index, and the
+    workspace keeps alpha / dropout(alpha) for `attn_band_backward`.  Returns (ctx, ws).  ctx / ws: buffers to write into (a caller that
+    captures the call, or checks what it leaves untouched).  Only enqueues work on the current stream."""
+    lib = _lib.load()
+    w = _band_aperture(aperture, "attn_band_train")
+    D = q.shape[1] if q.dim() == 2 else -1
+    _band_rows("attn_band_train", sb, D, q=q, k=k, v=v)
+    if ws is None:
+        nb = _nonzero(lib.sumk_attn_band_train_workspace_bytes(D, sb.n_seq, sb.off_host_p, w), "sumk_attn_band_train_workspace_bytes")
+        ws = workspace(nb, q.device, persistent=True)
+    if ctx is None:
+        ctx = torch.empty(sb.n_rows, D, dtype=torch.float32, device=q.device)
+    _lib.check(lib.sumk_attn_band_forward_train(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, sb.n_seq, sb.off_host_p,
+                                                sb.off_dev_p, float(scale), int(bool(ignore_self)), w, float(dropout_p), int(seed),
+                                                _seed_dev_p(seed_dev), _p(ctx), ctx.stride(0), _p(ws), ws.numel(), _stream()),
+               "sumk_attn_band_forward_train")
+    return ctx, ws
+
+
+def attn_band_backward(q, k, v, dctx, sb, aperture, scale, ws, ignore_self=False, dropout_p=0.0, seed=0, seed_dev=None, out=None):
+    """Gradients of `attn_band_train` (sumk_attn_band_backward): (dq, dk, dv), each (n_rows, D), from dctx and the workspace the forward
+    left; the options must be the forward's.  out: three buffers to write into.  Only enqueues work on the current stream."""
+    lib = _lib.load()
+    w = _band_aperture(aperture, "attn_band_backward")
+    D = q.shape[1] if q.dim() == 2 else -1
+    _band_rows("attn_band_backward", sb, D, q=q, k=k, v=v, dctx=dctx)
+    if not ws.is_cuda:
+        raise SumkError("attn_band_backward: the workspace must be the GPU buffer attn_band_train returned")
+    dq, dk, dv = out if out is not None else (torch.empty(sb.n_rows, D, dtype=torch.float32, device=q.device) for _ in range(3))
+    _band_rows("attn_band_backward", sb, D, dq=dq, dk=dk, dv=dv)
+    _lib.check(lib.sumk_attn_band_backward(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(dctx), dctx.stride(0), D, sb.n_seq,
+                                           sb.off_host_p, sb.off_dev_p, float(scale), int(bool(ignore_self)), w, float(dropout_p), int(seed),
+                                           _seed_dev_p(seed_dev), _p(dq), dq.stride(0), _p(dk), dk.stride(0), _p(dv), dv.stride(0), _p(ws),
+                                           ws.numel(), _stream()), "sumk_attn_band_backward")
+    return dq, dk, dv
+
+
+def _band_structs(params, opts, what):
+    w = _band_aperture(opts.get("aperture"), what)
+    return _vasnet_structs(params, dict({k: v for k, v in opts.items() if k not in ("tables", "x16", "xplanes", "wplanes")}, aperture=w)) + (w,)
+
+
+def vasnet_forward_band_train(x, sb, params, opts, ws=None):
+    """VASNet's training-mode forward with the attention on the band (sumk_vasnet_forward_band_train): x (n_rows, D) packed ->
+    (scores (n_rows,), workspace for `vasnet_backward_band`).  opts as for vasnet_forward_packed with an int aperture >= 0 and exact fp32;
+    x is not modified.  Only enqueues work."""
+    lib = _lib.load()
+    _check_rows(x, sb, "vasnet input")
+    D = x.shape[1]
+    wts, o, w = _band_structs(params, opts, "vasnet_forward_band_train")
+    if ws is None:
+        nb = _nonzero(lib.sumk_vasnet_band_train_workspace_bytes(D, sb.n_seq, sb.off_host_p, w), "sumk_vasnet_band_train_workspace_bytes")
+        ws = workspace(nb, x.device, persistent=True)
+    scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
+    _lib.check(lib.sumk_vasnet_forward_band_train(_p(x), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, C.byref(wts), C.byref(o), _p(scores), _p(ws),
+                                                  ws.numel(), _stream()), "sumk_vasnet_forward_band_train")
+    return scores, ws
+
+
+def vasnet_backward_band(x, sb, params, opts, dscores, ws, grads, want_dx=False):
+    """`vasnet_backward_packed` for a step whose forward was `vasnet_forward_band_train`: ACCUMULATES the weight gradients into `grads`,
+    returns dx (or None)."""
+    lib = _lib.load()
+    _check_rows(x, sb, "vasnet input")
+    D = x.shape[1]
+    wts, o, _ = _band_structs(params, opts, "vasnet_backward_band")
+    g = _lib.VasnetGrads()
+    for f, k in VASNET_FIELDS:
+        t = grads[k]
+        _require_gpu(t, f"VASNet grad {k}")
+        setattr(g, f, t.data_ptr())
+    dx = torch.empty_like(x) if want_dx else None
+    if not dscores.is_contiguous():
+        dscores = dscores.contiguous()
+    ev = opts.get("tail_grads_ready_event")
+    if ev is not None:
+        ev.record()                                  # materialise the lazy hipEvent_t handle (re-recorded by the library)
+    _lib.check(lib.sumk_vasnet_backward_band(_p(x), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, C.byref(wts), C.byref(o), _p(dscores), C.byref(g),
+                                             _p(dx), _p(ws), ws.numel(), _stream(),
+                                             C.c_void_p(ev.cuda_event) if ev is not None else C.c_void_p(0)), "sumk_vasnet_backward_band")
+    return dx
+
+
 # ------------------------------------------------------------------------------------------------ BiLSTM scorers
 # SUMK_CHECK=1 (set by the test-suite): synchronise after every recurrent layer and verify that the persistent kernel's
 # bounded waits did not time out.  Off by default (it costs a host sync per layer).

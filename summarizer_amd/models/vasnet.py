@@ -26,7 +26,7 @@ from ..training import FlatAdam, dist_info, plan_shards, resolve_batch_videos, s
 class VASNet(PositionalInput, nn.Module):
     def __init__(self, input_size=1024, max_length=None, pos_embed="simple", ignore_self=False,
                  attention_aperture=None, scale=None, epsilon=1e-6, weight_init="xavier", precision="fp32", fold_vo=False,
-                 local_attention="dense"):
+                 local_attention="dense", local_attention_train="dense"):
         super().__init__()
         # local_attention (not in the reference, opt-in): where the `attention_aperture` mask is computed when SCORING (no-grad calls).
         #   "dense"  the full (T x T) logits of every video with the mask applied afterwards: workspace and FLOPs grow with T^2 whatever
@@ -34,7 +34,15 @@ class VASNet(PositionalInput, nn.Module):
         #   "band"   only the keys [i - w, i + w] of every query row (kernels.vasnet_forward_band, csrc/attn_band.hip): O(T w), videos up
         #            to 1 048 576 steps -- the scorer in front of Summarizer(kts="banded", tail="long").  Needs an int
         #            attention_aperture >= 0, precision "fp32" and fold_vo=False.  It adds no parameter (same state_dict).
-        # TRAINING on the band is out of scope: a call that records a graph (the autograd branch of _score) stays on the dense masked path.
+        # local_attention_train (opt-in): where a call that records a graph (the autograd branch of _score) computes the attention.
+        #   "dense"  the dense masked path, whatever local_attention is (the default: a band model trains exactly as before);
+        #   "band"   forward AND backward on the band (autograd.VasnetBandFunction, csrc/attn_band_bwd.hip): a training step keeps three
+        #            O(T w) rectangle buffers instead of two (T x T) blocks per video.  Needs local_attention="band".  Dropout masks are those
+        #            of the dense path for the same seed.
+        if local_attention_train not in ("dense", "band"):
+            raise kernels.SumkError(f"VASNet: local_attention_train must be 'dense' or 'band', got {local_attention_train!r}")
+        if local_attention_train == "band" and local_attention != "band":
+            raise kernels.SumkError(f"VASNet(local_attention_train='band') needs local_attention='band', got {local_attention!r}")
         if local_attention not in ("dense", "band"):
             raise kernels.SumkError(f"VASNet: local_attention must be 'dense' or 'band', got {local_attention!r}")
         if local_attention == "band":
@@ -44,6 +52,7 @@ class VASNet(PositionalInput, nn.Module):
                 raise kernels.SumkError(f"VASNet(local_attention='band') runs in exact fp32 without fold_vo, got precision={precision!r} fold_vo={fold_vo!r}")
             attention_aperture = int(attention_aperture)
         self.local_attention = local_attention
+        self.local_attention_train = local_attention_train
         self.precision = precision      # GEMM arithmetic: "fp32" (exact) | "bf16x6" | "bf16x3" | "bf16" (kernels.precision_code); not in the reference
         # fold_vo (not in the reference, opt-in): inference folds the value and output projections into ONE matrix Wvo = Wo.Wv
         # (recomputed whenever the weights may have changed), which removes the out-projection GEMM: 18 % fewer FLOPs per frame,
@@ -120,14 +129,18 @@ class VASNet(PositionalInput, nn.Module):
         """extra: entries for the call's options that the caller derived from xp itself (score_packed: the bf16 shadow / the planes that
         came out of the positional add's launch).
         local_attention="band": the no-grad branch scores through kernels.vasnet_forward_band; the autograd branch stays on the dense masked
-        path -- training on the band is out of scope."""
+        path unless local_attention_train="band" (VasnetBandFunction)."""
         training = self.training and torch.is_grad_enabled()
         if training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
-            from ..autograd import VasnetFunction
+            from ..autograd import VasnetBandFunction, VasnetFunction
             names = [k for _, k in kernels.VASNET_FIELDS]
             p = self._params()
             opts = self._opts(self.training)
             opts.update(extra or {})
+            if self.local_attention_train == "band":
+                if self.precision != "fp32" or self.fold_vo or table is not None:
+                    raise kernels.SumkError("VASNet(local_attention_train='band') trains in exact fp32, without fold_vo, through score_packed")
+                return VasnetBandFunction.apply(xp, sb, opts, names, *[p[n] for n in names])
             return VasnetFunction.apply(xp, sb, opts, table, rows, names, *[p[n] for n in names])
         opts = self._opts(False)
         opts.update(extra or {})
@@ -197,7 +210,10 @@ class VASNetTrainer(Trainer):
     launches), per-video MSE, backward, fused Adam -- is captured once per video (its features and target stay at fixed addresses in
     the HBM cache) and replayed every later epoch, so the ~45 kernels of a step are not paced by the host (the eager step spends a
     third of its time waiting for Python between the forward and the backward).  Dropout masks stay fresh per replay through a
-    device-side seed word (sumk_vasnet_opts::seed_dev).  extra_params["hip_graph"] = "0" keeps every step eager."""
+    device-side seed word (sumk_vasnet_opts::seed_dev).  extra_params["hip_graph"] = "0" keeps every step eager.
+
+    extra_params["local_attention_train"] = "band" (with "local" and "local_attention" = "band") trains on the band (VASNet's argument of
+    that name).  Every step then runs eagerly: the per-video HIP-graph capture is not attempted, as with hip_graph = "0"."""
 
     def _init_model(self):
         ep = self.hps.extra_params
@@ -212,6 +228,7 @@ class VASNetTrainer(Trainer):
             precision=ep.get("precision", "fp32"),
             fold_vo=bool(ep.get("fold_vo", False)),
             local_attention=ep.get("local_attention", "dense"),
+            local_attention_train=ep.get("local_attention_train", "dense"),
             **({"input_size": int(ep["input_size"])} if "input_size" in ep else {}))
         if self.hps.use_cuda:
             self.log.info(f"Setting CUDA device: {self.hps.cuda_device}")
@@ -240,7 +257,7 @@ class VASNetTrainer(Trainer):
 
         best = self._fold_best()
         # reference schedule as HIP graphs: one captured step per video, replayed from the second epoch on (class docstring)
-        use_graph = (world == 1 and bv == 1 and dev.type == "cuda"
+        use_graph = (world == 1 and bv == 1 and dev.type == "cuda" and self.model.local_attention_train != "band"
                      and str(self.hps.extra_params.get("hip_graph", "1")) not in ("0", "False", "false"))
         graphs, graph_pool, graphs_zeroed = {}, None, False
         if use_graph:
