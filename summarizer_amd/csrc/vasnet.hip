@@ -873,6 +873,10 @@ static bool pw_long_ok(int D, int t_min, int t_max, int np) {
   return pw_ok(t_max, tn, D, tn, tn, np) && pw_ok(t_max, D, kpad, t_max, D, np);
 }
 static bool wplanes_ok(int D, int np) { return D >= 256 && D % 256 == 0 && (np == 2 || np == 3) && pw_ok(256, 3 * (int64_t)D, D, 256, 3 * (int64_t)D, np); }
+static int plane_count(int precision) { return precision == SUMK_PRECISION_BF16X6 ? 3 : precision == SUMK_PRECISION_BF16X3 ? 2 : 0; }
+// Can a batch run on planes at all?  What the size query and plan_forward both ask first; then attn_pw_ok (strips) and pw_long_ok decide
+// the attention, and with it the extra workspace (pw_extra / pw_long_layout).
+static bool pw_batch_ok(int D, int64_t R, int np, int training) { return !training && np && wplanes_ok(D, np) && R >= 256; }
 
 // one launcher for every LayerNorm call site: picks the register-resident form when the row fits (D <= 2048)
 template <bool HEAD>
@@ -1052,7 +1056,7 @@ static int rowwise_small_tile(int M, int N) {
 struct SkPlan { SkTab row[SR_COUNT], seq[TB_COUNT]; SkRowSpec spec[SR_COUNT]; int64_t slab_seq[TB_COUNT]; };
 struct Geometry {  // what both forward and backward derive from the batch
   VasnetWs L;
-  int R, st_qkv, st_d, tiles_s, tiles_pv, cfg_s, cfg_pv, t_max;
+  int R, st_qkv, st_d, tiles_s, tiles_pv, cfg_s, cfg_pv, t_max, t_min;
   bool b16;          // the mixed-precision training step on the bf16-source kernels (use_b16)
   bool attn_fused;   // ... with the per-video attention as fused strips (attn_b16.hip): t_max <= 320
   int sk;            // 1: the small-batch path (use_sk) -- every GEMM an in-launch split-K launch of gemm_lean.hip; P = its tables
@@ -1060,12 +1064,30 @@ struct Geometry {  // what both forward and backward derive from the batch
 };
 static bool use_b16(const Geometry& G, int D, int precision, int training);
 
+// The A/B switches of this unit, read once per process.  NAME=0 selects the reference path; anything else, or unset, the default.
+//   switch            set to 0 (SUMK_B16_WIDE: to a value)                                        the test that compares both settings
+//   SUMK_SK           the large-batch kernels for every batch, however small                      test_gpu_vasnet.py::test_small_batch_path_matches_large_batch_kernels
+//   SUMK_BF16_SRC     bf16 training on the plane kernels (fp32 operands converted per k-tile)     test_gpu_train_full.py::test_bf16_source_step_equals_the_plane_kernel_step
+//   SUMK_ATTN_FUSED   bf16 training attention as separate launches (GEMM -> softmax -> GEMM)      test_gpu_train_full.py::test_fused_attention_strips_equal_separate_launches
+//   SUMK_B16_WIDE     0: 128x128 bf16-source tiles everywhere; 192 / 256: that wide tile          (none on the step: scripts/probes/b16_k_sweep.py)
+//   SUMK_PW_LONG      long videos on the in-loop grouped kernels between plane GEMMs              test_gpu_planes.py::test_long_videos_on_the_plane_gemm (and test_gpu_vasnet_lengths.py)
+//   SUMK_FUSED_HEAD   inference tail on the separate k1 and LayerNorm + head kernels              test_gpu_vasnet.py::test_fused_inference_tail_equals_separate_kernels
+//   SUMK_FUSED_LN     the first LayerNorm as its own kernel (the head stays in the k1 epilogue)   test_gpu_vasnet.py::test_fused_inference_tail_equals_separate_kernels
+struct Switches { bool sk, bf16_src, attn_fused, pw_long, fused_head, fused_ln; int b16_wide; };
+static const Switches& switches() {
+  static const Switches s = [] {
+    auto on = [](const char* name) { const char* v = getenv(name); return !(v && v[0] == '0'); };
+    const char* wide = getenv("SUMK_B16_WIDE");
+    return Switches{on("SUMK_SK"), on("SUMK_BF16_SRC"), on("SUMK_ATTN_FUSED"), on("SUMK_PW_LONG"), on("SUMK_FUSED_HEAD"), on("SUMK_FUSED_LN"),
+                    wide ? atoi(wide) : -1};
+  }();
+  return s;
+}
+
 // Small-batch path (SK launches): a function of the batch geometry and the arithmetic only -- forward and backward must agree.
-// SUMK_SK=0 keeps the large-batch kernels for every batch (the A/B switch of tests/test_gpu_vasnet.py::test_small_batch_path_...).
 static int use_sk(int R, int D, int precision) {
-  static const bool on = !(getenv("SUMK_SK") && getenv("SUMK_SK")[0] == '0');
   // (D <= 2048: the row kernels that add K-slice slabs hold a row in registers)
-  return on && precision == SUMK_PRECISION_FP32 && sk_rows_ok(R) && D % 4 == 0 && D <= 2048 ? 1 : 0;
+  return switches().sk && precision == SUMK_PRECISION_FP32 && sk_rows_ok(R) && D % 4 == 0 && D <= 2048 ? 1 : 0;
 }
 // Every table of the step: requested slices, entries, (tile, slice) blocks and tickets -- the host mirror of vasnet_sk_setup_kernel.
 static void sk_plan(int R, int D, int n_seq, const int32_t* off, const VasnetWs& L, SkPlan* P) {
@@ -1127,7 +1149,9 @@ static void sk_plan(int R, int D, int n_seq, const int32_t* off, const VasnetWs&
   }
 }
 
-static int geometry(int D, int n_seq, const int32_t* off, int training, int precision, size_t workspace_bytes, Geometry* G) {
+// A function of the batch and the options ONLY (never of the workspace size: forward and backward must take the same path -- the
+// forward leaves the bf16 shadows and table layout the backward reads); a workspace without the shadows is refused by the callers.
+static int geometry(int D, int n_seq, const int32_t* off, int training, int precision, Geometry* G) {
   SUMK_TRY(carve(D, n_seq, off, training, &G->L));
   G->R = G->L.n_rows;
   G->st_qkv = rowwise_small_tile(G->R, 3 * D);
@@ -1137,17 +1161,11 @@ static int geometry(int D, int n_seq, const int32_t* off, int training, int prec
   // under-fill the resident slots); long videos (mean T >= 1024, e.g. BASELINE config 5) take the 128x128 tile, whose
   // 2x2 register blocking halves the LDS traffic per MFMA.
   G->cfg_s = G->cfg_pv = (G->R / n_seq >= 1024) ? 0 : 1;
-  G->t_max = 0;
-  for (int s = 0; s < n_seq; ++s) G->t_max = std::max(G->t_max, off[s + 1] - off[s]);
-  // A function of the batch and the options ONLY (never of workspace_bytes: forward and backward must take the same path -- the
-  // forward leaves the bf16 shadows and table layout the backward reads); a workspace without the shadows is refused below.
-  (void)workspace_bytes;
+  G->t_max = 0; G->t_min = off[1] - off[0];
+  for (int s = 0; s < n_seq; ++s) { G->t_max = std::max(G->t_max, off[s + 1] - off[s]); G->t_min = std::min(G->t_min, off[s + 1] - off[s]); }
   G->b16 = use_b16(*G, D, precision, training);
   if (G->b16) G->cfg_s = G->cfg_pv = 0;       // the bf16-source kernel has 128x128 tiles
-  {  // SUMK_ATTN_FUSED=0 keeps the separate launches (GEMM -> softmax kernel -> GEMM): the A/B switch of tests/test_gpu_train_full.py
-    static const bool fused_on = !(getenv("SUMK_ATTN_FUSED") && getenv("SUMK_ATTN_FUSED")[0] == '0');
-    G->attn_fused = G->b16 && fused_on && attn_strip_ok(G->t_max, D, G->R, 3 * D);
-  }
+  G->attn_fused = G->b16 && switches().attn_fused && attn_strip_ok(G->t_max, D, G->R, 3 * D);
   G->tiles_s = G->tiles_pv = 0;
   for (int s = 0; s < n_seq; ++s) {
     int T = off[s + 1] - off[s];
@@ -1159,10 +1177,9 @@ static int geometry(int D, int n_seq, const int32_t* off, int training, int prec
 }
 
 // Does the training step run its row-wise GEMMs on the bf16-source kernels (gemm_b16.hip)?  A function of the batch geometry and the
-// options only: forward and backward must agree (the forward leaves the bf16 shadows the backward reads).  SUMK_BF16_SRC=0 keeps
-// the plane kernels (fp32 operands converted per k-tile) -- the A/B switch.
+// options only: forward and backward must agree (the forward leaves the bf16 shadows the backward reads).
 static bool use_b16(const Geometry& G, int D, int precision, int training) {
-  static const bool on = !(getenv("SUMK_BF16_SRC") && getenv("SUMK_BF16_SRC")[0] == '0');
+  const bool on = switches().bf16_src;
   const int R = G.R;
   // (per-video attention blocks: T x ld16 bf16 with ld16 = T rounded up to 64 -- their byte offsets must fit 31 bits too)
   const int64_t ld16 = ((int64_t)G.t_max + 63) & ~(int64_t)63;
@@ -1175,7 +1192,7 @@ static bool use_b16(const Geometry& G, int D, int precision, int training) {
 // put a row-wise launch on the bf16-source kernels: bf16 operands and, where it fills the chip, the wide tile with its problem entry
 static void to_b16(GemmLaunch& g, const void* A16, const void* B16, int M, int N, GemmProb* prow, int slot_wide) {
   g.A = (const float*)A16; g.B[0] = (const float*)B16; g.B[1] = g.B[2] = g.B[3] = nullptr; g.n_group = 0; g.src16 = 1;
-  static const int force = getenv("SUMK_B16_WIDE") ? atoi(getenv("SUMK_B16_WIDE")) : -1;     // A/B switch: 0 = 128x128 tiles everywhere
+  const int force = switches().b16_wide;
   const int wide = force >= 0 ? force : gemm_b16_wide_bm(M, N);
   if (wide == 192 || wide == 256) { g.wide16 = wide; g.probs = prow + slot_wide; g.total_tiles = gemm_tiles_wide(M, N, wide); }
 }
@@ -1215,33 +1232,31 @@ static int launch_sk_setup(const Geometry& G, int D, int n_seq, const int32_t* o
   a.seq = (SeqInfo*)(ws + G.L.seq); a.row_seq = (int32_t*)(ws + G.L.row_seq); a.cnt = (unsigned*)(ws + G.L.sk_cnt);
   a.tabs = (GemmProb*)(ws + G.L.sk_tabs);
   a.tile = 64;
-  const bool tickets = true;
   for (int r = 0; r < SR_COUNT; ++r) a.rows[r] = G.P.spec[r];
   for (int t = 0; t < TB_COUNT; ++t) {
     a.S_seq[t] = G.P.seq[t].S_req; a.slab_seq[t] = G.P.slab_seq[t];
-    SUMK_ARG((!tickets || G.P.seq[t].tiles <= SK_TICKETS) && G.P.seq[t].entries <= n_seq * SK_MAX_SLICES, "vasnet: small-batch table %d out of range", t);
+    SUMK_ARG(G.P.seq[t].tiles <= SK_TICKETS && G.P.seq[t].entries <= n_seq * SK_MAX_SLICES, "vasnet: small-batch table %d out of range", t);
   }
   for (int r = 0; r < SR_COUNT; ++r)
-    SUMK_ARG((!tickets || G.P.row[r].tiles <= SK_TICKETS) && G.P.row[r].entries <= SK_ROW_ENTRIES, "vasnet: small-batch row table %d out of range", r);
+    SUMK_ARG(G.P.row[r].tiles <= SK_TICKETS && G.P.row[r].entries <= SK_ROW_ENTRIES, "vasnet: small-batch row table %d out of range", r);
   hipLaunchKernelGGL(vasnet_sk_setup_kernel, dim3((n_seq + 63) / 64, 2 + 8), dim3(64), 0, stream, a);   // y: 0 per-video tables, 1 row tables, 2.. row -> video table + tickets
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
 }
 
-static size_t sk_part_bytes(const Geometry& G, int n_seq) { return G.L.sk_part_bytes; }
 // one SK launch over table `tb` (row-wise table r >= 0, or per-video table t)
-struct SkCall { const float* A; const float* B[4]; float* C[4]; const float* R; const float* bias; int prof_tag; };
+struct SkCall { const float* A; const float* B[4]; float* C[4]; int prof_tag; };     // (pointers not named are null)
 static int launch_sk(const Geometry& G, int n_seq, char* ws, char* tbase, GemmLayout layout, GemmEpi epi, int row_tab, int seq_tab, const SkCall& c, hipStream_t stream) {
   const SkTab& tb = row_tab >= 0 ? G.P.row[row_tab] : G.P.seq[seq_tab];
   GemmProb* tabs = (GemmProb*)(tbase + G.L.sk_tabs);
   GemmLaunch g;
   g.A = c.A;
   for (int i = 0; i < 4; ++i) { g.B[i] = c.B[i]; g.Csel[i] = c.C[i]; }
-  g.C = c.C[0]; g.R = c.R; g.bias0[0] = c.bias;
+  g.C = c.C[0];
   g.probs = row_tab >= 0 ? sk_row_tab(tabs, row_tab) : sk_seq_tab(tabs, seq_tab, n_seq);
   g.nprob = tb.entries; g.total_tiles = tb.blocks; g.small_tile = 1; g.prof_tag = c.prof_tag;
   g.sk = 1; g.sk_part = (float*)(ws + G.L.sk_part); g.sk_cnt = (unsigned*)(tbase + G.L.sk_cnt);
-  SUMK_ARG(tb.blocks == tb.tiles || (size_t)tb.blocks * 64 * 64 * 4 <= sk_part_bytes(G, n_seq), "vasnet: small-batch launch needs %d partial tiles", tb.blocks);   // (blocks == tiles: nothing is sliced)
+  SUMK_ARG(tb.blocks == tb.tiles || (size_t)tb.blocks * 64 * 64 * 4 <= G.L.sk_part_bytes, "vasnet: small-batch launch needs %d partial tiles", tb.blocks);   // (blocks == tiles: nothing is sliced)
   return launch_gemm(layout, epi, g, stream);
 }
 
@@ -1347,7 +1362,7 @@ extern "C" int sumk_vasnet_build_tables(int32_t D, int32_t n_seq, const int32_t*
   SUMK_ARG(seq_off_dev && tables && ((uintptr_t)tables & 255) == 0, "vasnet_build_tables: null or misaligned (256 B) pointer");
   SUMK_ARG(precision >= SUMK_PRECISION_FP32 && precision <= SUMK_PRECISION_MAX, "vasnet_build_tables: unknown precision %d", precision);
   Geometry G;
-  SUMK_TRY(geometry(D, n_seq, seq_off_host, training, precision, 0, &G));
+  SUMK_TRY(geometry(D, n_seq, seq_off_host, training, precision, &G));
   if (tables_bytes < G.L.tab_bytes) { set_error("vasnet_build_tables: %zu bytes < required %zu", tables_bytes, G.L.tab_bytes); return SUMK_ERR_WORKSPACE; }
   launch_setup(G, D, n_seq, seq_off_dev, (char*)tables, stream);                 // the large-batch tables (also what a dX-producing backward uses)
   if (G.sk) SUMK_TRY(launch_sk_setup(G, D, n_seq, seq_off_dev, (char*)tables, stream));   // the small-batch tables + zeroed tickets
@@ -1387,134 +1402,189 @@ extern "C" size_t sumk_vasnet_workspace_bytes(int32_t D, int32_t n_seq, const in
   if (carve(D, n_seq, seq_off_host, training, &w) != SUMK_OK) return 0;
   return w.total;
 }
+// An upper bound for a caller that knows the arithmetic but not yet what the call brings (x planes, weight planes, a folded weight,
+// positions): plan_forward asks the same tests first and then only ever narrows.
 extern "C" size_t sumk_vasnet_workspace_bytes_for(int32_t D, int32_t n_seq, const int32_t* seq_off_host, int32_t training, int32_t precision) {
-  VasnetWs w;
-  if (carve(D, n_seq, seq_off_host, training, &w) != SUMK_OK) return 0;
-  const int np = precision == SUMK_PRECISION_BF16X6 ? 3 : precision == SUMK_PRECISION_BF16X3 ? 2 : 0;
-  if (!training && np && wplanes_ok(D, np)) {
-    int t_max = 0;
-    for (int s = 0; s < n_seq; ++s) t_max = std::max(t_max, seq_off_host[s + 1] - seq_off_host[s]);
-    if (w.n_rows >= 256 && attn_pw_ok(t_max, D, w.n_rows, np)) return pw_extra(D, w.n_rows, t_max, np, w.total_core).total;
-    int t_min = t_max;
-    for (int s = 0; s < n_seq; ++s) t_min = std::min(t_min, seq_off_host[s + 1] - seq_off_host[s]);
-    if (w.n_rows >= 256 && pw_long_ok(D, t_min, t_max, np)) return pw_long_layout(D, w.n_rows, t_max, np, w.total_core).total;
+  Geometry G;
+  if (geometry(D, n_seq, seq_off_host, training, precision, &G) != SUMK_OK) return 0;
+  const int np = plane_count(precision);
+  if (pw_batch_ok(D, G.R, np, training)) {
+    if (attn_pw_ok(G.t_max, D, G.R, np)) return pw_extra(D, G.R, G.t_max, np, G.L.total_core).total;
+    if (pw_long_ok(D, G.t_min, G.t_max, np)) return pw_long_layout(D, G.R, G.t_max, np, G.L.total_core).total;
   }
-  return (training && precision == SUMK_PRECISION_BF16) ? w.total : w.total_core;
+  return (training && precision == SUMK_PRECISION_BF16) ? G.L.total : G.L.total_core;
 }
 
-// The small-batch forward: the same nine stages as vasnet_forward_impl, every GEMM an SK launch (gemm_lean.hip) over the sliced tables
+// What forward and backward require whatever the path: the carve-up, with the bf16 shadows only for a step on the bf16-source kernels.
+static size_t core_bytes(const Geometry& G) { return G.b16 ? G.L.total : G.L.total_core; }
+
+// The first-LayerNorm fold of the dense inference tail keeps its scratch in the unused Y1 region, in floats from its start: per-row
+// moments, W1 diag(ln_w), {c1, c2}, {mean, rstd}.  The producer of Y0 sets the moment slots per row: the output projection (128x128
+// tiles, D / 32) or, on the folded path, the per-video alpha.(X Wvo) product with the residual (64x64 tiles, D / 16).
+struct LnFold { int slots; size_t w1g, c1, stats, total; };
+static LnFold ln_fold_layout(int R, int D, bool folded) {
+  LnFold f; f.slots = folded ? D / 16 : D / 32;
+  f.w1g = align_up((size_t)R * f.slots * 2, 64); f.c1 = f.w1g + (size_t)D * D; f.stats = f.c1 + align_up((size_t)2 * D, 64);
+  f.total = f.stats + (size_t)2 * R;
+  return f;
+}
+
+// ---- the plan: which path a forward call takes, with which layouts, and the workspace that path needs.  Asked once per call.
+enum { PATH_SK, PATH_DENSE, PATH_PLANES };
+enum { ATTN_STRIPS, ATTN_LONG, ATTN_GROUPED };     // attention of the plane path
+struct ForwardPlan {
+  int path, attn, np;
+  // Fused inference tail of the dense path (128x128 tiles, no dropout; training always runs the separate kernels):
+  //  fused_tail: the k1 epilogue reduces relu(.) to the LayerNorm + k2 moments -- Z never exists;
+  //  fused_ln:   the epilogue of the GEMM that produces Y0 also emits its per-row moments, one prep launch folds the first
+  //      LayerNorm's gain into W1 and turns the moments into {mean, rstd}, and the k1 GEMM reads the RAW Y0: the LayerNorm is
+  //      applied to the product in the k1 epilogue -- no LayerNorm kernel, Y1 never exists.  Its scratch (LnFold) lives in the
+  //      unused Y1 region, which must be large enough (R >~ 1.1 D).
+  bool fused_tail, fused_ln;     // (dense path only: the plane path has both built in)
+  WPlanes wl; PwExtra px; PwLong pl; LnFold lf;
+  size_t need;
+};
+static ForwardPlan plan_forward(const Geometry& G, int D, const sumk_vasnet_opts* opts, int training, bool has_pos, bool folded, size_t workspace_bytes) {
+  const Switches& sw = switches();
+  const int R = G.R;
+  ForwardPlan p{};
+  p.need = core_bytes(G);
+  if (G.sk && !folded) { p.path = PATH_SK; return p; }
+  // Plane path (inference in bf16x6 / bf16x3 with the caller's x planes and weight-plane block): the three row-wise GEMMs on gemm_pw.hip.
+  // (A/B: a call without the plane pointers runs the in-loop split kernels; tests/test_gpu_planes.py compares the two.)
+  p.np = plane_count(opts->precision);
+  if (pw_batch_ok(D, R, p.np, training) && opts->xplanes && opts->wplanes && !has_pos && G.st_qkv == 0 && G.st_d == 0 &&
+      pw_ok(R, 3 * (int64_t)D, D, R, 3 * (int64_t)D, p.np) && (!folded || G.cfg_pv == 1)) {
+    p.path = PATH_PLANES; p.wl = wplanes_layout(D, p.np);
+    // the per-video attention on planes as well (attn_pw.hip): T <= 320, the extra workspace present.  A workspace of the core size
+    // only (a caller that asked sumk_vasnet_workspace_bytes) keeps the grouped in-loop kernels between the plane GEMMs.
+    p.px = pw_extra(D, R, G.t_max, p.np, G.L.total_core);
+    if (attn_pw_ok(G.t_max, D, R, p.np) && workspace_bytes >= p.px.total) { p.attn = ATTN_STRIPS; p.need = p.px.total; return p; }
+    // long videos, one at a time on the plane GEMM itself
+    p.pl = pw_long_layout(D, R, G.t_max, p.np, G.L.total_core);
+    if (!folded && sw.pw_long && pw_long_ok(D, G.t_min, G.t_max, p.np) && workspace_bytes >= p.pl.total) { p.attn = ATTN_LONG; p.need = p.pl.total; return p; }
+    p.attn = ATTN_GROUPED;
+    return p;
+  }
+  p.path = PATH_DENSE;
+  p.lf = ln_fold_layout(R, D, folded);
+  p.fused_tail = sw.fused_head && !training && make_drop(opts).thr == 0 && G.st_d == 0 && D % 64 == 0;
+  p.fused_ln = p.fused_tail && sw.fused_ln && (!folded || G.cfg_pv == 1) && p.lf.total <= (size_t)R * D;
+  return p;
+}
+
+// The workspace and table pointers of one call (tb: the table base -- the caller's prebuilt block, or the front of the workspace, built
+// per call) and its dropout.  E2, stats, the gradients and the workspace copy of the scores exist in training mode only.
+struct StepBufs {
+  float *QKV, *E, *E2, *CTX, *Y0, *Y1, *Z, *stats, *scores;
+  float *dZ, *dY1, *dY0, *dCTX, *dQKV, *lnpart, *slab;
+  SeqInfo* seq; const int32_t* row_seq; GemmProb *prow, *tabs, *pskw;
+  Drop drop; bool use_e2;
+};
+static StepBufs step_bufs(char* ws, char* tb, const VasnetWs& L, const sumk_vasnet_opts* opts, int training) {
+  StepBufs B{};
+  auto f = [ws](size_t off) { return (float*)(ws + off); };
+  B.QKV = f(L.qkv); B.E = f(L.e); B.CTX = f(L.ctx); B.Y0 = f(L.y0); B.Y1 = f(L.y1); B.Z = f(L.z);
+  if (training) {
+    B.E2 = f(L.e2); B.stats = f(L.stats); B.scores = f(L.scores);
+    B.dZ = f(L.dz); B.dY1 = f(L.dy1); B.dY0 = f(L.dy0); B.dCTX = f(L.dctx); B.dQKV = f(L.dqkv); B.lnpart = f(L.lnpart); B.slab = f(L.slab);
+  }
+  B.seq = (SeqInfo*)(tb + L.seq); B.row_seq = (const int32_t*)(tb + L.row_seq);
+  B.prow = (GemmProb*)(tb + L.prob_row); B.tabs = (GemmProb*)(tb + L.prob_seq); B.pskw = (GemmProb*)(tb + L.prob_skw);
+  B.drop = make_drop(opts); B.use_e2 = training && B.drop.thr != 0;
+  return B;
+}
+
+// Softmax launchers: a row of up to 256 / 512 / 1024 keys stays in registers (NR = 4 / 8 / 16), a longer one loops (NR = 0).
+static int softmax_nr(int t_max) { return t_max <= 256 ? 4 : t_max <= 512 ? 8 : t_max <= 1024 ? 16 : 0; }
+// pre: the PRE instances (the small-batch path); eraw, n_slab, slab_stride: the raw logits as K-slice slabs (large batch: E itself, 0, 0)
+static void launch_softmax(int nr, bool pre, const StepBufs& B, int n_seq, int R, const sumk_vasnet_opts* opts, float* e2p, unsigned short* p16,
+                           const float* eraw, int n_slab, int64_t slab_stride, hipStream_t stream) {
+  const dim3 sg((R + 3) / 4), sb(256);
+#define SUMK_SOFTMAX_(NR, PRE) hipLaunchKernelGGL((vasnet_softmax_kernel<NR, PRE>), sg, sb, 0, stream, B.E, e2p, B.seq, B.row_seq, n_seq, R, opts->scale, opts->ignore_self, opts->aperture, B.drop, p16, eraw, n_slab, slab_stride)
+#define SUMK_SOFTMAX(NR) do { if (pre) SUMK_SOFTMAX_(NR, true); else SUMK_SOFTMAX_(NR, false); } while (0)
+  if (nr == 4) SUMK_SOFTMAX(4); else if (nr == 8) SUMK_SOFTMAX(8); else if (nr == 16) SUMK_SOFTMAX(16); else SUMK_SOFTMAX(0);
+#undef SUMK_SOFTMAX
+#undef SUMK_SOFTMAX_
+}
+// graw, n_slab, slab_stride: the incoming dAlphaD as K-slice slabs (large batch: E2 itself, 0, 0); s16: bf16(dLogits) of the bf16 step
+static void launch_softmax_bwd(int nr, const StepBufs& B, int n_seq, int R, const sumk_vasnet_opts* opts, unsigned short* s16, const float* graw,
+                               int n_slab, int64_t slab_stride, hipStream_t stream) {
+#define SUMK_SOFTMAX_BWD(NR) hipLaunchKernelGGL(vasnet_softmax_bwd_kernel<NR>, dim3((R + 3) / 4), dim3(256), 0, stream, B.E, B.E2, B.seq, B.row_seq, n_seq, R, opts->scale, B.drop, s16, graw, n_slab, slab_stride)
+  if (nr == 4) SUMK_SOFTMAX_BWD(4); else if (nr == 8) SUMK_SOFTMAX_BWD(8); else if (nr == 16) SUMK_SOFTMAX_BWD(16); else SUMK_SOFTMAX_BWD(0);
+#undef SUMK_SOFTMAX_BWD
+}
+
+// Stages 2-4 on the grouped per-video GEMMs of the large-batch path (fp32 operands, or the bf16 shadows of a G.b16 step).
+// folded: alpha U + x is Y0 itself (forward_dense), with its per-row moments when `moments` is given.
+static int attn_grouped(const Geometry& G, const StepBufs& B, int n_seq, const sumk_vasnet_opts* opts, const float* x, char* ws, bool folded,
+                        float* moments, hipStream_t stream) {
+  const VasnetWs& L = G.L;
+  {  // 2: logits per video
+    GemmLaunch g; g.precision = opts->precision;
+    g.A = B.QKV; g.B[0] = B.QKV; g.C = B.E; g.probs = B.tabs + TB_S * n_seq; g.nprob = n_seq; g.small_tile = G.cfg_s;
+    g.total_tiles = G.tiles_s; g.prof_tag = SUMK_PROF_GEMM_QKT;
+    if (G.b16) { g.A = g.B[0] = (const float*)(ws + L.qkv16); g.src16 = 1; }
+    SUMK_TRY(launch_gemm(GEMM_NT, EPI_NONE, g, stream));
+  }
+  // 3: softmax (+ dropout of alpha into E2 when training with p > 0)
+  launch_softmax(softmax_nr(G.t_max), false, B, n_seq, G.R, opts, B.use_e2 ? B.E2 : nullptr, G.b16 ? (unsigned short*)(ws + L.p16) : nullptr, B.E, 0, 0, stream);
+  {  // 4: context
+    GemmLaunch g; g.precision = opts->precision;
+    g.A = B.use_e2 ? B.E2 : B.E; g.B[0] = B.QKV; g.C = folded ? B.Y0 : B.CTX; g.R = x; g.probs = B.tabs + TB_PV * n_seq; g.nprob = n_seq; g.small_tile = G.cfg_pv;
+    g.total_tiles = G.tiles_pv; g.prof_tag = SUMK_PROF_GEMM_PV;
+    if (folded && moments) g.moments = moments;
+    if (G.b16) { g.A = (const float*)(ws + L.p16); g.B[0] = (const float*)(ws + L.qkv16); g.src16 = 1; g.C16 = ws + L.ctx16; g.C = nullptr; }
+    SUMK_TRY(launch_gemm(GEMM_NN, folded ? (moments ? EPI_RESIDUAL_MOMENTS : EPI_RESIDUAL) : EPI_NONE, g, stream));
+  }
+  return SUMK_OK;
+}
+
+// The small-batch forward: the same nine stages as forward_dense, every GEMM an SK launch (gemm_lean.hip) over the sliced tables
 // of vasnet_sk_setup_kernel, the row kernels unchanged.  Inference and training (the intermediates the backward needs are the same).
-static int vasnet_forward_sk(const Geometry& G, float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
-                             const sumk_vasnet_weights* w, const sumk_vasnet_opts* opts, const float* pos_table, const int32_t* pos_rows,
-                             float* scores, char* ws, char* tb, int32_t training, hipStream_t stream) {     // tb: table base (ws, or opts->tables: then already built)
+static int forward_sk(const Geometry& G, float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_dev, const sumk_vasnet_weights* w,
+                      const sumk_vasnet_opts* opts, const float* pos_table, const int32_t* pos_rows, float* scores, char* ws, char* tb,
+                      int32_t training, hipStream_t stream) {
   const VasnetWs& L = G.L;
   const int R = G.R;
-  float* QKV = (float*)(ws + L.qkv);
-  float* E = (float*)(ws + L.e);
-  float* E2 = training ? (float*)(ws + L.e2) : nullptr;
-  float* CTX = (float*)(ws + L.ctx);
-  float* Y0 = (float*)(ws + L.y0);
-  float* Y1 = (float*)(ws + L.y1);
-  float* Z = (float*)(ws + L.z);
-  SeqInfo* seq = (SeqInfo*)(tb + L.seq);
-  float* stats = training ? (float*)(ws + L.stats) : nullptr;
-  const Drop drop = make_drop(opts);
-  const bool use_e2 = training && drop.thr != 0;
-  if (pos_table) {
-    int64_t n4 = (int64_t)R * (D >> 2);
-    hipLaunchKernelGGL(add_pos_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, x, pos_table, pos_rows, R, D);
-  }
+  const StepBufs B = step_bufs(ws, tb, L, opts, training);
+  if (pos_table) SUMK_TRY(launch_add_pos(x, pos_table, pos_rows, R, D, stream));       // 0
   for (int S : {G.P.seq[TB_S].S, G.P.seq[TB_DP].S, G.P.row[SR_OPROJ].S, G.P.row[SR_K1].S, G.P.row[SR_DY1].S})     // slab sets the row kernels add: slab_sum's cases
     SUMK_ARG(S == 1 || S == 2 || S == 4 || S == 8, "vasnet: slab set of %d slices (internal: sk_plan builds 1, 2, 4 or 8)", S);
   if (tb == ws) SUMK_TRY(launch_sk_setup(G, D, n_seq, seq_off_dev, tb, stream));
-  {  // 1: QKV projection (three B pointers, one launch)
-    const SkCall c{x, {w->Wq, w->Wk, w->Wv, nullptr}, {QKV, nullptr, nullptr, nullptr}, nullptr, nullptr, SUMK_PROF_GEMM_QKV};
-    SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NT, EPI_NONE, SR_QKV, -1, c, stream));
-  }
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NT, EPI_NONE, SR_QKV, -1, SkCall{x, {w->Wq, w->Wk, w->Wv}, {B.QKV}, SUMK_PROF_GEMM_QKV}, stream));     // 1: QKV projection (three B pointers, one launch)
   // K-slice slabs (SlabIn): where a row kernel consumes a GEMM's output, the slices store their own slab in the scratch and the row
   // kernel adds them -- S slabs of the E layout / of (R, D)
   float* scratch = (float*)(ws + L.sk_part);
-  {  // 2: logits per video
-    const SkCall c{QKV, {QKV, nullptr, nullptr, nullptr}, {scratch, nullptr, nullptr, nullptr}, nullptr, nullptr, SUMK_PROF_GEMM_QKT};
-    SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NT, EPI_NONE, -1, TB_S, c, stream));
-  }
-  {  // 3: softmax (+ dropout of alpha into E2 when training with p > 0)
-    const dim3 sg((R + 3) / 4), sb(256);
-    float* e2p = use_e2 ? E2 : nullptr;
-    const float* eraw = scratch;
-    const int n_slab = G.P.seq[TB_S].S;
-#define SUMK_SOFTMAX(NR) hipLaunchKernelGGL((vasnet_softmax_kernel<NR, true>), sg, sb, 0, stream, E, e2p, seq, (const int32_t*)(tb + L.row_seq), n_seq, R, opts->scale, opts->ignore_self, opts->aperture, drop, (unsigned short*)nullptr, eraw, n_slab, (int64_t)L.e_elems)
-    if (G.t_max <= 256) SUMK_SOFTMAX(4); else if (G.t_max <= 512) SUMK_SOFTMAX(8); else if (G.t_max <= 1024) SUMK_SOFTMAX(16); else SUMK_SOFTMAX(0);
-#undef SUMK_SOFTMAX
-  }
-  {  // 4: context
-    const SkCall c{use_e2 ? E2 : E, {QKV, nullptr, nullptr, nullptr}, {CTX, nullptr, nullptr, nullptr}, nullptr, nullptr, SUMK_PROF_GEMM_PV};
-    SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NN, EPI_NONE, -1, TB_PV, c, stream));
-  }
-  {
-    // 5 + 6: output projection as K-slice slabs; the LayerNorm kernel adds them and the residual (Y0 itself is kept for the backward pass)
-    const SkCall c{CTX, {w->Wo, nullptr, nullptr, nullptr}, {scratch, nullptr, nullptr, nullptr}, nullptr, nullptr, SUMK_PROF_GEMM_OPROJ};
-    SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NT, EPI_NONE, SR_OPROJ, -1, c, stream));
-    SlabIn sl; sl.n = G.P.row[SR_OPROJ].S; sl.stride = (int64_t)R * D; sl.add = x; sl.store = training ? Y0 : nullptr;
-    launch_ln_rows<false>(scratch, Y1, w->ln_w, w->ln_b, nullptr, nullptr, nullptr, R, D, opts->eps, stats, drop, 1u, stream, nullptr, sl);
-    // 7 + 8: k1 as slabs; the LayerNorm + head kernel adds them, the bias and the ReLU (Z is kept for the backward pass)
-    const SkCall c2{Y1, {w->W1, nullptr, nullptr, nullptr}, {scratch, nullptr, nullptr, nullptr}, nullptr, nullptr, SUMK_PROF_GEMM_K1};
-    SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NT, EPI_NONE, SR_K1, -1, c2, stream));
-    SlabIn s2; s2.n = G.P.row[SR_K1].S; s2.stride = (int64_t)R * D; s2.bias = w->b1; s2.relu = 1; s2.store = training ? Z : nullptr;
-    launch_ln_rows<true>(scratch, training ? (float*)(ws + L.scores) : nullptr, w->ln_w, w->ln_b, w->w2, w->b2, scores, R, D, opts->eps, stats ? stats + 2 * (size_t)R : nullptr, drop, 2u, stream, nullptr, s2);      // (the backward reads the scores from the workspace: written here, not copied)
-  }
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NT, EPI_NONE, -1, TB_S, SkCall{B.QKV, {B.QKV}, {scratch}, SUMK_PROF_GEMM_QKT}, stream));     // 2: logits per video
+  // 3: softmax (+ dropout of alpha into E2 when training with p > 0)
+  launch_softmax(softmax_nr(G.t_max), true, B, n_seq, R, opts, B.use_e2 ? B.E2 : nullptr, nullptr, scratch, G.P.seq[TB_S].S, (int64_t)L.e_elems, stream);
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NN, EPI_NONE, -1, TB_PV, SkCall{B.use_e2 ? B.E2 : B.E, {B.QKV}, {B.CTX}, SUMK_PROF_GEMM_PV}, stream));     // 4: context
+  // 5 + 6: output projection as K-slice slabs; the LayerNorm kernel adds them and the residual (Y0 itself is kept for the backward pass)
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NT, EPI_NONE, SR_OPROJ, -1, SkCall{B.CTX, {w->Wo}, {scratch}, SUMK_PROF_GEMM_OPROJ}, stream));
+  SlabIn sl; sl.n = G.P.row[SR_OPROJ].S; sl.stride = (int64_t)R * D; sl.add = x; sl.store = training ? B.Y0 : nullptr;
+  launch_ln_rows<false>(scratch, B.Y1, w->ln_w, w->ln_b, nullptr, nullptr, nullptr, R, D, opts->eps, B.stats, B.drop, 1u, stream, nullptr, sl);
+  // 7 + 8: k1 as slabs; the LayerNorm + head kernel adds them, the bias and the ReLU (Z is kept for the backward pass)
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NT, EPI_NONE, SR_K1, -1, SkCall{B.Y1, {w->W1}, {scratch}, SUMK_PROF_GEMM_K1}, stream));
+  SlabIn s2; s2.n = G.P.row[SR_K1].S; s2.stride = (int64_t)R * D; s2.bias = w->b1; s2.relu = 1; s2.store = training ? B.Z : nullptr;
+  launch_ln_rows<true>(scratch, B.scores, w->ln_w, w->ln_b, w->w2, w->b2, scores, R, D, opts->eps, B.stats ? B.stats + 2 * (size_t)R : nullptr, B.drop, 2u, stream, nullptr, s2);      // (the backward reads the scores from the workspace: written here, not copied)
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
 }
 
+// The large-batch forward on the grouped GEMMs of gemm_f32.hip: exact fp32, the in-loop split (bf16x3 / bf16x6 / bf16 operands converted
+// per k-tile) and, for the mixed-precision training step, the bf16-source kernels (G.b16).  Inference and training.
 // Wvo != nullptr: inference with the value and output projections FOLDED (Wvo = Wo . Wv, computed once per weight change by the
 // caller): (alpha V) Wo^T = alpha (X Wv^T Wo^T) = alpha (X Wvo^T), so the third slice of the packed projection is U = X Wvo^T,
 // the per-video product alpha U lands directly in Y0 with the residual added in its epilogue, and the R x D x D output
 // projection (18 % of the step's FLOPs) disappears.  Same mathematics, a different association of the fp32 products.
-static int vasnet_forward_impl(float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host,
-                               const int32_t* seq_off_dev, const sumk_vasnet_weights* w,
-                               const sumk_vasnet_opts* opts, const float* pos_table, const int32_t* pos_rows,
-                               float* scores, void* workspace, size_t workspace_bytes, int32_t training,
-                               void* stream_, const float* Wvo) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SUMK_ARG(Wvo == nullptr || !training, "vasnet_forward: the folded projection is an inference-only path");
-  SUMK_ARG(x && seq_off_dev && w && opts && scores && workspace, "vasnet_forward: null pointer");
-  SUMK_ARG(w->Wk && w->Wq && w->Wv && w->Wo && w->W1 && w->b1 && w->w2 && w->b2 && w->ln_w && w->ln_b,
-           "vasnet_forward: null weight");
-  SUMK_ARG((pos_table == nullptr) == (pos_rows == nullptr), "vasnet_forward: pos_table and pos_rows go together");
-  SUMK_ARG(opts->dropout_p >= 0.f && opts->dropout_p < 1.f, "vasnet_forward: dropout_p=%f out of [0,1)", opts->dropout_p);
-  SUMK_ARG(opts->dropout_p == 0.f || training, "vasnet_forward: dropout needs training mode");
-  SUMK_ARG(opts->precision >= SUMK_PRECISION_FP32 && opts->precision <= SUMK_PRECISION_MAX, "vasnet_forward: unknown precision %d", opts->precision);
-  Geometry G;
-  SUMK_TRY(geometry(D, n_seq, seq_off_host, training, opts->precision, workspace_bytes, &G));
+static int forward_dense(const Geometry& G, const ForwardPlan& P, float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_dev,
+                         const sumk_vasnet_weights* w, const sumk_vasnet_opts* opts, const float* pos_table, const int32_t* pos_rows,
+                         float* scores, char* ws, char* tb, int32_t training, hipStream_t stream, const float* Wvo) {
   const VasnetWs& L = G.L;
-  if (workspace_bytes < (G.b16 ? L.total : L.total_core)) {
-    set_error("vasnet_forward: workspace %zu < required %zu", workspace_bytes, G.b16 ? L.total : L.total_core);
-    return SUMK_ERR_WORKSPACE;
-  }
-  char* ws = (char*)workspace;
-  char* tb = opts->tables ? (char*)opts->tables : ws;      // table base: the caller's prebuilt block, or the front of the workspace (built per call)
-  if (G.sk && !Wvo)
-    return vasnet_forward_sk(G, x, D, n_seq, seq_off_host, seq_off_dev, w, opts, pos_table, pos_rows, scores, ws, tb, training, stream);
   const int R = G.R;
-  float* QKV = (float*)(ws + L.qkv);
-  float* E = (float*)(ws + L.e);
-  float* E2 = training ? (float*)(ws + L.e2) : nullptr;
-  float* CTX = (float*)(ws + L.ctx);
-  float* Y0 = (float*)(ws + L.y0);
-  float* Y1 = (float*)(ws + L.y1);
-  float* Z = (float*)(ws + L.z);
-  SeqInfo* seq = (SeqInfo*)(tb + L.seq);
-  GemmProb* prow = (GemmProb*)(tb + L.prob_row);
-  GemmProb* tabs = (GemmProb*)(tb + L.prob_seq);
-  float* stats = training ? (float*)(ws + L.stats) : nullptr;
-  const Drop drop = make_drop(opts);
-  const bool use_e2 = training && drop.thr != 0;
-
-  if (pos_table) {
-    int64_t n4 = (int64_t)R * (D >> 2);
-    hipLaunchKernelGGL(add_pos_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, x, pos_table, pos_rows, R, D);
-  }
+  const StepBufs B = step_bufs(ws, tb, L, opts, training);
+  if (pos_table) SUMK_TRY(launch_add_pos(x, pos_table, pos_rows, R, D, stream));       // 0
   if (tb == ws) launch_setup(G, D, n_seq, seq_off_dev, tb, stream);
   // mixed-precision training: bf16 shadows of x and of the five weight matrices, then every row-wise GEMM reads bf16 from HBM
   const bool b16 = G.b16;
@@ -1530,70 +1600,138 @@ static int vasnet_forward_impl(float* x, int32_t D, int32_t n_seq, const int32_t
     const int64_t ne[6] = {dd, dd, dd, dd, dd, (int64_t)R * D};
     SUMK_TRY(cast_flat_b16(opts->x16 ? 5 : 6, src, dst, ne, stream));
   }
-
   // row-wise NT GEMMs with K = D: eligible for the buffer-load instances when D is a whole number of k-tiles and byte offsets fit 31 bits
   const int lean_rows = (D % 32 == 0 && (int64_t)R * 3 * D * 4 < ((int64_t)1 << 31)) ? 1 : 0;
-  // Plane path (inference in bf16x6 / bf16x3 with the caller's x planes and weight-plane block): the three row-wise GEMMs on gemm_pw.hip.
-  // (A/B: a call without the plane pointers runs the in-loop split kernels; tests/test_gpu_planes.py compares the two.)
-  const int np = opts->precision == SUMK_PRECISION_BF16X6 ? 3 : opts->precision == SUMK_PRECISION_BF16X3 ? 2 : 0;
-  const bool pw = np && !training && opts->xplanes && opts->wplanes && !pos_table && wplanes_ok(D, np) && R >= 256 && G.st_qkv == 0 &&
-                  G.st_d == 0 && pw_ok(R, 3 * (int64_t)D, D, R, 3 * (int64_t)D, np) && (Wvo == nullptr || G.cfg_pv == 1);
-  const WPlanes wl = pw ? wplanes_layout(D, np) : WPlanes();
-  const char* const wp = (const char*)opts->wplanes;
-  // ... and the per-video attention on planes as well (attn_pw.hip): T <= 320, the extra workspace present (folded path: the context strips add the residual and emit the moments)
-  const PwExtra px = pw ? pw_extra(D, R, G.t_max, np, L.total_core) : PwExtra();
-  const bool pw_attn = pw && attn_pw_ok(G.t_max, D, R, np) && workspace_bytes >= px.total;
-  // Long videos on planes (round 6): per video, logits and context on the plane GEMM itself; the context leaves as planes (rows of the video inside
-  // the batch's CTX planes), so the output projection below reads them as on the strip path.  SUMK_PW_LONG=0: the in-loop grouped kernels (A/B).
-  int t_min_h = G.t_max;
-  for (int q = 0; q < n_seq; ++q) t_min_h = std::min(t_min_h, seq_off_host[q + 1] - seq_off_host[q]);
-  static const bool pw_long_on = !(getenv("SUMK_PW_LONG") && getenv("SUMK_PW_LONG")[0] == '0');
-  const PwLong pl = (pw && !pw_attn) ? pw_long_layout(D, R, G.t_max, np, L.total_core) : PwLong();
-  const bool pw_long = pw && !pw_attn && !Wvo && pw_long_on && pw_long_ok(D, t_min_h, G.t_max, np) && workspace_bytes >= pl.total;
-  if (pw_attn) {  // 1-4: projection -> planes of [Q | K | V]; logits + softmax -> alpha planes; alpha . V -> context planes
-    PwLaunch g; g.A = opts->xplanes; g.a_rows = R; g.B = wp + wl.wqkv; g.b_rows = 3 * (int64_t)D; g.M = R; g.N = 3 * D; g.K = D; g.np = np;
-    // the context kernel multiplies V rows up to 31 past the last video's end by alpha = 0: every row up to the pitch is stored (zeros: x's pad rows are
-    // zero) and the slack a read past the LAST sub-array lands in is cleared -- 0 x (stale NaN bits) would be NaN
-    g.O = ws + px.qkv; g.o_rows = R; g.o_store_rows = pw_rows_pitch(R); g.prof_tag = SUMK_PROF_GEMM_QKV;
-    SUMK_HIP(hipMemsetAsync(ws + px.qkv + pw_planes_bytes(R, 3 * D, np) - 8192, 0, 8192, stream));
-    SUMK_TRY(launch_gemm_pw(PW_PLANES, g, stream));
-    prof_begin(SUMK_PROF_GEMM_QKT, stream);
-    SUMK_TRY(launch_attn_pw_logits(np, ws + px.qkv, R, D, nullptr, ws + px.ap, seq, n_seq, G.t_max, opts->scale, opts->ignore_self, opts->aperture, stream));
-    prof_end(SUMK_PROF_GEMM_QKT, stream);
-    prof_begin(SUMK_PROF_GEMM_PV, stream);
-    if (Wvo) {   // folded: "V" = x Wvo^T, so alpha . V + x IS Y0 -- it leaves as planes with its LayerNorm moments (D / 32 slots per row; the small arrays live in Z)
-      SUMK_TRY(launch_attn_pw_context(np, ws + px.qkv, R, D, ws + px.ap, ws + px.ctx, seq, n_seq, G.t_max, stream, 1, x, D, (float*)(ws + L.z)));
-    } else {
-      SUMK_TRY(launch_attn_pw_context(np, ws + px.qkv, R, D, ws + px.ap, ws + px.ctx, seq, n_seq, G.t_max, stream));
-    }
-    prof_end(SUMK_PROF_GEMM_PV, stream);
-  } else
-  if (pw_long && pl.qk_direct) {  // 1: [Q | K] straight to planes (every video's Q and K are row ranges of them), V as fp32 (R x D: its transpose is split per video)
-    PwLaunch g; g.A = opts->xplanes; g.a_rows = R; g.B = wp + wl.wqkv; g.b_rows = 3 * (int64_t)D; g.M = R; g.N = 2 * D; g.K = D; g.np = np;
-    g.O = ws + pl.qk; g.o_rows = R; g.o_store_rows = pw_rows_pitch(R); g.prof_tag = SUMK_PROF_GEMM_QKV;
-    SUMK_HIP(hipMemsetAsync(ws + pl.qk + pw_planes_bytes(R, 2 * D, np) - 8192, 0, 8192, stream));      // the last video's logits tiles read key rows past the array's last sub-array
-    SUMK_TRY(launch_gemm_pw(PW_PLANES, g, stream));
-    PwLaunch gv; gv.A = opts->xplanes; gv.a_rows = R; gv.B = wp + wl.wqkv + (size_t)2 * D * 16; gv.b_rows = 3 * (int64_t)D; gv.M = R; gv.N = D; gv.K = D; gv.np = np;
-    gv.C = QKV; gv.ldc = D; gv.prof_tag = SUMK_PROF_GEMM_QKV;
-    SUMK_TRY(launch_gemm_pw(PW_F32, gv, stream));
-  } else
-  if (pw) {  // 1: QKV projection from planes (fp32 output: the per-video products below read it)
-    PwLaunch g; g.A = opts->xplanes; g.a_rows = R; g.B = wp + wl.wqkv; g.b_rows = 3 * (int64_t)D; g.M = R; g.N = 3 * D; g.K = D; g.np = np;
-    g.C = QKV; g.ldc = 3 * D; g.prof_tag = SUMK_PROF_GEMM_QKV;
-    SUMK_TRY(launch_gemm_pw(PW_F32, g, stream));
-  } else
+  float *const ln_moments = B.Y1, *const ln_W1g = B.Y1 + P.lf.w1g, *const ln_c1 = B.Y1 + P.lf.c1, *const ln_stats = B.Y1 + P.lf.stats;   // (P.fused_ln)
+  auto fold_ln = [&]() -> int {    // W1 diag(ln_w), c1, c2 and Y0's moments -> {mean, rstd}
+    hipLaunchKernelGGL(ln_fold_stats_kernel, dim3(D + (R + 31) / 32), dim3(256), 0, stream, w->W1, w->ln_w, w->ln_b, D, ln_W1g, ln_c1,
+                       ln_c1 + D, (const float2*)ln_moments, P.lf.slots, R, opts->eps, (float2*)ln_stats);
+    SUMK_HIP(hipGetLastError());
+    return SUMK_OK;
+  };
   {  // 1: QKV projection
     GemmLaunch g; g.precision = opts->precision;
-    g.A = x; g.B[0] = w->Wq; g.B[1] = w->Wk; g.B[2] = Wvo ? Wvo : w->Wv; g.n_group = D; g.C = QKV; g.probs = prow + RP_QKV;
+    g.A = x; g.B[0] = w->Wq; g.B[1] = w->Wk; g.B[2] = Wvo ? Wvo : w->Wv; g.n_group = D; g.C = B.QKV; g.probs = B.prow + RP_QKV;
     g.small_tile = G.st_qkv; g.total_tiles = gemm_tiles(R, 3 * D, G.st_qkv); g.prof_tag = SUMK_PROF_GEMM_QKV;
     g.xcd_M = R; g.xcd_N = 3 * D;
     g.lean = lean_rows;
     // (b16: Q / K / V are read by bf16-source GEMMs only -- the fp32 form, 147 MB of stores on S-TVSum, is not written at all)
-    if (b16) { to_b16(g, x16, Wqkv16, R, 3 * D, prow, RP_QKV_W); g.C16 = ws + L.qkv16; g.C = nullptr; }
+    if (b16) { to_b16(g, x16, Wqkv16, R, 3 * D, B.prow, RP_QKV_W); g.C16 = ws + L.qkv16; g.C = nullptr; }
     SUMK_TRY(launch_gemm(GEMM_NT, EPI_NONE, g, stream));
   }
-  if (pw_long) {
-    char* const ctxp = ws + L.y0;                       // = pw_ctxp below: planes of the (R x D) context
+  if (G.attn_fused) {  // 2-4 in one launch per (video, 64-row strip): logits, softmax (+ dropout), context
+    AttnStripArgs at;
+    const unsigned short* qkv16 = (const unsigned short*)(ws + L.qkv16);
+    at.A16 = qkv16; at.lda = 3 * D; at.B16 = qkv16 + D; at.ldb = 3 * D; at.C16 = qkv16 + 2 * D; at.ldc = 3 * D;
+    at.O16 = (unsigned short*)(ws + L.ctx16); at.ldo = D; at.E = B.E; at.P16 = (unsigned short*)(ws + L.p16);
+    at.seq = B.seq; at.n_seq = n_seq; at.strips = (G.t_max + 63) / 64; at.D = D;
+    at.scale = opts->scale; at.ignore_self = opts->ignore_self; at.aperture = opts->aperture; at.drop = B.drop;
+    SUMK_TRY(launch_attn_strip(false, at, stream));
+  } else {
+    SUMK_TRY(attn_grouped(G, B, n_seq, opts, x, ws, Wvo != nullptr, P.fused_ln ? ln_moments : nullptr, stream));
+  }
+  if (Wvo) {   // (5 happened in the context product)
+    if (P.fused_ln) SUMK_TRY(fold_ln());
+  } else {  // 5: output projection + residual
+    GemmLaunch g; g.precision = opts->precision;
+    g.A = B.CTX; g.B[0] = w->Wo; g.C = B.Y0; g.R = x; g.probs = B.prow + RP_DD; g.small_tile = G.st_d;
+    g.total_tiles = gemm_tiles(R, D, G.st_d); g.xcd_M = R; g.xcd_N = D; g.prof_tag = SUMK_PROF_GEMM_OPROJ;
+    g.lean = lean_rows;
+    if (P.fused_ln) {
+      g.moments = ln_moments;
+      SUMK_TRY(launch_gemm(GEMM_NT, EPI_RESIDUAL_MOMENTS, g, stream));
+      SUMK_TRY(fold_ln());
+    } else {
+      if (b16) to_b16(g, ws + L.ctx16, Wo16, R, D, B.prow, RP_DD_W);
+      SUMK_TRY(launch_gemm(GEMM_NT, EPI_RESIDUAL, g, stream));
+    }
+  }
+  // 6: dropout + LayerNorm
+  // (b16: the LayerNorm output is consumed by bf16-source GEMMs only -- k1 here, dW1 in the backward -- so only its bf16 form is written)
+  if (!P.fused_ln) launch_ln_rows<false>(B.Y0, b16 ? nullptr : B.Y1, w->ln_w, w->ln_b, nullptr, nullptr, nullptr, R, D, opts->eps, B.stats, B.drop, 1u, stream,
+                                         b16 ? (unsigned short*)(ws + L.y116) : nullptr);
+  GemmLaunch g; g.precision = opts->precision;     // 7: k1 + bias + ReLU (fused tail: G.st_d == 0, the 128x128 tiles)
+  g.A = B.Y1; g.B[0] = w->W1; g.bias0[0] = w->b1; g.C = B.Z; g.probs = B.prow + RP_DD; g.small_tile = G.st_d;
+  g.total_tiles = gemm_tiles(R, D, G.st_d); g.xcd_M = R; g.xcd_N = D; g.prof_tag = SUMK_PROF_GEMM_K1;
+  g.lean = lean_rows;
+  if (P.fused_tail) {
+    // 7 + 8 fused (inference, 128x128 tiles): k1 + bias + ReLU with the LayerNorm + k2 moments taken in the GEMM epilogue -- the
+    // (R, D) activation matrix is neither written (49 MB in the lock-stepped store burst of this single-round launch) nor read
+    // back by a LayerNorm kernel: Z is reused as float4[R][D / 32] moments (R * D / 8 floats of the R * D region)
+    g.bias1[0] = w->ln_w; g.bias1[1] = w->w2;
+    if (P.fused_ln) { g.A = B.Y0; g.B[0] = ln_W1g; g.ln_stats = ln_stats; g.ln_c1 = ln_c1; g.ln_c2 = ln_c1 + D; }
+    SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS_RELU_HEAD, g, stream));
+    hipLaunchKernelGGL(head_finalize_kernel, dim3((R + 31) / 32), dim3(256), 0, stream, (const float4*)B.Z, D / 32, R, D, w->ln_w,
+                       w->ln_b, w->w2, w->b2, opts->eps, scores);
+  } else {
+    if (b16) to_b16(g, ws + L.y116, W116, R, D, B.prow, RP_DD_W);
+    SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS_RELU, g, stream));
+    // 8: dropout + LayerNorm (same weights) + k2 + sigmoid
+    launch_ln_rows<true>(B.Z, B.scores, w->ln_w, w->ln_b, w->w2, w->b2, scores, R, D, opts->eps, B.stats ? B.stats + 2 * (size_t)R : nullptr, B.drop, 2u, stream);
+  }
+  SUMK_HIP(hipGetLastError());
+  return SUMK_OK;
+}
+
+// The plane forward (inference in bf16x6 / bf16x3 from the caller's x planes and weight-plane block): the three row-wise GEMMs on
+// gemm_pw.hip, the per-video attention by P.attn.  No positions, no dropout; Y0 exists as planes + per-row moments only and the first
+// LayerNorm is applied in the k1 epilogue.  Wvo: as in forward_dense (the weight-plane block then holds Wvo's planes in Wv's place).
+static int forward_planes(const Geometry& G, const ForwardPlan& P, float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host,
+                          const int32_t* seq_off_dev, const sumk_vasnet_weights* w, const sumk_vasnet_opts* opts, float* scores, char* ws,
+                          char* tb, hipStream_t stream, const float* Wvo) {
+  const VasnetWs& L = G.L;
+  const int R = G.R, np = P.np;
+  const WPlanes& wl = P.wl; const PwExtra& px = P.px; const PwLong& pl = P.pl;
+  const StepBufs B = step_bufs(ws, tb, L, opts, 0);
+  const char* const wp = (const char*)opts->wplanes;
+  const bool strips = P.attn == ATTN_STRIPS;
+  // CTX planes span the Y0 / Y1 regions, Y0's planes take the (by then dead) fp32 Q/K/V region, the small per-row arrays live in Z;
+  // on strips both have regions of their own behind the carve-up
+  char* const ctxp = strips ? ws + px.ctx : ws + L.y0;
+  char* const y0p = (strips && Wvo) ? ws + px.ctx : strips ? ws + px.qkv : ws + L.qkv;          // ([Q | K | V]'s planes are dead once the context exists; folded: the context strips wrote Y0's planes)
+  float* const mom = B.Z;                                                       // float2[R][slots]
+  float* const stats = B.Z + align_up((size_t)R * (D / 16) * 2, 64);            // float2[R]
+  float* const part = stats + align_up((size_t)R * 2, 64);                      // float4[R][D / 64]
+  auto row_stats = [&](int slots) -> int {     // Y0's moments -> {mean, rstd}
+    hipLaunchKernelGGL(ln_row_stats_kernel, dim3((R + 31) / 32), dim3(256), 0, stream, (const float2*)mom, slots, R, D, opts->eps, (float2*)stats);
+    SUMK_HIP(hipGetLastError());
+    return SUMK_OK;
+  };
+  auto proj = [&](int n_cols) {                // 1: the first n_cols columns of [Q | K | V] = X [Wq; Wk; Wv]^T, from planes
+    PwLaunch g; g.A = opts->xplanes; g.a_rows = R; g.B = wp + wl.wqkv; g.b_rows = 3 * (int64_t)D; g.M = R; g.N = n_cols; g.K = D; g.np = np;
+    g.prof_tag = SUMK_PROF_GEMM_QKV;
+    return g;
+  };
+  if (tb == ws) launch_setup(G, D, n_seq, seq_off_dev, tb, stream);
+  if (strips) {  // 1-4 on planes (attn_pw.hip, T <= 320): projection -> planes of [Q | K | V]; logits + softmax -> alpha planes; alpha . V -> context planes
+    PwLaunch g = proj(3 * D);
+    // the context kernel multiplies V rows up to 31 past the last video's end by alpha = 0: every row up to the pitch is stored (zeros: x's pad rows are
+    // zero) and the slack a read past the LAST sub-array lands in is cleared -- 0 x (stale NaN bits) would be NaN
+    g.O = ws + px.qkv; g.o_rows = R; g.o_store_rows = pw_rows_pitch(R);
+    SUMK_HIP(hipMemsetAsync(ws + px.qkv + pw_planes_bytes(R, 3 * D, np) - 8192, 0, 8192, stream));
+    SUMK_TRY(launch_gemm_pw(PW_PLANES, g, stream));
+    prof_begin(SUMK_PROF_GEMM_QKT, stream);
+    SUMK_TRY(launch_attn_pw_logits(np, ws + px.qkv, R, D, nullptr, ws + px.ap, B.seq, n_seq, G.t_max, opts->scale, opts->ignore_self, opts->aperture, stream));
+    prof_end(SUMK_PROF_GEMM_QKT, stream);
+    prof_begin(SUMK_PROF_GEMM_PV, stream);
+    // folded: "V" = x Wvo^T, so alpha . V + x IS Y0 -- it leaves as planes with its LayerNorm moments (D / 32 slots per row)
+    SUMK_TRY(launch_attn_pw_context(np, ws + px.qkv, R, D, ws + px.ap, ws + px.ctx, B.seq, n_seq, G.t_max, stream, 1, Wvo ? x : nullptr, Wvo ? D : 0, Wvo ? mom : nullptr));
+    prof_end(SUMK_PROF_GEMM_PV, stream);
+    if (Wvo) SUMK_TRY(row_stats(D / 32));      // (5 happened in the context strips)
+  } else if (P.attn == ATTN_LONG) {
+    // Long videos, one at a time: logits and context on the plane GEMM itself; the context leaves as planes (rows of the video inside
+    // the batch's CTX planes), so the output projection below reads them as on the strip path.
+    if (pl.qk_direct) {  // 1: [Q | K] straight to planes (every video's Q and K are row ranges of them), V as fp32 (R x D: its transpose is split per video)
+      PwLaunch g = proj(2 * D);
+      g.O = ws + pl.qk; g.o_rows = R; g.o_store_rows = pw_rows_pitch(R);
+      SUMK_HIP(hipMemsetAsync(ws + pl.qk + pw_planes_bytes(R, 2 * D, np) - 8192, 0, 8192, stream));      // the last video's logits tiles read key rows past the array's last sub-array
+      SUMK_TRY(launch_gemm_pw(PW_PLANES, g, stream));
+      PwLaunch gv = proj(D); gv.B = wp + wl.wqkv + (size_t)2 * D * 16; gv.C = B.QKV; gv.ldc = D;
+      SUMK_TRY(launch_gemm_pw(PW_F32, gv, stream));
+    } else {  // 1: fp32 output: each video's Q, K and V are split below
+      PwLaunch g = proj(3 * D); g.C = B.QKV; g.ldc = 3 * D;
+      SUMK_TRY(launch_gemm_pw(PW_F32, g, stream));
+    }
     float* const Es = (float*)(ws + pl.e);
     for (int q = 0; q < n_seq; ++q) {
       const int r0 = seq_off_host[q], T = seq_off_host[q + 1] - r0;
@@ -1603,11 +1741,11 @@ static int vasnet_forward_impl(float* x, int32_t D, int32_t n_seq, const int32_t
       const char* qpl; const char* kpl; int64_t qrows, krows;
       if (pl.qk_direct) {
         qpl = ws + pl.qk + (size_t)r0 * 16; kpl = ws + pl.qk + (size_t)(D >> 4) * np * 2 * (pw_rows_pitch(R) * 16) + (size_t)r0 * 16; qrows = krows = R;
-        SUMK_TRY(split_planes_t(QKV + (size_t)r0 * D, T, D, D, np, ws + pl.vt, Kp, stream));
+        SUMK_TRY(split_planes_t(B.QKV + (size_t)r0 * D, T, D, D, np, ws + pl.vt, Kp, stream));
       } else {
-        SUMK_TRY(split_planes(QKV + (size_t)r0 * 3 * D, T, D, 3 * D, np, ws + pl.qp, stream));
-        SUMK_TRY(split_planes_pitched(QKV + (size_t)r0 * 3 * D + D, T, D, 3 * D, np, ws + pl.kp, Tn, stream));
-        SUMK_TRY(split_planes_t(QKV + (size_t)r0 * 3 * D + 2 * D, T, D, 3 * D, np, ws + pl.vt, Kp, stream));
+        SUMK_TRY(split_planes(B.QKV + (size_t)r0 * 3 * D, T, D, 3 * D, np, ws + pl.qp, stream));
+        SUMK_TRY(split_planes_pitched(B.QKV + (size_t)r0 * 3 * D + D, T, D, 3 * D, np, ws + pl.kp, Tn, stream));
+        SUMK_TRY(split_planes_t(B.QKV + (size_t)r0 * 3 * D + 2 * D, T, D, 3 * D, np, ws + pl.vt, Kp, stream));
         qpl = ws + pl.qp; kpl = ws + pl.kp; qrows = T; krows = Tn;
       }
       {  // 2: raw logits  E_s = Q_s K_s^T  (T x Tn, fp32)
@@ -1623,151 +1761,61 @@ static int vasnet_forward_impl(float* x, int32_t D, int32_t n_seq, const int32_t
         SUMK_TRY(launch_gemm_pw(PW_PLANES, g, stream));
       }
     }
-  } else
-  if (pw_attn) {
-  } else
-  if (G.attn_fused) {  // 2-4 in one launch per (video, 64-row strip): logits, softmax (+ dropout), context
-    AttnStripArgs at;
-    const unsigned short* qkv16 = (const unsigned short*)(ws + L.qkv16);
-    at.A16 = qkv16; at.lda = 3 * D; at.B16 = qkv16 + D; at.ldb = 3 * D; at.C16 = qkv16 + 2 * D; at.ldc = 3 * D;
-    at.O16 = (unsigned short*)(ws + L.ctx16); at.ldo = D; at.E = E; at.P16 = (unsigned short*)(ws + L.p16);
-    at.seq = seq; at.n_seq = n_seq; at.strips = (G.t_max + 63) / 64; at.D = D;
-    at.scale = opts->scale; at.ignore_self = opts->ignore_self; at.aperture = opts->aperture; at.drop = drop;
-    SUMK_TRY(launch_attn_strip(false, at, stream));
-  } else {
-  {  // 2: logits per video
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = QKV; g.B[0] = QKV; g.C = E; g.probs = tabs + TB_S * n_seq; g.nprob = n_seq; g.small_tile = G.cfg_s;
-    g.total_tiles = G.tiles_s; g.prof_tag = SUMK_PROF_GEMM_QKT;
-    if (b16) { g.A = g.B[0] = (const float*)(ws + L.qkv16); g.src16 = 1; }
-    SUMK_TRY(launch_gemm(GEMM_NT, EPI_NONE, g, stream));
-  }
-  // 3: softmax (+ dropout of alpha into E2 when training with p > 0)
-  {
-    int t_max = 0;
-    for (int q = 0; q < n_seq; ++q) t_max = std::max(t_max, seq_off_host[q + 1] - seq_off_host[q]);
-    const dim3 sg((R + 3) / 4), sb(256);
-    float* e2p = use_e2 ? E2 : nullptr;
-    unsigned short* p16 = b16 ? (unsigned short*)(ws + L.p16) : nullptr;
-#define SUMK_SOFTMAX(NR) hipLaunchKernelGGL(vasnet_softmax_kernel<NR>, sg, sb, 0, stream, E, e2p, seq, (const int32_t*)(tb + L.row_seq), n_seq, R, opts->scale, opts->ignore_self, opts->aperture, drop, p16, (const float*)E, 0, (int64_t)0)
-    if (t_max <= 256) SUMK_SOFTMAX(4); else if (t_max <= 512) SUMK_SOFTMAX(8); else if (t_max <= 1024) SUMK_SOFTMAX(16); else SUMK_SOFTMAX(0);
-#undef SUMK_SOFTMAX
-  }
-  }
-  // Fused inference tail (128x128 tiles, no dropout; SUMK_FUSED_HEAD=0 / SUMK_FUSED_LN=0 are the A/B switches, training always
-  // runs the separate kernels):
-  //  (b) fused_tail: the k1 epilogue reduces relu(.) to the LayerNorm + k2 moments -- Z never exists;
-  //  (a) fused_ln:   the epilogue of the GEMM that produces Y0 also emits its per-row moments, one prep launch folds the first
-  //      LayerNorm's gain into W1 and turns the moments into {mean, rstd}, and the k1 GEMM reads the RAW Y0: the LayerNorm is
-  //      applied to the product in the k1 epilogue -- no LayerNorm kernel, Y1 never exists.  Its scratch (moments, folded
-  //      weights, c1 / c2, stats) lives in the unused Y1 region, which must be large enough (R >~ 1.1 D).
-  static const bool fused_head_on = !(getenv("SUMK_FUSED_HEAD") && getenv("SUMK_FUSED_HEAD")[0] == '0');
-  static const bool fused_ln_on = !(getenv("SUMK_FUSED_LN") && getenv("SUMK_FUSED_LN")[0] == '0');
-  const bool fused_tail = fused_head_on && !training && drop.thr == 0 && G.st_d == 0 && D % 64 == 0;
-  // producer of Y0: the output projection (128x128 tiles, D / 32 moment slots per row) or, on the folded path, the per-video
-  // alpha.(X Wvo) product with the residual (64x64 tiles, D / 16 slots)
-  const int ln_slots = Wvo ? D / 16 : D / 32;
-  const size_t ln_mom_f = align_up((size_t)R * ln_slots * 2, 64), ln_w_f = (size_t)D * D, ln_c_f = align_up((size_t)2 * D, 64);
-  const bool fused_ln = pw || (fused_tail && fused_ln_on && (!Wvo || G.cfg_pv == 1) && ln_mom_f + ln_w_f + ln_c_f + (size_t)2 * R <= (size_t)R * D);
-  // plane path: CTX planes span the Y0 / Y1 regions, Y0's planes take the (by then dead) fp32 Q/K/V region, the small per-row arrays live in Z
-  char* const pw_ctxp = pw_attn ? ws + px.ctx : ws + L.y0;
-  char* const pw_y0p = (pw_attn && Wvo) ? ws + px.ctx : pw_attn ? ws + px.qkv : ws + L.qkv;          // ([Q | K | V]'s planes are dead once the context exists; folded: the context strips wrote Y0's planes)
-  float* const pw_mom = Z;                                                        // float2[R][slots]
-  float* const pw_stats = Z + align_up((size_t)R * (D / 16) * 2, 64);             // float2[R]
-  float* const pw_part = pw_stats + align_up((size_t)R * 2, 64);                  // float4[R][D / 64]
-  float* ln_moments = pw ? pw_mom : Y1;
-  float* ln_W1g = Y1 + ln_mom_f;
-  float* ln_c1 = ln_W1g + ln_w_f;
-  float* ln_stats = ln_c1 + ln_c_f;
-  if (!G.attn_fused && !pw_attn && !pw_long) {  // 4: context
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = use_e2 ? E2 : E; g.B[0] = QKV; g.C = Wvo ? Y0 : CTX; g.R = x; g.probs = tabs + TB_PV * n_seq; g.nprob = n_seq; g.small_tile = G.cfg_pv;
-    g.total_tiles = G.tiles_pv; g.prof_tag = SUMK_PROF_GEMM_PV;
-    if (Wvo && fused_ln) g.moments = ln_moments;
-    if (b16) { g.A = (const float*)(ws + L.p16); g.B[0] = (const float*)(ws + L.qkv16); g.src16 = 1; g.C16 = ws + L.ctx16; g.C = nullptr; }
-    SUMK_TRY(launch_gemm(GEMM_NN, Wvo ? (fused_ln ? EPI_RESIDUAL_MOMENTS : EPI_RESIDUAL) : EPI_NONE, g, stream));
-    if (Wvo && pw) {        // folded plane path: Y0 (fp32, with its moments) -> {mean, rstd}, and its planes for k1
-      hipLaunchKernelGGL(ln_row_stats_kernel, dim3((R + 31) / 32), dim3(256), 0, stream, (const float2*)pw_mom, ln_slots, R, D, opts->eps, (float2*)pw_stats);
-      SUMK_HIP(hipGetLastError());
-      SUMK_TRY(split_planes(Y0, R, D, D, np, pw_y0p, stream));
-    } else
-    if (Wvo && fused_ln) {
-      hipLaunchKernelGGL(ln_fold_stats_kernel, dim3(D + (R + 31) / 32), dim3(256), 0, stream, w->W1, w->ln_w, w->ln_b, D, ln_W1g, ln_c1,
-                         ln_c1 + D, (const float2*)ln_moments, ln_slots, R, opts->eps, (float2*)ln_stats);
-      SUMK_HIP(hipGetLastError());
+  } else {  // ATTN_GROUPED: the projection leaves as fp32 and 2-4 run on the grouped in-loop kernels, as in forward_dense
+    PwLaunch gq = proj(3 * D); gq.C = B.QKV; gq.ldc = 3 * D;
+    SUMK_TRY(launch_gemm_pw(PW_F32, gq, stream));
+    SUMK_TRY(attn_grouped(G, B, n_seq, opts, x, ws, Wvo != nullptr, mom, stream));     // 2-4 (folded: Y0 in fp32 with its moments, D / 16 slots per row)
+    if (Wvo) {  // Y0 -> {mean, rstd}, and its planes for k1
+      SUMK_TRY(row_stats(D / 16));
+      SUMK_TRY(split_planes(B.Y0, R, D, D, np, y0p, stream));
+    } else {    // CTX is split once for the output projection
+      SUMK_TRY(split_planes(B.CTX, R, D, D, np, ctxp, stream));
     }
   }
-  if (pw_attn && Wvo) {   // (4 + 5 happened in the context strips) moments -> {mean, rstd}
-    hipLaunchKernelGGL(ln_row_stats_kernel, dim3((R + 31) / 32), dim3(256), 0, stream, (const float2*)pw_mom, D / 32, R, D, opts->eps, (float2*)pw_stats);
-    SUMK_HIP(hipGetLastError());
-  } else
-  if (pw && !Wvo) {  // 5: output projection + residual from planes: CTX is split once, Y0 leaves as planes + per-row moments only
-    if (!pw_attn && !pw_long) SUMK_TRY(split_planes(CTX, R, D, D, np, pw_ctxp, stream));
-    PwLaunch g; g.A = pw_ctxp; g.a_rows = R; g.B = wp + wl.wo; g.b_rows = D; g.M = R; g.N = D; g.K = D; g.np = np;
-    g.R = x; g.ldr = D; g.moments = pw_mom; g.O = pw_y0p; g.o_rows = R; g.prof_tag = SUMK_PROF_GEMM_OPROJ;
+  if (!Wvo) {  // 5: output projection + residual from planes: Y0 leaves as planes + per-row moments only
+    PwLaunch g; g.A = ctxp; g.a_rows = R; g.B = wp + wl.wo; g.b_rows = D; g.M = R; g.N = D; g.K = D; g.np = np;
+    g.R = x; g.ldr = D; g.moments = mom; g.O = y0p; g.o_rows = R; g.prof_tag = SUMK_PROF_GEMM_OPROJ;
     SUMK_TRY(launch_gemm_pw(PW_RES_MOM_PLANES, g, stream));
-    hipLaunchKernelGGL(ln_row_stats_kernel, dim3((R + 31) / 32), dim3(256), 0, stream, (const float2*)pw_mom, D / 64, R, D, opts->eps, (float2*)pw_stats);
-    SUMK_HIP(hipGetLastError());
-  } else
-  if (!Wvo) {  // 5: output projection + residual
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = CTX; g.B[0] = w->Wo; g.C = Y0; g.R = x; g.probs = prow + RP_DD; g.small_tile = G.st_d;
-    g.total_tiles = gemm_tiles(R, D, G.st_d); g.xcd_M = R; g.xcd_N = D; g.prof_tag = SUMK_PROF_GEMM_OPROJ;
-    g.lean = lean_rows;
-    if (fused_ln) {
-      g.moments = ln_moments;
-      SUMK_TRY(launch_gemm(GEMM_NT, EPI_RESIDUAL_MOMENTS, g, stream));
-      hipLaunchKernelGGL(ln_fold_stats_kernel, dim3(D + (R + 31) / 32), dim3(256), 0, stream, w->W1, w->ln_w, w->ln_b, D, ln_W1g, ln_c1,
-                         ln_c1 + D, (const float2*)ln_moments, ln_slots, R, opts->eps, (float2*)ln_stats);
-      SUMK_HIP(hipGetLastError());
-    } else {
-      if (b16) to_b16(g, ws + L.ctx16, Wo16, R, D, prow, RP_DD_W);
-      SUMK_TRY(launch_gemm(GEMM_NT, EPI_RESIDUAL, g, stream));
-    }
+    SUMK_TRY(row_stats(D / 64));
   }
-  // 6: dropout + LayerNorm
-  // (b16: the LayerNorm output is consumed by bf16-source GEMMs only -- k1 here, dW1 in the backward -- so only its bf16 form is written)
-  if (!fused_ln) launch_ln_rows<false>(Y0, b16 ? nullptr : Y1, w->ln_w, w->ln_b, nullptr, nullptr, nullptr, R, D, opts->eps, stats, drop, 1u, stream,
-                                       b16 ? (unsigned short*)(ws + L.y116) : nullptr);
-  // 7 + 8 fused (inference, 128x128 tiles): k1 + bias + ReLU with the LayerNorm + k2 moments taken in the GEMM epilogue -- the
-  // (R, D) activation matrix is neither written (49 MB in the lock-stepped store burst of this single-round launch) nor read
-  // back by a LayerNorm kernel.
-  if (pw) {   // 7 + 8: k1 on the RAW Y0 planes with the LayerNorm applied to the product, moments of relu(.) per 64-column slot, then the head
-    PwLaunch g; g.A = pw_y0p; g.a_rows = R; g.B = wp + wl.w1g; g.b_rows = D; g.M = R; g.N = D; g.K = D; g.np = np;
-    g.bias = (const float*)(wp + wl.biasc); g.gw = (const float*)(wp + wl.gw); g.ln_c1 = (const float*)(wp + wl.c1); g.ln_stats = pw_stats;
-    g.head_part = pw_part; g.prof_tag = SUMK_PROF_GEMM_K1;
+  {  // 7 + 8: k1 on the RAW Y0 planes with the LayerNorm applied to the product, moments of relu(.) per 64-column slot, then the head
+    PwLaunch g; g.A = y0p; g.a_rows = R; g.B = wp + wl.w1g; g.b_rows = D; g.M = R; g.N = D; g.K = D; g.np = np;
+    g.bias = (const float*)(wp + wl.biasc); g.gw = (const float*)(wp + wl.gw); g.ln_c1 = (const float*)(wp + wl.c1); g.ln_stats = stats;
+    g.head_part = part; g.prof_tag = SUMK_PROF_GEMM_K1;
     SUMK_TRY(launch_gemm_pw(PW_HEAD, g, stream));
-    hipLaunchKernelGGL(head_finalize_kernel, dim3((R + 31) / 32), dim3(256), 0, stream, (const float4*)pw_part, D / 64, R, D, w->ln_w,
+    hipLaunchKernelGGL(head_finalize_kernel, dim3((R + 31) / 32), dim3(256), 0, stream, (const float4*)part, D / 64, R, D, w->ln_w,
                        w->ln_b, w->w2, w->b2, opts->eps, scores);
     SUMK_HIP(hipGetLastError());
-    return SUMK_OK;
   }
-  if (fused_tail) {
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = Y1; g.B[0] = w->W1; g.bias0[0] = w->b1; g.bias1[0] = w->ln_w; g.bias1[1] = w->w2;
-    if (fused_ln) { g.A = Y0; g.B[0] = ln_W1g; g.ln_stats = ln_stats; g.ln_c1 = ln_c1; g.ln_c2 = ln_c1 + D; }
-    g.C = Z;                       // reused as float4[R][D / 32] moments (R * D / 8 floats of the R * D region)
-    g.probs = prow + RP_DD; g.small_tile = 0;
-    g.total_tiles = gemm_tiles(R, D, 0); g.xcd_M = R; g.xcd_N = D; g.prof_tag = SUMK_PROF_GEMM_K1;
-    g.lean = lean_rows;
-    SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS_RELU_HEAD, g, stream));
-    hipLaunchKernelGGL(head_finalize_kernel, dim3((R + 31) / 32), dim3(256), 0, stream, (const float4*)Z, D / 32, R, D, w->ln_w,
-                       w->ln_b, w->w2, w->b2, opts->eps, scores);
-    SUMK_HIP(hipGetLastError());
-    return SUMK_OK;
-  }
-  {  // 7: k1 + bias + ReLU
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = Y1; g.B[0] = w->W1; g.bias0[0] = w->b1; g.C = Z; g.probs = prow + RP_DD; g.small_tile = G.st_d;
-    g.total_tiles = gemm_tiles(R, D, G.st_d); g.xcd_M = R; g.xcd_N = D; g.prof_tag = SUMK_PROF_GEMM_K1;
-    g.lean = lean_rows;
-    if (b16) to_b16(g, ws + L.y116, W116, R, D, prow, RP_DD_W);
-    SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS_RELU, g, stream));
-  }
-  // 8: dropout + LayerNorm (same weights) + k2 + sigmoid
-  launch_ln_rows<true>(Z, training ? (float*)(ws + L.scores) : nullptr, w->ln_w, w->ln_b, w->w2, w->b2, scores, R, D, opts->eps, stats ? stats + 2 * (size_t)R : nullptr, drop, 2u, stream);
-  SUMK_HIP(hipGetLastError());
   return SUMK_OK;
+}
+
+// Argument checks, the plan, and the path it names.
+static int vasnet_forward_impl(float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_vasnet_weights* w,
+                               const sumk_vasnet_opts* opts, const float* pos_table, const int32_t* pos_rows, float* scores, void* workspace,
+                               size_t workspace_bytes, int32_t training, void* stream_, const float* Wvo) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SUMK_ARG(Wvo == nullptr || !training, "vasnet_forward: the folded projection is an inference-only path");
+  SUMK_ARG(x && seq_off_dev && w && opts && scores && workspace, "vasnet_forward: null pointer");
+  SUMK_ARG(w->Wk && w->Wq && w->Wv && w->Wo && w->W1 && w->b1 && w->w2 && w->b2 && w->ln_w && w->ln_b, "vasnet_forward: null weight");
+  SUMK_ARG((pos_table == nullptr) == (pos_rows == nullptr), "vasnet_forward: pos_table and pos_rows go together");
+  SUMK_ARG(opts->dropout_p >= 0.f && opts->dropout_p < 1.f, "vasnet_forward: dropout_p=%f out of [0,1)", opts->dropout_p);
+  SUMK_ARG(opts->dropout_p == 0.f || training, "vasnet_forward: dropout needs training mode");
+  SUMK_ARG(opts->precision >= SUMK_PRECISION_FP32 && opts->precision <= SUMK_PRECISION_MAX, "vasnet_forward: unknown precision %d", opts->precision);
+  Geometry G;
+  SUMK_TRY(geometry(D, n_seq, seq_off_host, training, opts->precision, &G));
+  const ForwardPlan P = plan_forward(G, D, opts, training, pos_table != nullptr, Wvo != nullptr, workspace_bytes);
+  if (workspace_bytes < P.need) {     // (only ever the core size: the plan takes a path with extra regions when they are there)
+    set_error("vasnet_forward: workspace %zu < required %zu", workspace_bytes, P.need);
+    return SUMK_ERR_WORKSPACE;
+  }
+  char* ws = (char*)workspace;
+  char* tb = opts->tables ? (char*)opts->tables : ws;      // table base: the caller's prebuilt block, or the front of the workspace (built per call)
+  switch (P.path) {
+    case PATH_SK: return forward_sk(G, x, D, n_seq, seq_off_dev, w, opts, pos_table, pos_rows, scores, ws, tb, training, stream);
+    case PATH_PLANES: return forward_planes(G, P, x, D, n_seq, seq_off_host, seq_off_dev, w, opts, scores, ws, tb, stream, Wvo);
+    default: return forward_dense(G, P, x, D, n_seq, seq_off_dev, w, opts, pos_table, pos_rows, scores, ws, tb, training, stream, Wvo);
+  }
 }
 
 extern "C" int sumk_vasnet_forward(float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host,
@@ -1775,8 +1823,7 @@ extern "C" int sumk_vasnet_forward(float* x, int32_t D, int32_t n_seq, const int
                                    const sumk_vasnet_opts* opts, const float* pos_table, const int32_t* pos_rows,
                                    float* scores, void* workspace, size_t workspace_bytes, int32_t training,
                                    void* stream) {
-  return vasnet_forward_impl(x, D, n_seq, seq_off_host, seq_off_dev, w, opts, pos_table, pos_rows, scores, workspace,
-                             workspace_bytes, training, stream, nullptr);
+  return vasnet_forward_impl(x, D, n_seq, seq_off_host, seq_off_dev, w, opts, pos_table, pos_rows, scores, workspace, workspace_bytes, training, stream, nullptr);
 }
 
 extern "C" int sumk_vasnet_forward_folded(float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host,
@@ -1784,8 +1831,7 @@ extern "C" int sumk_vasnet_forward_folded(float* x, int32_t D, int32_t n_seq, co
                                           const sumk_vasnet_opts* opts, const float* pos_table, const int32_t* pos_rows,
                                           float* scores, void* workspace, size_t workspace_bytes, void* stream) {
   SUMK_ARG(Wvo != nullptr, "vasnet_forward_folded: null folded weight");
-  return vasnet_forward_impl(x, D, n_seq, seq_off_host, seq_off_dev, w, opts, pos_table, pos_rows, scores, workspace,
-                             workspace_bytes, 0, stream, Wvo);
+  return vasnet_forward_impl(x, D, n_seq, seq_off_host, seq_off_dev, w, opts, pos_table, pos_rows, scores, workspace, workspace_bytes, 0, stream, Wvo);
 }
 
 template <bool HEAD>
@@ -1827,6 +1873,142 @@ int launch_ln_head_bwd(int D, int R, const float* Z, const float* stats, const f
 }
 }  // namespace sumk
 
+// The small-batch backward: the stages of backward_dense, every GEMM an SK launch over the tables the forward built.  No dx.
+static int backward_sk(const Geometry& G, const float* x, int32_t D, int32_t n_seq, const sumk_vasnet_weights* w, const sumk_vasnet_opts* opts,
+                       const float* dscores, const sumk_vasnet_grads* gr, char* ws, char* tb, hipStream_t stream, void* tail_grads_ready_event) {
+  const VasnetWs& L = G.L;
+  const int R = G.R;
+  const StepBufs B = step_bufs(ws, tb, L, opts, 1);
+  int nw = 0;
+  SUMK_TRY(launch_ln_bwd<true>(D, R, B.Z, B.stats + 2 * (size_t)R, w->ln_w, w->ln_b, nullptr, w->w2, B.scores, dscores, B.dZ, B.lnpart, B.drop, 2u, &nw, stream));
+  SUMK_TRY(ln_bwd_reduce(B.lnpart, nw, D, gr->ln_w, gr->ln_b, gr->w2, gr->b2, gr->b1, stream));
+  float* scratch = (float*)(ws + L.sk_part);
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NN, EPI_NONE, SR_DY1, -1, SkCall{B.dZ, {w->W1}, {scratch}, -1}, stream));     // dY1 = dZ W1 as K-slice slabs: the LayerNorm backward kernel adds them
+  SUMK_TRY(launch_ln_bwd<false>(D, R, B.Y0, B.stats, w->ln_w, w->ln_b, scratch, nullptr, nullptr, nullptr, B.dY0, B.lnpart, B.drop, 1u, &nw, stream, nullptr,
+                                G.P.row[SR_DY1].S, (int64_t)R * D));
+  SUMK_TRY(ln_bwd_reduce(B.lnpart, nw, D, gr->ln_w, gr->ln_b, nullptr, nullptr, nullptr, stream));
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_TN, EPI_ACCUM, SR_DWO1, -1, SkCall{B.dY0, {B.CTX}, {gr->Wo, gr->W1}, -1}, stream));     // dWo += dY0^T CTX and dW1 += dZ^T Y1 (group 1)
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NN, EPI_NONE, SR_DCTX, -1, SkCall{B.dY0, {w->Wo}, {B.dCTX}, -1}, stream));     // dCTX = dY0 Wo
+  if (tail_grads_ready_event) SUMK_HIP(hipEventRecord((hipEvent_t)tail_grads_ready_event, stream));
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_TN, EPI_NONE, -1, TB_DV, SkCall{B.use_e2 ? B.E2 : B.E, {B.dCTX}, {B.dQKV}, -1}, stream));     // dV = alphaD^T dC
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NT, EPI_NONE, -1, TB_DP, SkCall{B.dCTX, {B.QKV}, {scratch}, -1}, stream));     // dAlphaD = dC V^T as slabs: the softmax backward kernel adds them
+  launch_softmax_bwd(softmax_nr(G.t_max), B, n_seq, R, opts, nullptr, scratch, G.P.seq[TB_DP].S, (int64_t)L.e_elems, stream);
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NN, EPI_NONE, -1, TB_DQ, SkCall{B.E2, {B.QKV}, {B.dQKV}, -1}, stream));     // dQ = dS K
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_TN, EPI_NONE, -1, TB_DK, SkCall{B.E2, {B.QKV}, {B.dQKV}, -1}, stream));     // dK = dS^T Q
+  SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_TN, EPI_ACCUM, SR_DWQKV, -1, SkCall{B.dQKV, {x}, {gr->Wq, gr->Wk, gr->Wv}, -1}, stream));     // d[Wq;Wk;Wv] += dQKV^T X
+  SUMK_HIP(hipGetLastError());
+  return SUMK_OK;
+}
+
+// The large-batch backward, stage by stage in reverse (n': the backward of forward stage n); also a small batch's when dx is asked for.
+static int backward_dense(const Geometry& G, const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_dev, const sumk_vasnet_weights* w,
+                          const sumk_vasnet_opts* opts, const float* dscores, const sumk_vasnet_grads* gr, float* dx, char* ws, char* tb,
+                          hipStream_t stream, void* tail_grads_ready_event) {
+  const VasnetWs& L = G.L;
+  const int R = G.R;
+  const StepBufs B = step_bufs(ws, tb, L, opts, 1);
+  // K-slice tables of the two weight-gradient launches (B.pskw): in the table block; prebuilt when the caller keeps the block (opts->tables)
+  const bool skw_ready = tb != ws;
+  int nw = 0;
+  // bf16-source row-wise GEMMs (see forward_dense): dZ and dY0 are produced in bf16 by the LayerNorm backward kernels, dQKV by the
+  // per-video GEMM epilogues; fp32 dZ is never needed, fp32 dY0 only for the residual branch of dx
+  const bool b16 = G.b16;
+  const float* x16 = (G.b16 && opts->x16) ? (const float*)opts->x16 : (const float*)(ws + L.x16);
+  const unsigned short* Wqkv16 = (const unsigned short*)(ws + L.w16);
+  const float *Wo16 = (const float*)(Wqkv16 + (size_t)3 * D * D), *W116 = (const float*)(Wqkv16 + (size_t)4 * D * D);
+  const float *CTX16 = (const float*)(ws + L.ctx16), *Y116 = (const float*)(ws + L.y116);
+  unsigned short *dZ16 = (unsigned short*)(ws + L.dz16), *dY016 = (unsigned short*)(ws + L.dy016), *dQKV16 = (unsigned short*)(ws + L.dqkv16);
+  if (G.sk && tb == ws) launch_setup(G, D, n_seq, seq_off_dev, tb, stream);   // (a small batch with dx: the large-batch tables were not built by the SK forward)
+  // 8': head + second LayerNorm + dropout + ReLU  ->  dZ (w.r.t. the k1 pre-activation), dw2, db2, dgamma, dbeta
+  SUMK_TRY(launch_ln_bwd<true>(D, R, B.Z, B.stats + 2 * (size_t)R, w->ln_w, w->ln_b, nullptr, w->w2, B.scores, dscores, b16 ? nullptr : B.dZ, B.lnpart,
+                               B.drop, 2u, &nw, stream, b16 ? dZ16 : nullptr));
+  SUMK_TRY(ln_bwd_reduce(B.lnpart, nw, D, gr->ln_w, gr->ln_b, gr->w2, gr->b2, gr->b1, stream));   // db1 = column sums of dZ, from the same slots
+  // 7': k1 -- dY1 = dZ . W1 (its weight gradient is taken together with the output projection's below: one split-K launch)
+  {
+    GemmLaunch g; g.precision = opts->precision;
+    g.A = B.dZ; g.B[0] = w->W1; g.C = B.dY1; g.probs = B.prow + RP_DD; g.small_tile = G.st_d; g.total_tiles = gemm_tiles(R, D, G.st_d); g.xcd_M = R; g.xcd_N = D;
+    if (b16) to_b16(g, dZ16, W116, R, D, B.prow, RP_DD_W);
+    SUMK_TRY(launch_gemm(GEMM_NN, EPI_NONE, g, stream));
+  }
+  // 6': first LayerNorm + dropout -> dY0 (gradient of the residual sum)
+  SUMK_TRY(launch_ln_bwd<false>(D, R, B.Y0, B.stats, w->ln_w, w->ln_b, B.dY1, nullptr, nullptr, nullptr, (b16 && !dx) ? nullptr : B.dY0, B.lnpart, B.drop, 1u, &nw, stream,
+                                b16 ? dY016 : nullptr));
+  SUMK_TRY(ln_bwd_reduce(B.lnpart, nw, D, gr->ln_w, gr->ln_b, nullptr, nullptr, nullptr, stream));
+  // 5' + 7': dWo += dY0^T CTX and dW1 += dZ^T Y1 -- two (D x D) products over all R rows in ONE split-K launch (twice as long K
+  // slices per block, one slab reduce) -- then dCTX = dY0 . Wo (+ residual branch into dx)
+  {
+    const float* const As[2] = {b16 ? (const float*)dY016 : B.dY0, b16 ? (const float*)dZ16 : B.dZ};
+    const float* const Bs[2] = {b16 ? CTX16 : B.CTX, b16 ? Y116 : B.Y1};
+    float* out[4] = {gr->Wo, gr->W1, nullptr, nullptr};
+    SUMK_TRY(gemm_tn_splitk_accum_multi(2, As, Bs, D, D, D, D, R, B.slab, L.slab_elems, B.pskw, SPLITK_PROBS, out, D, D, 1.f, stream, opts->precision, b16,
+                                        skw_ready ? SPLITK_TABLE_READY : SPLITK_BUILD_AND_RUN));
+    GemmLaunch g; g.precision = opts->precision;  // dCTX = dY0 . Wo
+    g.A = B.dY0; g.B[0] = w->Wo; g.C = B.dCTX; g.probs = B.prow + RP_DD; g.small_tile = G.st_d; g.total_tiles = gemm_tiles(R, D, G.st_d); g.xcd_M = R; g.xcd_N = D;
+    if (b16) { to_b16(g, dY016, Wo16, R, D, B.prow, RP_DD_W); g.C16 = ws + L.dctx16; g.C = nullptr; }
+    SUMK_TRY(launch_gemm(GEMM_NN, EPI_NONE, g, stream));
+  }
+  // Wo, W1, b1, w2, b2 (the tail of the parameter order) are final from here on: a data-parallel caller starts their
+  // all-reduce on a side stream now, under the attention backward and the QKV weight gradients (60 % of the bucket).
+  if (tail_grads_ready_event) SUMK_HIP(hipEventRecord((hipEvent_t)tail_grads_ready_event, stream));
+  if (G.attn_fused) {  // 4' - 2' on strips: dAlphaD, softmax backward and dQ in one launch per (video, 64-row strip); bf16(dLogits) lands beside bf16(alphaD)
+    AttnStripArgs at;
+    const unsigned short* qkv16 = (const unsigned short*)(ws + L.qkv16);
+    at.A16 = (const unsigned short*)(ws + L.dctx16); at.lda = D; at.B16 = qkv16 + 2 * D; at.ldb = 3 * D; at.C16 = qkv16 + D; at.ldc = 3 * D;
+    at.O16 = (unsigned short*)dQKV16; at.ldo = 3 * D; at.E = B.E; at.P16 = (unsigned short*)(ws + L.s16);      // bf16(dLogits): beside P16, not over it
+    at.seq = B.seq; at.n_seq = n_seq; at.strips = (G.t_max + 63) / 64; at.D = D;
+    at.scale = opts->scale; at.ignore_self = opts->ignore_self; at.aperture = opts->aperture; at.drop = B.drop;
+    SUMK_TRY(launch_attn_strip(true, at, stream));
+    // dV = P^T dC and dK = dS^T Q: the two products that contract over the query rows of ALL strips, as ONE launch of 2 n_seq problems
+    // (separately each was 800-960 tiles on 768 resident blocks -- one and a quarter rounds of latency-bound tiles, 25 us per launch)
+    GemmLaunch g; g.precision = opts->precision;
+    g.A = (const float*)(ws + L.p16); g.B[0] = (const float*)(ws + L.dctx16); g.src16 = 1; g.C16 = dQKV16; g.C = nullptr;
+    g.probs = (GemmProb*)(tb + L.prob_dvk); g.nprob = 2 * n_seq; g.small_tile = G.cfg_pv; g.total_tiles = 2 * G.tiles_pv;
+    SUMK_TRY(launch_gemm(GEMM_TN, EPI_NONE, g, stream));
+  } else {
+    {  // 4': dV = alphaD^T dC
+      GemmLaunch g; g.precision = opts->precision;
+      g.A = B.use_e2 ? B.E2 : B.E; g.B[0] = B.dCTX; g.C = B.dQKV; g.probs = B.tabs + TB_DV * n_seq; g.nprob = n_seq; g.small_tile = G.cfg_pv; g.total_tiles = G.tiles_pv;
+      if (b16) { g.A = (const float*)(ws + L.p16); g.B[0] = (const float*)(ws + L.dctx16); g.src16 = 1; g.C16 = dQKV16; g.C = nullptr; }
+      SUMK_TRY(launch_gemm(GEMM_TN, EPI_NONE, g, stream));
+    }
+    {  // ... and dAlphaD = dC V^T, into E2
+      GemmLaunch g; g.precision = opts->precision;
+      g.A = B.dCTX; g.B[0] = B.QKV; g.C = B.E2; g.probs = B.tabs + TB_DP * n_seq; g.nprob = n_seq; g.small_tile = G.cfg_s; g.total_tiles = G.tiles_s;
+      if (b16) { g.A = (const float*)(ws + L.dctx16); g.B[0] = (const float*)(ws + L.qkv16); g.src16 = 1; }
+      SUMK_TRY(launch_gemm(GEMM_NT, EPI_NONE, g, stream));
+    }
+    // 3': softmax (+dropout, +scale) backward, in place on E2 -- the looping instance (NR = 0) at every length
+    // (b16: bf16(dLogits) goes where bf16(alpha) was -- its last reader, the dV product, is queued before this kernel)
+    launch_softmax_bwd(0, B, n_seq, R, opts, b16 ? (unsigned short*)(ws + L.p16) : nullptr, B.E2, 0, 0, stream);
+    // 2': dQ = dS K ; dK = dS^T Q
+    for (int t : {TB_DQ, TB_DK}) {
+      GemmLaunch g; g.precision = opts->precision;
+      g.A = B.E2; g.B[0] = B.QKV; g.C = B.dQKV; g.probs = B.tabs + t * n_seq; g.nprob = n_seq; g.small_tile = G.cfg_pv; g.total_tiles = G.tiles_pv;
+      if (b16) { g.A = (const float*)(ws + L.p16); g.B[0] = (const float*)(ws + L.qkv16); g.src16 = 1; g.C16 = dQKV16; g.C = nullptr; }
+      SUMK_TRY(launch_gemm(t == TB_DQ ? GEMM_NN : GEMM_TN, EPI_NONE, g, stream));
+    }
+  }
+  // 1': projection weights  d[Wq;Wk;Wv] += dQKV^T X
+  {
+    float* out[4] = {gr->Wq, gr->Wk, gr->Wv, nullptr};
+    SUMK_TRY(gemm_tn_splitk_accum(b16 ? (const float*)dQKV16 : B.dQKV, 3 * D, b16 ? x16 : x, D, 3 * D, D, R, B.slab, L.slab_elems, B.pskw + SPLITK_PROBS, SPLITK_PROBS, out, D, D, 1.f,
+                                  stream, opts->precision, b16, skw_ready ? SPLITK_TABLE_READY : SPLITK_BUILD_AND_RUN));
+  }
+  if (dx) {  // dX = dY0 (residual) + dQ Wq + dK Wk + dV Wv
+    SUMK_HIP(hipMemcpyAsync(dx, B.dY0, (size_t)R * D * 4, hipMemcpyDeviceToDevice, stream));
+    const float* Ws[3] = {w->Wq, w->Wk, w->Wv};
+    for (int part = 0; part < 3; ++part) {
+      GemmLaunch g; g.precision = opts->precision;
+      g.A = B.dQKV + (size_t)part * D; g.B[0] = Ws[part]; g.C = dx; g.probs = B.prow + RP_DX; g.small_tile = G.st_d;
+      g.total_tiles = gemm_tiles(R, D, G.st_d); g.xcd_M = R; g.xcd_N = D;
+      if (b16) to_b16(g, dQKV16 + (size_t)part * D, Wqkv16 + (size_t)part * D * D, R, D, B.prow, RP_DX_W);
+      SUMK_TRY(launch_gemm(GEMM_NN, EPI_ACCUM, g, stream));
+    }
+  }
+  SUMK_HIP(hipGetLastError());
+  return SUMK_OK;
+}
+
 extern "C" int sumk_vasnet_backward(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host,
                                     const int32_t* seq_off_dev, const sumk_vasnet_weights* w,
                                     const sumk_vasnet_opts* opts, const float* dscores, const sumk_vasnet_grads* gr,
@@ -1837,200 +2019,13 @@ extern "C" int sumk_vasnet_backward(const float* x, int32_t D, int32_t n_seq, co
   SUMK_ARG(gr->Wk && gr->Wq && gr->Wv && gr->Wo && gr->W1 && gr->b1 && gr->w2 && gr->b2 && gr->ln_w && gr->ln_b,
            "vasnet_backward: null gradient target");
   Geometry G;
-  SUMK_TRY(geometry(D, n_seq, seq_off_host, 1, opts->precision, workspace_bytes, &G));
-  const VasnetWs& L = G.L;
-  if (workspace_bytes < (G.b16 ? L.total : L.total_core)) {
-    set_error("vasnet_backward: workspace %zu < required %zu (needs the training-mode forward's workspace)", workspace_bytes, G.b16 ? L.total : L.total_core);
+  SUMK_TRY(geometry(D, n_seq, seq_off_host, 1, opts->precision, &G));
+  if (workspace_bytes < core_bytes(G)) {
+    set_error("vasnet_backward: workspace %zu < required %zu (needs the training-mode forward's workspace)", workspace_bytes, core_bytes(G));
     return SUMK_ERR_WORKSPACE;
   }
   char* ws = (char*)workspace;
-  const int R = G.R;
-  float* QKV = (float*)(ws + L.qkv);
-  float* E = (float*)(ws + L.e);
-  float* E2 = (float*)(ws + L.e2);
-  float* CTX = (float*)(ws + L.ctx);
-  float* Y0 = (float*)(ws + L.y0);
-  float* Y1 = (float*)(ws + L.y1);
-  float* Z = (float*)(ws + L.z);
-  float* dZ = (float*)(ws + L.dz);
-  float* dY1 = (float*)(ws + L.dy1);
-  float* dY0 = (float*)(ws + L.dy0);
-  float* dCTX = (float*)(ws + L.dctx);
-  float* dQKV = (float*)(ws + L.dqkv);
-  float* lnpart = (float*)(ws + L.lnpart);
-  float* slab = (float*)(ws + L.slab);
-  float* stats = (float*)(ws + L.stats);
-  const float* scores = (const float*)(ws + L.scores);
-  char* tb = opts->tables ? (char*)opts->tables : ws;      // as in the forward
-  SeqInfo* seq = (SeqInfo*)(tb + L.seq);
-  GemmProb* prow = (GemmProb*)(tb + L.prob_row);
-  GemmProb* tabs = (GemmProb*)(tb + L.prob_seq);
-  // K-slice tables of the two weight-gradient launches: in the table block; prebuilt when the caller keeps the block (opts->tables)
-  GemmProb* pskw = (GemmProb*)(tb + L.prob_skw);
-  const bool skw_ready = tb != ws;
-  const Drop drop = make_drop(opts);
-  const bool use_e2 = drop.thr != 0;
-  int nw = 0;
-  // bf16-source row-wise GEMMs (see the forward): dZ and dY0 are produced in bf16 by the LayerNorm backward kernels, dQKV by the
-  // per-video GEMM epilogues; fp32 dZ is never needed, fp32 dY0 only for the residual branch of dx
-  const bool b16 = G.b16;
-  const float* x16 = (G.b16 && opts->x16) ? (const float*)opts->x16 : (const float*)(ws + L.x16);
-  const unsigned short* Wqkv16 = (const unsigned short*)(ws + L.w16);
-  const float* Wo16 = (const float*)(Wqkv16 + (size_t)3 * D * D);
-  const float* W116 = (const float*)(Wqkv16 + (size_t)4 * D * D);
-  const float* CTX16 = (const float*)(ws + L.ctx16);
-  const float* Y116 = (const float*)(ws + L.y116);
-  unsigned short* dZ16 = (unsigned short*)(ws + L.dz16);
-  unsigned short* dY016 = (unsigned short*)(ws + L.dy016);
-  unsigned short* dQKV16 = (unsigned short*)(ws + L.dqkv16);
-
-  if (G.sk && dx && tb == ws) launch_setup(G, D, n_seq, seq_off_dev, tb, stream);   // (dx asked for: the large-batch kernels below; their tables were not built by the SK forward)
-  if (G.sk && !dx) {   // the small-batch backward: the same stages below, every GEMM an SK launch over the tables the forward built
-    const SkCall none{};
-    (void)none;
-    SUMK_TRY(launch_ln_bwd<true>(D, R, Z, stats + 2 * (size_t)R, w->ln_w, w->ln_b, nullptr, w->w2, scores, dscores, dZ, lnpart, drop, 2u, &nw, stream));
-    SUMK_TRY(ln_bwd_reduce(lnpart, nw, D, gr->ln_w, gr->ln_b, gr->w2, gr->b2, gr->b1, stream));
-    float* scratch = (float*)(ws + L.sk_part);
-    {
-      const SkCall c{dZ, {w->W1, nullptr, nullptr, nullptr}, {scratch, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};       // dY1 = dZ W1 as K-slice slabs: the LayerNorm backward kernel adds them
-      SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NN, EPI_NONE, SR_DY1, -1, c, stream));
-    }
-    SUMK_TRY(launch_ln_bwd<false>(D, R, Y0, stats, w->ln_w, w->ln_b, scratch, nullptr, nullptr, nullptr, dY0, lnpart, drop, 1u, &nw, stream, nullptr,
-                                  G.P.row[SR_DY1].S, (int64_t)R * D));
-    SUMK_TRY(ln_bwd_reduce(lnpart, nw, D, gr->ln_w, gr->ln_b, nullptr, nullptr, nullptr, stream));
-    {
-      const SkCall c{dY0, {CTX, nullptr, nullptr, nullptr}, {gr->Wo, gr->W1, nullptr, nullptr}, nullptr, nullptr, -1};      // dWo += dY0^T CTX and dW1 += dZ^T Y1 (group 1)
-      SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_TN, EPI_ACCUM, SR_DWO1, -1, c, stream));
-    }
-    {
-      const SkCall c{dY0, {w->Wo, nullptr, nullptr, nullptr}, {dCTX, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};     // dCTX = dY0 Wo
-      SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NN, EPI_NONE, SR_DCTX, -1, c, stream));
-    }
-    if (tail_grads_ready_event) SUMK_HIP(hipEventRecord((hipEvent_t)tail_grads_ready_event, stream));
-    const float* Pd = use_e2 ? E2 : E;
-    {
-      const SkCall c{Pd, {dCTX, nullptr, nullptr, nullptr}, {dQKV, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};       // dV = alphaD^T dC
-      SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_TN, EPI_NONE, -1, TB_DV, c, stream));
-    }
-    {
-      const SkCall c{dCTX, {QKV, nullptr, nullptr, nullptr}, {scratch, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};        // dAlphaD = dC V^T as slabs: the softmax backward kernel adds them
-      SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NT, EPI_NONE, -1, TB_DP, c, stream));
-    }
-#define SUMK_SOFTMAX_BWD(NR) hipLaunchKernelGGL(vasnet_softmax_bwd_kernel<NR>, dim3((R + 3) / 4), dim3(256), 0, stream, E, E2, seq, (const int32_t*)(tb + L.row_seq), n_seq, R, \
-                       opts->scale, drop, (unsigned short*)nullptr, (const float*)scratch, G.P.seq[TB_DP].S, (int64_t)L.e_elems)
-    if (G.t_max <= 256) SUMK_SOFTMAX_BWD(4); else if (G.t_max <= 512) SUMK_SOFTMAX_BWD(8); else if (G.t_max <= 1024) SUMK_SOFTMAX_BWD(16); else SUMK_SOFTMAX_BWD(0);
-#undef SUMK_SOFTMAX_BWD
-    {
-      const SkCall c{E2, {QKV, nullptr, nullptr, nullptr}, {dQKV, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};        // dQ = dS K
-      SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_NN, EPI_NONE, -1, TB_DQ, c, stream));
-    }
-    {
-      const SkCall c{E2, {QKV, nullptr, nullptr, nullptr}, {dQKV, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};        // dK = dS^T Q
-      SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_TN, EPI_NONE, -1, TB_DK, c, stream));
-    }
-    {
-      const SkCall c{dQKV, {x, nullptr, nullptr, nullptr}, {gr->Wq, gr->Wk, gr->Wv, nullptr}, nullptr, nullptr, -1};        // d[Wq;Wk;Wv] += dQKV^T X
-      SUMK_TRY(launch_sk(G, n_seq, ws, tb, GEMM_TN, EPI_ACCUM, SR_DWQKV, -1, c, stream));
-    }
-    SUMK_HIP(hipGetLastError());
-    return SUMK_OK;
-  }
-
-  // 8': head + second LayerNorm + dropout + ReLU  ->  dZ (w.r.t. the k1 pre-activation), dw2, db2, dgamma, dbeta
-  SUMK_TRY(launch_ln_bwd<true>(D, R, Z, stats + 2 * (size_t)R, w->ln_w, w->ln_b, nullptr, w->w2, scores, dscores, b16 ? nullptr : dZ, lnpart,
-                               drop, 2u, &nw, stream, b16 ? dZ16 : nullptr));
-  SUMK_TRY(ln_bwd_reduce(lnpart, nw, D, gr->ln_w, gr->ln_b, gr->w2, gr->b2, gr->b1, stream));   // db1 = column sums of dZ, from the same slots
-  // 7': k1 -- dY1 = dZ . W1 (its weight gradient is taken together with the output projection's below: one split-K launch)
-  {
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = dZ; g.B[0] = w->W1; g.C = dY1; g.probs = prow + RP_DD; g.small_tile = G.st_d; g.total_tiles = gemm_tiles(R, D, G.st_d); g.xcd_M = R; g.xcd_N = D;
-    if (b16) to_b16(g, dZ16, W116, R, D, prow, RP_DD_W);
-    SUMK_TRY(launch_gemm(GEMM_NN, EPI_NONE, g, stream));
-  }
-  // 6': first LayerNorm + dropout -> dY0 (gradient of the residual sum)
-  SUMK_TRY(launch_ln_bwd<false>(D, R, Y0, stats, w->ln_w, w->ln_b, dY1, nullptr, nullptr, nullptr, (b16 && !dx) ? nullptr : dY0, lnpart, drop, 1u, &nw, stream,
-                                b16 ? dY016 : nullptr));
-  SUMK_TRY(ln_bwd_reduce(lnpart, nw, D, gr->ln_w, gr->ln_b, nullptr, nullptr, nullptr, stream));
-  // 5' + 7': dWo += dY0^T CTX and dW1 += dZ^T Y1 -- two (D x D) products over all R rows in ONE split-K launch (twice as long K
-  // slices per block, one slab reduce) -- then dCTX = dY0 . Wo (+ residual branch into dx)
-  {
-    const float* const As[2] = {b16 ? (const float*)dY016 : dY0, b16 ? (const float*)dZ16 : dZ};
-    const float* const Bs[2] = {b16 ? CTX16 : CTX, b16 ? Y116 : Y1};
-    float* out[4] = {gr->Wo, gr->W1, nullptr, nullptr};
-    SUMK_TRY(gemm_tn_splitk_accum_multi(2, As, Bs, D, D, D, D, R, slab, L.slab_elems, pskw, SPLITK_PROBS, out, D, D, 1.f, stream, opts->precision, b16,
-                                        skw_ready ? SPLITK_TABLE_READY : SPLITK_BUILD_AND_RUN));
-    GemmLaunch g; g.precision = opts->precision;  // dCTX = dY0 . Wo
-    g.A = dY0; g.B[0] = w->Wo; g.C = dCTX; g.probs = prow + RP_DD; g.small_tile = G.st_d; g.total_tiles = gemm_tiles(R, D, G.st_d); g.xcd_M = R; g.xcd_N = D;
-    if (b16) { to_b16(g, dY016, Wo16, R, D, prow, RP_DD_W); g.C16 = ws + L.dctx16; g.C = nullptr; }
-    SUMK_TRY(launch_gemm(GEMM_NN, EPI_NONE, g, stream));
-  }
-  // Wo, W1, b1, w2, b2 (the tail of the parameter order) are final from here on: a data-parallel caller starts their
-  // all-reduce on a side stream now, under the attention backward and the QKV weight gradients (60 % of the bucket).
-  if (tail_grads_ready_event) SUMK_HIP(hipEventRecord((hipEvent_t)tail_grads_ready_event, stream));
-  // 4': dV = alphaD^T dC ; dAlphaD = dC V^T
-  const float* Pd = use_e2 ? E2 : E;
-  if (!G.attn_fused) {
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = Pd; g.B[0] = dCTX; g.C = dQKV; g.probs = tabs + TB_DV * n_seq; g.nprob = n_seq; g.small_tile = G.cfg_pv; g.total_tiles = G.tiles_pv;
-    if (b16) { g.A = (const float*)(ws + L.p16); g.B[0] = (const float*)(ws + L.dctx16); g.src16 = 1; g.C16 = dQKV16; g.C = nullptr; }
-    SUMK_TRY(launch_gemm(GEMM_TN, EPI_NONE, g, stream));
-  }
-  if (G.attn_fused) {  // dAlphaD, softmax backward and dQ in one launch per (video, 64-row strip); bf16(dLogits) replaces bf16(alphaD) in place
-    AttnStripArgs at;
-    const unsigned short* qkv16 = (const unsigned short*)(ws + L.qkv16);
-    at.A16 = (const unsigned short*)(ws + L.dctx16); at.lda = D; at.B16 = qkv16 + 2 * D; at.ldb = 3 * D; at.C16 = qkv16 + D; at.ldc = 3 * D;
-    at.O16 = (unsigned short*)dQKV16; at.ldo = 3 * D; at.E = E; at.P16 = (unsigned short*)(ws + L.s16);      // bf16(dLogits): beside P16, not over it
-    at.seq = seq; at.n_seq = n_seq; at.strips = (G.t_max + 63) / 64; at.D = D;
-    at.scale = opts->scale; at.ignore_self = opts->ignore_self; at.aperture = opts->aperture; at.drop = drop;
-    SUMK_TRY(launch_attn_strip(true, at, stream));
-    // dV = P^T dC and dK = dS^T Q: the two products that contract over the query rows of ALL strips, as ONE launch of 2 n_seq problems
-    // (separately each was 800-960 tiles on 768 resident blocks -- one and a quarter rounds of latency-bound tiles, 25 us per launch)
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = (const float*)(ws + L.p16); g.B[0] = (const float*)(ws + L.dctx16); g.src16 = 1; g.C16 = dQKV16; g.C = nullptr;
-    g.probs = (GemmProb*)(tb + L.prob_dvk); g.nprob = 2 * n_seq; g.small_tile = G.cfg_pv; g.total_tiles = 2 * G.tiles_pv;
-    SUMK_TRY(launch_gemm(GEMM_TN, EPI_NONE, g, stream));
-  } else {
-  {
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = dCTX; g.B[0] = QKV; g.C = E2; g.probs = tabs + TB_DP * n_seq; g.nprob = n_seq; g.small_tile = G.cfg_s; g.total_tiles = G.tiles_s;
-    if (b16) { g.A = (const float*)(ws + L.dctx16); g.B[0] = (const float*)(ws + L.qkv16); g.src16 = 1; }
-    SUMK_TRY(launch_gemm(GEMM_NT, EPI_NONE, g, stream));
-  }
-  // 3': softmax (+dropout, +scale) backward, in place on E2
-  // (b16: bf16(dLogits) goes where bf16(alpha) was -- its last reader, the dV product, is queued before this kernel)
-  hipLaunchKernelGGL(vasnet_softmax_bwd_kernel<0>, dim3((R + 3) / 4), dim3(256), 0, stream, E, E2, seq, (const int32_t*)(tb + L.row_seq), n_seq, R,
-                     opts->scale, drop, b16 ? (unsigned short*)(ws + L.p16) : nullptr, (const float*)E2, 0, (int64_t)0);
-  // 2': dQ = dS K ; dK = dS^T Q
-  {
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = E2; g.B[0] = QKV; g.C = dQKV; g.probs = tabs + TB_DQ * n_seq; g.nprob = n_seq; g.small_tile = G.cfg_pv; g.total_tiles = G.tiles_pv;
-    if (b16) { g.A = (const float*)(ws + L.p16); g.B[0] = (const float*)(ws + L.qkv16); g.src16 = 1; g.C16 = dQKV16; g.C = nullptr; }
-    SUMK_TRY(launch_gemm(GEMM_NN, EPI_NONE, g, stream));
-  }
-  }
-  if (!G.attn_fused) {
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = E2; g.B[0] = QKV; g.C = dQKV; g.probs = tabs + TB_DK * n_seq; g.nprob = n_seq; g.small_tile = G.cfg_pv; g.total_tiles = G.tiles_pv;
-    if (b16) { g.A = (const float*)(ws + L.p16); g.B[0] = (const float*)(ws + L.qkv16); g.src16 = 1; g.C16 = dQKV16; g.C = nullptr; }
-    SUMK_TRY(launch_gemm(GEMM_TN, EPI_NONE, g, stream));
-  }
-  // 1': projection weights  d[Wq;Wk;Wv] += dQKV^T X
-  {
-    float* out[4] = {gr->Wq, gr->Wk, gr->Wv, nullptr};
-    SUMK_TRY(gemm_tn_splitk_accum(b16 ? (const float*)dQKV16 : dQKV, 3 * D, b16 ? x16 : x, D, 3 * D, D, R, slab, L.slab_elems, pskw + SPLITK_PROBS, SPLITK_PROBS, out, D, D, 1.f,
-                                  stream, opts->precision, b16, skw_ready ? SPLITK_TABLE_READY : SPLITK_BUILD_AND_RUN));
-  }
-  if (dx) {  // dX = dY0 (residual) + dQ Wq + dK Wk + dV Wv
-    SUMK_HIP(hipMemcpyAsync(dx, dY0, (size_t)R * D * 4, hipMemcpyDeviceToDevice, stream));
-    const float* Ws[3] = {w->Wq, w->Wk, w->Wv};
-    for (int part = 0; part < 3; ++part) {
-      GemmLaunch g; g.precision = opts->precision;
-      g.A = dQKV + (size_t)part * D; g.B[0] = Ws[part]; g.C = dx; g.probs = prow + RP_DX; g.small_tile = G.st_d;
-      g.total_tiles = gemm_tiles(R, D, G.st_d); g.xcd_M = R; g.xcd_N = D;
-      if (b16) to_b16(g, dQKV16 + (size_t)part * D, Wqkv16 + (size_t)part * D * D, R, D, prow, RP_DX_W);
-      SUMK_TRY(launch_gemm(GEMM_NN, EPI_ACCUM, g, stream));
-    }
-  }
-  SUMK_HIP(hipGetLastError());
-  return SUMK_OK;
+  char* tb = opts->tables ? (char*)opts->tables : ws;
+  if (G.sk && !dx) return backward_sk(G, x, D, n_seq, w, opts, dscores, gr, ws, tb, stream, tail_grads_ready_event);
+  return backward_dense(G, x, D, n_seq, seq_off_dev, w, opts, dscores, gr, dx, ws, tb, stream, tail_grads_ready_event);
 }
