@@ -1,6 +1,7 @@
 """Stock-PyTorch (CPU, fp32) functional port of the reference scorers.  TEST INFRASTRUCTURE ONLY.
 The SumGAN recurrences (lstm_stack_ref, dlstm_ref) and make_gru also run in float64: the high-precision oracles of
-tests/test_gpu_sumgan_full.py; transformer_ref likewise for tests/test_gpu_transformer_f64.py, bilstm_stack_ref for
+tests/test_gpu_sumgan_full.py; transformer_ref likewise for tests/test_gpu_transformer_f64.py, tf_encoder_stack_ref / tf_decoder_stack_ref for
+tests/test_gpu_sumgan_att_f64.py, bilstm_stack_ref for
 tests/test_gpu_lstm_f64.py (float64 reference and, in fp32 with the kernels' gate formulas, its yardstick).
 
 This is (1) a second, autograd-capable checker for the HIP path (forward AND gradients), and
@@ -138,6 +139,72 @@ class TransformerPort(torch.nn.Module):
         return torch.sigmoid(self.k2(self.layer_norm(torch.relu(self.k1(e)))))
 
 
+def _relu_logged(a, w, b, relu_log):
+    """relu(a W^T + b); relu_log (optional list) gets (pre-activation, sum_k |w_k a_k| + |b|), see transformer_ref."""
+    pre = F.linear(a, w, b)
+    if relu_log is not None:
+        relu_log.append((pre.detach(), F.linear(a.detach().abs(), w.detach().abs(), b.detach().abs())))
+    return torch.relu(pre)
+
+
+def _tf_attend(q, k, v, lens, n_heads, amasks):
+    """Multi-head attention per video over packed rows: q, k, v (R, D) -> context (R, D).  amasks: [(heads, T_i, T_i)] or None."""
+    D = q.shape[1]
+    dh = D // n_heads
+    ctx, r0 = [], 0
+    for i, T in enumerate(lens):
+        qh, kh, vh = (t[r0:r0 + T].reshape(T, n_heads, dh).transpose(0, 1) for t in (q, k, v))
+        a = torch.softmax(qh @ kh.transpose(1, 2) / math.sqrt(dh), dim=-1)               # (heads, T, T)
+        if amasks is not None:
+            a = a * amasks[i]
+        ctx.append((a @ vh).transpose(0, 1).reshape(T, D))
+        r0 += T
+    return torch.cat(ctx)
+
+
+def _tf_self_attn(h, g, pre, lens, n_heads, amasks, omask):
+    """dropout1(out_proj(MHA(h, h, h))) of a stock post-norm layer (keys pre + "self_attn.*"), without residual and norm."""
+    D = h.shape[1]
+    qkv = F.linear(h, g(pre + "self_attn.in_proj_weight"), g(pre + "self_attn.in_proj_bias"))
+    ctx = _tf_attend(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], lens, n_heads, amasks)
+    o = F.linear(ctx, g(pre + "self_attn.out_proj.weight"), g(pre + "self_attn.out_proj.bias"))
+    return o if omask is None else o * omask
+
+
+def _tf_cross_attn(h, mem, g, pre, lens, n_heads, amasks, omask):
+    """dropout2(out_proj(MHA(h, mem, mem))) of a stock decoder layer (keys pre + "multihead_attn.*"): Q from rows [0, D) of
+    in_proj, K / V from rows [D, 3D) applied to the memory."""
+    D = h.shape[1]
+    w, b = g(pre + "multihead_attn.in_proj_weight"), g(pre + "multihead_attn.in_proj_bias")
+    q = F.linear(h, w[0:D], b[0:D])
+    kv = F.linear(mem, w[D:3 * D], b[D:3 * D])
+    ctx = _tf_attend(q, kv[:, 0:D], kv[:, D:2 * D], lens, n_heads, amasks)
+    o = F.linear(ctx, g(pre + "multihead_attn.out_proj.weight"), g(pre + "multihead_attn.out_proj.bias"))
+    return o if omask is None else o * omask
+
+
+def _tf_ff(h, g, pre, m1, m2, relu_log):
+    """dropout_b(linear2(dropout_a(relu(linear1(h))))) of a stock layer; F is linear1's row count."""
+    f = _relu_logged(h, g(pre + "linear1.weight"), g(pre + "linear1.bias"), relu_log)
+    if m1 is not None:
+        f = f * m1
+    f = F.linear(f, g(pre + "linear2.weight"), g(pre + "linear2.bias"))
+    return f if m2 is None else f * m2
+
+
+def _tf_encoder_layers(h, g, prefix, lens, n_layers, n_heads, layer_eps, masks, relu_log):
+    """n stock post-norm nn.TransformerEncoderLayer over packed rows h (R, D); keys prefix + f"{l}." + the layer's own."""
+    D = h.shape[1]
+    for l in range(n_layers):
+        pre = f"{prefix}{l}."
+        mk = (lambda site: masks[site][l]) if masks is not None else (lambda site: None)
+        o = _tf_self_attn(h, g, pre, lens, n_heads, mk("attn"), mk("out"))
+        h = F.layer_norm(h + o, (D,), g(pre + "norm1.weight"), g(pre + "norm1.bias"), layer_eps)
+        f = _tf_ff(h, g, pre, mk("ff1"), mk("ff2"), relu_log)
+        h = F.layer_norm(h + f, (D,), g(pre + "norm2.weight"), g(pre + "norm2.bias"), layer_eps)
+    return h
+
+
 def transformer_ref(xs, params, n_layers, n_heads, layer_eps=1e-5, final_eps=1e-5, more_residuals=False, pos=None, masks=None,
                     relu_log=None):
     """Functional restatement of the reference Transformer scorer (transformer.py:74-103 over stock post-norm
@@ -152,51 +219,69 @@ def transformer_ref(xs, params, n_layers, n_heads, layer_eps=1e-5, final_eps=1e-
     relu_log: optional list; for every ReLU (linear1 of each layer, then k1) appends (pre-activation, sum_k |w_k a_k| + |b|) -- the scale of
     the rounding error an fp32 evaluation of that pre-activation carries (how close to the kink a unit may lie before it can flip).
     Returns (scores, logits): packed (R,) each."""
-    def relu(a, w, b):
-        pre = F.linear(a, w, b)
-        if relu_log is not None:
-            relu_log.append((pre.detach(), F.linear(a.detach().abs(), w.detach().abs(), b.detach().abs())))
-        return torch.relu(pre)
     g = lambda k: params[k]
     lens = [int(x.shape[0]) for x in xs]
     x = torch.cat(list(xs))
     if pos is not None:
         x = x + pos[0][torch.as_tensor(pos[1], device=x.device).long()]
-    R, D = x.shape
-    dh = D // n_heads
-    h = x
-    for l in range(n_layers):
-        pre = f"transformer_encoder.layers.{l}."
-        mk = (lambda site: masks[site][l]) if masks is not None else (lambda site: None)
-        qkv = F.linear(h, g(pre + "self_attn.in_proj_weight"), g(pre + "self_attn.in_proj_bias"))
-        ctx, r0 = [], 0
-        for i, T in enumerate(lens):
-            q, k, v = (qkv[r0:r0 + T, j * D:(j + 1) * D].reshape(T, n_heads, dh).transpose(0, 1) for j in range(3))
-            a = torch.softmax(q @ k.transpose(1, 2) / math.sqrt(dh), dim=-1)             # (heads, T, T)
-            if masks is not None:
-                a = a * masks["attn"][l][i]
-            ctx.append((a @ v).transpose(0, 1).reshape(T, D))
-            r0 += T
-        o = F.linear(torch.cat(ctx), g(pre + "self_attn.out_proj.weight"), g(pre + "self_attn.out_proj.bias"))
-        if mk("out") is not None:
-            o = o * mk("out")
-        h = F.layer_norm(h + o, (D,), g(pre + "norm1.weight"), g(pre + "norm1.bias"), layer_eps)
-        f = relu(h, g(pre + "linear1.weight"), g(pre + "linear1.bias"))
-        if mk("ff1") is not None:
-            f = f * mk("ff1")
-        f = F.linear(f, g(pre + "linear2.weight"), g(pre + "linear2.bias"))
-        if mk("ff2") is not None:
-            f = f * mk("ff2")
-        h = F.layer_norm(h + f, (D,), g(pre + "norm2.weight"), g(pre + "norm2.bias"), layer_eps)
+    D = x.shape[1]
+    h = _tf_encoder_layers(x, g, "transformer_encoder.layers.", lens, n_layers, n_heads, layer_eps, masks, relu_log)
     h = F.layer_norm(h, (D,), g("layer_norm.weight"), g("layer_norm.bias"), final_eps)       # encoder's final norm = the shared LN
     if more_residuals:
         h = h + x
-    z = relu(h, g("k1.weight"), g("k1.bias"))
+    z = _relu_logged(h, g("k1.weight"), g("k1.bias"), relu_log)
     if masks is not None:
         z = z * masks["head"]
     z = F.layer_norm(z, (D,), g("layer_norm.weight"), g("layer_norm.bias"), final_eps)        # the same LN again
     u = F.linear(z, g("k2.weight"), g("k2.bias"))[:, 0]
     return torch.sigmoid(u), u
+
+
+def tf_encoder_stack_ref(xs, params, prefix, n_layers, n_heads, layer_eps=1e-5, final_norm=None, final_eps=1e-5, masks=None,
+                         relu_log=None):
+    """SumGAN-Att's encoder stack (sumgan_att.py:20-80: n stock post-norm nn.TransformerEncoderLayer, then an optional final
+    LayerNorm) for a ragged list of videos, in the dtype of the inputs, with plain torch ops: the float64 oracle (and, in fp32, the
+    yardstick) of tests/test_gpu_sumgan_att_f64.py.  Differentiable in xs and params.
+
+    xs: [(T_i, D)]; params: keys prefix + f"{l}." + nn.TransformerEncoderLayer's own (kernels.tf_encoder_param_names); the
+    feed-forward width F is linear1's row count.  final_norm: key prefix of the final LayerNorm (e.g. "norm."), or None.
+    masks: optional already-scaled keep-masks as built by recipes.tf_stack_drop_masks(decoder=False), in transformer_ref's layout
+    (packed rows); relu_log: as transformer_ref.  Returns the packed hidden states (R, D)."""
+    g = lambda k: params[k]
+    lens = [int(x.shape[0]) for x in xs]
+    h = torch.cat(list(xs))
+    D = h.shape[1]
+    h = _tf_encoder_layers(h, g, prefix, lens, n_layers, n_heads, layer_eps, masks, relu_log)
+    if final_norm is not None:
+        h = F.layer_norm(h, (D,), g(final_norm + "weight"), g(final_norm + "bias"), final_eps)
+    return h
+
+
+def tf_decoder_stack_ref(tgts, mems, params, prefix, n_layers, n_heads, layer_eps=1e-5, masks=None, relu_log=None):
+    """SumGAN-Att's decoder stack (n stock post-norm nn.TransformerDecoderLayer, ReLU, no attention masks: norm1(t + SA(t)),
+    norm2(. + CA(., memory)), norm3(. + FF(.))) for a ragged list of videos, in the dtype of the inputs, with plain torch ops.
+    Differentiable in tgts, mems and params.
+
+    tgts, mems: [(T_i, D)], video i of the target attends to video i of the memory; params: keys prefix + f"{l}." +
+    nn.TransformerDecoderLayer's own (kernels.tf_decoder_param_names).  masks: optional already-scaled keep-masks as built by
+    recipes.tf_stack_drop_masks(decoder=True): transformer_ref's per-layer entries plus "cattn" [[(heads, T_i, T_i) per video] per
+    layer] on the cross-attention weights and "cout" [(R, D) per layer] on its out-projection (dropout2).  relu_log: as
+    transformer_ref.  Returns the packed outputs (R, D)."""
+    g = lambda k: params[k]
+    lens = [int(x.shape[0]) for x in tgts]
+    assert lens == [int(x.shape[0]) for x in mems]
+    h, mem = torch.cat(list(tgts)), torch.cat(list(mems))
+    D = h.shape[1]
+    for l in range(n_layers):
+        pre = f"{prefix}{l}."
+        mk = (lambda site: masks[site][l]) if masks is not None else (lambda site: None)
+        h = F.layer_norm(h + _tf_self_attn(h, g, pre, lens, n_heads, mk("attn"), mk("out")), (D,), g(pre + "norm1.weight"),
+                         g(pre + "norm1.bias"), layer_eps)
+        h = F.layer_norm(h + _tf_cross_attn(h, mem, g, pre, lens, n_heads, mk("cattn"), mk("cout")), (D,), g(pre + "norm2.weight"),
+                         g(pre + "norm2.bias"), layer_eps)
+        h = F.layer_norm(h + _tf_ff(h, g, pre, mk("ff1"), mk("ff2"), relu_log), (D,), g(pre + "norm3.weight"),
+                         g(pre + "norm3.bias"), layer_eps)
+    return h
 
 
 def make_gru(p, prefix, input_size, hidden_size, num_layers, dtype=torch.float32):

@@ -427,6 +427,28 @@ def vasnet_drop_masks(seed, p, lens, D):
     return out
 
 
+def _scaled_keep(seed, p, site, idx):
+    """Scaled keep-mask (0 or 1/(1-p), float32) of one dropout site at the element indices idx (uint64 array)."""
+    sc = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+    return dropout_keep(seed, site, idx, p).astype(np.float32) * sc
+
+
+def _flat_idx(R, N):
+    """row * N + col over a packed (R, N) matrix: the GEMM epilogue's dropout index."""
+    return np.arange(R, dtype=np.uint64)[:, None] * np.uint64(N) + np.arange(N, dtype=np.uint64)[None, :]
+
+
+def _attn_masks(seed, p, site, lens, heads):
+    """[(heads, T, T) per video]: index ((row*heads + h) << 20) | j with `row` the packed query row (tf_softmax_kernel)."""
+    rows = np.arange(int(sum(lens)), dtype=np.uint64)
+    per_video, r0 = [], 0
+    for T in lens:
+        wid = (rows[r0:r0 + T][None, :] * np.uint64(heads) + np.arange(heads, dtype=np.uint64)[:, None])      # (heads, T)
+        per_video.append(_scaled_keep(seed, p, site, (wid[:, :, None] << np.uint64(20)) | np.arange(T, dtype=np.uint64)[None, None, :]))
+        r0 += T
+    return per_video
+
+
 def transformer_drop_masks(seed, p_layer, p_head, lens, D, F, heads, n_layers):
     """Scaled keep-masks (0 or 1/(1-p)) of every dropout site of the Transformer scorer's training forward for a packed batch, in the
     layout oracle/torch_port.transformer_ref takes: {"attn": [[(heads, T, T) per video] per layer], "out": [(R, D)], "ff1": [(R, F)],
@@ -437,24 +459,35 @@ def transformer_drop_masks(seed, p_layer, p_head, lens, D, F, heads, n_layers):
       site 10*l + 2  linear1 after ReLU        row * F + col                  same epilogue (EPI_BIAS_RELU), tf_ff_fwd site_a
       site 10*l + 3  linear2 (dropout2)        row * D + col                  same epilogue (EPI_BIAS_RESIDUAL), tf_ff_fwd site_b
       site 1000      after ReLU(k1)            row * D + col                  csrc/vasnet.hip launch_ln_rows (layernorm_kernel, drop.thr branch)"""
-    def scaled(p, site, idx):
-        sc = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
-        return dropout_keep(seed, site, idx, p).astype(np.float32) * sc
+    out = tf_stack_drop_masks(seed, p_layer, lens, D, F, heads, n_layers, decoder=False)
+    out["head"] = _scaled_keep(seed, p_head, 1000, _flat_idx(int(sum(lens)), D))
+    return out
+
+
+def tf_stack_drop_masks(seed, p, lens, D, F, heads, n_layers, decoder):
+    """Scaled keep-masks (0 or 1/(1-p), float32) of every dropout site of the SumGAN-Att stacks' training forward
+    (csrc/tf_decoder.hip: sumk_tf_encoder_forward / sumk_tf_decoder_forward, site = 10 * l) for a packed batch, in the layout
+    oracle/torch_port.tf_encoder_stack_ref / tf_decoder_stack_ref take.  `seed` is sumk_tf_opts.seed, p its layer_dropout_p.
+    Sites +0 .. +3 are transformer_drop_masks' (the same blocks: tf_sa_fwd, tf_ff_fwd); with decoder=True also (`row` = PACKED row):
+      "cattn" [[(heads, T, T) per video] per layer]  site 10*l + 4  cross-attention weights    ((row*heads + h) << 20) | j
+            csrc/transformer.hip tf_softmax_kernel (wid = row*heads + h) via tf_attn_core_fwd(..., site + 4) in
+            sumk_tf_decoder_forward; the backward draws the same index in tf_softmax_bwd_kernel via tf_attn_core_bwd(..., site + 4)
+      "cout"  [(R, D) per layer]                     site 10*l + 5  cross out-proj (dropout2)  row * D + col
+            csrc/gemm_device.h GEMM epilogue (EPI_BIAS_RESIDUAL: row * N + col, N = D) via tf_out_proj(..., site + 5); the backward
+            is mask_scale_kernel (csrc/transformer.hip: flat index i = row * D + col) launched by sumk_tf_decoder_backward at site + 5"""
     R = int(sum(lens))
-    rows = np.arange(R, dtype=np.uint64)
-    flat = lambda N: rows[:, None] * np.uint64(N) + np.arange(N, dtype=np.uint64)[None, :]
     out = {"attn": [], "out": [], "ff1": [], "ff2": []}
+    if decoder:
+        out.update(cattn=[], cout=[])
     for l in range(n_layers):
-        site, per_video, r0 = 10 * l, [], 0
-        for T in lens:
-            wid = (rows[r0:r0 + T][None, :] * np.uint64(heads) + np.arange(heads, dtype=np.uint64)[:, None])      # (heads, T)
-            per_video.append(scaled(p_layer, site, (wid[:, :, None] << np.uint64(20)) | np.arange(T, dtype=np.uint64)[None, None, :]))
-            r0 += T
-        out["attn"].append(per_video)
-        out["out"].append(scaled(p_layer, site + 1, flat(D)))
-        out["ff1"].append(scaled(p_layer, site + 2, flat(F)))
-        out["ff2"].append(scaled(p_layer, site + 3, flat(D)))
-    out["head"] = scaled(p_head, 1000, flat(D))
+        site = 10 * l
+        out["attn"].append(_attn_masks(seed, p, site, lens, heads))
+        out["out"].append(_scaled_keep(seed, p, site + 1, _flat_idx(R, D)))
+        out["ff1"].append(_scaled_keep(seed, p, site + 2, _flat_idx(R, F)))
+        out["ff2"].append(_scaled_keep(seed, p, site + 3, _flat_idx(R, D)))
+        if decoder:
+            out["cattn"].append(_attn_masks(seed, p, site + 4, lens, heads))
+            out["cout"].append(_scaled_keep(seed, p, site + 5, _flat_idx(R, D)))
     return out
 
 
