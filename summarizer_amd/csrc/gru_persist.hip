@@ -19,9 +19,6 @@
 
 namespace sumk {
 
-constexpr int GRU_STATE_WORDS = 16 + 16384;   // word 0: the per-call error flag; words 16..: the BPTT's step counters
-constexpr int GRU_SPARE_WORDS = 512;
-
 struct GruWs {
   size_t g, prob, pstate, ll, ll_bytes;                                     // inference and training
   size_t sv, hprev, dgx, dghn, slab, slab_elems, prob_sk, colpart, pstate_b, xchg, xchg_bytes;   // training only
@@ -29,25 +26,16 @@ struct GruWs {
   int32_t n_rows, t_max, gsize, n_groups;
 };
 
-static int gru_group_size(int n_seq) { return std::min(32, std::max(1, (2 * n_seq + PK_TEAMS - 1) / PK_TEAMS)); }
-
 static int gru_carve(int In, int H, int n_seq, const int32_t* off, int training, GruWs* w) {
   SUMK_ARG(In > 0 && In % 4 == 0, "bigru: input size %d must be a positive multiple of 4", In);
   SUMK_ARG(H > 0 && H % 4 == 0 && H <= 256, "bigru: hidden size %d must be a multiple of 4 in [4, 256] (larger cells run the step path: sumk_gru_cell_forward)", H);
-  SUMK_ARG(n_seq > 0 && off != nullptr && off[0] == 0, "bigru: empty batch / seq_off[0] != 0");
-  int tmax = 0;
-  for (int s = 0; s < n_seq; ++s) {
-    const int T = off[s + 1] - off[s];
-    SUMK_ARG(T > 0, "bigru: video %d has %d frames", s, T);
-    tmax = T > tmax ? T : tmax;
-  }
-  const size_t R = (size_t)off[n_seq];
+  SUMK_TRY(scan_sequences(n_seq, off, "bigru", "video", "frames", &w->n_rows, &w->t_max));
+  const size_t R = (size_t)w->n_rows;
   SUMK_ARG(R * 2 * H * 4 < 0x7fffffffull, "bigru: %zu frames x 2H = %d exceed the 2 GB the kernels address with 32-bit offsets", R, 2 * H);
   size_t p = 0;
   auto take = [&](size_t bytes) { size_t at = p; p += align_up(bytes, 256); return at; };
-  w->n_rows = (int32_t)R; w->t_max = tmax;
-  w->gsize = gru_group_size(n_seq); w->n_groups = (n_seq + w->gsize - 1) / w->gsize;
-  SUMK_ARG(2 * w->n_groups <= GRU_STATE_WORDS - 16, "bigru: %d videos are more than one call takes", n_seq);
+  w->gsize = pk_group_size(n_seq); w->n_groups = (n_seq + w->gsize - 1) / w->gsize;
+  SUMK_ARG(pk_items_fit(2 * w->n_groups), "bigru: %d videos are more than one call takes", n_seq);
   w->g = take(R * 6 * H * 4);                        // Gx: [direction][r | z | n]
   w->prob = take(8 * sizeof(GemmProb));
   w->pstate = take(16 * 4);                          // forward: the error word alone (the hand-off carries its flags in the data)
@@ -67,7 +55,7 @@ static int gru_carve(int In, int H, int n_seq, const int32_t* off, int training,
     w->slab = take(w->slab_elems * 4);
     w->prob_sk = take(64 * sizeof(GemmProb));
     w->colpart = take((size_t)128 * 6 * H * 4);
-    w->pstate_b = take(GRU_STATE_WORDS * 4);
+    w->pstate_b = take(PSTATE_WORDS * 4);            // the BPTT's error word and step counters
     w->xchg_bytes = (size_t)2 * (2 * w->n_groups) * 32 * 32 * H * 4;   // BPTT exchange: [step parity 2][item][member 32][video 32][H] partial sums of dh
     w->xchg = take(w->xchg_bytes);
   }
@@ -499,11 +487,7 @@ __global__ __launch_bounds__(PK_THREADS) void gru_persist_bwd_kernel(GruPersistB
 
 static int gru_check_common(int In, int H, int n_seq, const int32_t* off, int training, GruWs* L, size_t workspace_bytes, const char* who) {
   SUMK_TRY(gru_carve(In, H, n_seq, off, training, L));
-  if (workspace_bytes < L->total) {
-    set_error("%s: workspace %zu < required %zu", who, workspace_bytes, L->total);
-    return SUMK_ERR_WORKSPACE;
-  }
-  return SUMK_OK;
+  return workspace_fits(who, workspace_bytes, L->total);
 }
 
 }  // namespace sumk
@@ -557,15 +541,8 @@ extern "C" int sumk_bigru_layer_forward(const float* x, int32_t In, int32_t H, i
   pa.ll = (unsigned long long*)(ws + L.ll); pa.ll_bytes = (int32_t)L.ll_bytes;
   const bool m16 = L.gsize <= 16;
   const void* fn = m16 ? (const void*)gru_persist_kernel<true> : (const void*)gru_persist_kernel<false>;
-  static bool attr_set[2] = {false, false};
-  if (!attr_set[m16]) {
-    SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set[m16] = true;
-  }
-  void* kargs[] = {&pa};
-  const size_t shmem = 96 * 1024;   // 33 KB used; > 80 KB keeps one block per CU
   prof_begin(SUMK_PROF_LSTM_REC, stream);
-  SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(PK_TEAMS * 32), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
+  SUMK_TRY(persist_launch(fn, &pa, 96 * 1024, stream));   // 33 KB used; > 80 KB keeps one block per CU
   prof_end(SUMK_PROF_LSTM_REC, stream);
   return SUMK_OK;
 }
@@ -594,7 +571,7 @@ extern "C" int sumk_bigru_layer_backward(const float* x, const float* h_out, con
   GemmProb* prob = (GemmProb*)(ws + L.prob);
   GemmProb* psk = (GemmProb*)(ws + L.prob_sk);
 
-  SUMK_TRY(persist_zero_words((unsigned*)(ws + L.pstate_b), GRU_STATE_WORDS, stream));
+  SUMK_TRY(persist_zero_words((unsigned*)(ws + L.pstate_b), PSTATE_WORDS, stream));
   {
     GruPersistBwdArgs pa;
     pa.whh[0] = w->w_hh[0]; pa.whh[1] = w->w_hh[1]; pa.dHout = dh_out; pa.sv = (const float*)(ws + L.sv); pa.hprev = hprev;
@@ -602,18 +579,11 @@ extern "C" int sumk_bigru_layer_backward(const float* x, const float* h_out, con
     pa.off = seq_off_dev; pa.state = (unsigned*)(ws + L.pstate_b); pa.health = health;
     pa.n_seq = n_seq; pa.H = H; pa.gsize = L.gsize; pa.n_groups = L.n_groups; pa.n_items = 2 * L.n_groups;
     pa.upm = std::min(8, (H + 31) / 32); pa.n_active = (H + pa.upm - 1) / pa.upm;
-    const bool shard = pa.n_items * 128 <= GRU_STATE_WORDS - 16 - GRU_SPARE_WORDS;
-    pa.item_words = shard ? 128 : 1; pa.n_shards = shard ? 4 : 1;
+    const bool shard = pk_items_shard(pa.n_items);
+    pa.item_words = shard ? PSTATE_ITEM_WORDS : 1; pa.n_shards = shard ? 4 : 1;
     const bool m16 = L.gsize <= 16;
     const void* fn = m16 ? (const void*)gru_persist_bwd_kernel<true> : (const void*)gru_persist_bwd_kernel<false>;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[m16]) {
-      SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_set[m16] = true;
-    }
-    void* kargs[] = {&pa};
-    const size_t shmem = 96 * 1024;   // 24 x 260 + 32 x 36 floats + tables = 30 KB used; > 80 KB keeps one block per CU
-    SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(PK_TEAMS * 32), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
+    SUMK_TRY(persist_launch(fn, &pa, 96 * 1024, stream));   // 24 x 260 + 32 x 36 floats + tables = 30 KB used; > 80 KB keeps one block per CU
   }
   // weight gradients: dW_ih[d] += dGx_d^T X (both directions in one split-K launch); dW_hh[d] += dGh_d^T h_prev_d with
   // dGh_d = [dr | dz] of dGx_d (rows 0 .. 2H of W_hh) and the stored n block (rows 2H .. 3H)

@@ -27,89 +27,7 @@ namespace sumk {
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int PSTATE_WORDS = 16 + 16384;  // word 0: error flag; words 16..: step counters per work item (one word; lstm_wide2_kernel: four shards on
-                                          // lines of their own, 128 words per item)
-constexpr int PSTATE_SPARE_WORDS = 512;   // the last words of the block, unused: the sharded counter layouts stay clear of them (their eligibility
-                                          // bounds, and so which kernel a batch gets, are as measured)
-
-struct LstmWs {
-  size_t g, cstate, prob, pstate, gates, call, hprev, dg, slab, dhrec, dcstate, prob_sk, colpart, pstate_b, xchg, partial, total;
-  size_t xchg_bytes;
-  size_t ll, ll_bytes;     // forward recurrence hand-off buffer (H <= 256): directly behind pstate, zeroed with it
-  size_t wx, wx_bytes;     // forward recurrence exchange of lstm_wide2_kernel (256 < H <= 1024): [group][step parity 2][direction 2][k/4 256][row 64][4 floats]
-  size_t slab_elems;
-  int32_t n_rows, t_max;
-};
-
 constexpr int GV_MAXB = 8;      // "a few sequences": the small-batch mat-vec step kernels below take over up to this many
-// geometry of the transposed mat-vec: strips of 256 columns x k splits sized for ~2048 blocks
-struct TGemvGeom { int strips, n_ksplit, rows_per_split; };
-static TGemvGeom tgemv_geom(int H) {
-  TGemvGeom g;
-  g.strips = (H + 255) / 256;
-  const int H4 = 4 * H;
-  int want = std::max(1, 2048 / g.strips);                // ~8 blocks = 32 waves per CU: the weight stream needs the loads in flight
-  want = std::min(want, std::max(1, H4 / 32));            // at least 32 rows per split (8 per wave)
-  want = std::min(want, 128);
-  g.rows_per_split = ((H4 + want - 1) / want + 3) / 4 * 4;
-  g.n_ksplit = (H4 + g.rows_per_split - 1) / g.rows_per_split;
-  return g;
-}
-static size_t tgemv_partial_bytes(int H, int n_seq, int nd = 1) {
-  return (size_t)tgemv_geom(H).n_ksplit * (size_t)std::min(n_seq, GV_MAXB) * nd * H * 4;
-}
-
-static int lstm_carve(int In, int H, int n_seq, const int32_t* off, int training, LstmWs* w) {
-  SUMK_ARG(In > 0 && In % 4 == 0, "bilstm: input size %d must be a positive multiple of 4", In);
-  SUMK_ARG(H > 0 && H % 4 == 0, "bilstm: hidden size %d must be a positive multiple of 4", H);
-  SUMK_ARG(n_seq > 0 && off != nullptr && off[0] == 0, "bilstm: empty batch / seq_off[0] != 0");
-  int tmax = 0;
-  for (int s = 0; s < n_seq; ++s) {
-    int T = off[s + 1] - off[s];
-    SUMK_ARG(T > 0, "bilstm: video %d has %d frames", s, T);
-    tmax = T > tmax ? T : tmax;
-  }
-  const size_t R = (size_t)off[n_seq];
-  size_t p = 0;
-  auto take = [&](size_t bytes) { size_t at = p; p += align_up(bytes, 256); return at; };
-  w->n_rows = (int32_t)R; w->t_max = tmax;
-  w->g = take(R * 8 * H * 4);                       // pre-activations from the input projection
-  w->cstate = take((size_t)n_seq * 2 * H * 4);      // running cell state (inference)
-  w->prob = take(8 * sizeof(GemmProb));
-  w->pstate = take(PSTATE_WORDS * 4);               // persistent-kernel error flag + per-item step counters
-  // flag-in-data hand-off of the H <= 256 forward recurrence: [step parity 2][direction 2][video][H] x {float h, uint32 step tag}
-  w->ll_bytes = H <= 256 ? (size_t)4 * n_seq * H * 8 : 0;
-  w->ll = take(w->ll_bytes);
-  w->wx_bytes = (H > 256 && H <= 1024) ? (size_t)((n_seq + 63) / 64) * 4 * 256 * 64 * 16 : 0;
-  w->wx = take(w->wx_bytes);
-  w->gates = w->call = w->hprev = w->dg = w->slab = w->dhrec = w->dcstate = w->prob_sk = w->colpart = 0;
-  w->pstate_b = w->xchg = 0; w->xchg_bytes = 0;
-  w->slab_elems = 0;
-  if (training) {
-    w->gates = take(R * 8 * H * 4);                 // post-nonlinearity i,f,g,o per row and direction
-    w->call = take(R * 2 * H * 4);                  // cell state per row and direction
-    w->hprev = take(R * 2 * H * 4);                 // h_{t-1} per row and direction (0 at a sequence start)
-    w->dg = take(R * 8 * H * 4);                    // gradient w.r.t. gate pre-activations
-    w->dcstate = take((size_t)n_seq * 2 * H * 4);
-    size_t big = (size_t)(8 * H) * (size_t)(In > H ? In : H);
-    w->slab_elems = (size_t)8 * big;                // split-K partial slabs for the weight gradients
-    w->slab = take(w->slab_elems * 4);
-    w->prob_sk = take(64 * sizeof(GemmProb));
-    w->colpart = take((size_t)128 * 8 * H * 4);
-    w->pstate_b = take(PSTATE_WORDS * 4);
-    {  // persistent BPTT exchange: [parity 2][item][member 32][video 32][H] partial sums of dh (H <= 256 only)
-      int gsize = std::min(32, std::max(1, (2 * n_seq + 7) / 8));
-      int items = 2 * ((n_seq + gsize - 1) / gsize);
-      w->xchg_bytes = H <= 256 ? (size_t)2 * items * 32 * 32 * H * 4 : 0;
-      // wide persistent BPTT (256 < H <= 1024, H % 128 == 0): [dir 2][group parity 2][step parity 2][KG = H/32][64 videos][H]
-      if (H > 256 && H <= 1024 && H % 128 == 0) w->xchg_bytes = (size_t)8 * (H / 32) * 64 * H * 4;
-      w->xchg = take(w->xchg_bytes);
-    }
-    w->partial = take(n_seq <= GV_MAXB ? tgemv_partial_bytes(H, n_seq, 2) : 0);   // small-batch transposed mat-vec (H > 256 at a few videos)
-  }
-  w->total = p;
-  return SUMK_OK;
-}
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
 
@@ -1763,10 +1681,125 @@ int sumk::persist_zero_words(unsigned* p, size_t words, hipStream_t stream) {
   return SUMK_OK;
 }
 
+// ------------------------------------------------------------------------------------------- workspace and path plan
+// ONE carve for the bidirectional layer (nd = 2) and the one-direction layer (nd = 1), and with it everything that follows from the
+// shape alone: which persistent recurrence each pass is eligible for, its work items, and the blocks that go with each form -- a block is
+// sized and used by the same line.  Pure host arithmetic on its arguments (the size queries run it without a GPU); the run-time gates are
+// applied on top of it by lstm_usable() and, inside a persistent path, lstm_switches().
+//   LSTM_PERSIST  H <= 256: 8 XCD teams with an LDS panel, work item = (group of <= 32 videos, direction)
+//   LSTM_WIDE     256 < H <= 1024: the two-team register-resident kernels, work item = (group of 64 videos, direction); the BPTT also
+//                 needs H % 128 == 0 and more than GV_MAXB videos
+//   LSTM_STEPS    everything else, and every one-direction layer: one launch per time step
+enum LstmForm { LSTM_STEPS, LSTM_PERSIST, LSTM_WIDE };
+
+struct LstmWs {
+  // blocks in workspace order; one that the shape has no path for is empty
+  size_t g, cstate, prob, pstate, ll, wx, gates, call, hprev, dg, dcstate, slab, prob_sk, colpart, pstate_b, xchg, partial, total;
+  size_t ll_bytes;           // forward hand-off buffer of LSTM_PERSIST: directly behind pstate, zeroed with it
+  size_t wx_bytes;           // forward exchange of LSTM_WIDE: [group][step parity 2][direction 2][k/4 256][row 64][4 floats]
+  size_t xchg_bytes;         // BPTT exchange of either persistent form
+  size_t slab_elems;
+  int32_t nd, H, n_seq, training, n_rows, t_max;
+  bool few;                  // at most GV_MAXB sequences: a step is a mat-vec
+  LstmForm fwd, bwd;         // the persistent form the shape is eligible for, per pass
+  int32_t gsize, n_groups;   // LSTM_PERSIST: videos per work item, groups
+  int32_t upm, n_active;     // LSTM_PERSIST: hidden units per team member (teams of 32), members with work
+  int32_t n_wgroups;         // LSTM_WIDE: groups
+  bool ll_ok;                // the hand-off buffer's byte offsets fit 31 bits: the flag-in-data forward instances can run
+};
+
+// geometry of the transposed mat-vec: strips of 256 columns x k splits sized for ~2048 blocks
+struct TGemvGeom { int strips, n_ksplit, rows_per_split; };
+static TGemvGeom tgemv_geom(int H) {
+  TGemvGeom g;
+  g.strips = (H + 255) / 256;
+  const int H4 = 4 * H;
+  int want = std::max(1, 2048 / g.strips);                // ~8 blocks = 32 waves per CU: the weight stream needs the loads in flight
+  want = std::min(want, std::max(1, H4 / 32));            // at least 32 rows per split (8 per wave)
+  want = std::min(want, 128);
+  g.rows_per_split = ((H4 + want - 1) / want + 3) / 4 * 4;
+  g.n_ksplit = (H4 + g.rows_per_split - 1) / g.rows_per_split;
+  return g;
+}
+static bool few_sequences(int n_seq) { return n_seq <= GV_MAXB; }
+// split partial sums of the small-batch transposed mat-vec: (n_ksplit, n_seq, nd, H)
+static size_t tgemv_partial_bytes(int H, int n_seq, int nd) {
+  return (size_t)tgemv_geom(H).n_ksplit * (size_t)std::min(n_seq, GV_MAXB) * nd * H * 4;
+}
+
+static int lstm_carve(int nd, int In, int H, int n_seq, const int32_t* off, int training, LstmWs* w) {
+  const bool bi = nd == 2;
+  const char* who = bi ? "bilstm" : "lstm";
+  SUMK_ARG(In > 0 && In % 4 == 0, "%s: input size %d must be a positive multiple of 4", who, In);
+  SUMK_ARG(H > 0 && H % 4 == 0, "%s: hidden size %d must be a positive multiple of 4", who, H);
+  *w = LstmWs{};
+  SUMK_TRY(scan_sequences(n_seq, off, who, bi ? "video" : "sequence", bi ? "frames" : "steps", &w->n_rows, &w->t_max));
+  const size_t R = (size_t)w->n_rows, hout_bytes = R * 2 * H * 4;
+  w->nd = nd; w->H = H; w->n_seq = n_seq; w->training = training;
+  // the plan
+  const bool narrow = bi && H <= 256, wide = bi && H > 256 && H <= 1024, wide_bptt = wide && H % 128 == 0;
+  w->few = few_sequences(n_seq);
+  w->gsize = pk_group_size(n_seq); w->n_groups = (n_seq + w->gsize - 1) / w->gsize;
+  w->upm = std::min(8, (H + 31) / 32); w->n_active = (H + w->upm - 1) / w->upm;
+  w->n_wgroups = (n_seq + WK_GROUP - 1) / WK_GROUP;
+  // (rows that fit 31-bit byte offsets; four counter shards per wide item fit the state block up to 62 groups = 3 968 videos)
+  w->fwd = narrow && hout_bytes < 0x7fffffff && pk_items_fit(2 * w->n_groups) && w->n_active <= 32 ? LSTM_PERSIST
+         : wide && hout_bytes < 0x7fffffe0 && pk_items_shard(2 * w->n_wgroups)                      ? LSTM_WIDE
+                                                                                                    : LSTM_STEPS;
+  if (training)
+    w->bwd = narrow && pk_items_fit(2 * w->n_groups)                   ? LSTM_PERSIST
+           : wide_bptt && !w->few && pk_items_fit(2 * w->n_wgroups)    ? LSTM_WIDE
+                                                                       : LSTM_STEPS;
+  // the blocks
+  size_t p = 0;
+  auto take = [&](size_t bytes) { size_t at = p; p += align_up(bytes, 256); return at; };
+  w->g = take(R * 4 * nd * H * 4);                    // pre-activations from the input projection
+  w->cstate = take((size_t)n_seq * nd * H * 4);       // running cell state (inference)
+  w->prob = take(8 * sizeof(GemmProb));
+  w->pstate = take(bi ? PSTATE_WORDS * 4 : 0);        // persistent-kernel error flag + per-item step counters
+  // flag-in-data hand-off: [step parity 2][direction 2][video][H] x {float h, uint32 step tag}
+  w->ll_bytes = narrow ? (size_t)4 * n_seq * H * 8 : 0;
+  w->ll_ok = w->ll_bytes > 0 && w->ll_bytes < 0x7fffffe0;
+  w->ll = take(w->ll_bytes);
+  w->wx_bytes = wide ? (size_t)w->n_wgroups * 4 * 256 * 64 * 16 : 0;
+  w->wx = take(w->wx_bytes);
+  if (training) {
+    w->gates = take(R * 4 * nd * H * 4);              // post-nonlinearity i,f,g,o per row and direction
+    w->call = take(R * nd * H * 4);                   // cell state per row and direction
+    w->hprev = take(R * nd * H * 4);                  // h_{t-1} per row and direction (0 at a sequence start)
+    w->dg = take(R * 4 * nd * H * 4);                 // gradient w.r.t. gate pre-activations
+    w->dcstate = take((size_t)n_seq * nd * H * 4);
+    w->slab_elems = (size_t)8 * ((size_t)(4 * nd * H) * (size_t)(In > H ? In : H));   // split-K partial slabs for the weight gradients
+    w->slab = take(w->slab_elems * 4);
+    w->prob_sk = take(64 * sizeof(GemmProb));
+    w->colpart = take((size_t)128 * 4 * nd * H * 4);
+    w->pstate_b = take(bi ? PSTATE_WORDS * 4 : 0);
+    // LSTM_PERSIST: [parity 2][item][member 32][video 32][H] partial sums of dh;
+    // LSTM_WIDE: [dir 2][group parity 2][step parity 2][KG = H/32][64 videos][H]
+    w->xchg_bytes = narrow ? (size_t)2 * (2 * w->n_groups) * 32 * 32 * H * 4 : wide_bptt ? (size_t)8 * (H / 32) * 64 * H * 4 : 0;
+    w->xchg = take(w->xchg_bytes);
+    // the bidirectional layer carries the mat-vec block at a few videos only; the one-direction layer has always carried it (sized for
+    // GV_MAXB sequences) at every batch size, and callers allocate by that
+    w->partial = take(bi && !w->few ? 0 : tgemv_partial_bytes(H, n_seq, nd));
+  }
+  w->total = p;
+  return SUMK_OK;
+}
+
+// the run-time gate on top of the plan: the persistent forms need the full chip and SUMK_LSTM_PERSIST != 0
+static LstmForm lstm_usable(LstmForm planned) { return persistent_kernels_usable() ? planned : LSTM_STEPS; }
+
+// where a forward recurrence keeps its cell: the per-row saves of the backward pass (training) or the running state alone
+struct LstmSaves { float* cstate; float* gates; float* c_all; float* hprev; };
+static LstmSaves lstm_saves(const LstmWs& L, char* ws) {
+  if (!L.training) return {(float*)(ws + L.cstate), nullptr, nullptr, nullptr};
+  return {nullptr, (float*)(ws + L.gates), (float*)(ws + L.call), (float*)(ws + L.hprev)};
+}
+
 extern "C" size_t sumk_bilstm_workspace_bytes(int32_t In, int32_t H, int32_t n_seq, const int32_t* seq_off_host,
                                               int32_t training) {
   LstmWs w;
-  if (lstm_carve(In, H, n_seq, seq_off_host, training, &w) != SUMK_OK) return 0;
+  if (lstm_carve(2, In, H, n_seq, seq_off_host, training, &w) != SUMK_OK) return 0;
   return w.total;
 }
 
@@ -1796,6 +1829,111 @@ extern "C" int sumk_bilstm_wplanes_build(int32_t In, int32_t H, const sumk_lstm_
   return SUMK_OK;
 }
 
+// ------------------------------------------------------------------------------------------- forward recurrences, one function per path
+// what a forward recurrence reads and writes besides the workspace (the bidirectional layer has no initial state: h0 = c0 = nullptr;
+// the one-direction layer has whh[1] = nullptr)
+struct LstmFwdIo { const float* whh[2]; const float* h0; const float* c0; float* h_out; const int32_t* off; };
+
+static_assert(W2_ITEM_WORDS == PSTATE_ITEM_WORDS, "lstm_wide2_kernel's counters are the sharded layout pk_items_shard() bounds");
+
+// LSTM_PERSIST.  The flag-in-data hand-off (LL) runs unless SUMK_LSTM_LL=0 picks the counter hand-off (A/B switch) or its buffer's byte
+// offsets pass 31 bits; its 16-row MFMA form (M16) serves groups of <= 16 videos.
+static int fwd_persist(const LstmWs& L, char* ws, const LstmFwdIo& io, hipStream_t stream) {
+  const LstmSwitches& sw = lstm_switches();
+  const LstmSaves sv = lstm_saves(L, ws);
+  const int H = L.H;
+  PersistArgs pa;
+  pa.G = (const float*)(ws + L.g); pa.whh[0] = io.whh[0]; pa.whh[1] = io.whh[1]; pa.Hout = io.h_out;
+  pa.gates = sv.gates; pa.c_all = sv.c_all; pa.hprev = sv.hprev;
+  pa.off = io.off; pa.state = (unsigned*)(ws + L.pstate);
+  pa.n_seq = L.n_seq; pa.H = H; pa.hout_bytes = (int32_t)std::min<size_t>((size_t)L.n_rows * 2 * H * 4, 0x7fffffff);
+  pa.ll = (unsigned long long*)(ws + L.ll); pa.ll_bytes = (int32_t)std::min<size_t>(L.ll_bytes, 0x7fffffe0);
+  pa.n_teams = PK_TEAMS;                     // 8 teams of 32 CUs (one XCD each)
+  pa.upm = L.upm; pa.n_active = L.n_active; pa.gsize = L.gsize; pa.n_groups = L.n_groups;
+  const size_t shmem = std::max<size_t>(((size_t)L.gsize * (H + 4) + 8 * 32 * 32 + 96) * sizeof(float), 96 * 1024);  // >80 KB: one block per CU
+  const bool ll = sw.ll && L.ll_ok;
+  const bool m16 = ll && sw.m16 && L.gsize <= 16;
+  const void* fn = m16 ? (const void*)lstm_persist_kernel<true, true>
+                 : ll  ? (const void*)lstm_persist_kernel<true>
+                       : (const void*)lstm_persist_kernel<>;
+  return persist_launch(fn, &pa, shmem, stream);
+}
+
+// LSTM_WIDE.  The recurrent product follows the layer's arithmetic: exact fp32 MFMA, bf16x3 (hi / lo) or the fp32-grade bf16x6 (three
+// planes); training keeps exact fp32 in the bf16x6 mode (the BPTT multiplies in fp32).
+static int fwd_wide(const LstmWs& L, char* ws, const LstmFwdIo& io, int precision, hipStream_t stream) {
+  const LstmSaves sv = lstm_saves(L, ws);
+  const int H = L.H;
+  Wide2Args w2;
+  w2.G = (const float*)(ws + L.g); w2.whh[0] = io.whh[0]; w2.whh[1] = io.whh[1]; w2.Hout = io.h_out;
+  w2.gates = sv.gates; w2.c_all = sv.c_all; w2.hprev = sv.hprev;
+  w2.off = io.off; w2.state = (unsigned*)(ws + L.pstate);
+  w2.xchg = (float*)(ws + L.wx);
+  w2.n_seq = L.n_seq; w2.H = H; w2.n_groups = L.n_wgroups;
+  w2.upm = (H + 127) / 128; w2.n_active = (H + w2.upm - 1) / w2.upm;     // <= 8 units per member, <= 128 members per team
+  w2.pack16 = (w2.upm == 8 && w2.n_active * 8 == H) ? 1 : 0;
+  const int mode = precision == SUMK_PRECISION_BF16X3 ? 1 : (precision == SUMK_PRECISION_BF16X6 && !L.training) ? 2 : 0;
+  const void* fn = mode == 2 ? (const void*)lstm_wide2_kernel<2> : mode == 1 ? (const void*)lstm_wide2_kernel<1> : (const void*)lstm_wide2_kernel<0>;
+  const size_t shmem = mode == 2 ? (size_t)(64 + 1 + 64) * 1024 : (size_t)96 * 1024;   // 65 KB (+ 64 KB of W_hh plane 3); > 80 KB keeps one block per CU
+  return persist_launch(fn, &w2, shmem, stream);
+}
+
+// LSTM_STEPS, one or two directions: one lstm_step_kernel per time step over every (sequence, direction) still running
+static int fwd_chain(const LstmWs& L, char* ws, const LstmFwdIo& io, hipStream_t stream) {
+  const LstmSaves sv = lstm_saves(L, ws);
+  StepArgs a;
+  a.G = (const float*)(ws + L.g); a.whh[0] = io.whh[0]; a.whh[1] = io.whh[1]; a.Hout = io.h_out;
+  a.cstate = sv.cstate; a.gates = sv.gates; a.c_all = sv.c_all; a.hprev = sv.hprev;
+  a.off = io.off; a.n_seq = L.n_seq; a.H = L.H; a.n_ublk = (L.H + 7) / 8;
+  a.nd = L.nd; a.h0 = io.h0; a.c0 = io.c0;
+  const int n_mtiles = (L.n_seq + 31) / 32;
+  const dim3 grid((unsigned)(n_mtiles * a.n_ublk * L.nd)), block(256);
+  for (int t = 0; t < L.t_max; ++t) {
+    a.t = t;
+    hipLaunchKernelGGL(lstm_step_kernel, grid, block, 0, stream, a);
+  }
+  SUMK_HIP(hipGetLastError());
+  return SUMK_OK;
+}
+
+// LSTM_STEPS of a one-direction layer with a few sequences: bandwidth-shaped mat-vec steps
+static int fwd_matvec(const LstmWs& L, char* ws, const LstmFwdIo& io, hipStream_t stream) {
+  const LstmSaves sv = lstm_saves(L, ws);
+  GemvStepArgs ga;
+  ga.a1 = nullptr; ga.a1_shift = 0; ga.w1 = nullptr; ga.G = (const float*)(ws + L.g); ga.b1 = ga.b2 = nullptr; ga.w2 = io.whh[0];
+  ga.h0 = io.h0; ga.c0 = io.c0; ga.hseq = io.h_out; ga.c_all = sv.c_all; ga.cstate = sv.cstate;
+  ga.gates = sv.gates; ga.hprev = sv.hprev; ga.xin = nullptr;
+  ga.off = io.off; ga.n_seq = L.n_seq; ga.H = L.H;
+  for (int t = 0; t < L.t_max; ++t) {
+    ga.t = t;
+    hipLaunchKernelGGL(lstm_gemv_step_kernel, dim3((unsigned)((L.H + 3) / 4)), dim3(256), 0, stream, ga);
+  }
+  SUMK_HIP(hipGetLastError());
+  return SUMK_OK;
+}
+
+// G = X . [W_ih_fwd ; W_ih_rev]^T + b_ih + b_hh for both directions, biases fused
+static int bilstm_input_projection(const LstmWs& L, char* ws, const float* x, int In, const sumk_lstm_layer_weights* w, int precision, hipStream_t stream) {
+  const int R = L.n_rows, H = L.H;
+  float* G = (float*)(ws + L.g);
+  const int np_in = precision == SUMK_PRECISION_BF16X6 ? 3 : precision == SUMK_PRECISION_BF16X3 ? 2 : 0;
+  if (!L.training && np_in && w->x_planes && w->w_planes && bilstm_wplanes_ok(In, H, np_in) && R >= 1024 && pw_ok(R, 8 * (int64_t)H, In, R, 8 * (int64_t)H, np_in)) {
+    // operand planes (x per dataset / per call, weights per weight change): the plane-aware wide GEMM, no split in the k-loop
+    PwLaunch g; g.A = w->x_planes; g.a_rows = R; g.B = w->w_planes; g.b_rows = 8 * (int64_t)H; g.M = R; g.N = 8 * H; g.K = In; g.np = np_in;
+    g.C = G; g.ldc = 8 * H; g.bias = (const float*)((const char*)w->w_planes + align_up(pw_planes_bytes(8 * (int64_t)H, In, np_in), 256));
+    return launch_gemm_pw(PW_F32, g, stream);
+  }
+  GemmProb* prob = (GemmProb*)(ws + L.prob);
+  const int small = gemm_tiles(R, 8 * H, 0) >= 512 ? 0 : 1;
+  SUMK_TRY(fill_single_prob(prob, R, 8 * H, In, In, In, 8 * H, 0, small, stream));
+  GemmLaunch g;
+  g.A = x; g.B[0] = w->w_ih[0]; g.B[1] = w->w_ih[1]; g.n_group = 4 * H;
+  g.bias0[0] = w->b_ih[0]; g.bias0[1] = w->b_ih[1]; g.bias1[0] = w->b_hh[0]; g.bias1[1] = w->b_hh[1];
+  g.C = G; g.probs = prob; g.small_tile = small; g.total_tiles = gemm_tiles(R, 8 * H, small);
+  g.precision = precision; g.lean = gemm_lean_ok(R, 4 * H, In, In, In);
+  return launch_gemm(GEMM_NT, EPI_BIAS2, g, stream);
+}
+
 extern "C" int sumk_bilstm_layer_forward(const float* x, int32_t In, int32_t H, int32_t n_seq,
                                          const int32_t* seq_off_host, const int32_t* seq_off_dev,
                                          const sumk_lstm_layer_weights* w, float* h_out, void* workspace,
@@ -1806,128 +1944,24 @@ extern "C" int sumk_bilstm_layer_forward(const float* x, int32_t In, int32_t H, 
   for (int d = 0; d < 2; ++d)
     SUMK_ARG(w->w_ih[d] && w->w_hh[d] && w->b_ih[d] && w->b_hh[d], "bilstm_forward: null weight (dir %d)", d);
   LstmWs L;
-  SUMK_TRY(lstm_carve(In, H, n_seq, seq_off_host, training, &L));
-  if (workspace_bytes < L.total) {
-    set_error("bilstm_forward: workspace %zu < required %zu", workspace_bytes, L.total);
-    return SUMK_ERR_WORKSPACE;
-  }
+  SUMK_TRY(lstm_carve(2, In, H, n_seq, seq_off_host, training, &L));
+  SUMK_TRY(workspace_fits("bilstm_forward", workspace_bytes, L.total));
   char* ws = (char*)workspace;
-  const int R = L.n_rows;
-  float* G = (float*)(ws + L.g);
-  GemmProb* prob = (GemmProb*)(ws + L.prob);
-
-  // 1: input projection for both directions, biases fused
-  const int small = gemm_tiles(R, 8 * H, 0) >= 512 ? 0 : 1;
-  const int np_in = precision == SUMK_PRECISION_BF16X6 ? 3 : precision == SUMK_PRECISION_BF16X3 ? 2 : 0;
-  static const bool persist_ok = persistent_kernels_usable();
-  const LstmSwitches& sw = lstm_switches();
-  const bool planes_in = !training && np_in && w->x_planes && w->w_planes && bilstm_wplanes_ok(In, H, np_in) && R >= 1024 && pw_ok(R, 8 * (int64_t)H, In, R, 8 * (int64_t)H, np_in);
-  if (planes_in) {
-    // operand planes (x per dataset / per call, weights per weight change): the plane-aware wide GEMM, no split in the k-loop
-    PwLaunch g; g.A = w->x_planes; g.a_rows = R; g.B = w->w_planes; g.b_rows = 8 * (int64_t)H; g.M = R; g.N = 8 * H; g.K = In; g.np = np_in;
-    g.C = G; g.ldc = 8 * H; g.bias = (const float*)((const char*)w->w_planes + align_up(pw_planes_bytes(8 * (int64_t)H, In, np_in), 256));
-    SUMK_TRY(launch_gemm_pw(PW_F32, g, stream));
-  } else {
-  SUMK_TRY(fill_single_prob(prob, R, 8 * H, In, In, In, 8 * H, 0, small, stream));
-  {
-    GemmLaunch g;
-    g.A = x; g.B[0] = w->w_ih[0]; g.B[1] = w->w_ih[1]; g.n_group = 4 * H;
-    g.bias0[0] = w->b_ih[0]; g.bias0[1] = w->b_ih[1]; g.bias1[0] = w->b_hh[0]; g.bias1[1] = w->b_hh[1];
-    g.C = G; g.probs = prob; g.small_tile = small; g.total_tiles = gemm_tiles(R, 8 * H, small);
-    g.precision = precision; g.lean = gemm_lean_ok(R, 4 * H, In, In, In);
-    SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS2, g, stream));
-  }
-  }
-  // 2: recurrence.  The health word is cleared on BOTH paths so sumk_bilstm_check never reads stale workspace bytes.
+  SUMK_TRY(bilstm_input_projection(L, ws, x, In, w, precision, stream));
+  // The health word is cleared on EVERY path so sumk_bilstm_check never reads stale workspace bytes.
   // (the flag-in-data hand-off buffer lies directly behind the state words: one launch clears both -- a tag of 0 matches no step)
   {
     const size_t words = (L.ll + L.ll_bytes - L.pstate) / 4;
     hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)std::min<size_t>(64, (words + 255) / 256)), dim3(256), 0, stream, (unsigned*)(ws + L.pstate), (int)words);
   }
-  // H <= 256: 8 XCD teams with an LDS panel; 256 < H <= 1024: the two-team register-resident kernel; otherwise the launch chain
-  if (persist_ok && H <= 256 && (size_t)R * 2 * H * 4 < 0x7fffffff) {
-    PersistArgs pa;
-    pa.G = G; pa.whh[0] = w->w_hh[0]; pa.whh[1] = w->w_hh[1]; pa.Hout = h_out;
-    pa.gates = training ? (float*)(ws + L.gates) : nullptr;
-    pa.c_all = training ? (float*)(ws + L.call) : nullptr;
-    pa.hprev = training ? (float*)(ws + L.hprev) : nullptr;
-    pa.off = seq_off_dev; pa.state = (unsigned*)(ws + L.pstate);
-    pa.n_seq = n_seq; pa.H = H; pa.hout_bytes = (int32_t)std::min<size_t>((size_t)R * 2 * H * 4, 0x7fffffff);
-    pa.ll = (unsigned long long*)(ws + L.ll); pa.ll_bytes = (int32_t)std::min<size_t>(L.ll_bytes, 0x7fffffe0);
-    pa.n_teams = PK_TEAMS;                     // 8 teams of 32 CUs (one XCD each)
-    const int team_size = 256 / pa.n_teams;
-    pa.upm = std::min(8, (H + team_size - 1) / team_size); pa.n_active = (H + pa.upm - 1) / pa.upm;
-    // videos per work item: at most 32 (the LDS map keeps gsize x (H+4) floats in front of the partial tiles)
-    const int gsize = std::min(32, std::max(1, (2 * n_seq + pa.n_teams - 1) / pa.n_teams));
-    pa.gsize = gsize; pa.n_groups = (n_seq + gsize - 1) / gsize;
-    if (2 * pa.n_groups <= PSTATE_WORDS - 16 && pa.n_active <= team_size) {
-      const size_t shmem = std::max<size_t>(((size_t)gsize * (H + 4) + 8 * 32 * 32 + 96) * sizeof(float), 96 * 1024);  // >80 KB: one block per CU
-      // SUMK_LSTM_LL=0: the counter hand-off (A/B switch); the flag-in-data one needs the exchange buffer's byte offsets in 31 bits
-      const bool ll = sw.ll && L.ll_bytes > 0 && L.ll_bytes < 0x7fffffe0;
-      const bool m16 = ll && sw.m16 && gsize <= 16;
-      const int which = m16 ? 2 : ll ? 1 : 0;
-      const void* fn = m16 ? (const void*)lstm_persist_kernel<true, true>
-                     : ll ? (const void*)lstm_persist_kernel<true>
-                          : (const void*)lstm_persist_kernel<>;
-      static bool attr_set[3] = {false, false, false};
-      if (!attr_set[which]) {
-        SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[which] = true;
-      }
-      void* kargs[] = {&pa};
-      prof_begin(SUMK_PROF_LSTM_REC, stream);
-      SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(256), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
-      prof_end(SUMK_PROF_LSTM_REC, stream);
-      return SUMK_OK;
-    }
-  }
-  // (the exchange buffer exists for 256 < H <= 64 WK_CPW; four counter shards per item fit the state block up to 62 groups = 3 968
-  //  videos -- a larger batch takes the launch chain below)
-  const int n_wgroups = (n_seq + WK_GROUP - 1) / WK_GROUP;
-  if (persist_ok && L.wx_bytes > 0 && (size_t)R * 2 * H * 4 < 0x7fffffe0 &&
-      2 * n_wgroups * W2_ITEM_WORDS <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS) {
-    Wide2Args w2;
-    w2.G = G; w2.whh[0] = w->w_hh[0]; w2.whh[1] = w->w_hh[1]; w2.Hout = h_out;
-    w2.gates = training ? (float*)(ws + L.gates) : nullptr;
-    w2.c_all = training ? (float*)(ws + L.call) : nullptr;
-    w2.hprev = training ? (float*)(ws + L.hprev) : nullptr;
-    w2.off = seq_off_dev; w2.state = (unsigned*)(ws + L.pstate);
-    w2.xchg = (float*)(ws + L.wx);
-    w2.n_seq = n_seq; w2.H = H; w2.n_groups = n_wgroups;
-    w2.upm = (H + 127) / 128; w2.n_active = (H + w2.upm - 1) / w2.upm;     // <= 8 units per member, <= 128 members per team
-    w2.pack16 = (w2.upm == 8 && w2.n_active * 8 == H) ? 1 : 0;
-    // the recurrent product follows the layer's arithmetic: exact fp32 MFMA, bf16x3 (hi / lo) or the fp32-grade bf16x6 (three planes);
-    // training keeps exact fp32 in the bf16x6 mode (the BPTT multiplies in fp32)
-    const int mode = precision == SUMK_PRECISION_BF16X3 ? 1 : (precision == SUMK_PRECISION_BF16X6 && !training) ? 2 : 0;
-    const void* fn = mode == 2 ? (const void*)lstm_wide2_kernel<2> : mode == 1 ? (const void*)lstm_wide2_kernel<1> : (const void*)lstm_wide2_kernel<0>;
-    static bool w2_attr_set[3] = {false, false, false};
-    if (!w2_attr_set[mode]) {
-      SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      w2_attr_set[mode] = true;
-    }
-    const size_t shmem = mode == 2 ? (size_t)(64 + 1 + 64) * 1024 : (size_t)96 * 1024;   // 65 KB (+ 64 KB of W_hh plane 3); > 80 KB keeps one block per CU
-    void* kargs[] = {&w2};
-    prof_begin(SUMK_PROF_LSTM_REC, stream);
-    SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(256), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
-    prof_end(SUMK_PROF_LSTM_REC, stream);
-    return SUMK_OK;
-  }
-  StepArgs a;
-  a.G = G; a.whh[0] = w->w_hh[0]; a.whh[1] = w->w_hh[1]; a.Hout = h_out;
-  a.cstate = training ? nullptr : (float*)(ws + L.cstate);
-  a.gates = training ? (float*)(ws + L.gates) : nullptr;
-  a.c_all = training ? (float*)(ws + L.call) : nullptr;
-  a.hprev = training ? (float*)(ws + L.hprev) : nullptr;
-  a.off = seq_off_dev; a.n_seq = n_seq; a.H = H; a.n_ublk = (H + 7) / 8;
-  const int n_mtiles = (n_seq + 31) / 32;
-  const dim3 grid((unsigned)(n_mtiles * a.n_ublk * 2)), block(256);
+  const LstmFwdIo io = {{w->w_hh[0], w->w_hh[1]}, nullptr, nullptr, h_out, seq_off_dev};
   prof_begin(SUMK_PROF_LSTM_REC, stream);
-  for (int t = 0; t < L.t_max; ++t) {
-    a.t = t;
-    hipLaunchKernelGGL(lstm_step_kernel, grid, block, 0, stream, a);
+  switch (lstm_usable(L.fwd)) {
+    case LSTM_PERSIST: SUMK_TRY(fwd_persist(L, ws, io, stream)); break;
+    case LSTM_WIDE:    SUMK_TRY(fwd_wide(L, ws, io, precision, stream)); break;
+    case LSTM_STEPS:   SUMK_TRY(fwd_chain(L, ws, io, stream)); break;
   }
   prof_end(SUMK_PROF_LSTM_REC, stream);
-  SUMK_HIP(hipGetLastError());
   return SUMK_OK;
 }
 
@@ -1941,6 +1975,97 @@ extern "C" int sumk_frame_head_forward(const float* h, int32_t n_rows, int32_t F
   return SUMK_OK;
 }
 
+// ------------------------------------------------------------------------------------------- BPTT recurrences, one function per path
+// what a BPTT reads and writes besides the workspace; c0 / dh_last / dc_last / dh0 / dc0 are the one-direction layer's (nullptr in
+// the bidirectional one, whose whh[1] is set instead).  Every path leaves dG in the workspace.
+struct LstmBwdIo {
+  const float* whh[2]; const float* dh_out; const float* c0; const float* dh_last; const float* dc_last; float* dh0; float* dc0;
+  const int32_t* off;
+};
+
+// LSTM_PERSIST.  The BPTT hands off through the step COUNTER: its exchange is a reduce-scatter of 32 partials per element, and a
+// flag-in-data form (each epilogue thread polls 32 packets, the exchange bytes double) measured slower.  The 16-row MFMA form
+// serves groups of <= 16 videos.
+static int bwd_persist(const LstmWs& L, char* ws, const LstmBwdIo& io, hipStream_t stream) {
+  const LstmSwitches& sw = lstm_switches();
+  const int H = L.H;
+  PersistBwdArgs pa;
+  pa.whh[0] = io.whh[0]; pa.whh[1] = io.whh[1]; pa.dHout = io.dh_out; pa.gates = (const float*)(ws + L.gates);
+  pa.c_all = (const float*)(ws + L.call); pa.dG = (float*)(ws + L.dg); pa.xchg = (float*)(ws + L.xchg);
+  pa.off = io.off; pa.state = (unsigned*)(ws + L.pstate_b);
+  pa.n_seq = L.n_seq; pa.H = H;
+  pa.upm = L.upm; pa.n_active = L.n_active; pa.gsize = L.gsize; pa.n_groups = L.n_groups; pa.n_items = 2 * L.n_groups;
+  // round 6: sharded step counter (while the items fit the state block, short of its spare words) and the reader-shaped
+  // exchange (members own 8 aligned units); SUMK_LSTM_BWD_R6=0 keeps the round-5 forms (A/B: tests/test_gpu_lstm.py)
+  const bool shard = sw.bwd_r6 && pk_items_shard(pa.n_items);
+  pa.item_words = shard ? PSTATE_ITEM_WORDS : 1; pa.n_shards = shard ? 4 : 1;
+  pa.coal = (sw.bwd_r6 && pa.upm == 8 && pa.n_active * 8 == H) ? 1 : 0;
+  const size_t shmem = std::max<size_t>(((size_t)32 * (H + 4) + 32 * 36 + 96) * sizeof(float), 96 * 1024);  // >80 KB: one block per CU
+  const bool m16 = sw.m16 && L.gsize <= 16;
+  return persist_launch(m16 ? (const void*)lstm_persist_bwd_kernel<true> : (const void*)lstm_persist_bwd_kernel<false>, &pa, shmem, stream);
+}
+
+// LSTM_WIDE
+static int bwd_wide(const LstmWs& L, char* ws, const LstmBwdIo& io, hipStream_t stream) {
+  const int H = L.H;
+  WideBwdArgs wa;
+  wa.whh[0] = io.whh[0]; wa.whh[1] = io.whh[1]; wa.dHout = io.dh_out; wa.gates = (const float*)(ws + L.gates);
+  wa.c_all = (const float*)(ws + L.call); wa.dG = (float*)(ws + L.dg); wa.xchg = (float*)(ws + L.xchg);
+  wa.off = io.off; wa.state = (unsigned*)(ws + L.pstate_b);
+  wa.n_seq = L.n_seq; wa.H = H; wa.n_groups = L.n_wgroups;
+  wa.KG = H / 32; wa.NG = (H + 255) / 256; wa.n_active = wa.KG * wa.NG;
+  wa.xchg_dir_bytes = (int32_t)(L.xchg_bytes / 2);
+  // round 6: sharded step counter while the items fit the state block (SUMK_LSTM_BWD_R6=0: one word per item, as round 5)
+  const bool shard = lstm_switches().bwd_r6 && pk_items_shard(2 * wa.n_groups);
+  wa.item_words = shard ? PSTATE_ITEM_WORDS : 1; wa.n_shards = shard ? 4 : 1;
+  return persist_launch((const void*)lstm_wide_bwd_kernel, &wa, 96 * 1024, stream);   // 35 KB used; > 80 KB keeps one block per CU
+}
+
+// the extra pass t = -1 writes dh0 / dc0
+static int bptt_last_step(const LstmBwdIo& io) { return (io.dh0 || io.dc0) ? -1 : 0; }
+
+// LSTM_STEPS with a few sequences, one or two directions: bandwidth-shaped transposed mat-vec + cell kernel per step
+static int bwd_matvec(const LstmWs& L, char* ws, const LstmBwdIo& io, hipStream_t stream) {
+  const int H = L.H;
+  const TGemvGeom tg = tgemv_geom(H);
+  TGemvArgs ta;
+  ta.dGa = (const float*)(ws + L.dg); ta.wa = io.whh[0]; ta.wa1 = io.whh[1]; ta.dGb = nullptr; ta.wb = nullptr; ta.b_shift = 0; ta.nd = L.nd;
+  ta.partial = (float*)(ws + L.partial); ta.off = io.off; ta.n_seq = L.n_seq; ta.H = H; ta.rows_per_split = tg.rows_per_split;
+  CellBwdArgs ca;
+  ca.dext = io.dh_out; ca.dh_last = io.dh_last; ca.dc_last = io.dc_last; ca.partial = ta.partial; ca.n_ksplit = tg.n_ksplit; ca.nd = L.nd;
+  ca.gates = (const float*)(ws + L.gates); ca.c_all = (const float*)(ws + L.call); ca.c0 = io.c0;
+  ca.dG = (float*)(ws + L.dg); ca.dcstate = (float*)(ws + L.dcstate); ca.dh0 = io.dh0; ca.dc0 = io.dc0;
+  ca.off = io.off; ca.n_seq = L.n_seq; ca.H = H;
+  for (int t = L.t_max - 1; t >= bptt_last_step(io); --t) {
+    ta.t = ca.t = t;
+    hipLaunchKernelGGL(lstm_tgemv_partial_kernel, dim3((unsigned)tg.strips, (unsigned)tg.n_ksplit, (unsigned)L.nd), dim3(256), 0, stream, ta);
+    hipLaunchKernelGGL(lstm_cellbwd_kernel, dim3((unsigned)((H + 63) / 64), (unsigned)L.n_seq, (unsigned)L.nd), dim3(256), 0, stream, ca);
+  }
+  SUMK_HIP(hipGetLastError());
+  return SUMK_OK;
+}
+
+// LSTM_STEPS otherwise, one or two directions: one lstm_bwd_step_kernel per time step
+static int bwd_chain(const LstmWs& L, char* ws, const LstmBwdIo& io, hipStream_t stream) {
+  BwdStepArgs a;
+  a.whh[0] = io.whh[0]; a.whh[1] = io.whh[1]; a.dHout = io.dh_out; a.gates = (const float*)(ws + L.gates);
+  a.c_all = (const float*)(ws + L.call); a.dG = (float*)(ws + L.dg); a.dcstate = (float*)(ws + L.dcstate);
+  a.off = io.off; a.n_seq = L.n_seq; a.H = L.H; a.n_jblk = (L.H + 31) / 32;
+  a.nd = L.nd; a.c0 = io.c0; a.dh_last = io.dh_last; a.dc_last = io.dc_last; a.dh0 = io.dh0; a.dc0 = io.dc0;
+  const int n_mtiles = (L.n_seq + 31) / 32;
+  const dim3 grid((unsigned)(n_mtiles * a.n_jblk * L.nd)), block(512);
+  for (int t = L.t_max - 1; t >= bptt_last_step(io); --t) {
+    a.t = t;
+    hipLaunchKernelGGL(lstm_bwd_step_kernel, grid, block, 0, stream, a);
+  }
+  SUMK_HIP(hipGetLastError());
+  return SUMK_OK;
+}
+
+static int bwd_steps(const LstmWs& L, char* ws, const LstmBwdIo& io, hipStream_t stream) {
+  return L.few ? bwd_matvec(L, ws, io, stream) : bwd_chain(L, ws, io, stream);
+}
+
 extern "C" int sumk_bilstm_layer_backward(const float* x, const float* h_out, const float* dh_out, int32_t In, int32_t H,
                                           int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
                                           const sumk_lstm_layer_weights* w, const sumk_lstm_layer_grads* gr, float* dx,
@@ -1952,11 +2077,8 @@ extern "C" int sumk_bilstm_layer_backward(const float* x, const float* h_out, co
     SUMK_ARG(w->w_ih[d] && w->w_hh[d] && gr->w_ih[d] && gr->w_hh[d] && gr->b_ih[d] && gr->b_hh[d],
              "bilstm_backward: null weight/grad (dir %d)", d);
   LstmWs L;
-  SUMK_TRY(lstm_carve(In, H, n_seq, seq_off_host, 1, &L));
-  if (workspace_bytes < L.total) {
-    set_error("bilstm_backward: workspace %zu < required %zu (needs the training-mode forward's workspace)", workspace_bytes, L.total);
-    return SUMK_ERR_WORKSPACE;
-  }
+  SUMK_TRY(lstm_carve(2, In, H, n_seq, seq_off_host, 1, &L));
+  SUMK_TRY(workspace_fits("bilstm_backward", workspace_bytes, L.total, " (needs the training-mode forward's workspace)"));
   char* ws = (char*)workspace;
   const int R = L.n_rows;
   float* dG = (float*)(ws + L.dg);
@@ -1966,94 +2088,12 @@ extern "C" int sumk_bilstm_layer_backward(const float* x, const float* h_out, co
   GemmProb* prob = (GemmProb*)(ws + L.prob);
   GemmProb* psk = (GemmProb*)(ws + L.prob_sk);
 
-  static const bool persist_ok = persistent_kernels_usable();
-  const LstmSwitches& sw = lstm_switches();
   hipLaunchKernelGGL(zero_words_kernel, dim3((PSTATE_WORDS + 255) / 256), dim3(256), 0, stream, (unsigned*)(ws + L.pstate_b), PSTATE_WORDS);
-  bool done = false;
-  if (persist_ok && H <= 256 && L.xchg_bytes > 0) {
-    PersistBwdArgs pa;
-    pa.whh[0] = w->w_hh[0]; pa.whh[1] = w->w_hh[1]; pa.dHout = dh_out; pa.gates = (const float*)(ws + L.gates);
-    pa.c_all = (const float*)(ws + L.call); pa.dG = dG; pa.xchg = (float*)(ws + L.xchg);
-    pa.off = seq_off_dev; pa.state = (unsigned*)(ws + L.pstate_b);
-    pa.n_seq = n_seq; pa.H = H;
-    pa.upm = std::min(8, (H + 31) / 32); pa.n_active = (H + pa.upm - 1) / pa.upm;
-    int gsize = std::min(32, std::max(1, (2 * n_seq + PK_TEAMS - 1) / PK_TEAMS));
-    pa.gsize = gsize; pa.n_groups = (n_seq + gsize - 1) / gsize; pa.n_items = 2 * pa.n_groups;
-    // round 6: sharded step counter (while the items fit the state block, short of its spare words) and the reader-shaped
-    // exchange (members own 8 aligned units); SUMK_LSTM_BWD_R6=0 keeps the round-5 forms (A/B: tests/test_gpu_lstm.py)
-    const bool shard = sw.bwd_r6 && pa.n_items * 128 <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS;
-    pa.item_words = shard ? 128 : 1; pa.n_shards = shard ? 4 : 1;
-    pa.coal = (sw.bwd_r6 && pa.upm == 8 && pa.n_active * 8 == H) ? 1 : 0;
-    if (pa.n_items <= PSTATE_WORDS - 16) {
-      const size_t shmem = std::max<size_t>(((size_t)32 * (H + 4) + 32 * 36 + 96) * sizeof(float), 96 * 1024);  // >80 KB: one block per CU
-      // The BPTT hands off through the step COUNTER: its exchange is a reduce-scatter of 32 partials per element, and a flag-in-data
-      // form (each epilogue thread polls 32 packets, the exchange bytes double) measured slower.  The 16-row MFMA form
-      // serves groups of <= 16 videos.
-      const bool m16 = sw.m16 && gsize <= 16;
-      const void* fn = m16 ? (const void*)lstm_persist_bwd_kernel<true> : (const void*)lstm_persist_bwd_kernel<false>;
-      static bool attr_set[2] = {false, false};
-      if (!attr_set[m16]) {
-        SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[m16] = true;
-      }
-      void* kargs[] = {&pa};
-      SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(PK_TEAMS * 32), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
-      done = true;
-    }
-  }
-  if (!done && persist_ok && n_seq > GV_MAXB && H > 256 && H <= 1024 && H % 128 == 0 && L.xchg_bytes > 0 &&
-      2 * ((n_seq + WK_GROUP - 1) / WK_GROUP) <= PSTATE_WORDS - 16) {
-    WideBwdArgs wa;
-    wa.whh[0] = w->w_hh[0]; wa.whh[1] = w->w_hh[1]; wa.dHout = dh_out; wa.gates = (const float*)(ws + L.gates);
-    wa.c_all = (const float*)(ws + L.call); wa.dG = dG; wa.xchg = (float*)(ws + L.xchg);
-    wa.off = seq_off_dev; wa.state = (unsigned*)(ws + L.pstate_b);
-    wa.n_seq = n_seq; wa.H = H; wa.n_groups = (n_seq + WK_GROUP - 1) / WK_GROUP;
-    wa.KG = H / 32; wa.NG = (H + 255) / 256; wa.n_active = wa.KG * wa.NG;
-    wa.xchg_dir_bytes = (int32_t)(L.xchg_bytes / 2);
-    {   // round 6: sharded step counter while the items fit the state block (SUMK_LSTM_BWD_R6=0: one word per item, as round 5)
-      const bool shard = sw.bwd_r6 && 2 * wa.n_groups * 128 <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS;
-      wa.item_words = shard ? 128 : 1; wa.n_shards = shard ? 4 : 1;
-    }
-    static bool wb_attr_set = false;
-    if (!wb_attr_set) {
-      SUMK_HIP(hipFuncSetAttribute((const void*)lstm_wide_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      wb_attr_set = true;
-    }
-    void* kargs[] = {&wa};
-    SUMK_HIP(hipLaunchCooperativeKernel((const void*)lstm_wide_bwd_kernel, dim3(256), dim3(PK_THREADS), kargs,
-                                        (unsigned)(96 * 1024), stream));   // 35 KB used; > 80 KB keeps one block per CU
-    done = true;
-  }
-  if (!done && n_seq <= GV_MAXB) {   // a few videos and no persistent BPTT (H > 256): bandwidth-shaped transposed mat-vec per step
-    const TGemvGeom tg = tgemv_geom(H);
-    TGemvArgs ta;
-    ta.dGa = dG; ta.wa = w->w_hh[0]; ta.wa1 = w->w_hh[1]; ta.dGb = nullptr; ta.wb = nullptr; ta.b_shift = 0; ta.nd = 2;
-    ta.partial = (float*)(ws + L.partial); ta.off = seq_off_dev; ta.n_seq = n_seq; ta.H = H; ta.rows_per_split = tg.rows_per_split;
-    CellBwdArgs ca;
-    ca.dext = dh_out; ca.dh_last = ca.dc_last = nullptr; ca.partial = ta.partial; ca.n_ksplit = tg.n_ksplit; ca.nd = 2;
-    ca.gates = (const float*)(ws + L.gates); ca.c_all = (const float*)(ws + L.call); ca.c0 = nullptr;
-    ca.dG = dG; ca.dcstate = (float*)(ws + L.dcstate); ca.dh0 = ca.dc0 = nullptr;
-    ca.off = seq_off_dev; ca.n_seq = n_seq; ca.H = H;
-    for (int t = L.t_max - 1; t >= 0; --t) {
-      ta.t = ca.t = t;
-      hipLaunchKernelGGL(lstm_tgemv_partial_kernel, dim3((unsigned)tg.strips, (unsigned)tg.n_ksplit, 2), dim3(256), 0, stream, ta);
-      hipLaunchKernelGGL(lstm_cellbwd_kernel, dim3((unsigned)((H + 63) / 64), (unsigned)n_seq, 2), dim3(256), 0, stream, ca);
-    }
-    SUMK_HIP(hipGetLastError());
-    done = true;
-  }
-  if (!done) {
-    BwdStepArgs a;
-    a.whh[0] = w->w_hh[0]; a.whh[1] = w->w_hh[1]; a.dHout = dh_out; a.gates = (const float*)(ws + L.gates);
-    a.c_all = (const float*)(ws + L.call); a.dG = dG; a.dcstate = (float*)(ws + L.dcstate);
-    a.off = seq_off_dev; a.n_seq = n_seq; a.H = H; a.n_jblk = (H + 31) / 32;
-    const int n_mtiles = (n_seq + 31) / 32;
-    const dim3 grid((unsigned)(n_mtiles * a.n_jblk * 2)), block(512);
-    for (int t = L.t_max - 1; t >= 0; --t) {
-      a.t = t;
-      hipLaunchKernelGGL(lstm_bwd_step_kernel, grid, block, 0, stream, a);
-    }
-    SUMK_HIP(hipGetLastError());
+  const LstmBwdIo io = {{w->w_hh[0], w->w_hh[1]}, dh_out, nullptr, nullptr, nullptr, nullptr, nullptr, seq_off_dev};
+  switch (lstm_usable(L.bwd)) {
+    case LSTM_PERSIST: SUMK_TRY(bwd_persist(L, ws, io, stream)); break;
+    case LSTM_WIDE:    SUMK_TRY(bwd_wide(L, ws, io, stream)); break;
+    case LSTM_STEPS:   SUMK_TRY(bwd_steps(L, ws, io, stream)); break;
   }
   // weight gradients: dW_ih[d] += dG_d^T X (both directions in one split-K launch), dW_hh[d] += dG_d^T h_prev_d
   auto dw_hh = [&](int d) -> int {
@@ -2100,45 +2140,18 @@ extern "C" int sumk_bilstm_layer_backward(const float* x, const float* h_out, co
 // One forward-running LSTM direction with an optional initial state and the final state as an output -- the layers of
 // SumGAN's eLSTM / dLSTM / cLSTM (summarizer/models/sumgan.py:48-115,185-210: nn.LSTM(bidirectional=False), `(h_0, c_0)`
 // inputs, `(h_n, c_n)` outputs).  Runs the launch-per-step kernels with nd = 1 (row layouts (R, H) / (R, 4H)).
-struct Lstm1Ws {
-  size_t g, cstate, prob, gates, call, hprev, dg, dcstate, slab, prob_sk, colpart, partial, total;
-  size_t slab_elems;
-  int32_t n_rows, t_max;
-};
+// The workspace is lstm_carve's with nd = 1: no persistent blocks, LSTM_STEPS in both passes.
 
-static int lstm1_carve(int In, int H, int n_seq, const int32_t* off, int training, Lstm1Ws* w) {
-  SUMK_ARG(In > 0 && In % 4 == 0, "lstm: input size %d must be a positive multiple of 4", In);
-  SUMK_ARG(H > 0 && H % 4 == 0, "lstm: hidden size %d must be a positive multiple of 4", H);
-  SUMK_ARG(n_seq > 0 && off != nullptr && off[0] == 0, "lstm: empty batch / seq_off[0] != 0");
-  int tmax = 0;
-  for (int s = 0; s < n_seq; ++s) {
-    int T = off[s + 1] - off[s];
-    SUMK_ARG(T > 0, "lstm: sequence %d has %d steps", s, T);
-    tmax = T > tmax ? T : tmax;
-  }
-  const size_t R = (size_t)off[n_seq];
-  size_t p = 0;
-  auto take = [&](size_t bytes) { size_t at = p; p += align_up(bytes, 256); return at; };
-  w->n_rows = (int32_t)R; w->t_max = tmax;
-  w->g = take(R * 4 * H * 4);
-  w->cstate = take((size_t)n_seq * H * 4);
-  w->prob = take(8 * sizeof(GemmProb));
-  w->gates = w->call = w->hprev = w->dg = w->dcstate = w->slab = w->prob_sk = w->colpart = w->partial = 0;
-  w->slab_elems = 0;
-  if (training) {
-    w->gates = take(R * 4 * H * 4);
-    w->call = take(R * H * 4);
-    w->hprev = take(R * H * 4);
-    w->dg = take(R * 4 * H * 4);
-    w->dcstate = take((size_t)n_seq * H * 4);
-    w->slab_elems = (size_t)8 * (4 * H) * (size_t)(In > H ? In : H);
-    w->slab = take(w->slab_elems * 4);
-    w->prob_sk = take(64 * sizeof(GemmProb));
-    w->colpart = take((size_t)128 * 4 * H * 4);
-    w->partial = take(tgemv_partial_bytes(H, n_seq));     // split partial sums of the small-batch transposed mat-vec
-  }
-  w->total = p;
-  return SUMK_OK;
+// weight and bias gradients of one direction with row layouts (R, 4H) / (R, H) -- this layer's and each decoder layer's:
+// dW_ih += dG^T X, dW_hh += dG^T h_prev, and b_ih and b_hh both receive the column sums of dG (one pass)
+static int dir_grad_tail(const float* dG, const float* x, int In, const float* hprev, int H, int R, float* slab, size_t slab_elems,
+                         GemmProb* psk, float* colpart, const sumk_lstm_dir_grads& gr, hipStream_t stream, int precision = SUMK_PRECISION_FP32) {
+  float* o_ih[4] = {gr.w_ih, nullptr, nullptr, nullptr};
+  SUMK_TRY(gemm_tn_splitk_accum(dG, 4 * H, x, In, 4 * H, In, R, slab, slab_elems, psk, 64, o_ih, 4 * H, In, 1.f, stream, precision));
+  float* o_hh[4] = {gr.w_hh, nullptr, nullptr, nullptr};
+  SUMK_TRY(gemm_tn_splitk_accum(dG, 4 * H, hprev, H, 4 * H, H, R, slab, slab_elems, psk, 64, o_hh, 4 * H, H, 1.f, stream, precision));
+  const ReduceSeg segs[2] = {{0, 4 * H, gr.b_ih}, {0, 4 * H, gr.b_hh}};
+  return colsum_multi(dG, 4 * H, R, 4 * H, colpart, 128, segs, 2, stream);
 }
 
 // h_last[s][j] = h_out[last row of s][j]; c_last from the per-row cell states (training) or the running state (inference)
@@ -2154,8 +2167,8 @@ __global__ void lstm_last_state_kernel(const float* __restrict__ h_out, const fl
 }
 
 extern "C" size_t sumk_lstm_workspace_bytes(int32_t In, int32_t H, int32_t n_seq, const int32_t* seq_off_host, int32_t training) {
-  Lstm1Ws w;
-  if (lstm1_carve(In, H, n_seq, seq_off_host, training, &w) != SUMK_OK) return 0;
+  LstmWs w;
+  if (lstm_carve(1, In, H, n_seq, seq_off_host, training, &w) != SUMK_OK) return 0;
   return w.total;
 }
 
@@ -2167,63 +2180,30 @@ extern "C" int sumk_lstm_layer_forward(const float* x, int32_t In, int32_t H, in
   SUMK_ARG(x && seq_off_dev && w && h_out && workspace, "lstm_forward: null pointer");
   SUMK_ARG(w->w_ih && w->w_hh && w->b_ih && w->b_hh, "lstm_forward: null weight");
   SUMK_ARG(precision >= SUMK_PRECISION_FP32 && precision <= SUMK_PRECISION_MAX, "lstm_forward: unknown precision %d", precision);
-  Lstm1Ws L;
-  SUMK_TRY(lstm1_carve(In, H, n_seq, seq_off_host, training, &L));
-  if (workspace_bytes < L.total) {
-    set_error("lstm_forward: workspace %zu < required %zu", workspace_bytes, L.total);
-    return SUMK_ERR_WORKSPACE;
-  }
+  LstmWs L;
+  SUMK_TRY(lstm_carve(1, In, H, n_seq, seq_off_host, training, &L));
+  SUMK_TRY(workspace_fits("lstm_forward", workspace_bytes, L.total));
   char* ws = (char*)workspace;
   const int R = L.n_rows;
-  float* G = (float*)(ws + L.g);
   GemmProb* prob = (GemmProb*)(ws + L.prob);
   const int small = gemm_tiles(R, 4 * H, 0) >= 512 ? 0 : 1;
   SUMK_TRY(fill_single_prob(prob, R, 4 * H, In, In, In, 4 * H, 0, small, stream));
   {
     GemmLaunch g;   // G = X W_ih^T + b_ih + b_hh
     g.A = x; g.B[0] = w->w_ih; g.bias0[0] = w->b_ih; g.bias1[0] = w->b_hh;
-    g.C = G; g.probs = prob; g.small_tile = small; g.total_tiles = gemm_tiles(R, 4 * H, small); g.precision = precision;
+    g.C = (float*)(ws + L.g); g.probs = prob; g.small_tile = small; g.total_tiles = gemm_tiles(R, 4 * H, small); g.precision = precision;
     g.lean = gemm_lean_ok(R, 4 * H, In, In, In);
     SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS2, g, stream));
   }
-  if (n_seq <= GV_MAXB) {      // a few sequences: bandwidth-shaped mat-vec steps
-    GemvStepArgs ga;
-    ga.a1 = nullptr; ga.a1_shift = 0; ga.w1 = nullptr; ga.G = G; ga.b1 = ga.b2 = nullptr; ga.w2 = w->w_hh; ga.h0 = h0; ga.c0 = c0;
-    ga.hseq = h_out; ga.c_all = training ? (float*)(ws + L.call) : nullptr; ga.cstate = training ? nullptr : (float*)(ws + L.cstate);
-    ga.gates = training ? (float*)(ws + L.gates) : nullptr; ga.hprev = training ? (float*)(ws + L.hprev) : nullptr; ga.xin = nullptr;
-    ga.off = seq_off_dev; ga.n_seq = n_seq; ga.H = H;
-    for (int t = 0; t < L.t_max; ++t) {
-      ga.t = t;
-      hipLaunchKernelGGL(lstm_gemv_step_kernel, dim3((unsigned)((H + 3) / 4)), dim3(256), 0, stream, ga);
-    }
-    if (h_last || c_last) {
-      const int64_t n = (int64_t)n_seq * H;
-      hipLaunchKernelGGL(lstm_last_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, h_out,
-                         (const float*)ga.c_all, (const float*)ga.cstate, seq_off_dev, n_seq, H, h_last, c_last);
-    }
-    SUMK_HIP(hipGetLastError());
-    return SUMK_OK;
-  }
-  StepArgs a;
-  a.G = G; a.whh[0] = w->w_hh; a.whh[1] = nullptr; a.Hout = h_out;
-  a.cstate = training ? nullptr : (float*)(ws + L.cstate);
-  a.gates = training ? (float*)(ws + L.gates) : nullptr;
-  a.c_all = training ? (float*)(ws + L.call) : nullptr;
-  a.hprev = training ? (float*)(ws + L.hprev) : nullptr;
-  a.off = seq_off_dev; a.n_seq = n_seq; a.H = H; a.n_ublk = (H + 7) / 8;
-  a.nd = 1; a.h0 = h0; a.c0 = c0;
-  const int n_mtiles = (n_seq + 31) / 32;
-  const dim3 grid((unsigned)(n_mtiles * a.n_ublk)), block(256);
-  for (int t = 0; t < L.t_max; ++t) {
-    a.t = t;
-    hipLaunchKernelGGL(lstm_step_kernel, grid, block, 0, stream, a);
-  }
+  const LstmFwdIo io = {{w->w_hh, nullptr}, h0, c0, h_out, seq_off_dev};
+  SUMK_TRY(L.few ? fwd_matvec(L, ws, io, stream) : fwd_chain(L, ws, io, stream));
   if (h_last || c_last) {
+    const LstmSaves sv = lstm_saves(L, ws);
     const int64_t n = (int64_t)n_seq * H;
     hipLaunchKernelGGL(lstm_last_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, h_out,
-                       (const float*)a.c_all, (const float*)a.cstate, seq_off_dev, n_seq, H, h_last, c_last);
+                       (const float*)sv.c_all, (const float*)sv.cstate, seq_off_dev, n_seq, H, h_last, c_last);
+    SUMK_HIP(hipGetLastError());
   }
-  SUMK_HIP(hipGetLastError());
   return SUMK_OK;
 }
 
@@ -2237,59 +2217,17 @@ extern "C" int sumk_lstm_layer_backward(const float* x, const float* h_out, cons
   SUMK_ARG(x && h_out && seq_off_dev && w && gr && workspace, "lstm_backward: null pointer");
   SUMK_ARG(w->w_ih && w->w_hh && gr->w_ih && gr->w_hh && gr->b_ih && gr->b_hh, "lstm_backward: null weight/grad");
   SUMK_ARG(precision >= SUMK_PRECISION_FP32 && precision <= SUMK_PRECISION_MAX, "lstm_backward: unknown precision %d", precision);
-  Lstm1Ws L;
-  SUMK_TRY(lstm1_carve(In, H, n_seq, seq_off_host, 1, &L));
-  if (workspace_bytes < L.total) {
-    set_error("lstm_backward: workspace %zu < required %zu (needs the training-mode forward's workspace)", workspace_bytes, L.total);
-    return SUMK_ERR_WORKSPACE;
-  }
+  LstmWs L;
+  SUMK_TRY(lstm_carve(1, In, H, n_seq, seq_off_host, 1, &L));
+  SUMK_TRY(workspace_fits("lstm_backward", workspace_bytes, L.total, " (needs the training-mode forward's workspace)"));
   char* ws = (char*)workspace;
   const int R = L.n_rows;
   float* dG = (float*)(ws + L.dg);
-  float* hprev = (float*)(ws + L.hprev);
-  float* slab = (float*)(ws + L.slab);
-  float* colpart = (float*)(ws + L.colpart);
   GemmProb* prob = (GemmProb*)(ws + L.prob);
-  GemmProb* psk = (GemmProb*)(ws + L.prob_sk);
-  if (n_seq <= GV_MAXB) {      // a few sequences: bandwidth-shaped transposed mat-vec + cell kernel per step
-    const TGemvGeom tg = tgemv_geom(H);
-    TGemvArgs ta;
-    ta.dGa = dG; ta.wa = w->w_hh; ta.dGb = nullptr; ta.wb = nullptr; ta.b_shift = 0; ta.partial = (float*)(ws + L.partial);
-    ta.off = seq_off_dev; ta.n_seq = n_seq; ta.H = H; ta.rows_per_split = tg.rows_per_split;
-    CellBwdArgs ca;
-    ca.dext = dh_out; ca.dh_last = dh_last; ca.dc_last = dc_last; ca.partial = ta.partial; ca.n_ksplit = tg.n_ksplit;
-    ca.gates = (const float*)(ws + L.gates); ca.c_all = (const float*)(ws + L.call); ca.c0 = c0;
-    ca.dG = dG; ca.dcstate = (float*)(ws + L.dcstate); ca.dh0 = dh0; ca.dc0 = dc0;
-    ca.off = seq_off_dev; ca.n_seq = n_seq; ca.H = H;
-    for (int t = L.t_max - 1; t >= ((dh0 || dc0) ? -1 : 0); --t) {
-      ta.t = ca.t = t;
-      hipLaunchKernelGGL(lstm_tgemv_partial_kernel, dim3((unsigned)tg.strips, (unsigned)tg.n_ksplit), dim3(256), 0, stream, ta);
-      hipLaunchKernelGGL(lstm_cellbwd_kernel, dim3((unsigned)((H + 63) / 64), (unsigned)n_seq), dim3(256), 0, stream, ca);
-    }
-  } else {
-  BwdStepArgs a;
-  a.whh[0] = w->w_hh; a.whh[1] = nullptr; a.dHout = dh_out; a.gates = (const float*)(ws + L.gates);
-  a.c_all = (const float*)(ws + L.call); a.dG = dG; a.dcstate = (float*)(ws + L.dcstate);
-  a.off = seq_off_dev; a.n_seq = n_seq; a.H = H; a.n_jblk = (H + 31) / 32;
-  a.nd = 1; a.c0 = c0; a.dh_last = dh_last; a.dc_last = dc_last; a.dh0 = dh0; a.dc0 = dc0;
-  const int n_mtiles = (n_seq + 31) / 32;
-  const dim3 grid((unsigned)(n_mtiles * a.n_jblk)), block(512);
-  for (int t = L.t_max - 1; t >= ((dh0 || dc0) ? -1 : 0); --t) {
-    a.t = t;
-    hipLaunchKernelGGL(lstm_bwd_step_kernel, grid, block, 0, stream, a);
-  }
-  }
-  SUMK_HIP(hipGetLastError());
-  {
-    float* out[4] = {gr->w_ih, nullptr, nullptr, nullptr};
-    SUMK_TRY(gemm_tn_splitk_accum(dG, 4 * H, x, In, 4 * H, In, R, slab, L.slab_elems, psk, 64, out, 4 * H, In, 1.f, stream, precision));
-  }
-  {
-    float* out[4] = {gr->w_hh, nullptr, nullptr, nullptr};
-    SUMK_TRY(gemm_tn_splitk_accum(dG, 4 * H, hprev, H, 4 * H, H, R, slab, L.slab_elems, psk, 64, out, 4 * H, H, 1.f, stream, precision));
-    const ReduceSeg segs[2] = {{0, 4 * H, gr->b_ih}, {0, 4 * H, gr->b_hh}};
-    SUMK_TRY(colsum_multi(dG, 4 * H, R, 4 * H, colpart, 128, segs, 2, stream));
-  }
+  const LstmBwdIo io = {{w->w_hh, nullptr}, dh_out, c0, dh_last, dc_last, dh0, dc0, seq_off_dev};
+  SUMK_TRY(bwd_steps(L, ws, io, stream));
+  SUMK_TRY(dir_grad_tail(dG, x, In, (const float*)(ws + L.hprev), H, R, (float*)(ws + L.slab), L.slab_elems, (GemmProb*)(ws + L.prob_sk),
+                         (float*)(ws + L.colpart), *gr, stream, precision));
   if (dx) {
     const int small = gemm_tiles(R, In, 0) >= 512 ? 0 : 1;
     SUMK_TRY(fill_single_prob(prob + 1, R, In, 4 * H, 4 * H, In, In, 0, small, stream));
@@ -2501,17 +2439,16 @@ struct DecWs {
   size_t s_hseq, s_gates, s_dcstate;
   size_t xin0, slab, prob_sk, colpart, partial, total, slab_elems;
   int32_t n_rows, t_max;
+  bool few;              // at most GV_MAXB sequences: the mat-vec steps
 };
 static int dec_carve(int H, int Lr, int n_seq, const int32_t* off, DecWs* w) {
   SUMK_ARG(H > 0 && H % 4 == 0, "lstm_decoder: hidden size %d must be a positive multiple of 4", H);
   SUMK_ARG(Lr >= 1 && Lr <= 8, "lstm_decoder: %d layers (supported: 1..8)", Lr);
-  SUMK_ARG(n_seq > 0 && off != nullptr && off[0] == 0, "lstm_decoder: empty batch / seq_off[0] != 0");
-  int tmax = 0;
-  for (int s = 0; s < n_seq; ++s) { int T = off[s + 1] - off[s]; SUMK_ARG(T > 0, "lstm_decoder: sequence %d has %d steps", s, T); tmax = T > tmax ? T : tmax; }
-  const size_t R = (size_t)off[n_seq];
+  SUMK_TRY(scan_sequences(n_seq, off, "lstm_decoder", "sequence", "steps", &w->n_rows, &w->t_max));
+  const size_t R = (size_t)w->n_rows;
   size_t p = 0;
   auto take = [&](size_t bytes) { size_t at = p; p += align_up(bytes, 256); return at; };
-  w->n_rows = (int32_t)R; w->t_max = tmax;
+  w->few = few_sequences(n_seq);
   w->s_hseq = align_up(R * H * 4, 256); w->s_gates = align_up(R * 4 * H * 4, 256); w->s_dcstate = align_up((size_t)n_seq * H * 4, 256);
   w->hseq = take(w->s_hseq * Lr); w->call = take(w->s_hseq * Lr); w->hprev = take(w->s_hseq * Lr);
   w->gates = take(w->s_gates * Lr); w->dg = take(w->s_gates * Lr); w->dcstate = take(w->s_dcstate * Lr);
@@ -2520,7 +2457,7 @@ static int dec_carve(int H, int Lr, int n_seq, const int32_t* off, DecWs* w) {
   w->slab = take(w->slab_elems * 4);
   w->prob_sk = take(64 * sizeof(GemmProb));
   w->colpart = take((size_t)128 * 4 * H * 4);
-  w->partial = take(tgemv_partial_bytes(H, n_seq));
+  w->partial = take(tgemv_partial_bytes(H, n_seq, 1));   // carried at every batch size, as in the one-direction layer
   w->total = p;
   return SUMK_OK;
 }
@@ -2539,39 +2476,33 @@ extern "C" int sumk_lstm_decoder_forward(int32_t H, int32_t n_layers, int32_t n_
   DecWs L;
   SUMK_TRY(dec_carve(H, n_layers, n_seq, seq_off_host, &L));
   for (int l = 0; l < n_layers; ++l) SUMK_ARG(w[l].w_ih && w[l].w_hh && w[l].b_ih && w[l].b_hh, "lstm_decoder_forward: null weight (layer %d)", l);
-  if (workspace_bytes < L.total) { set_error("lstm_decoder_forward: workspace %zu < required %zu", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
+  SUMK_TRY(workspace_fits("lstm_decoder_forward", workspace_bytes, L.total));
   char* ws = (char*)workspace;
   const int top = n_layers - 1;
   auto hseq = [&](int l) { return l == top ? out : (float*)(ws + L.hseq + L.s_hseq * l); };   // the top layer writes the output itself
-  if (n_seq <= GV_MAXB) {      // a few sequences: bandwidth-shaped mat-vec steps
-    GemvStepArgs ga;
-    ga.G = nullptr; ga.cstate = nullptr; ga.off = seq_off_dev; ga.n_seq = n_seq; ga.H = H;
-    for (int t = 0; t < L.t_max; ++t) {
-      ga.t = t;
-      for (int l = 0; l < n_layers; ++l) {
-        ga.a1 = l == 0 ? hseq(top) : hseq(l - 1); ga.a1_shift = l == 0 ? -1 : 0;
-        ga.w1 = w[l].w_ih; ga.w2 = w[l].w_hh; ga.b1 = w[l].b_ih; ga.b2 = w[l].b_hh;
-        ga.h0 = h0 ? h0 + (size_t)l * n_seq * H : nullptr; ga.c0 = c0 ? c0 + (size_t)l * n_seq * H : nullptr;
-        ga.hseq = hseq(l); ga.c_all = (float*)(ws + L.call + L.s_hseq * l); ga.gates = (float*)(ws + L.gates + L.s_gates * l);
-        ga.hprev = (float*)(ws + L.hprev + L.s_hseq * l); ga.xin = l == 0 ? (float*)(ws + L.xin0) : nullptr;
-        hipLaunchKernelGGL(lstm_gemv_step_kernel, dim3((unsigned)((H + 3) / 4)), dim3(256), 0, stream, ga);
-      }
-    }
-    SUMK_HIP(hipGetLastError());
-    return SUMK_OK;
-  }
+  // the per-layer pointers of a step, the same in both step kernels' argument structs
+  auto layer = [&](auto& a, int l) {
+    a.a1 = l == 0 ? hseq(top) : hseq(l - 1); a.a1_shift = l == 0 ? -1 : 0;
+    a.w1 = w[l].w_ih; a.w2 = w[l].w_hh; a.b1 = w[l].b_ih; a.b2 = w[l].b_hh;
+    a.h0 = h0 ? h0 + (size_t)l * n_seq * H : nullptr; a.c0 = c0 ? c0 + (size_t)l * n_seq * H : nullptr;
+    a.hseq = hseq(l); a.c_all = (float*)(ws + L.call + L.s_hseq * l); a.gates = (float*)(ws + L.gates + L.s_gates * l);
+    a.hprev = (float*)(ws + L.hprev + L.s_hseq * l); a.xin = l == 0 ? (float*)(ws + L.xin0) : nullptr;
+  };
+  GemvStepArgs ga;             // a few sequences: bandwidth-shaped mat-vec steps
+  ga.G = nullptr; ga.cstate = nullptr; ga.off = seq_off_dev; ga.n_seq = n_seq; ga.H = H;
   DecStepArgs a;
   a.off = seq_off_dev; a.n_seq = n_seq; a.H = H; a.n_ublk = (H + 7) / 8;
   const dim3 grid((unsigned)(((n_seq + 31) / 32) * a.n_ublk)), block(256);
   for (int t = 0; t < L.t_max; ++t) {
-    a.t = t;
+    ga.t = a.t = t;
     for (int l = 0; l < n_layers; ++l) {
-      a.a1 = l == 0 ? hseq(top) : hseq(l - 1); a.a1_shift = l == 0 ? -1 : 0;
-      a.w1 = w[l].w_ih; a.w2 = w[l].w_hh; a.b1 = w[l].b_ih; a.b2 = w[l].b_hh;
-      a.h0 = h0 ? h0 + (size_t)l * n_seq * H : nullptr; a.c0 = c0 ? c0 + (size_t)l * n_seq * H : nullptr;
-      a.hseq = hseq(l); a.c_all = (float*)(ws + L.call + L.s_hseq * l); a.gates = (float*)(ws + L.gates + L.s_gates * l);
-      a.hprev = (float*)(ws + L.hprev + L.s_hseq * l); a.xin = l == 0 ? (float*)(ws + L.xin0) : nullptr;
-      hipLaunchKernelGGL(lstm_dec_step_kernel, grid, block, 0, stream, a);
+      if (L.few) {
+        layer(ga, l);
+        hipLaunchKernelGGL(lstm_gemv_step_kernel, dim3((unsigned)((H + 3) / 4)), dim3(256), 0, stream, ga);
+      } else {
+        layer(a, l);
+        hipLaunchKernelGGL(lstm_dec_step_kernel, grid, block, 0, stream, a);
+      }
     }
   }
   SUMK_HIP(hipGetLastError());
@@ -2586,13 +2517,13 @@ extern "C" int sumk_lstm_decoder_backward(int32_t H, int32_t n_layers, int32_t n
   SUMK_ARG(seq_off_dev && w && out && dout && gr && workspace, "lstm_decoder_backward: null pointer");
   DecWs L;
   SUMK_TRY(dec_carve(H, n_layers, n_seq, seq_off_host, &L));
-  if (workspace_bytes < L.total) { set_error("lstm_decoder_backward: workspace %zu < required %zu", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
+  SUMK_TRY(workspace_fits("lstm_decoder_backward", workspace_bytes, L.total));
   char* ws = (char*)workspace;
   const int R = L.n_rows, top = n_layers - 1;
   auto dG = [&](int l) { return (float*)(ws + L.dg + L.s_gates * l); };
   auto hseq = [&](int l) { return l == top ? out : (const float*)(ws + L.hseq + L.s_hseq * l); };
   const bool want0 = dh0 || dc0;
-  if (n_seq <= GV_MAXB) {      // a few sequences: transposed mat-vec partials + cell kernel per (layer, step)
+  if (L.few) {                 // a few sequences: transposed mat-vec partials + cell kernel per (layer, step)
     const TGemvGeom tg = tgemv_geom(H);
     TGemvArgs ta;
     ta.partial = (float*)(ws + L.partial); ta.off = seq_off_dev; ta.n_seq = n_seq; ta.H = H; ta.rows_per_split = tg.rows_per_split;
@@ -2639,13 +2570,7 @@ extern "C" int sumk_lstm_decoder_backward(int32_t H, int32_t n_layers, int32_t n
   for (int l = 0; l < n_layers; ++l) {
     SUMK_ARG(gr[l].w_ih && gr[l].w_hh && gr[l].b_ih && gr[l].b_hh, "lstm_decoder_backward: null grad (layer %d)", l);
     const float* xin = l == 0 ? (const float*)(ws + L.xin0) : hseq(l - 1);
-    { float* o[4] = {gr[l].w_ih, nullptr, nullptr, nullptr};
-      SUMK_TRY(gemm_tn_splitk_accum(dG(l), 4 * H, xin, H, 4 * H, H, R, slab, L.slab_elems, psk, 64, o, 4 * H, H, 1.f, stream)); }
-    { float* o[4] = {gr[l].w_hh, nullptr, nullptr, nullptr};
-      SUMK_TRY(gemm_tn_splitk_accum(dG(l), 4 * H, (const float*)(ws + L.hprev + L.s_hseq * l), H, 4 * H, H, R, slab, L.slab_elems, psk, 64, o,
-                                    4 * H, H, 1.f, stream)); }
-    const ReduceSeg segs[2] = {{0, 4 * H, gr[l].b_ih}, {0, 4 * H, gr[l].b_hh}};
-    SUMK_TRY(colsum_multi(dG(l), 4 * H, R, 4 * H, colpart, 128, segs, 2, stream));
+    SUMK_TRY(dir_grad_tail(dG(l), xin, H, (const float*)(ws + L.hprev + L.s_hseq * l), H, R, slab, L.slab_elems, psk, colpart, gr[l], stream));
   }
   return SUMK_OK;
 }
@@ -2675,7 +2600,7 @@ extern "C" int sumk_linear_forward(const float* x, const float* w, const float* 
   SUMK_ARG(M > 0 && N > 0 && K > 0 && K % 4 == 0, "linear_forward: bad shape M=%d N=%d K=%d (K must be a multiple of 4)", M, N, K);
   SUMK_ARG(precision >= SUMK_PRECISION_FP32 && precision <= SUMK_PRECISION_MAX, "linear_forward: unknown precision %d", precision);
   LinWs L; linear_carve(N, K, &L);
-  if (workspace_bytes < L.total) { set_error("linear_forward: workspace %zu < required %zu", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
+  SUMK_TRY(workspace_fits("linear_forward", workspace_bytes, L.total));
   GemmProb* prob = (GemmProb*)((char*)workspace + L.prob);
   const int small = gemm_tiles(M, N, 0) >= 512 ? 0 : 1;
   SUMK_TRY(fill_single_prob(prob, M, N, K, K, K, N, 0, small, stream));
@@ -2692,7 +2617,7 @@ extern "C" int sumk_linear_backward(const float* x, const float* w, const float*
   SUMK_ARG(M > 0 && N > 0 && K > 0 && K % 4 == 0 && N % 4 == 0, "linear_backward: bad shape M=%d N=%d K=%d (N, K multiples of 4)", M, N, K);
   SUMK_ARG(precision >= SUMK_PRECISION_FP32 && precision <= SUMK_PRECISION_MAX, "linear_backward: unknown precision %d", precision);
   LinWs L; linear_carve(N, K, &L);
-  if (workspace_bytes < L.total) { set_error("linear_backward: workspace %zu < required %zu", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
+  SUMK_TRY(workspace_fits("linear_backward", workspace_bytes, L.total));
   char* ws = (char*)workspace;
   GemmProb* prob = (GemmProb*)(ws + L.prob);
   if (dw) {   // dW (N, K) += dY^T X
@@ -2720,10 +2645,7 @@ extern "C" int sumk_frame_head_backward(const float* h, const float* scores, con
   hipStream_t stream = (hipStream_t)stream_;
   SUMK_ARG(h && scores && dscores && w && dh && dw && db && workspace, "frame_head_backward: null pointer");
   SUMK_ARG(n_rows > 0 && F > 0 && F % 4 == 0, "frame_head_backward: bad shape n_rows=%d F=%d", n_rows, F);
-  if (workspace_bytes < sumk_frame_head_workspace_bytes(F)) {
-    set_error("frame_head_backward: workspace %zu < required %zu", workspace_bytes, sumk_frame_head_workspace_bytes(F));
-    return SUMK_ERR_WORKSPACE;
-  }
+  SUMK_TRY(workspace_fits("frame_head_backward", workspace_bytes, sumk_frame_head_workspace_bytes(F)));
   int blocks = std::max(1, std::min((n_rows + 3) / 4, 256));
   float* part = (float*)workspace;
   hipLaunchKernelGGL(frame_head_bwd_kernel, dim3(blocks), dim3(256), 0, stream, h, scores, dscores, w, dh, part, n_rows, F);
@@ -2740,7 +2662,7 @@ extern "C" int sumk_bilstm_check(const void* workspace, int32_t In, int32_t H, i
   hipStream_t stream = (hipStream_t)stream_;
   SUMK_ARG(workspace, "bilstm_check: null workspace");
   LstmWs L;
-  SUMK_TRY(lstm_carve(In, H, n_seq, seq_off_host, training, &L));
+  SUMK_TRY(lstm_carve(2, In, H, n_seq, seq_off_host, training, &L));
   unsigned flags[2] = {0u, 0u};
   SUMK_HIP(hipMemcpyAsync(&flags[0], (const char*)workspace + L.pstate, 4, hipMemcpyDeviceToHost, stream));
   if (training && after_backward) SUMK_HIP(hipMemcpyAsync(&flags[1], (const char*)workspace + L.pstate_b, 4, hipMemcpyDeviceToHost, stream));

@@ -1,8 +1,10 @@
 // Shared by the persistent recurrence kernels (lstm.hip, gru_persist.hip): vector types, the gate math of the per-step latency chain,
-// the bounded-wait constants of the hand-off protocol (written out at the top of the "persistent recurrence" section of lstm.hip) and
-// the host-side helpers that lstm.hip owns.
+// the bounded-wait constants of the hand-off protocol (written out at the top of the "persistent recurrence" section of lstm.hip), the
+// host-side helpers that lstm.hip owns, and the host arithmetic the layers' workspace plans share (state block, group size, sequence
+// scan, workspace check, cooperative launch).
 #pragma once
 #include "sumk_internal.h"
+#include <algorithm>
 
 namespace sumk {
 
@@ -41,5 +43,57 @@ __device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p
 bool persistent_kernels_usable();
 unsigned* persist_health_word();
 int persist_zero_words(unsigned* p, size_t words, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------- host: what the layers' plans share
+// State block of a persistent launch.  Word 0: the per-call error flag; words 16..: step counters per work item -- one word each, or
+// (lstm_wide2_kernel always, the BPTTs while the items fit) four shards on lines of their own, 128 words per item.  The last
+// PSTATE_SPARE_WORDS words are unused: the sharded layouts stay clear of them (their eligibility bounds, and so which kernel a batch
+// gets, are as measured).
+constexpr int PSTATE_WORDS = 16 + 16384;
+constexpr int PSTATE_SPARE_WORDS = 512;
+constexpr int PSTATE_ITEM_WORDS = 128;        // a sharded item
+inline bool pk_items_fit(int n_items) { return n_items <= PSTATE_WORDS - 16; }
+inline bool pk_items_shard(int n_items) { return n_items * PSTATE_ITEM_WORDS <= PSTATE_WORDS - 16 - PSTATE_SPARE_WORDS; }
+
+// videos per work item of the H <= 256 recurrences: a batch spreads over the 8 teams in both directions, and at most 32 fit the LDS map
+// (gsize x (H + 4) floats in front of the partial tiles)
+inline int pk_group_size(int n_seq) { return std::min(32, std::max(1, (2 * n_seq + PK_TEAMS - 1) / PK_TEAMS)); }
+
+// Packed batch on the host: seq_off[0] = 0 and every sequence has a step.  `who` prefixes the messages; `item` / `steps` name a sequence
+// and its steps in the caller's words ("video" / "frames").
+inline int scan_sequences(int n_seq, const int32_t* off, const char* who, const char* item, const char* steps, int32_t* n_rows, int32_t* t_max) {
+  SUMK_ARG(n_seq > 0 && off != nullptr && off[0] == 0, "%s: empty batch / seq_off[0] != 0", who);
+  int tmax = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    const int T = off[s + 1] - off[s];
+    SUMK_ARG(T > 0, "%s: %s %d has %d %s", who, item, s, T, steps);
+    tmax = T > tmax ? T : tmax;
+  }
+  *n_rows = off[n_seq]; *t_max = tmax;
+  return SUMK_OK;
+}
+
+// `note` follows the two sizes (" (needs the training-mode forward's workspace)")
+inline int workspace_fits(const char* who, size_t have, size_t need, const char* note = "") {
+  if (have >= need) return SUMK_OK;
+  set_error("%s: workspace %zu < required %zu%s", who, have, need, note);
+  return SUMK_ERR_WORKSPACE;
+}
+
+// Cooperative launch of one persistent kernel instance over the chip: 256 blocks of PK_THREADS, `shmem` bytes of dynamic LDS (callers ask
+// for > 80 KB to keep one block per CU).  The instance's dynamic-LDS ceiling is raised the first time it is launched.
+inline int persist_launch(const void* fn, void* args, size_t shmem, hipStream_t stream) {
+  static const void* raised[16];
+  static int n_raised = 0;
+  bool seen = false;
+  for (int i = 0; i < n_raised; ++i) seen |= raised[i] == fn;
+  if (!seen) {
+    SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (n_raised < 16) raised[n_raised++] = fn;
+  }
+  void* kargs[] = {args};
+  SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(PK_TEAMS * 32), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
+  return SUMK_OK;
+}
 
 }  // namespace sumk

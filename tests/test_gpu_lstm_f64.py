@@ -1,5 +1,7 @@
-"""GPU: the bidirectional LSTM recurrences of csrc/lstm.hip -- every forward form and every BPTT form the dispatch of
-sumk_bilstm_layer_forward / sumk_bilstm_layer_backward can reach -- against float64, video by video and gate block by gate block.
+"""GPU: the bidirectional LSTM recurrences of csrc/lstm.hip -- every forward form and every BPTT form that the layer's path plan can
+give a shape (lstm_carve records the persistent form each pass is eligible for, LstmWs::fwd / bwd; lstm_usable applies the run-time
+gates, and without a persistent form a few videos take the mat-vec BPTT, more the launch chain) -- against float64, video by video and
+gate block by gate block.
 
 tests/test_gpu_lstm.py and tests/test_gpu_train_full.py compare one kernel form with another (an error both share passes), scores within
 1e-4 and whole-tensor gradient norms within 3e-4 (an error confined to one video, one 16/32-row tile, one gate block or one member's
@@ -27,7 +29,7 @@ Every case runs with uninitialised device allocations poisoned (Poison of tests/
 kernels.health_check().  Each video has its own feature seed; every batch of more than three videos holds a one-frame video, a two-frame
 video and ties in length.  References are cached per (case, arithmetic): forms and precisions share one CPU run.
 
-Cases (H, D, videos; what the dispatch gives them):
+Cases (H, D, videos; what the plan gives them):
   a  256, 128,   9 (<= 64 frames)  groups of 3: forward and BPTT on 16-row MFMAs, coalesced BPTT exchange (8 aligned units per member)
   b  256, 128,  70 (<= 40)         groups of 18: 32-row MFMAs, the last group partial
   c  256, 128, 140 (<= 24)         groups of 32, 10 work items on 8 teams (a team runs a second item); >= 1024 rows: in bf16x6 / bf16x3
