@@ -448,6 +448,23 @@ size_t sumk_dsn_reward_workspace_bytes(int32_t D, int32_t n_seq, const int32_t* 
 int sumk_dsn_reward(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host,
                     const int32_t* seq_off_dev, const float* actions, int32_t n_episodes, int32_t far_sim,
                     int32_t temp_dist_thre, float* reward, void* workspace, size_t workspace_bytes, void* stream);
+/* The same reward without the (T x T) Gram matrix (csrc/reward_stream.hip): every Gram tile is consumed in registers as the MFMA
+ * produces it, so the workspace is O(n_episodes x n_rows) and a video may have up to 1 048 576 frames (n_rows < 2^31, D % 4 == 0,
+ * x 16-byte aligned, any number of episodes; every offset into x is 64-bit).  Arguments, semantics, status codes and
+ * sumk_last_error() as sumk_dsn_reward: a frame is picked where its action is non-zero (-0.0 is not a pick), no pick gives exactly
+ * 0, one pick gives r_div = 0 with r_rep evaluated, a picked zero-norm frame among two or more picks gives NaN for that (episode,
+ * video) only.  col_split: 0 = the library's plan (sumk_dsn_reward_stream_plan), 1..8 = that many splits of a video's 64-column
+ * key tiles among workgroups (a video never gets more splits than it has key tiles); every split count gives a result within
+ * rounding of the others, and one split count gives the same bits on every call.  The workspace size does not depend on col_split.
+ * Episodes are served in chunks of SUMK_REWARD_STREAM_EC per pass over the tiles.  No cooperative launch, no float atomics;
+ * the whole call may be captured into a HIP graph. */
+#define SUMK_REWARD_STREAM_EC 8
+size_t sumk_dsn_reward_stream_workspace_bytes(int32_t D, int32_t n_seq, const int32_t* seq_off_host, int32_t n_episodes);
+int32_t sumk_dsn_reward_stream_plan(int32_t n_seq, const int32_t* seq_off_host);   /* the split count col_split = 0 stands for; 0 on a bad argument */
+int sumk_dsn_reward_stream(const float* x, int32_t D, int32_t n_seq, const int32_t* seq_off_host,
+                           const int32_t* seq_off_dev, const float* actions, int32_t n_episodes, int32_t far_sim,
+                           int32_t temp_dist_thre, int32_t col_split, float* reward, void* workspace, size_t workspace_bytes,
+                           void* stream);
 /* The loss glue of DSNTrainer.train for a packed batch (dsn.py:113-140), per video v:
  *   loss_per_video[v] = [ beta (mean_t p_t - eps_target)^2 - sum_e (rewards[e,v] - base[v]) mean_t log P(actions[e,t] | p_t) ] / E
  * with torch.distributions.Bernoulli's log_prob (probabilities clamped to [eps, 1 - eps], eps = float32 epsilon), and its
@@ -965,7 +982,13 @@ int sumk_pack_rows_bf16(uint16_t* dst_bf16, const float* const* srcs, const int3
 #define SUMK_PROF_BAND_BWD_DQ 12           /* dQ = dLogits K              */
 #define SUMK_PROF_BAND_BWD_TRANSPOSE_S 13  /* transpose(dLogits)          */
 #define SUMK_PROF_BAND_BWD_DK 14           /* dK = dLogits^T Q            */
-#define SUMK_PROF_NTAGS 15
+/* the launches of sumk_dsn_reward_stream (csrc/reward_stream.hip) */
+#define SUMK_PROF_REWARD_STREAM_PREP 15    /* descriptors + pick bits               */
+#define SUMK_PROF_REWARD_STREAM_NORM 16    /* squared norms: the diagonal Gram tiles */
+#define SUMK_PROF_REWARD_STREAM_PASS 17    /* the streaming passes (one per chunk)  */
+#define SUMK_PROF_REWARD_STREAM_ROWS 18    /* splits and rows joined per row block  */
+#define SUMK_PROF_REWARD_STREAM_JOIN 19    /* per (episode, video): the reward      */
+#define SUMK_PROF_NTAGS 20
 /* The small-batch GEMM form by itself (tests, probes): C = epilogue(A . B) for ONE exact-fp32 problem on 64x64 tiles whose K is cut
  * into `slices` (1 .. 8) slices INSIDE the launch -- every (tile, slice) block stores a partial tile, the last one to arrive adds
  * them in slice order and runs the epilogue (csrc/gemm_lean.hip, SK instances; what sumk_vasnet_forward / _backward launch for batches

@@ -818,14 +818,48 @@ def frame_head_backward(h, scores, dscores, w, dw, db):
 
 
 # ------------------------------------------------------------------------------------------------ DSN reward
-def dsn_reward(x, sb, actions, far_sim=False, temp_dist_thre=20):
-    """actions: (E, n_rows) 0/1 floats -> rewards (E, n_seq) (dsn.py:185-236) for a packed batch."""
+REWARD_PATHS = ("gram", "stream")
+REWARD_STREAM_EC = 8       # episodes per pass of the streaming reward (include/sumk.h: SUMK_REWARD_STREAM_EC)
+
+
+def _reward_path(path):
+    if path not in REWARD_PATHS:
+        raise SumkError(f"dsn_reward: path must be one of {REWARD_PATHS}, got {path!r}")
+    return path
+
+
+def dsn_reward_workspace_bytes(D, sb, E, path="gram"):
+    """Bytes of scratch one dsn_reward call takes: O(sum T^2) on the "gram" path, O(E * n_rows) on the "stream" path."""
     lib = _lib.load()
+    name = "sumk_dsn_reward_workspace_bytes" if _reward_path(path) == "gram" else "sumk_dsn_reward_stream_workspace_bytes"
+    return _nonzero(getattr(lib, name)(int(D), sb.n_seq, sb.off_host_p, int(E)), name)
+
+
+def dsn_reward_stream_plan(sb):
+    """The column split count that col_split=0 stands for on the "stream" path."""
+    return int(_lib.load().sumk_dsn_reward_stream_plan(sb.n_seq, sb.off_host_p))
+
+
+def dsn_reward(x, sb, actions, far_sim=False, temp_dist_thre=20, path="gram", col_split=0):
+    """actions: (E, n_rows) 0/1 floats -> rewards (E, n_seq) (dsn.py:185-236) for a packed batch.
+    path="gram": one Gram matrix per video in the workspace (csrc/reward.hip); path="stream": the Gram tiles are consumed in registers
+    (csrc/reward_stream.hip; videos of up to 1 048 576 frames), col_split forces the number of column splits (0: the library's plan)."""
+    lib = _lib.load()
+    _reward_path(path)
     _require_gpu(x, "dsn_reward features"); _require_gpu(actions, "dsn_reward actions")
     E = actions.shape[0]
     if actions.dim() != 2 or actions.shape[1] != sb.n_rows or not actions.is_contiguous():
         raise SumkError(f"dsn_reward: actions must be contiguous (E, {sb.n_rows}), got {tuple(actions.shape)}")
     D = x.shape[1]
+    if path == "stream":
+        _check_rows(x, sb, "dsn_reward features")
+        nb = dsn_reward_workspace_bytes(D, sb, E, "stream")
+        ws = workspace(nb, x.device)
+        out = torch.empty(E, sb.n_seq, dtype=torch.float32, device=x.device)
+        rc = lib.sumk_dsn_reward_stream(_p(x), D, sb.n_seq, sb.off_host_p, sb.off_dev_p, _p(actions), E, int(bool(far_sim)),
+                                        int(temp_dist_thre), int(col_split), _p(out), _p(ws), ws.numel(), _stream())
+        _lib.check(rc, "sumk_dsn_reward_stream")
+        return out
     nb = _nonzero(lib.sumk_dsn_reward_workspace_bytes(D, sb.n_seq, sb.off_host_p, E), "sumk_dsn_reward_workspace_bytes")
     ws = workspace(nb, x.device)
     out = torch.empty(E, sb.n_seq, dtype=torch.float32, device=x.device)

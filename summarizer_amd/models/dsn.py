@@ -57,7 +57,8 @@ class DSNTrainer(Trainer):
 
     Differences underneath: the reward of all episodes comes from ONE HIP call (one Gram GEMM + masked reductions,
     csrc/reward.hip) instead of 2 matmuls per episode; the optimiser is the flat-bucket HIP Adam with the clip folded in.
-    Extensions: extra_params["batch_videos"], and sharding of the training videos over torch.distributed ranks with one
+    Extensions: extra_params["reward_path"] = "stream" (the reward without a (T x T) Gram matrix per video, csrc/reward_stream.hip: long
+    videos; default "gram"), extra_params["batch_videos"], and sharding of the training videos over torch.distributed ranks with one
     gradient all-reduce per step; per-video baselines stay on the rank that owns the video (static assignment)."""
 
     def _init_model(self):
@@ -66,6 +67,10 @@ class DSNTrainer(Trainer):
         self.num_episodes = int(ep.get("num_episodes", 5))
         self.eps = float(ep.get("eps", 0.5))
         self.far_sim = bool(ep.get("far_sim", False))
+        # not in the reference: "gram" (one Gram matrix per video, csrc/reward.hip) | "stream" (no (T x T) array, csrc/reward_stream.hip)
+        self.reward_path = ep.get("reward_path", "gram")
+        if self.reward_path not in kernels.REWARD_PATHS:
+            raise SumkError(f"DSNTrainer: reward_path must be one of {kernels.REWARD_PATHS}, got {self.reward_path!r}")
         self.temp_dist_thre = int(ep.get("temp_dist_thre", 20))
         self.sup = bool(ep.get("sup", False))
         model = DSN(**({"input_size": int(ep["input_size"])} if "input_size" in ep else {}),
@@ -83,7 +88,7 @@ class DSNTrainer(Trainer):
             raise IndexError("Dimension out of range (expected to be in range of [-1, 0], but got 1)")
         sb = kernels.SeqBatch.get([T], seq.device)
         r = kernels.dsn_reward(seq.detach().reshape(T, -1).contiguous(), sb, actions.detach().reshape(1, T).contiguous(),
-                               far_sim=far_sim, temp_dist_thre=temp_dist_thre)
+                               far_sim=far_sim, temp_dist_thre=temp_dist_thre, path=getattr(self, "reward_path", "gram"))
         return r.reshape(())
 
     def _sample_actions(self, dist, n_episodes, keys):
@@ -134,7 +139,7 @@ class DSNTrainer(Trainer):
                     dist = Bernoulli(probs, validate_args=False)          # (argument validation is a D2H sync; probs come from the sigmoid kernel)
                     actions = self._sample_actions(dist, E, keys)         # (E, sum T)   dsn.py:125
                     rewards = kernels.dsn_reward(x, sb, actions.contiguous(), far_sim=self.far_sim,
-                                                 temp_dist_thre=self.temp_dist_thre)       # (E, n_videos)  dsn.py:129-131
+                                                 temp_dist_thre=self.temp_dist_thre, path=self.reward_path)       # (E, n_videos)  dsn.py:129-131
                     idx = order[step * bv:step * bv + len(keys)]
                     base = baselines[idx].float()
                     # all videos of the step at once; for one video this is exactly dsn.py:115-140:
