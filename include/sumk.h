@@ -425,6 +425,32 @@ int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t n_heads, in
                              const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
                              const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows, float* scores,
                              void* workspace, size_t workspace_bytes, int32_t training, void* stream);
+/* Multi-head attention WITHOUT the (T x T) logits (csrc/attn_stream.hip), exact fp32, no mask, for a packed batch: per video v and head h
+ *   ctx[rows of v, h dh : (h + 1) dh] = softmax_j(scale Q_h K_h^T) V_h,   dh = D / n_heads,
+ * with head h at column h * dh of Q, K, V and ctx (leading dimensions >= D and % 4 == 0, pointers 16-byte aligned: the in-place
+ * [Q | K | V] buffer with ld = 3 D works) and one segment table for Q and K / V.  lse: NULL, or (n_rows, n_heads) floats that receive
+ * log sum_j exp(scale q . k_j) per (row, head).  One setup launch and one attention launch -- a workgroup per (128-row query strip,
+ * head) walks the video's 64-key tiles in ascending order with an online softmax rescaled every tile; logits live in MFMA accumulator
+ * registers only, so nothing of size T x T exists and the workspace is 16 bytes per video.  No cooperative launch, no atomics: every
+ * call gives the same bits, and the call only enqueues work (it may be captured into a HIP graph).  Every global offset is 64-bit.
+ * Limits: dh % 4 == 0 and dh <= 256; 1 <= T < 2^20 frames per video; at most 65 535 videos; scale positive and finite.  Anything else
+ * returns SUMK_ERR_ARG, a short workspace SUMK_ERR_WORKSPACE; both set sumk_last_error() and launch nothing.  NaN in a Q row gives NaN
+ * in that row of ctx; NaN in a K or V row reaches the rows of its own video (and the heads whose columns hold it) only.
+ * The size queries are host arithmetic (0 = bad arguments).
+ * sumk_transformer_forward_stream: the inference of sumk_transformer_forward (same arguments without `training`) with the attention
+ * of every layer on that launch and no logits block in its workspace (sumk_transformer_stream_workspace_bytes: O(n_rows (D + F))).
+ * opts->precision must be SUMK_PRECISION_FP32, opts->wplanes NULL and both dropout probabilities 0; the limits above apply. */
+size_t sumk_attn_stream_workspace_bytes(int32_t D, int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host);
+int sumk_attn_stream(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, int32_t D,
+                     int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale,
+                     float* ctx, int32_t ldc, float* lse, void* workspace, size_t workspace_bytes, void* stream);
+size_t sumk_transformer_stream_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                               const int32_t* seq_off_host);
+int sumk_transformer_forward_stream(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                    const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                    const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                    const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows, float* scores,
+                                    void* workspace, size_t workspace_bytes, void* stream);
 /* Gradient targets, same shapes as the weights; ACCUMULATED into (caller zeroes them). */
 typedef struct sumk_tf_layer_grads {
   float* in_proj_w; float* in_proj_b; float* out_proj_w; float* out_proj_b; float* lin1_w; float* lin1_b;
@@ -988,7 +1014,11 @@ int sumk_pack_rows_bf16(uint16_t* dst_bf16, const float* const* srcs, const int3
 #define SUMK_PROF_REWARD_STREAM_PASS 17    /* the streaming passes (one per chunk)  */
 #define SUMK_PROF_REWARD_STREAM_ROWS 18    /* splits and rows joined per row block  */
 #define SUMK_PROF_REWARD_STREAM_JOIN 19    /* per (episode, video): the reward      */
-#define SUMK_PROF_NTAGS 20
+/* the Transformer scorer's attention, per layer: the three launches of the dense core (logits, softmax, context: csrc/transformer.hip
+ * tf_attn_core_fwd) and the one launch of the stream form (csrc/attn_stream.hip, without its descriptor setup) */
+#define SUMK_PROF_TF_ATTN_DENSE 20
+#define SUMK_PROF_ATTN_STREAM 21
+#define SUMK_PROF_NTAGS 22
 /* The small-batch GEMM form by itself (tests, probes): C = epilogue(A . B) for ONE exact-fp32 problem on 64x64 tiles whose K is cut
  * into `slices` (1 .. 8) slices INSIDE the launch -- every (tile, slice) block stores a partial tile, the last one to arrive adds
  * them in slice order and runs the epilogue (csrc/gemm_lean.hip, SK instances; what sumk_vasnet_forward / _backward launch for batches

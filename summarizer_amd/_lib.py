@@ -21,6 +21,13 @@ class SumkError(RuntimeError):
     pass
 
 
+# Profiler tags of sumk_prof_enable / sumk_prof_read that Python callers name (include/sumk.h SUMK_PROF_*; tests/test_attn_stream_host.py
+# holds these to the header)
+PROF_TF_ATTN_DENSE = 20     # the dense attention core's three launches, per layer
+PROF_ATTN_STREAM = 21       # the streaming attention launch (csrc/attn_stream.hip)
+PROF_NTAGS = 22
+
+
 class VasnetWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("Wk", "Wq", "Wv", "Wo", "W1", "b1", "w2", "b2", "ln_w", "ln_b")]
 
@@ -206,6 +213,13 @@ _SIGS = {
     "sumk_transformer_forward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, c_i32p, c_f32p, C.c_void_p, C.c_size_t,
                                            C.c_int32, C.c_void_p]),
+    "sumk_attn_stream_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, HOST_I32P]),
+    "sumk_attn_stream": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P,
+                                   c_i32p, C.c_float, c_f32p, C.c_int32, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_transformer_stream_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P]),
+    "sumk_transformer_forward_stream": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, c_i32p, c_f32p, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p]),
     "sumk_transformer_backward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p, c_f32p,
                                             C.c_void_p, C.c_size_t, C.c_void_p]),

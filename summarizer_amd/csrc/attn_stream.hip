@@ -1,0 +1,358 @@
+// Multi-head attention WITHOUT the (T x T) logits: the streaming, exact-fp32 form of tf_attn_core_fwd (transformer.hip) for long videos.
+//
+//   ctx[rows of v, h dh : (h + 1) dh] = softmax_j(scale Q_h K_h^T) V_h          per video v and head h of a packed batch, no mask
+//
+// tf_attn_core_fwd stores heads x T x T logits per video (2.1 GB at T = 8192, 8 heads) and makes four passes over them.  Here a logit
+// lives in an MFMA accumulator register from the first product to the second: nothing of size T x T, or T x anything that grows with T,
+// exists beyond the inputs and the outputs.  Workspace: one 16-byte descriptor per video.
+//
+// Launches of one call (both on the caller's stream, nothing else: the call captures into a HIP graph):
+//   as_setup_kernel    per-video descriptors (first row, frames, first query strip) from the device offsets
+//   as_stream_kernel   one workgroup (4 waves) per (query strip of 128 rows, head); block = strip * heads + head, so the heads of a strip
+//                      run side by side and a head's K / V tiles are shared through L2 by the strips running at that time.  A wave owns
+//                      32 WHOLE query rows; the workgroup walks the video's 64-key tiles in ascending order.  No column split.
+// No cooperative launch, no flag polled across workgroups, no atomics: bit-deterministic.
+//
+// Lane layout (v_mfma_f32_32x32x2_f32 for both products; lane = (li = lane & 31, lh = lane >> 5)):
+//   S^T = K_tile (A) x Q_strip^T (B), the swapped product of rs_stream_kernel: A[row li][k lh] = K[key 32 s + li][d], B[k lh][col li] =
+//     Q[query li][d]; one ds_read_b128 of a K row feeds four MFMAs, so MFMA j of group g contracts d = 8 g + j (lh 0) then 8 g + 4 + j
+//     (lh 1), groups ascending.  Accumulator register r of sub-tile s then holds, for QUERY li, key 32 s + crow(r, lh),
+//     crow(r, lh) = (r & 3) + 8 (r >> 2) + 4 lh: a lane owns one query row and 32 of the tile's 64 keys, its partner lane ^ 32 the others.
+//   O^T[d][q] += V^T[d][key] P^T[key][q]: with f32 operands that accumulator register IS the B operand of MFMA step (s, r) -- B[k lh][col li]
+//     = P[query li][key 32 s + crow(r, lh)] -- so P is never converted, never goes through LDS and never changes lane.  The matching A
+//     value is V[key 32 s + crow(r, lh)][d] with d chosen by the lane: d = (b % W) + W li + 32 W (b / W) for accumulator block b,
+//     W = min(NB, 4), so that ONE ds_read_b128 (W = 4) of a V row feeds the MFMAs of four blocks.  O block b register r of lane
+//     (li, lh) is O[query li][d = (b % W) + W crow(r, lh) + 32 W (b / W)]: the running rescale of O is a per-lane multiply.
+//   Row maximum: 31 fmax in the lane + one exchange with lane ^ 32.  Row sum: each lane half keeps its own partial (same rescale factor
+//     in both), joined once after the walk.
+//
+// Online softmax per tile, UNCONDITIONALLY (no deferred-max threshold, hence no rare data-dependent branch): m' = max(m, scale max_j s_j),
+// f = exp(m - m'), p_j = exp(fma(s_j, scale, -m')) (the dense kernel's expression), l = l f + sum p, O = O f + P V; at the end O / l and
+// lse = m + log(l).  m starts at -inf: the first tile's f is exp(-inf) = 0.  Keys past T get the logit -inf (p = 0 exactly) and their V
+// rows are staged as zeros; their K rows and the query rows past T are the video's last row (clamped) and such queries are never stored.
+//
+// Head width: one kernel body, instantiated for NB = 1, 2, 4, 8 blocks of 32 columns (dh <= 32 NB; the columns dh .. 32 NB - 1 of Q, K
+// and V are staged as zeros, so dh = 36 or 100 take the same loop as 128: their padded k-steps add fma(0, 0, acc)).  Per workgroup:
+//   dh      NB   LDS: K tile + V tile, 64 x (32 NB + 4) floats each    registers per lane: Q 16 NB + O 16 NB + S 32 + staging 4 NB + fragments
+//   128     4    66 KiB  -> 2 workgroups per CU (132 of 160 KiB)         64 + 64 + 32 + 16 + 16 = 192 by count; the compiler takes 239 of 256, no
+//                                                                       spill: 2 waves per SIMD
+//   256     8    130 KiB -> 1 workgroup per CU                          128 + 128 + 32 + 32 + 24 = 344 of 512 by count (1 wave per SIMD); the compiler
+//                                                                       fills 256 VGPRs + 256 AGPRs and still spills 117 to scratch: correct (the
+//                                                                       strips test runs it), not yet tuned: 103 TFLOP/s at T = 8192
+// K and V are single-buffered in LDS: two 64 x 256 tiles are 64 KiB each, so dh = 256 could not double-buffer both at 64 keys.  The
+// next tile travels in the staging registers instead, HALF a tile at a time (a whole one would not fit the budget at dh = 128): V(c)
+// is loaded under the first product of tile c, K(c + 1) under the softmax and the second product.  Two barriers per tile; at dh <= 128
+// the second workgroup of the CU fills them.  The fragment reads are software-pipelined by one step with a scheduling barrier per step:
+// left alone, the compiler hoists every ds_read of a phase and spills.
+//
+// Vector-ALU work per tile and lane beside the 64 NB MFMAs (fp32 MFMA issues on the vector ALU here, so it adds to them): 32 fmax,
+// 1 multiply + 1 fmax + 1 exchange, 32 fma + 32 exp + 32 adds, 16 NB multiplies of O.  exp is the accurate expf (about 15
+// instructions), which makes this roughly 700 instructions x 4 cycles against 256 MFMAs x 64 cycles at dh = 128: about 17 % by count, not
+// the 5 % a bare v_exp_f32 would give.  Measured (scripts/attn_stream_timing.py, D = 1024, 8 heads): 122 TFLOP/s at T = 8192, 129 at
+// T = 65 536 -- the two waves of a SIMD overlap one's softmax with the other's MFMAs.
+#include "gemm_device.h"
+#include <math.h>
+#include <algorithm>
+#include <atomic>
+
+namespace sumk {
+
+namespace {
+constexpr int AS_KT = 64;                 // keys per tile
+constexpr int AS_QS = 128;                // query rows per strip: 4 waves x 32
+constexpr int AS_MAX_T = 1 << 20;
+constexpr int AS_MAX_SEQ = 65535;
+constexpr int AS_MAX_DH = 256;
+
+struct AsSeq { int64_t row0; int32_t T; int32_t strip0; };   // first packed row, frames, first strip of the video
+
+struct AsArgs {
+  const float* Q; const float* K; const float* V; float* ctx; float* lse; const AsSeq* seq;
+  int32_t ldq, ldk, ldv, ldc, dh, heads, n_seq; float scale;
+};
+
+__global__ void as_setup_kernel(const int32_t* off, int n_seq, AsSeq* seq) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_seq) return;
+  int strip0 = 0;
+  for (int q = 0; q < s; ++q) strip0 += (off[q + 1] - off[q] + AS_QS - 1) / AS_QS;
+  AsSeq d; d.row0 = off[s]; d.T = off[s + 1] - off[s]; d.strip0 = strip0;
+  seq[s] = d;
+}
+
+__device__ __forceinline__ int as_crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
+template <int W> struct AsVec;
+template <> struct AsVec<1> { float v[1]; __device__ __forceinline__ void load(const float* p) { v[0] = *p; } };
+template <> struct AsVec<2> { float v[2]; __device__ __forceinline__ void load(const float* p) { const float2 t = *reinterpret_cast<const float2*>(p); v[0] = t.x; v[1] = t.y; } };
+template <> struct AsVec<4> { float v[4]; __device__ __forceinline__ void load(const float* p) { const float4 t = *reinterpret_cast<const float4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; } };
+
+template <int NB>
+__global__ __launch_bounds__(256, NB <= 4 ? 2 : 1) void as_stream_kernel(AsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float as_lds[];
+  constexpr int DP = 32 * NB, P = DP + 4;        // staged columns; LDS pitch (conflict-free ds_read_b128 of both images)
+  constexpr int C4 = DP / 4, NST = NB;           // float4 columns of a tile row; float4 per thread and half tile (32 C4 / 256)
+  constexpr int W = NB < 4 ? NB : 4, NQ = NB / W;
+  const int blk = blockIdx.x;
+  const int h = blk % a.heads, sg = blk / a.heads;
+  int lo = 0, hi = a.n_seq - 1;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (a.seq[mid].strip0 <= sg) lo = mid; else hi = mid - 1; }
+  const AsSeq d = a.seq[lo];
+  const int T = d.T, dh = a.dh;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 31, lh = lane >> 5;
+  const int q0 = (sg - d.strip0) * AS_QS + wave * 32;          // this wave's first query row inside the video
+  const bool live = q0 < T;                                    // wave-uniform: a wave past the video only stages
+  const int64_t hcol = (int64_t)h * dh;
+  const float* Qh = a.Q + d.row0 * (int64_t)a.ldq + hcol;
+  const float* Kh = a.K + d.row0 * (int64_t)a.ldk + hcol;
+  const float* Vh = a.V + d.row0 * (int64_t)a.ldv + hcol;
+
+  // Q fragments: group g, MFMA j -> Q[query][8 g + 4 lh + j]
+  float qf[4 * NB][4];
+  {
+    const float* qp = Qh + (int64_t)min(q0 + li, T - 1) * a.ldq;
+#pragma unroll
+    for (int g = 0; g < 4 * NB; ++g) {
+      const int dc = 8 * g + 4 * lh;
+      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (live && dc < dh) t = *reinterpret_cast<const float4*>(qp + dc);
+      qf[g][0] = t.x; qf[g][1] = t.y; qf[g][2] = t.z; qf[g][3] = t.w;
+    }
+  }
+
+  // staging of HALF a 64-row tile (the whole one would not fit the register budget): thread -> NST float4 of rows 32 half .. 32 half + 31
+  // (row = 32 half + idx / C4, float4 column = idx % C4, idx = tid + 256 i)
+  float4 st[NST];
+  auto gload = [&](const float* base, int ld, int c, int half, bool zero_rows) {
+#pragma unroll
+    for (int i = 0; i < NST; ++i) {
+      const int idx = tid + 256 * i, r = 32 * half + idx / C4, c4 = idx % C4;
+      const int key = c * AS_KT + r;
+      const bool ok = 4 * c4 < dh && !(zero_rows && key >= T);
+      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (ok) t = *reinterpret_cast<const float4*>(base + (int64_t)min(key, T - 1) * ld + 4 * c4);
+      st[i] = t;
+    }
+  };
+  auto swrite = [&](float* img, int half) {
+#pragma unroll
+    for (int i = 0; i < NST; ++i) {
+      const int idx = tid + 256 * i, r = 32 * half + idx / C4, c4 = idx % C4;
+      *reinterpret_cast<float4*>(img + r * P + 4 * c4) = st[i];
+    }
+  };
+
+  float* Kimg = as_lds;
+  float* Vimg = as_lds + AS_KT * P;
+  const int nt = (T + AS_KT - 1) / AS_KT;
+  f32x16 o[NB], s[2];
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[b][r] = 0.f;
+  float m = -INFINITY, l = 0.f;                   // running maximum of the row; this lane half's share of the running sum
+
+  // S^T += K Q^T over the groups [g0, g0 + 2 NB); the K fragments of group g + 1 are read under the MFMAs of group g
+  auto s_groups = [&](int g0) {
+    float4 kf[2], kn[2];
+    auto kread = [&](int g, float4 (&dst)[2]) {
+#pragma unroll
+      for (int sb = 0; sb < 2; ++sb) dst[sb] = *reinterpret_cast<const float4*>(Kimg + (32 * sb + li) * P + 8 * g + 4 * lh);
+    };
+    kread(g0, kf);
+#pragma unroll
+    for (int gi = 0; gi < 2 * NB; ++gi) {         // every group: the columns past dh are zeros in both operands
+      const int g = g0 + gi;
+      if (gi + 1 < 2 * NB) kread(g + 1, kn);
+#pragma unroll
+      for (int sb = 0; sb < 2; ++sb) {
+        s[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].x, qf[g][0], s[sb], 0, 0, 0);
+        s[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].y, qf[g][1], s[sb], 0, 0, 0);
+        s[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].z, qf[g][2], s[sb], 0, 0, 0);
+        s[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].w, qf[g][3], s[sb], 0, 0, 0);
+      }
+      kf[0] = kn[0]; kf[1] = kn[1];
+      __builtin_amdgcn_sched_barrier(0);          // keep the compiler from hoisting every group's reads (register budget)
+    }
+  };
+  // O^T += V^T P^T over the 16 steps of sub-tile sb; the V fragments of step r + 1 are read under the MFMAs of step r
+  auto pv_steps = [&](int sb) {
+    AsVec<W> vc[NQ], vn[NQ];
+    auto vread = [&](int r, AsVec<W> (&dst)[NQ]) {
+      const float* vp = Vimg + (32 * sb + as_crow(r, lh)) * P + W * li;
+#pragma unroll
+      for (int bq = 0; bq < NQ; ++bq) dst[bq].load(vp + 32 * W * bq);
+    };
+    vread(0, vc);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (r + 1 < 16) vread(r + 1, vn);
+#pragma unroll
+      for (int bq = 0; bq < NQ; ++bq)
+#pragma unroll
+        for (int bb = 0; bb < W; ++bb)
+          o[bq * W + bb] = __builtin_amdgcn_mfma_f32_32x32x2f32(vc[bq].v[bb], s[sb][r], o[bq * W + bb], 0, 0, 0);
+#pragma unroll
+      for (int bq = 0; bq < NQ; ++bq) vc[bq] = vn[bq];
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  gload(Kh, a.ldk, 0, 0, false); swrite(Kimg, 0);
+  gload(Kh, a.ldk, 0, 1, false); swrite(Kimg, 1);
+  for (int c = 0; c < nt; ++c) {
+    const bool more = c + 1 < nt;
+    __syncthreads();                              // K(c) is visible; every wave is done with V(c - 1)
+#pragma unroll
+    for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[sb][r] = 0.f;
+    gload(Vh, a.ldv, c, 0, true);                 // V(c) travels under the first product, half a tile at a time
+    if (live) s_groups(0);
+    swrite(Vimg, 0);
+    gload(Vh, a.ldv, c, 1, true);
+    if (live) s_groups(2 * NB);
+    swrite(Vimg, 1);
+    __syncthreads();                              // V(c) is visible; every wave is done with K(c)
+    if (more) gload(Kh, a.ldk, c + 1, 0, false);  // K(c + 1) travels under the softmax and the second product
+    if (live) {
+      if ((c + 1) * AS_KT > T) {                  // the video's last, partial tile: keys past T get the logit -inf
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[sb][r] = (c * AS_KT + 32 * sb + as_crow(r, lh) < T) ? s[sb][r] : -INFINITY;
+      }
+      float tm = -INFINITY;
+#pragma unroll
+      for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tm = fmaxf(tm, s[sb][r]);
+      tm = fmaxf(tm, __shfl_xor(tm, 32));
+      const float mn = fmaxf(m, tm * a.scale);    // scale > 0: max_j (s_j scale) = (max_j s_j) scale, rounding is monotone
+      const float f = expf(m - mn);
+      float ps = 0.f;
+#pragma unroll
+      for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float p = expf(__builtin_fmaf(s[sb][r], a.scale, -mn));
+          s[sb][r] = p; ps += p;
+          if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+      l = l * f + ps;
+      m = mn;
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[b][r] *= f;
+      pv_steps(0);
+    }
+    if (more) { swrite(Kimg, 0); gload(Kh, a.ldk, c + 1, 1, false); }
+    if (live) pv_steps(1);
+    if (more) swrite(Kimg, 1);
+  }
+
+  if (!live) return;
+  const float lt = l + __shfl_xor(l, 32);
+  const int q = q0 + li;
+  if (q >= T) return;
+  float* cp = a.ctx + (d.row0 + q) * (int64_t)a.ldc + hcol;
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int dd = (b % W) + W * as_crow(r, lh) + 32 * W * (b / W);
+      if (dd < dh) cp[dd] = o[b][r] / lt;
+    }
+  if (a.lse && lh == 0) a.lse[(d.row0 + q) * (int64_t)a.heads + h] = m + logf(lt);
+}
+
+std::atomic<uint64_t> g_as_attr[4];
+
+template <int NB>
+int as_launch(const AsArgs& a, unsigned blocks, int inst, hipStream_t stream) {
+  constexpr int LDS = 2 * AS_KT * (32 * NB + 4) * 4;
+  if (LDS > 64 * 1024) {                          // once per device: more dynamic LDS than the default limit
+    int dev = 0;
+    SUMK_HIP(hipGetDevice(&dev));
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(g_as_attr[inst].load(std::memory_order_acquire) & bit)) {
+      SUMK_HIP(hipFuncSetAttribute((const void*)as_stream_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+      g_as_attr[inst].fetch_or(bit, std::memory_order_release);
+    }
+  }
+  hipLaunchKernelGGL(as_stream_kernel<NB>, dim3(blocks), dim3(256), LDS, stream, a);
+  return SUMK_OK;
+}
+
+// the batch's limits; *strips = query strips of all videos
+int as_check(int D, int heads, int n_seq, const int32_t* off, int64_t* strips) {
+  SUMK_ARG(D > 0 && heads > 0 && D % heads == 0, "attn_stream: D=%d is not a positive multiple of n_heads=%d", D, heads);
+  const int dh = D / heads;
+  SUMK_ARG(dh % 4 == 0 && dh <= AS_MAX_DH, "attn_stream: head width %d (D=%d, n_heads=%d) must be a multiple of 4, at most %d", dh, D, heads, AS_MAX_DH);
+  SUMK_ARG(n_seq > 0 && n_seq <= AS_MAX_SEQ && off && off[0] == 0, "attn_stream: n_seq=%d (1 .. %d videos, seq_off[0] == 0)", n_seq, AS_MAX_SEQ);
+  int64_t n = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    const int T = off[s + 1] - off[s];
+    SUMK_ARG(T > 0, "attn_stream: video %d has %d frames", s, T);
+    SUMK_ARG(T < AS_MAX_T, "attn_stream: video %d has %d frames (limit 2^20)", s, T);
+    n += (T + AS_QS - 1) / AS_QS;
+  }
+  SUMK_ARG(n * heads < ((int64_t)1 << 31), "attn_stream: %lld workgroups", (long long)(n * heads));
+  *strips = n;
+  return SUMK_OK;
+}
+}  // namespace
+
+size_t attn_stream_ws_bytes(int n_seq) { return align_up((size_t)n_seq * sizeof(AsSeq), 256); }
+
+int attn_stream_check(int D, int heads, int n_seq, const int32_t* off) {
+  int64_t strips;
+  return as_check(D, heads, n_seq, off, &strips);
+}
+
+int launch_attn_stream(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
+                       const int32_t* off_host, const int32_t* off_dev, float scale, float* ctx, int ldc, float* lse, void* ws,
+                       hipStream_t stream) {
+  SUMK_ARG(Q && K && V && ctx && off_dev && ws, "attn_stream: null pointer");
+  int64_t strips;
+  SUMK_TRY(as_check(D, heads, n_seq, off_host, &strips));
+  SUMK_ARG(ldq >= D && ldk >= D && ldv >= D && ldc >= D, "attn_stream: leading dimensions (%d, %d, %d, %d) must be at least D=%d", ldq, ldk, ldv, ldc, D);
+  SUMK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldc % 4 == 0, "attn_stream: leading dimensions (%d, %d, %d, %d) must be multiples of 4", ldq, ldk, ldv, ldc);
+  SUMK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)ctx) & 15) == 0, "attn_stream: Q, K, V and ctx must be 16-byte aligned");
+  SUMK_ARG(scale > 0.f && scale < INFINITY, "attn_stream: scale=%g must be positive and finite", (double)scale);
+  AsArgs a;
+  a.Q = Q; a.K = K; a.V = V; a.ctx = ctx; a.lse = lse; a.seq = (const AsSeq*)ws;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldc = ldc; a.dh = D / heads; a.heads = heads; a.n_seq = n_seq; a.scale = scale;
+  hipLaunchKernelGGL(as_setup_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, stream, off_dev, n_seq, (AsSeq*)ws);
+  const unsigned blocks = (unsigned)(strips * heads);
+  prof_begin(SUMK_PROF_ATTN_STREAM, stream);
+  if (a.dh <= 32) SUMK_TRY(as_launch<1>(a, blocks, 0, stream));
+  else if (a.dh <= 64) SUMK_TRY(as_launch<2>(a, blocks, 1, stream));
+  else if (a.dh <= 128) SUMK_TRY(as_launch<4>(a, blocks, 2, stream));
+  else SUMK_TRY(as_launch<8>(a, blocks, 3, stream));
+  prof_end(SUMK_PROF_ATTN_STREAM, stream);
+  SUMK_HIP(hipGetLastError());
+  return SUMK_OK;
+}
+
+}  // namespace sumk
+
+using namespace sumk;
+
+extern "C" size_t sumk_attn_stream_workspace_bytes(int32_t D, int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host) {
+  if (attn_stream_check(D, n_heads, n_seq, seq_off_host) != SUMK_OK) return 0;
+  return attn_stream_ws_bytes(n_seq);
+}
+
+extern "C" int sumk_attn_stream(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, int32_t D,
+                                int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale,
+                                float* ctx, int32_t ldc, float* lse, void* workspace, size_t workspace_bytes, void* stream) {
+  SUMK_ARG(workspace, "attn_stream: null pointer");
+  SUMK_TRY(attn_stream_check(D, n_heads, n_seq, seq_off_host));
+  const size_t need = attn_stream_ws_bytes(n_seq);
+  if (workspace_bytes < need) { set_error("attn_stream: workspace %zu < required %zu", workspace_bytes, need); return SUMK_ERR_WORKSPACE; }
+  return launch_attn_stream(Q, ldq, K, ldk, V, ldv, D, n_heads, n_seq, seq_off_host, seq_off_dev, scale, ctx, ldc, lse, workspace,
+                            (hipStream_t)stream);
+}

@@ -331,6 +331,15 @@ int launch_attn_pw_logits(int np, const void* qkv_planes, int64_t rows, int D, f
 int launch_attn_pw_context(int np, const void* qkv_planes, int64_t rows, int D, const void* alpha_planes, void* ctx_planes, const SeqInfo* seq,
                            int n_seq, int t_max, hipStream_t stream, int heads = 1, const float* R = nullptr, int ldr = 0, float* moments = nullptr);
 
+// Multi-head attention without the logits (attn_stream.hip): ctx[rows of v, h dh ..] = softmax(scale Q_h K_h^T) V_h per (video, head) in exact
+// fp32, head h at column h * (D / heads) of Q, K, V and ctx; lse (may be null): (rows, heads).  ws: attn_stream_ws_bytes(n_seq) bytes.
+// attn_stream_check: the batch's limits (dh % 4 == 0, dh <= 256, 1 <= T < 2^20, at most 65 535 videos), SUMK_ERR_ARG past them.
+size_t attn_stream_ws_bytes(int n_seq);
+int attn_stream_check(int D, int heads, int n_seq, const int32_t* off_host);
+int launch_attn_stream(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
+                       const int32_t* off_host, const int32_t* off_dev, float scale, float* ctx, int ldc, float* lse, void* ws,
+                       hipStream_t stream);
+
 // ------------------------------------------------------------------------------------------- shared row kernels (vasnet.hip)
 // Y = LayerNorm(X) * g + b over D (one wave per row); optional (mean, rstd) per row into stats.
 int launch_layernorm(const float* X, float* Y, const float* g, const float* b, int n_rows, int D, float eps, float* stats,

@@ -15,6 +15,7 @@ struct TfWs {
   size_t hfin, z, stats_fin, scores, g0, g1, g2, dqkv, dff, lnpart, colpart, slab, prob_sk;
   size_t slab_elems;
   int64_t e_elems; int32_t n_rows;
+  size_t as_seq;   // the stream carve (sumk_transformer_forward_stream): attn_stream.hip's descriptors; it has no `e`
 };
 // per-(video, head) sub-problem tables, each n_seq * heads entries: logits, context, and the four attention-backward products
 enum { TT_S = 0, TT_PV = 1, TT_DV = 2, TT_DP = 3, TT_DQ = 4, TT_DK = 5, TT_COUNT = 6 };
@@ -26,7 +27,9 @@ enum { P_QKV = 0, P_DD = 1, P_DF = 2, P_FD = 3, P_DQKV = 4, P_NN_DF = 5, P_NN_FD
 
 int tf_carve(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, TfWs* w);
 int tf_geometry(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, TfGeom* G);
-int tf_tables(const TfGeom& G, int D, int F, int heads, int n_seq, const int32_t* off_dev, char* ws, hipStream_t stream);
+// head_tables = false: only the single-problem tables (the stream path has no per-(video, head) GEMMs)
+int tf_tables(const TfGeom& G, int D, int F, int heads, int n_seq, const int32_t* off_dev, char* ws, hipStream_t stream,
+              bool head_tables = true);
 
 __global__ void tf_softmax_kernel(float* E, float* E2, const TfSeq* seq, const int32_t* off, int n_seq, int n_rows, int heads,
                                   float scale, Drop drop, uint32_t site);

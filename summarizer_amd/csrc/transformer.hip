@@ -64,7 +64,8 @@ static int tf_np(int precision) { return precision == SUMK_PRECISION_BF16X6 ? 3 
 static bool tf_pw_rows_ok(int D, int F, int64_t R, int np) {
   return R >= 128 && pw_ok(R, 3 * (int64_t)D, D, R, 3 * (int64_t)D, np) && pw_ok(R, F, D, R, F, np) && pw_ok(R, D, F, R, D, np);
 }
-int tf_carve(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, TfWs* w) {
+// logits = false: the inference carve of the stream path -- no `e`, `seq` or `prob_tabs`; attn_stream.hip's descriptors instead
+static int tf_carve_any(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, bool logits, TfWs* w) {
   SUMK_ARG(D > 0 && D % 4 == 0 && F > 0 && F % 4 == 0, "transformer: D=%d / F=%d must be positive multiples of 4", D, F);
   SUMK_ARG(heads > 0 && D % heads == 0 && (D / heads) % 4 == 0, "transformer: head dim must be a multiple of 4 (D=%d heads=%d)", D, heads);
   SUMK_ARG(n_seq > 0 && off && off[0] == 0, "transformer: empty batch / seq_off[0] != 0");
@@ -79,12 +80,15 @@ int tf_carve(int D, int F, int heads, int n_layers, int n_seq, const int32_t* of
   size_t p = 0;
   auto take = [&](size_t bytes) { size_t at = p; p += align_up(bytes, 256); return at; };
   w->n_rows = (int32_t)R; w->e_elems = e;
-  w->seq = take((size_t)n_seq * sizeof(TfSeq));
+  w->seq = w->prob_tabs = 0;
+  if (logits) w->seq = take((size_t)n_seq * sizeof(TfSeq));
   w->prob_row = take(8 * sizeof(GemmProb));
-  w->prob_tabs = take((size_t)TT_COUNT * n_seq * heads * sizeof(GemmProb));
+  if (logits) w->prob_tabs = take((size_t)TT_COUNT * n_seq * heads * sizeof(GemmProb));   // (the stream path has no per-(video, head) GEMMs)
   w->t1 = take(R * D * 4);
   if (!training) {
-    w->qkv = take(R * 3 * D * 4); w->e = take((size_t)e * 4); w->ctx = take(R * D * 4);
+    w->qkv = take(R * 3 * D * 4);
+    if (logits) w->e = take((size_t)e * 4); else w->as_seq = take(attn_stream_ws_bytes(n_seq));
+    w->ctx = take(R * D * 4);
     w->h0 = take(R * D * 4); w->h1 = take(R * D * 4); w->h2 = take(R * D * 4); w->ff = take(R * (size_t)F * 4);
   } else {
     size_t q = 0;
@@ -105,6 +109,9 @@ int tf_carve(int D, int F, int heads, int n_layers, int n_seq, const int32_t* of
   }
   w->total = p;
   return SUMK_OK;
+}
+int tf_carve(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, TfWs* w) {
+  return tf_carve_any(D, F, heads, n_layers, n_seq, off, training, true, w);
 }
 
 __global__ void tf_setup_kernel(const int32_t* off, int n_seq, int D, int heads, TfSeq* seq, GemmProb* tabs) {
@@ -246,10 +253,10 @@ __global__ void relu_drop_bwd_kernel(float* __restrict__ g, const float* __restr
   if (i < n) g[i] = act[i] > 0.f ? g[i] * scale : 0.f;
 }
 
-int tf_geometry(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, TfGeom* G) {
-  SUMK_TRY(tf_carve(D, F, heads, n_layers, n_seq, off, training, &G->L));
+static int tf_geometry_any(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, bool logits, TfGeom* G) {
+  SUMK_TRY(tf_carve_any(D, F, heads, n_layers, n_seq, off, training, logits, &G->L));
   G->R = G->L.n_rows; G->dh = D / heads; G->tiles_s = G->tiles_pv = 0;
-  for (int s = 0; s < n_seq; ++s) {
+  for (int s = 0; logits && s < n_seq; ++s) {
     int T = off[s + 1] - off[s], tm = (T + 63) / 64;
     G->tiles_s += heads * tm * tm; G->tiles_pv += heads * tm * ((G->dh + 63) / 64);
   }
@@ -257,12 +264,16 @@ int tf_geometry(int D, int F, int heads, int n_layers, int n_seq, const int32_t*
   G->c_qkv = cfg(G->R, 3 * D); G->c_dd = cfg(G->R, D); G->c_df = cfg(G->R, F);
   return SUMK_OK;
 }
+int tf_geometry(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, TfGeom* G) {
+  return tf_geometry_any(D, F, heads, n_layers, n_seq, off, training, true, G);
+}
 
-int tf_tables(const TfGeom& G, int D, int F, int heads, int n_seq, const int32_t* off_dev, char* ws, hipStream_t stream) {
+int tf_tables(const TfGeom& G, int D, int F, int heads, int n_seq, const int32_t* off_dev, char* ws, hipStream_t stream, bool head_tables) {
   const int R = G.R;
   GemmProb* prow = (GemmProb*)(ws + G.L.prob_row);
-  hipLaunchKernelGGL(tf_setup_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, stream, off_dev, n_seq, D, heads,
-                     (TfSeq*)(ws + G.L.seq), (GemmProb*)(ws + G.L.prob_tabs));
+  if (head_tables)
+    hipLaunchKernelGGL(tf_setup_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, stream, off_dev, n_seq, D, heads,
+                       (TfSeq*)(ws + G.L.seq), (GemmProb*)(ws + G.L.prob_tabs));
   SUMK_TRY(fill_single_prob(prow + P_QKV, R, 3 * D, D, D, D, 3 * D, 0, G.c_qkv, stream));   // (R,3D) <- (R,D) x (3D,D)^T
   SUMK_TRY(fill_single_prob(prow + P_DD, R, D, D, D, D, D, D, G.c_dd, stream));             // (R,D)  <- (R,D) x (D,D)   [+R ld D]
   SUMK_TRY(fill_single_prob(prow + P_DF, R, F, D, D, D, F, 0, G.c_df, stream));             // (R,F)  <- (R,D) x (F,D)^T ; also NN with B (D,F)
@@ -296,6 +307,7 @@ int tf_out_proj(const TfRun& r, const float* CTX, const float* out_w, const floa
 int tf_attn_core_fwd(const TfRun& r, const GemmProb* tabs, const float* qbase, const float* kvbase, float* E, float* E2, float* CTX,
                      Drop dl, uint32_t site) {
   const TfGeom& G = *r.G; const int R = G.R, np = r.n_seq * r.heads;
+  prof_begin(SUMK_PROF_TF_ATTN_DENSE, r.stream);
   {  // logits per (video, head)
     GemmLaunch g; g.precision = r.precision;
     g.A = qbase; g.B[0] = kvbase; g.C = E; g.probs = tabs + (size_t)TT_S * np; g.nprob = np; g.small_tile = 1; g.total_tiles = G.tiles_s;
@@ -310,6 +322,7 @@ int tf_attn_core_fwd(const TfRun& r, const GemmProb* tabs, const float* qbase, c
     g.total_tiles = G.tiles_pv;
     SUMK_TRY(launch_gemm(GEMM_NN, EPI_NONE, g, r.stream));
   }
+  prof_end(SUMK_PROF_TF_ATTN_DENSE, r.stream);
   return SUMK_OK;
 }
 
@@ -419,6 +432,29 @@ int tf_ff_bwd(const TfRun& r, const TfFfW& W, const TfFfG& Gd, const float* h, c
   return tf_nn(r, dFF, W.w1, dT, P_NN_FD, EPI_ACCUM, D);                    // dH = dT + dFF . W1   (W1 stored (F,D) = (K,N))
 }
 
+// The tail of the scorer: final (shared) LayerNorm of the encoder, optional extra residual, scoring head (k1 + ReLU on the exact-fp32
+// GEMM, or -- planes = true, the dense entry's plane path -- by the caller's `k1_planes()`; then the same LayerNorm + k2 + sigmoid)
+template <typename K1>
+static int tf_tail(const TfRun& r, const float* x, const float* hin, float* hfin, float* Z, float* sfin, const sumk_tf_head_weights* head,
+                   const sumk_tf_opts* opts, Drop dhd, float* scores, bool planes, K1 k1_planes) {
+  const TfGeom& G = *r.G; const int R = G.R, D = r.D; hipStream_t stream = r.stream;
+  SUMK_TRY(launch_layernorm(hin, hfin, head->ln_w, head->ln_b, R, D, opts->final_eps, sfin, stream));
+  if (opts->more_residuals) {
+    int64_t n4 = (int64_t)R * (D >> 2);
+    hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, hfin, x, n4);
+  }
+  if (planes) {
+    SUMK_TRY(k1_planes());
+  } else {
+    GemmLaunch g; g.precision = opts->precision;
+    g.A = hfin; g.B[0] = head->k1_w; g.bias0[0] = head->k1_b; g.C = Z; g.probs = (const GemmProb*)(r.ws + G.L.prob_row) + P_DD; g.small_tile = G.c_dd;
+    g.total_tiles = gemm_tiles(R, D, G.c_dd); g.xcd_M = R; g.xcd_N = D; g.lean = gemm_lean_ok(R, D, D, D, D);
+    SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS_RELU, g, stream));
+  }
+  return launch_ln_head_drop(Z, head->ln_w, head->ln_b, head->k2_w, head->k2_b, scores, R, D, opts->final_eps,
+                             sfin ? sfin + 2 * (size_t)R : nullptr, dhd, 1000u, stream);
+}
+
 }  // namespace sumk
 
 using namespace sumk;
@@ -511,7 +547,6 @@ extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t 
     g.bias = bias; g.R = Rs; g.ldr = N; g.relu = relu; g.C = C_; g.ldc = N; g.O = O_; g.o_rows = R;
     return launch_gemm_pw(O_ ? PW_PLANES : Rs ? PW_RES_F32 : PW_F32, g, stream);
   };
-  GemmProb* prow = (GemmProb*)(ws + L.prob_row);
   GemmProb* tabs = (GemmProb*)(ws + L.prob_tabs);
   float* T1 = (float*)(ws + L.t1);
   const Drop dl = make_drop(opts->layer_dropout_p, opts->seed), dhd = make_drop(opts->head_dropout_p, opts->seed);
@@ -575,27 +610,74 @@ extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t 
     SUMK_TRY(launch_layernorm(T1b, hout, W.norm2_w, W.norm2_b, R, D, opts->layer_eps, stats ? stats + 2 * (size_t)R : nullptr, stream));
     hin = hout;
   }
-  // final (shared) LayerNorm of the encoder, optional extra residual, scoring head
   float* hfin = training ? (float*)(ws + L.hfin) : (float*)(ws + L.h0);
   float* Z = training ? (float*)(ws + L.z) : T1;
   float* sfin = training ? (float*)(ws + L.stats_fin) : nullptr;
-  SUMK_TRY(launch_layernorm(hin, hfin, head->ln_w, head->ln_b, R, D, opts->final_eps, sfin, stream));
-  if (opts->more_residuals) {
-    int64_t n4 = (int64_t)R * (D >> 2);
-    hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, hfin, x, n4);
-  }
-  if (pw) {
+  SUMK_TRY(tf_tail(run, x, hin, hfin, Z, sfin, head, opts, dhd, scores, pw, [&]() -> int {
     SUMK_TRY(split_planes(hfin, R, D, D, npl, PA, stream));
-    SUMK_TRY(pw_linear(PA, wpl + WL.k1, D, D, head->k1_b, nullptr, 1, Z, nullptr));
-  } else {
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = hfin; g.B[0] = head->k1_w; g.bias0[0] = head->k1_b; g.C = Z; g.probs = prow + P_DD; g.small_tile = G.c_dd;
-    g.total_tiles = gemm_tiles(R, D, G.c_dd); g.xcd_M = R; g.xcd_N = D; g.lean = gemm_lean_ok(R, D, D, D, D);
-    SUMK_TRY(launch_gemm(GEMM_NT, EPI_BIAS_RELU, g, stream));
-  }
-  SUMK_TRY(launch_ln_head_drop(Z, head->ln_w, head->ln_b, head->k2_w, head->k2_b, scores, R, D, opts->final_eps,
-                               sfin ? sfin + 2 * (size_t)R : nullptr, dhd, 1000u, stream));
+    return pw_linear(PA, wpl + WL.k1, D, D, head->k1_b, nullptr, 1, Z, nullptr);
+  }));
   if (training) SUMK_HIP(hipMemcpyAsync(ws + L.scores, scores, (size_t)R * 4, hipMemcpyDeviceToDevice, stream));
+  SUMK_HIP(hipGetLastError());
+  return SUMK_OK;
+}
+
+// ---- the stream path: the inference of sumk_transformer_forward with tf_attn_core_fwd replaced by attn_stream.hip's launch; no `e` in the carve
+extern "C" size_t sumk_transformer_stream_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                          const int32_t* seq_off_host) {
+  TfWs w;
+  if (n_layers < 1 || tf_carve_any(D, F, n_heads, n_layers, n_seq, seq_off_host, 0, false, &w) != SUMK_OK) return 0;
+  if (attn_stream_check(D, n_heads, n_seq, seq_off_host) != SUMK_OK) return 0;
+  return w.total;
+}
+
+extern "C" int sumk_transformer_forward_stream(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                               const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                               const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                               const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
+                                               float* scores, void* workspace, size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SUMK_ARG(x && seq_off_dev && layers && head && opts && scores && workspace, "transformer_forward_stream: null pointer");
+  SUMK_ARG(n_layers > 0, "transformer_forward_stream: n_layers=%d", n_layers);
+  SUMK_ARG((pos_table == nullptr) == (pos_rows == nullptr), "transformer_forward_stream: pos_table and pos_rows go together");
+  SUMK_ARG(head->ln_w && head->ln_b && head->k1_w && head->k1_b && head->k2_w && head->k2_b, "transformer_forward_stream: null head weight");
+  SUMK_ARG(opts->precision == SUMK_PRECISION_FP32 && !opts->wplanes, "transformer_forward_stream: exact fp32 only (precision=%d, wplanes %s)",
+           opts->precision, opts->wplanes ? "given" : "null");
+  SUMK_ARG(opts->layer_dropout_p == 0.f && opts->head_dropout_p == 0.f, "transformer_forward_stream: inference only (dropout must be 0)");
+  for (int l = 0; l < n_layers; ++l) {
+    const sumk_tf_layer_weights& W = layers[l];
+    SUMK_ARG(W.in_proj_w && W.in_proj_b && W.out_proj_w && W.out_proj_b && W.lin1_w && W.lin1_b && W.lin2_w && W.lin2_b &&
+             W.norm1_w && W.norm1_b && W.norm2_w && W.norm2_b, "transformer_forward_stream: null weight in layer %d", l);
+  }
+  TfGeom G;
+  SUMK_TRY(tf_geometry_any(D, F, n_heads, n_layers, n_seq, seq_off_host, 0, false, &G));
+  SUMK_TRY(attn_stream_check(D, n_heads, n_seq, seq_off_host));
+  const TfWs& L = G.L;
+  if (workspace_bytes < L.total) { set_error("transformer_forward_stream: workspace %zu < required %zu", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
+  char* ws = (char*)workspace;
+  const int R = G.R;
+  float* T1 = (float*)(ws + L.t1); float* QKV = (float*)(ws + L.qkv); float* CTX = (float*)(ws + L.ctx); float* FF = (float*)(ws + L.ff);
+  float* Hb[3] = {(float*)(ws + L.h0), (float*)(ws + L.h1), (float*)(ws + L.h2)};
+  const Drop none = make_drop(0.f, 0);
+  const float att_scale = 1.0f / sqrtf((float)G.dh);
+  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, SUMK_PRECISION_FP32, stream};
+
+  if (pos_table) SUMK_TRY(launch_add_pos(x, pos_table, pos_rows, R, D, stream));
+  SUMK_TRY(tf_tables(G, D, F, n_heads, n_seq, seq_off_dev, ws, stream, false));
+  const float* hin = x;
+  for (int l = 0; l < n_layers; ++l) {
+    const sumk_tf_layer_weights& W = layers[l];
+    float* hmid = Hb[0]; float* hout = Hb[1 + (l & 1)];      // never aliases this layer's input (x or the previous hout)
+    SUMK_TRY(tf_in_proj(run, hin, W.in_proj_w, W.in_proj_b, QKV));
+    SUMK_TRY(launch_attn_stream(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, n_heads, n_seq, seq_off_host, seq_off_dev, att_scale, CTX, D,
+                                nullptr, ws + L.as_seq, stream));
+    SUMK_TRY(tf_out_proj(run, CTX, W.out_proj_w, W.out_proj_b, hin, T1, none, 0u));
+    SUMK_TRY(launch_layernorm(T1, hmid, W.norm1_w, W.norm1_b, R, D, opts->layer_eps, nullptr, stream));
+    SUMK_TRY(tf_ff_fwd(run, TfFfW{W.lin1_w, W.lin1_b, W.lin2_w, W.lin2_b}, hmid, FF, T1, none, 0u, 0u));
+    SUMK_TRY(launch_layernorm(T1, hout, W.norm2_w, W.norm2_b, R, D, opts->layer_eps, nullptr, stream));
+    hin = hout;
+  }
+  SUMK_TRY(tf_tail(run, x, hin, Hb[0], T1, nullptr, head, opts, none, scores, false, [] { return (int)SUMK_OK; }));
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
 }

@@ -2,6 +2,7 @@
 torch.autograd.Function wrappers.  Every arithmetic result comes from libsumk.so; nothing here computes on
 the CPU or through torch ops (torch only allocates the buffers and carries the stream)."""
 import ctypes as C
+import math
 import os
 import numpy as np
 import torch
@@ -1083,13 +1084,76 @@ def transformer_wplanes(params, D, dff, n_layers, n_planes, out=None):
     return view
 
 
-def transformer_forward_packed(x, sb, params, n_layers, n_heads, dff, opts, pos_table=None, pos_rows=None, training=False):
-    """x: (n_rows, D) packed -> (scores (n_rows,), workspace or None).  params: state_dict-keyed tensors."""
+TF_ATTENTION = ("dense", "stream")
+
+
+def _tf_attention(attention):
+    if attention not in TF_ATTENTION:
+        raise SumkError(f"transformer: attention must be one of {TF_ATTENTION}, got {attention!r}")
+    return attention
+
+
+def attn_stream_workspace_bytes(D, n_heads, sb):
+    """Bytes of scratch one attn_stream call takes: 16 per video (sumk_attn_stream_workspace_bytes)."""
+    return _nonzero(_lib.load().sumk_attn_stream_workspace_bytes(int(D), int(n_heads), sb.n_seq, sb.off_host_p), "sumk_attn_stream_workspace_bytes")
+
+
+def attn_stream(q, k, v, sb, n_heads, scale=None, want_lse=False):
+    """Multi-head attention of a packed batch without the (T x T) logits (csrc/attn_stream.hip; exact fp32, no mask): q, k, v are (n_rows, D)
+    float32, each with unit column stride and any row stride >= D that is a multiple of 4 -- three buffers, or the column slices of one
+    (n_rows, 3 D) [Q | K | V] buffer; head h is columns [h D / n_heads, (h + 1) D / n_heads).  scale: None = 1 / sqrt(D / n_heads); it must
+    be positive and finite (the kernel takes a row's maximum before scaling), anything else is refused.
+    Returns ctx (n_rows, D), or (ctx, lse (n_rows, n_heads)) with want_lse.  Only enqueues work."""
+    lib = _lib.load()
+    for t, what in ((q, "q"), (k, "k"), (v, "v")):
+        _require_gpu(t, "attn_stream " + what)
+        if t.dim() != 2 or t.shape != q.shape or t.shape[0] != sb.n_rows or t.stride(1) != 1:
+            raise SumkError(f"attn_stream: {what} must be (n_rows={sb.n_rows}, D) with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
+    D = q.shape[1]
+    nb = attn_stream_workspace_bytes(D, n_heads, sb)
+    ws = workspace(nb, q.device)
+    ctx = torch.empty(sb.n_rows, D, dtype=torch.float32, device=q.device)
+    lse = torch.empty(sb.n_rows, int(n_heads), dtype=torch.float32, device=q.device) if want_lse else None
+    sc = 1.0 / math.sqrt(D // int(n_heads)) if scale is None else float(scale)
+    rc = lib.sumk_attn_stream(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq, sb.off_host_p,
+                              sb.off_dev_p, sc, _p(ctx), D, _p(lse), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "sumk_attn_stream")
+    return (ctx, lse) if want_lse else ctx
+
+
+def transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, attention="dense"):
+    """Bytes of scratch one no-grad scoring call takes in exact fp32: "dense" holds heads x T x T logits per video
+    (sumk_transformer_workspace_bytes), "stream" none (sumk_transformer_stream_workspace_bytes)."""
+    lib = _lib.load()
+    if _tf_attention(attention) == "stream":
+        return _nonzero(lib.sumk_transformer_stream_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq, sb.off_host_p),
+                        "sumk_transformer_stream_workspace_bytes")
+    return _nonzero(lib.sumk_transformer_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq, sb.off_host_p, 0),
+                    "sumk_transformer_workspace_bytes")
+
+
+def transformer_forward_packed(x, sb, params, n_layers, n_heads, dff, opts, pos_table=None, pos_rows=None, training=False,
+                               attention="dense"):
+    """x: (n_rows, D) packed -> (scores (n_rows,), workspace or None).  params: state_dict-keyed tensors.
+    attention="stream" (inference in exact fp32 only): every layer's attention on csrc/attn_stream.hip, no (T x T) logits in the
+    workspace (sumk_transformer_forward_stream)."""
     lib = _lib.load()
     _check_rows(x, sb, "transformer input")
     D = x.shape[1]
     layers, head = _tf_structs(params, n_layers, "weight", _lib.TfLayerWeights, _lib.TfHeadWeights)
     o = _tf_opts(opts)
+    if _tf_attention(attention) == "stream":
+        if training:
+            raise SumkError("transformer_forward_packed: attention='stream' is the inference path (training=False)")
+        nbytes = transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, "stream")
+        ws = workspace(nbytes, x.device)
+        scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
+        rc = lib.sumk_transformer_forward_stream(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
+                                                 C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
+                                                 C.cast(C.pointer(o), C.c_void_p), _p(pos_table), _p(pos_rows), _p(scores), _p(ws),
+                                                 ws.numel(), _stream())
+        _lib.check(rc, "sumk_transformer_forward_stream")
+        return scores, None
     nbytes = _nonzero(lib.sumk_transformer_workspace_bytes_for(D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, int(training),
                                                                o.precision if o.wplanes else 0), "sumk_transformer_workspace_bytes_for")
     ws = workspace(nbytes, x.device, persistent=training)

@@ -22,8 +22,16 @@ from ..training import FlatAdam, dist_info, plan_shards, step_video_total
 
 class Transformer(PositionalInput, nn.Module):
     def __init__(self, input_size=1024, encoder_layers=6, attention_heads=8, more_residuals=False, max_length=None,
-                 pos_embed="simple", epsilon=1e-5, weight_init=None):
+                 pos_embed="simple", epsilon=1e-5, weight_init=None, attention="dense"):
         super().__init__()
+        # attention (not in the reference, opt-in): how a no-grad call computes the multi-head attention of every layer.
+        #   "dense"   heads x T x T logits per video in the workspace (csrc/transformer.hip): the default, every precision;
+        #   "stream"  no logits anywhere: one fused launch per layer (csrc/attn_stream.hip), exact fp32 only -- the workspace is
+        #             O(T (D + F)), so a video of 65 536 steps scores in under 8 GiB where "dense" would ask for over 100 GB.
+        #             A call that records a graph (training) keeps the dense path: the backward of the stream form is not built.
+        if attention not in kernels.TF_ATTENTION:
+            raise ValueError(f"Transformer: attention must be one of {kernels.TF_ATTENTION}, got {attention!r}")
+        self.attention = attention
         self.input_size = input_size
         self.encoder_layers, self.attention_heads, self.epsilon = encoder_layers, attention_heads, epsilon
         self._init_pos_embed(max_length, pos_embed)
@@ -60,6 +68,8 @@ class Transformer(PositionalInput, nn.Module):
         return self._score(xp, sb, None, None)
 
     def _score(self, xp, sb, table, rows):
+        """attention="stream": the no-grad branch scores through sumk_transformer_forward_stream (exact fp32; any other `precision`
+        raises ValueError); the autograd branch stays on the dense path, whose gradients are those of attention="dense" bit for bit."""
         p = dict(self.named_parameters())
         opts = dict(layer_eps=1e-5, final_eps=self.epsilon, more_residuals=self.more_residuals,
                     precision=getattr(self, "precision", "fp32"))
@@ -73,6 +83,13 @@ class Transformer(PositionalInput, nn.Module):
             names = kernels.transformer_param_names(self.encoder_layers)
             cfg = dict(n_layers=self.encoder_layers, n_heads=self.attention_heads, dff=self.input_size)
             return TransformerFunction.apply(xp, sb, cfg, opts, table, rows, names, *[p[n] for n in names])
+        if self.attention == "stream":
+            if opts["precision"] not in (None, "fp32"):
+                raise ValueError(f"Transformer(attention='stream') scores in exact fp32: precision={opts['precision']!r} needs "
+                                 "attention='dense' (or precision='fp32' with attention='stream')")
+            scores, _ = kernels.transformer_forward_packed(xp, sb, p, self.encoder_layers, self.attention_heads, self.input_size,
+                                                           opts, table, rows, attention="stream")
+            return scores
         if opts["precision"] in kernels.PLANES_OF:          # inference in a split-bf16 arithmetic: every projection on the plane GEMM
             opts["wplanes"] = self._wplanes(p, opts["precision"])
         scores, _ = kernels.transformer_forward_packed(xp, sb, p, self.encoder_layers, self.attention_heads, self.input_size,
@@ -90,7 +107,8 @@ class Transformer(PositionalInput, nn.Module):
 class TransformerTrainer(Trainer):
     """Mirror of the reference trainer (transformer.py:106-192): per-video MSE regression with Adam, periodic test, best-
     correlation weights; same `extra_params`.  Extensions as for VASNetTrainer: `batch_videos`, video sharding + one
-    flat-bucket gradient all-reduce per step under torch.distributed."""
+    flat-bucket gradient all-reduce per step under torch.distributed.  extra_params["attention"] = "stream" scores (test, summaries)
+    without the (T x T) logits (Transformer's argument of that name); training stays on the dense path."""
     def _init_model(self):
         ep = self.hps.extra_params
         model = Transformer(
@@ -101,6 +119,7 @@ class TransformerTrainer(Trainer):
             pos_embed=ep.get("pos_embed", "simple"),
             epsilon=float(ep.get("epsilon", 1e-5)),
             weight_init=ep.get("weight_init", None),
+            attention=ep.get("attention", "dense"),
             **({"input_size": int(ep["input_size"])} if "input_size" in ep else {}))
         model.precision = ep.get("precision", "fp32")      # "fp32" | "bf16x3" (kernels.precision_code)
         if self.hps.use_cuda:
