@@ -465,6 +465,45 @@ int sumk_transformer_backward(const float* x, int32_t D, int32_t F, int32_t n_he
                               const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* layer_grads,
                               const sumk_tf_head_grads* head_grads, float* dx, void* workspace, size_t workspace_bytes,
                               void* stream);
+/* Training on the stream form: sumk_attn_stream under autograd, still without anything of size T x T.
+ * sumk_attn_stream_train: sumk_attn_stream with dropout of the weights (a~ = keep ? alpha / (1 - p) : 0, keep = the library's hash of
+ * (seed, site, ((packed row * n_heads + h) << 20) | key), the index the dense path uses, so one seed gives both paths the same masks)
+ * and stats (n_rows, n_heads, 2) floats, 8-byte aligned: the row maximum m of the scaled logits and l = sum_j exp(s_j - m) per (row,
+ * head).  With dropout_p == 0 ctx has the bits of sumk_attn_stream.  Workspace: sumk_attn_stream_workspace_bytes.
+ * sumk_attn_stream_backward: dQ, dK, dV (written, not accumulated; they may be the three column blocks of one (n_rows, 3 D) buffer) from
+ * Q, K, V, the forward's ctx and stats, and dctx, with the forward's scale, dropout_p, seed and site.  Three launches after the setup:
+ * delta = dctx . ctx per (row, head); a pass per (128-row query strip, head) over the video's 64-key tiles for dQ; a pass per (128-row
+ * key strip, head) over its 64-query tiles for dK and dV.  The weights are recomputed per tile from Q, K and stats and the masks
+ * regenerated in registers; no atomics, every call gives the same bits; seven products of 2 T^2 D FLOP instead of five.  Workspace
+ * (sumk_attn_stream_backward_workspace_bytes): the descriptors + 4 bytes per (row, head).
+ * Limits as sumk_attn_stream, but dh <= 128 in the backward (and hence in the transformer entries below) and dropout_p in [0, 1).
+ * sumk_transformer_forward_stream_train / sumk_transformer_backward_stream: the training forward and the backward of
+ * sumk_transformer_forward / sumk_transformer_backward (same arguments, dropout sites and gradient accumulation) with every layer's
+ * attention on these launches; the workspace (sumk_transformer_stream_train_workspace_bytes) is the dense training carve without the
+ * logits scratch and the two heads x T x T blocks per layer, plus stats per layer.  Exact fp32 only, opts->wplanes NULL. */
+int sumk_attn_stream_train(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, int32_t D,
+                           int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale,
+                           float dropout_p, uint64_t seed, uint32_t site, float* ctx, int32_t ldc, float* stats, void* workspace,
+                           size_t workspace_bytes, void* stream);
+size_t sumk_attn_stream_backward_workspace_bytes(int32_t D, int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host);
+int sumk_attn_stream_backward(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, const float* ctx,
+                              int32_t ldc, const float* dctx, int32_t ldd, const float* stats, int32_t D, int32_t n_heads,
+                              int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale, float dropout_p,
+                              uint64_t seed, uint32_t site, float* dQ, int32_t lddq, float* dK, int32_t lddk, float* dV, int32_t lddv,
+                              void* workspace, size_t workspace_bytes, void* stream);
+size_t sumk_transformer_stream_train_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                     const int32_t* seq_off_host);
+int sumk_transformer_forward_stream_train(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                          const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                          const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                          const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows, float* scores,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+int sumk_transformer_backward_stream(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                     const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                     const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                     const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* layer_grads,
+                                     const sumk_tf_head_grads* head_grads, float* dx, void* workspace, size_t workspace_bytes,
+                                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------ DSN reward
  * DSNTrainer.compute_reward (dsn.py:185-236) for E episodes of one or more packed videos:
@@ -1018,7 +1057,13 @@ int sumk_pack_rows_bf16(uint16_t* dst_bf16, const float* const* srcs, const int3
  * tf_attn_core_fwd) and the one launch of the stream form (csrc/attn_stream.hip, without its descriptor setup) */
 #define SUMK_PROF_TF_ATTN_DENSE 20
 #define SUMK_PROF_ATTN_STREAM 21
-#define SUMK_PROF_NTAGS 22
+/* the stream form under training: the training-forward launch (csrc/attn_stream.hip with the statistic and the dropout), and the three
+ * launches of its backward one by one (csrc/attn_stream_bwd.hip) */
+#define SUMK_PROF_ATTN_STREAM_TRAIN 22
+#define SUMK_PROF_ATTN_STREAM_BWD_DELTA 23
+#define SUMK_PROF_ATTN_STREAM_BWD_DQ 24
+#define SUMK_PROF_ATTN_STREAM_BWD_DKV 25
+#define SUMK_PROF_NTAGS 26
 /* The small-batch GEMM form by itself (tests, probes): C = epilogue(A . B) for ONE exact-fp32 problem on 64x64 tiles whose K is cut
  * into `slices` (1 .. 8) slices INSIDE the launch -- every (tile, slice) block stores a partial tile, the last one to arrive adds
  * them in slice order and runs the epilogue (csrc/gemm_lean.hip, SK instances; what sumk_vasnet_forward / _backward launch for batches

@@ -25,7 +25,11 @@ class SumkError(RuntimeError):
 # holds these to the header)
 PROF_TF_ATTN_DENSE = 20     # the dense attention core's three launches, per layer
 PROF_ATTN_STREAM = 21       # the streaming attention launch (csrc/attn_stream.hip)
-PROF_NTAGS = 22
+PROF_ATTN_STREAM_TRAIN = 22  # the streaming attention launch in its training form (statistic + dropout)
+PROF_ATTN_STREAM_BWD_DELTA = 23     # its backward's three launches (csrc/attn_stream_bwd.hip), one by one
+PROF_ATTN_STREAM_BWD_DQ = 24
+PROF_ATTN_STREAM_BWD_DKV = 25
+PROF_NTAGS = 26
 
 
 class VasnetWeights(C.Structure):
@@ -223,6 +227,21 @@ _SIGS = {
     "sumk_transformer_backward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p, c_f32p,
                                             C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_attn_stream_train": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P,
+                                         c_i32p, C.c_float, C.c_float, C.c_uint64, C.c_uint32, c_f32p, C.c_int32, c_f32p, C.c_void_p,
+                                         C.c_size_t, C.c_void_p]),
+    "sumk_attn_stream_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, HOST_I32P]),
+    "sumk_attn_stream_backward": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32,
+                                            c_f32p, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p, C.c_float, C.c_float, C.c_uint64,
+                                            C.c_uint32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_void_p, C.c_size_t,
+                                            C.c_void_p]),
+    "sumk_transformer_stream_train_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P]),
+    "sumk_transformer_forward_stream_train": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, c_i32p, c_f32p, C.c_void_p,
+                                                        C.c_size_t, C.c_void_p]),
+    "sumk_transformer_backward_stream": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p, c_f32p,
+                                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     "sumk_tf_encoder_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, C.c_int32]),
     "sumk_tf_encoder_forward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p, C.c_void_p,
                                           c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),

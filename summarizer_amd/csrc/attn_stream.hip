@@ -37,7 +37,7 @@
 //   128     4    66 KiB  -> 2 workgroups per CU (132 of 160 KiB)         64 + 64 + 32 + 16 + 16 = 192 by count; the compiler takes 239 of 256, no
 //                                                                       spill: 2 waves per SIMD
 //   256     8    130 KiB -> 1 workgroup per CU                          128 + 128 + 32 + 32 + 24 = 344 of 512 by count (1 wave per SIMD); the compiler
-//                                                                       fills 256 VGPRs + 256 AGPRs and still spills 117 to scratch: correct (the
+//                                                                       fills 256 VGPRs + 256 AGPRs and still spills 113 to scratch: correct (the
 //                                                                       strips test runs it), not yet tuned: 103 TFLOP/s at T = 8192
 // K and V are single-buffered in LDS: two 64 x 256 tiles are 64 KiB each, so dh = 256 could not double-buffer both at 64 keys.  The
 // next tile travels in the staging registers instead, HALF a tile at a time (a whole one would not fit the budget at dh = 128): V(c)
@@ -50,7 +50,15 @@
 // instructions), which makes this roughly 700 instructions x 4 cycles against 256 MFMAs x 64 cycles at dh = 128: about 17 % by count, not
 // the 5 % a bare v_exp_f32 would give.  Measured (scripts/attn_stream_timing.py, D = 1024, 8 heads): 122 TFLOP/s at T = 8192, 129 at
 // T = 65 536 -- the two waves of a SIMD overlap one's softmax with the other's MFMAs.
-#include "gemm_device.h"
+//
+// The training form (sumk_attn_stream_train; its backward: attn_stream_bwd.hip) is the same kernel with two additions.  The statistic of
+// a row, (m, l) per (row, head), is written whenever a.ml is given.  DROP instances drop the weights: the running sum l takes the
+// undropped p, the B operand of the second product keep ? p / (1 - p) : 0 with keep = dropout_keep(seed, site, ((packed row * heads + h)
+// << 20) | key, thr), the index of tf_softmax_kernel.  Without dropout the non-DROP instances run: no hash in the instruction stream, ctx
+// has the bits of the inference call.  The hash (three 64-bit multiplies per weight) costs registers: as_stream_kernel<4, true> takes all
+// 256 VGPRs of its two-waves-per-SIMD budget and spills 85 (27 scratch instructions in the tile loop beside its 256 MFMAs); measured
+// 95 TFLOP/s at T = 8192 against 122 without dropout.
+#include "attn_stream_common.h"
 #include <math.h>
 #include <algorithm>
 #include <atomic>
@@ -58,17 +66,13 @@
 namespace sumk {
 
 namespace {
-constexpr int AS_KT = 64;                 // keys per tile
-constexpr int AS_QS = 128;                // query rows per strip: 4 waves x 32
-constexpr int AS_MAX_T = 1 << 20;
-constexpr int AS_MAX_SEQ = 65535;
 constexpr int AS_MAX_DH = 256;
-
-struct AsSeq { int64_t row0; int32_t T; int32_t strip0; };   // first packed row, frames, first strip of the video
 
 struct AsArgs {
   const float* Q; const float* K; const float* V; float* ctx; float* lse; const AsSeq* seq;
   int32_t ldq, ldk, ldv, ldc, dh, heads, n_seq; float scale;
+  // the training form: the statistic (m, l) per (row, head) for the backward, and the dropout of the weights (DROP instances only)
+  float2* ml; uint64_t seed; uint32_t site, thr; float keep_scale;
 };
 
 __global__ void as_setup_kernel(const int32_t* off, int n_seq, AsSeq* seq) {
@@ -80,14 +84,9 @@ __global__ void as_setup_kernel(const int32_t* off, int n_seq, AsSeq* seq) {
   seq[s] = d;
 }
 
-__device__ __forceinline__ int as_crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
-
-template <int W> struct AsVec;
-template <> struct AsVec<1> { float v[1]; __device__ __forceinline__ void load(const float* p) { v[0] = *p; } };
-template <> struct AsVec<2> { float v[2]; __device__ __forceinline__ void load(const float* p) { const float2 t = *reinterpret_cast<const float2*>(p); v[0] = t.x; v[1] = t.y; } };
-template <> struct AsVec<4> { float v[4]; __device__ __forceinline__ void load(const float* p) { const float4 t = *reinterpret_cast<const float4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; } };
-
-template <int NB>
+// DROP: the training form with dropout of the weights -- the running sum takes the undropped p, the second product keep ? p / (1 - p) : 0
+// (mask index as tf_softmax_kernel's).  Without it the instruction stream holds no hash and ctx has the bits of the inference call.
+template <int NB, bool DROP>
 __global__ __launch_bounds__(256, NB <= 4 ? 2 : 1) void as_stream_kernel(AsArgs a) {
   extern __shared__ __attribute__((aligned(16))) float as_lds[];
   constexpr int DP = 32 * NB, P = DP + 4;        // staged columns; LDS pitch (conflict-free ds_read_b128 of both images)
@@ -152,6 +151,7 @@ __global__ __launch_bounds__(256, NB <= 4 ? 2 : 1) void as_stream_kernel(AsArgs 
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[b][r] = 0.f;
   float m = -INFINITY, l = 0.f;                   // running maximum of the row; this lane half's share of the running sum
+  const int64_t prow = d.row0 + min(q0 + li, T - 1);      // the packed row whose masks this lane draws (DROP)
 
   // S^T += K Q^T over the groups [g0, g0 + 2 NB); the K fragments of group g + 1 are read under the MFMAs of group g
   auto s_groups = [&](int g0) {
@@ -237,7 +237,9 @@ __global__ __launch_bounds__(256, NB <= 4 ? 2 : 1) void as_stream_kernel(AsArgs 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float p = expf(__builtin_fmaf(s[sb][r], a.scale, -mn));
-          s[sb][r] = p; ps += p;
+          ps += p;
+          if (DROP) s[sb][r] = dropout_keep(a.seed, a.site, as_drop_idx(prow, a.heads, h, c * AS_KT + 32 * sb + as_crow(r, lh)), a.thr) ? p * a.keep_scale : 0.f;
+          else s[sb][r] = p;
           if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
         }
       l = l * f + ps;
@@ -266,11 +268,12 @@ __global__ __launch_bounds__(256, NB <= 4 ? 2 : 1) void as_stream_kernel(AsArgs 
       if (dd < dh) cp[dd] = o[b][r] / lt;
     }
   if (a.lse && lh == 0) a.lse[(d.row0 + q) * (int64_t)a.heads + h] = m + logf(lt);
+  if (a.ml && lh == 0) a.ml[(d.row0 + q) * (int64_t)a.heads + h] = make_float2(m, lt);
 }
 
-std::atomic<uint64_t> g_as_attr[4];
+std::atomic<uint64_t> g_as_attr[8];
 
-template <int NB>
+template <int NB, bool DROP>
 int as_launch(const AsArgs& a, unsigned blocks, int inst, hipStream_t stream) {
   constexpr int LDS = 2 * AS_KT * (32 * NB + 4) * 4;
   if (LDS > 64 * 1024) {                          // once per device: more dynamic LDS than the default limit
@@ -278,11 +281,11 @@ int as_launch(const AsArgs& a, unsigned blocks, int inst, hipStream_t stream) {
     SUMK_HIP(hipGetDevice(&dev));
     const uint64_t bit = 1ull << (dev & 63);
     if (!(g_as_attr[inst].load(std::memory_order_acquire) & bit)) {
-      SUMK_HIP(hipFuncSetAttribute((const void*)as_stream_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+      SUMK_HIP(hipFuncSetAttribute((const void*)as_stream_kernel<NB, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
       g_as_attr[inst].fetch_or(bit, std::memory_order_release);
     }
   }
-  hipLaunchKernelGGL(as_stream_kernel<NB>, dim3(blocks), dim3(256), LDS, stream, a);
+  hipLaunchKernelGGL((as_stream_kernel<NB, DROP>), dim3(blocks), dim3(256), LDS, stream, a);
   return SUMK_OK;
 }
 
@@ -312,29 +315,58 @@ int attn_stream_check(int D, int heads, int n_seq, const int32_t* off) {
   return as_check(D, heads, n_seq, off, &strips);
 }
 
-int launch_attn_stream(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
-                       const int32_t* off_host, const int32_t* off_dev, float scale, float* ctx, int ldc, float* lse, void* ws,
-                       hipStream_t stream) {
-  SUMK_ARG(Q && K && V && ctx && off_dev && ws, "attn_stream: null pointer");
+void attn_stream_setup(const int32_t* off_dev, int n_seq, void* ws, hipStream_t stream) {
+  hipLaunchKernelGGL(as_setup_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, stream, off_dev, n_seq, (AsSeq*)ws);
+}
+
+// tag: the profiler tag of the attention launch; ml / dl / site: the training form (ml null and dl.thr == 0: the inference call)
+static int as_run(const char* who, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
+                  const int32_t* off_host, const int32_t* off_dev, float scale, float* ctx, int ldc, float* lse, float2* ml, Drop dl,
+                  uint32_t site, void* ws, int tag, hipStream_t stream) {
+  SUMK_ARG(Q && K && V && ctx && off_dev && ws, "%s: null pointer", who);
   int64_t strips;
   SUMK_TRY(as_check(D, heads, n_seq, off_host, &strips));
-  SUMK_ARG(ldq >= D && ldk >= D && ldv >= D && ldc >= D, "attn_stream: leading dimensions (%d, %d, %d, %d) must be at least D=%d", ldq, ldk, ldv, ldc, D);
-  SUMK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldc % 4 == 0, "attn_stream: leading dimensions (%d, %d, %d, %d) must be multiples of 4", ldq, ldk, ldv, ldc);
-  SUMK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)ctx) & 15) == 0, "attn_stream: Q, K, V and ctx must be 16-byte aligned");
-  SUMK_ARG(scale > 0.f && scale < INFINITY, "attn_stream: scale=%g must be positive and finite", (double)scale);
+  SUMK_ARG(ldq >= D && ldk >= D && ldv >= D && ldc >= D, "%s: leading dimensions (%d, %d, %d, %d) must be at least D=%d", who, ldq, ldk, ldv, ldc, D);
+  SUMK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldc % 4 == 0, "%s: leading dimensions (%d, %d, %d, %d) must be multiples of 4", who, ldq, ldk, ldv, ldc);
+  SUMK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)ctx) & 15) == 0, "%s: Q, K, V and ctx must be 16-byte aligned", who);
+  SUMK_ARG(scale > 0.f && scale < INFINITY, "%s: scale=%g must be positive and finite", who, (double)scale);
   AsArgs a;
   a.Q = Q; a.K = K; a.V = V; a.ctx = ctx; a.lse = lse; a.seq = (const AsSeq*)ws;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldc = ldc; a.dh = D / heads; a.heads = heads; a.n_seq = n_seq; a.scale = scale;
-  hipLaunchKernelGGL(as_setup_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, stream, off_dev, n_seq, (AsSeq*)ws);
+  a.ml = ml; a.seed = dl.seed; a.site = site; a.thr = dl.thr; a.keep_scale = dl.scale;
+  attn_stream_setup(off_dev, n_seq, ws, stream);
   const unsigned blocks = (unsigned)(strips * heads);
-  prof_begin(SUMK_PROF_ATTN_STREAM, stream);
-  if (a.dh <= 32) SUMK_TRY(as_launch<1>(a, blocks, 0, stream));
-  else if (a.dh <= 64) SUMK_TRY(as_launch<2>(a, blocks, 1, stream));
-  else if (a.dh <= 128) SUMK_TRY(as_launch<4>(a, blocks, 2, stream));
-  else SUMK_TRY(as_launch<8>(a, blocks, 3, stream));
-  prof_end(SUMK_PROF_ATTN_STREAM, stream);
+  prof_begin(tag, stream);
+  if (dl.thr) {
+    if (a.dh <= 32) SUMK_TRY((as_launch<1, true>(a, blocks, 4, stream)));
+    else if (a.dh <= 64) SUMK_TRY((as_launch<2, true>(a, blocks, 5, stream)));
+    else if (a.dh <= 128) SUMK_TRY((as_launch<4, true>(a, blocks, 6, stream)));
+    else SUMK_TRY((as_launch<8, true>(a, blocks, 7, stream)));
+  } else {
+    if (a.dh <= 32) SUMK_TRY((as_launch<1, false>(a, blocks, 0, stream)));
+    else if (a.dh <= 64) SUMK_TRY((as_launch<2, false>(a, blocks, 1, stream)));
+    else if (a.dh <= 128) SUMK_TRY((as_launch<4, false>(a, blocks, 2, stream)));
+    else SUMK_TRY((as_launch<8, false>(a, blocks, 3, stream)));
+  }
+  prof_end(tag, stream);
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
+}
+
+int launch_attn_stream(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
+                       const int32_t* off_host, const int32_t* off_dev, float scale, float* ctx, int ldc, float* lse, void* ws,
+                       hipStream_t stream) {
+  return as_run("attn_stream", Q, ldq, K, ldk, V, ldv, D, heads, n_seq, off_host, off_dev, scale, ctx, ldc, lse, nullptr, make_drop(0.f, 0), 0u, ws,
+                SUMK_PROF_ATTN_STREAM, stream);
+}
+
+int launch_attn_stream_train(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
+                             const int32_t* off_host, const int32_t* off_dev, float scale, Drop dl, uint32_t site, float* ctx, int ldc,
+                             float* stats, void* ws, hipStream_t stream) {
+  SUMK_ARG(stats && ((uintptr_t)stats & 7) == 0, "attn_stream_train: stats must be a non-null, 8-byte aligned (n_rows, n_heads, 2) array");
+  SUMK_ARG(!dl.seed_dev, "attn_stream_train: no device seed word");
+  return as_run("attn_stream_train", Q, ldq, K, ldk, V, ldv, D, heads, n_seq, off_host, off_dev, scale, ctx, ldc, nullptr, (float2*)stats, dl, site,
+                ws, SUMK_PROF_ATTN_STREAM_TRAIN, stream);
 }
 
 }  // namespace sumk
@@ -355,4 +387,17 @@ extern "C" int sumk_attn_stream(const float* Q, int32_t ldq, const float* K, int
   if (workspace_bytes < need) { set_error("attn_stream: workspace %zu < required %zu", workspace_bytes, need); return SUMK_ERR_WORKSPACE; }
   return launch_attn_stream(Q, ldq, K, ldk, V, ldv, D, n_heads, n_seq, seq_off_host, seq_off_dev, scale, ctx, ldc, lse, workspace,
                             (hipStream_t)stream);
+}
+
+extern "C" int sumk_attn_stream_train(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, int32_t D,
+                                      int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale,
+                                      float dropout_p, uint64_t seed, uint32_t site, float* ctx, int32_t ldc, float* stats, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  SUMK_ARG(workspace, "attn_stream_train: null pointer");
+  SUMK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "attn_stream_train: dropout_p=%g must lie in [0, 1)", (double)dropout_p);
+  SUMK_TRY(attn_stream_check(D, n_heads, n_seq, seq_off_host));
+  const size_t need = attn_stream_ws_bytes(n_seq);
+  if (workspace_bytes < need) { set_error("attn_stream_train: workspace %zu < required %zu", workspace_bytes, need); return SUMK_ERR_WORKSPACE; }
+  return launch_attn_stream_train(Q, ldq, K, ldk, V, ldv, D, n_heads, n_seq, seq_off_host, seq_off_dev, scale, make_drop(dropout_p, seed), site,
+                                  ctx, ldc, stats, workspace, (hipStream_t)stream);
 }

@@ -339,6 +339,20 @@ int attn_stream_check(int D, int heads, int n_seq, const int32_t* off_host);
 int launch_attn_stream(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
                        const int32_t* off_host, const int32_t* off_dev, float scale, float* ctx, int ldc, float* lse, void* ws,
                        hipStream_t stream);
+// The training form (attn_stream.hip): the weights dropped at `site` (dl.thr == 0: none, and then ctx has launch_attn_stream's bits; mask index
+// ((packed row * heads + h) << 20) | key as tf_softmax_kernel), and stats (rows, heads, 2) = the row maximum m and the sum l of exp(s - m) per
+// (row, head) for the backward.  Same workspace.
+int launch_attn_stream_train(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
+                             const int32_t* off_host, const int32_t* off_dev, float scale, Drop dl, uint32_t site, float* ctx, int ldc,
+                             float* stats, void* ws, hipStream_t stream);
+// Its backward (attn_stream_bwd.hip), head widths up to 128 (attn_stream_bwd_check): dQ, dK, dV from Q, K, V, ctx, dctx and stats, the
+// weights recomputed per tile and the masks regenerated in registers.  ws: attn_stream_bwd_ws_bytes(heads, n_seq, n_rows) bytes.
+size_t attn_stream_bwd_ws_bytes(int heads, int n_seq, int64_t n_rows);
+int attn_stream_bwd_check(int D, int heads, int n_seq, const int32_t* off_host);
+int launch_attn_stream_bwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* ctx, int ldc,
+                           const float* dctx, int ldd, const float* stats, int D, int heads, int n_seq, const int32_t* off_host,
+                           const int32_t* off_dev, float scale, Drop dl, uint32_t site, float* dQ, int lddq, float* dK, int lddk, float* dV,
+                           int lddv, void* ws, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------- shared row kernels (vasnet.hip)
 // Y = LayerNorm(X) * g + b over D (one wave per row); optional (mean, rstd) per row into stats.

@@ -15,7 +15,9 @@ struct TfWs {
   size_t hfin, z, stats_fin, scores, g0, g1, g2, dqkv, dff, lnpart, colpart, slab, prob_sk;
   size_t slab_elems;
   int64_t e_elems; int32_t n_rows;
-  size_t as_seq;   // the stream carve (sumk_transformer_forward_stream): attn_stream.hip's descriptors; it has no `e`
+  size_t as_seq;   // the stream carves (sumk_transformer_forward_stream, _forward_stream_train): attn_stream.hip's descriptors (training:
+                   // with attn_stream_bwd.hip's delta behind them); they have no `e`, `l_p`, `l_pd`
+  size_t l_astats; // the stream training carve: per layer, the attention statistic (m, l) per (row, head)
 };
 // per-(video, head) sub-problem tables, each n_seq * heads entries: logits, context, and the four attention-backward products
 enum { TT_S = 0, TT_PV = 1, TT_DV = 2, TT_DP = 3, TT_DQ = 4, TT_DK = 5, TT_COUNT = 6 };
@@ -40,6 +42,7 @@ __global__ void mask_scale_kernel(float* __restrict__ dst, const float* __restri
 // One call's geometry and workspace as the blocks below see it
 struct TfRun {
   const TfGeom* G; char* ws; int D, F, heads, n_seq; const int32_t* off_dev; int precision; hipStream_t stream;
+  const int32_t* off_host;   // the stream form of the attention blocks needs the host offsets too (null elsewhere)
 };
 struct TfAttnW { const float* in_w; const float* in_b; const float* out_w; const float* out_b; };
 struct TfAttnG { float* in_w; float* in_b; float* out_w; float* out_b; };
@@ -59,12 +62,19 @@ int tf_attn_core_fwd(const TfRun& r, const GemmProb* tabs, const float* qbase, c
 // TT_DQ / TT_DK / TT_DV entries point from `dq_base` / `dkv_base`.
 int tf_attn_core_bwd(const TfRun& r, const GemmProb* tabs, const float* qbase, const float* kvbase, const float* P, float* E2,
                      const float* dCTX, float* dq_base, float* dkv_base, Drop dl, uint32_t site);
+// the stream form of the two cores above for self-attention on the in-place [Q | K | V] (R,3D) buffer (attn_stream.hip,
+// attn_stream_bwd.hip; the stream training carve): no E, E2; astats (R, heads, 2) is the statistic the forward saves for the backward
+int tf_attn_stream_fwd(const TfRun& r, const float* QKV, float* CTX, float* astats, Drop dl, uint32_t site);
+int tf_attn_stream_bwd(const TfRun& r, const float* QKV, const float* CTX, const float* dCTX, const float* astats, float* dQKV, Drop dl,
+                       uint32_t site);
 // self-attention block without its norm: T1a = dropout1(SA(hin)) + hin   (sites site+0: weights, site+1: dropout1)
+// astats non-null: the stream form of the core (E, E2 unused)
 int tf_sa_fwd(const TfRun& r, const TfAttnW& W, const float* hin, float* QKV, float* E, float* E2, float* CTX, float* T1a, Drop dl,
-              uint32_t site);
+              uint32_t site, float* astats = nullptr);
 // backward of tf_sa_fwd: dT (in: dT1a, out: dHin = dT1a + the attention path); s1, s2 (R,D) scratch; dQKV (R,3D) scratch
+// astats non-null: the stream form of the core (P, E2 unused)
 int tf_sa_bwd(const TfRun& r, const TfAttnW& W, const TfAttnG& Gd, const float* hin, const float* QKV, const float* P, float* E2,
-              const float* CTX, float* dT, float* s1, float* s2, float* dQKV, Drop dl, uint32_t site);
+              const float* CTX, float* dT, float* s1, float* s2, float* dQKV, Drop dl, uint32_t site, const float* astats = nullptr);
 // feed-forward block without its norm: T = dropout_b(lin2(dropout_a(relu(lin1(h))))) + h   (sites site_a, site_b)
 int tf_ff_fwd(const TfRun& r, const TfFfW& W, const float* h, float* FF, float* T, Drop dl, uint32_t site_a, uint32_t site_b);
 // backward of tf_ff_fwd: dT (in: dT, out: dH = dT + the feed-forward path); s1 (R,D) scratch; dFF (R,F) scratch

@@ -64,7 +64,8 @@ static int tf_np(int precision) { return precision == SUMK_PRECISION_BF16X6 ? 3 
 static bool tf_pw_rows_ok(int D, int F, int64_t R, int np) {
   return R >= 128 && pw_ok(R, 3 * (int64_t)D, D, R, 3 * (int64_t)D, np) && pw_ok(R, F, D, R, F, np) && pw_ok(R, D, F, R, D, np);
 }
-// logits = false: the inference carve of the stream path -- no `e`, `seq` or `prob_tabs`; attn_stream.hip's descriptors instead
+// logits = false: the carves of the stream path -- no `e`, `seq` or `prob_tabs`, in training no `l_p` / `l_pd` either; attn_stream.hip's
+// descriptors instead, in training with attn_stream_bwd.hip's delta behind them and the attention statistic among the per-layer saves
 static int tf_carve_any(int D, int F, int heads, int n_layers, int n_seq, const int32_t* off, int training, bool logits, TfWs* w) {
   SUMK_ARG(D > 0 && D % 4 == 0 && F > 0 && F % 4 == 0, "transformer: D=%d / F=%d must be positive multiples of 4", D, F);
   SUMK_ARG(heads > 0 && D % heads == 0 && (D / heads) % 4 == 0, "transformer: head dim must be a multiple of 4 (D=%d heads=%d)", D, heads);
@@ -80,7 +81,7 @@ static int tf_carve_any(int D, int F, int heads, int n_layers, int n_seq, const 
   size_t p = 0;
   auto take = [&](size_t bytes) { size_t at = p; p += align_up(bytes, 256); return at; };
   w->n_rows = (int32_t)R; w->e_elems = e;
-  w->seq = w->prob_tabs = 0;
+  w->seq = w->prob_tabs = w->e = w->l_p = w->l_pd = w->l_astats = w->as_seq = 0;
   if (logits) w->seq = take((size_t)n_seq * sizeof(TfSeq));
   w->prob_row = take(8 * sizeof(GemmProb));
   if (logits) w->prob_tabs = take((size_t)TT_COUNT * n_seq * heads * sizeof(GemmProb));   // (the stream path has no per-(video, head) GEMMs)
@@ -93,11 +94,14 @@ static int tf_carve_any(int D, int F, int heads, int n_layers, int n_seq, const 
   } else {
     size_t q = 0;
     auto lt = [&](size_t bytes) { size_t at = q; q += align_up(bytes, 256); return at; };
-    w->l_qkv = lt(R * 3 * D * 4); w->l_p = lt((size_t)e * 4); w->l_pd = lt((size_t)e * 4); w->l_ctx = lt(R * D * 4);
+    w->l_qkv = lt(R * 3 * D * 4);
+    if (logits) { w->l_p = lt((size_t)e * 4); w->l_pd = lt((size_t)e * 4); } else w->l_astats = lt(R * (size_t)heads * 8);
+    w->l_ctx = lt(R * D * 4);
     w->l_t1a = lt(R * D * 4); w->l_hmid = lt(R * D * 4); w->l_ff = lt(R * (size_t)F * 4); w->l_t1b = lt(R * D * 4);
     w->l_hout = lt(R * D * 4); w->l_stats = lt(R * 4 * 4);
     w->lay_stride = q;
     w->lay0 = take(q * (size_t)n_layers);
+    if (!logits) w->as_seq = take(attn_stream_bwd_ws_bytes(heads, n_seq, (int64_t)R));
     w->hfin = take(R * D * 4); w->z = take(R * D * 4); w->stats_fin = take(R * 4 * 4); w->scores = take(R * 4);
     w->g0 = take(R * D * 4); w->g1 = take(R * D * 4); w->g2 = take(R * D * 4);
     w->dqkv = take(R * 3 * D * 4); w->dff = take(R * (size_t)F * 4);
@@ -355,10 +359,25 @@ int tf_attn_core_bwd(const TfRun& r, const GemmProb* tabs, const float* qbase, c
   return SUMK_OK;
 }
 
+int tf_attn_stream_fwd(const TfRun& r, const float* QKV, float* CTX, float* astats, Drop dl, uint32_t site) {
+  const int D = r.D;
+  return launch_attn_stream_train(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, r.heads, r.n_seq, r.off_host, r.off_dev,
+                                  1.0f / sqrtf((float)r.G->dh), dl, site, CTX, D, astats, r.ws + r.G->L.as_seq, r.stream);
+}
+
+int tf_attn_stream_bwd(const TfRun& r, const float* QKV, const float* CTX, const float* dCTX, const float* astats, float* dQKV, Drop dl,
+                       uint32_t site) {
+  const int D = r.D;
+  return launch_attn_stream_bwd(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, CTX, D, dCTX, D, astats, D, r.heads, r.n_seq, r.off_host,
+                                r.off_dev, 1.0f / sqrtf((float)r.G->dh), dl, site, dQKV, 3 * D, dQKV + D, 3 * D, dQKV + 2 * D, 3 * D,
+                                r.ws + r.G->L.as_seq, r.stream);
+}
+
 int tf_sa_fwd(const TfRun& r, const TfAttnW& W, const float* hin, float* QKV, float* E, float* E2, float* CTX, float* T1a, Drop dl,
-              uint32_t site) {
+              uint32_t site, float* astats) {
   SUMK_TRY(tf_in_proj(r, hin, W.in_w, W.in_b, QKV));
-  SUMK_TRY(tf_attn_core_fwd(r, (const GemmProb*)(r.ws + r.G->L.prob_tabs), QKV, QKV, E, E2, CTX, dl, site + 0));
+  if (astats) SUMK_TRY(tf_attn_stream_fwd(r, QKV, CTX, astats, dl, site + 0));
+  else SUMK_TRY(tf_attn_core_fwd(r, (const GemmProb*)(r.ws + r.G->L.prob_tabs), QKV, QKV, E, E2, CTX, dl, site + 0));
   return tf_out_proj(r, CTX, W.out_w, W.out_b, hin, T1a, dl, site + 1);
 }
 
@@ -380,7 +399,7 @@ int tf_nn(const TfRun& r, const float* A, const float* B, float* C, int prob, Ge
 static dim3 tf_blocks(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 int tf_sa_bwd(const TfRun& r, const TfAttnW& W, const TfAttnG& Gd, const float* hin, const float* QKV, const float* P, float* E2,
-              const float* CTX, float* dT, float* s1, float* s2, float* dQKV, Drop dl, uint32_t site) {
+              const float* CTX, float* dT, float* s1, float* s2, float* dQKV, Drop dl, uint32_t site, const float* astats) {
   const int R = r.G->R, D = r.D; const int64_t nRD = (int64_t)R * D;
   float* colpart = (float*)(r.ws + r.G->L.colpart);
   const float* dAO = dT;
@@ -389,7 +408,8 @@ int tf_sa_bwd(const TfRun& r, const TfAttnW& W, const TfAttnG& Gd, const float* 
   SUMK_TRY(tf_wgrad(r, dAO, D, D, CTX, D, D, Gd.out_w));
   SUMK_TRY(tf_nn(r, dAO, W.out_w, s1, P_DD, EPI_NONE, D));                  // s1 = dCTX
   // multi-head attention backward, per (video, head)
-  SUMK_TRY(tf_attn_core_bwd(r, (const GemmProb*)(r.ws + r.G->L.prob_tabs), QKV, QKV, P, E2, s1, dQKV, dQKV, dl, site + 0));
+  if (astats) SUMK_TRY(tf_attn_stream_bwd(r, QKV, CTX, s1, astats, dQKV, dl, site + 0));
+  else SUMK_TRY(tf_attn_core_bwd(r, (const GemmProb*)(r.ws + r.G->L.prob_tabs), QKV, QKV, P, E2, s1, dQKV, dQKV, dl, site + 0));
   SUMK_TRY(colsum_accum(dQKV, 3 * D, R, 3 * D, colpart, TF_COLSUM_CHUNKS, Gd.in_b, r.stream));
   SUMK_TRY(tf_wgrad(r, dQKV, 3 * D, 3 * D, hin, D, D, Gd.in_w));
   return tf_nn(r, dQKV, W.in_w, dT, P_DQKV, EPI_ACCUM, D);                  // dHin = dT1a + dQKV . Win   (Win stored (3D,D) = (K,N))
@@ -504,20 +524,25 @@ extern "C" int sumk_transformer_wplanes_build(int32_t D, int32_t F, int32_t n_la
   return SUMK_OK;
 }
 
-extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
-                                        const int32_t* seq_off_host, const int32_t* seq_off_dev,
-                                        const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
-                                        const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
-                                        float* scores, void* workspace, size_t workspace_bytes, int32_t training,
-                                        void* stream_) {
+// The forward of sumk_transformer_forward and, stream_attn = true (training only, exact fp32), of sumk_transformer_forward_stream_train:
+// the same layer loop with every layer's attention core on attn_stream.hip's training form, on the stream training carve.
+static int tf_forward_any(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                          const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_tf_layer_weights* layers,
+                          const sumk_tf_head_weights* head, const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
+                          float* scores, void* workspace, size_t workspace_bytes, int32_t training, bool stream_attn, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SUMK_ARG(x && seq_off_dev && layers && head && opts && scores && workspace, "transformer_forward: null pointer");
+  if (stream_attn) {
+    SUMK_ARG(opts->precision == SUMK_PRECISION_FP32 && !opts->wplanes, "transformer_forward_stream_train: exact fp32 only (precision=%d, wplanes %s)",
+             opts->precision, opts->wplanes ? "given" : "null");
+    SUMK_TRY(attn_stream_bwd_check(D, n_heads, n_seq, seq_off_host));
+  }
   SUMK_ARG(n_layers > 0, "transformer_forward: n_layers=%d", n_layers);
   SUMK_ARG((pos_table == nullptr) == (pos_rows == nullptr), "transformer_forward: pos_table and pos_rows go together");
   SUMK_ARG(head->ln_w && head->ln_b && head->k1_w && head->k1_b && head->k2_w && head->k2_b, "transformer_forward: null head weight");
   SUMK_ARG((opts->layer_dropout_p == 0.f && opts->head_dropout_p == 0.f) || training, "transformer_forward: dropout needs training mode");
   TfGeom G;
-  SUMK_TRY(tf_geometry(D, F, n_heads, n_layers, n_seq, seq_off_host, training, &G));
+  SUMK_TRY(tf_geometry_any(D, F, n_heads, n_layers, n_seq, seq_off_host, training, !stream_attn, &G));
   const TfWs& L = G.L;
   if (workspace_bytes < L.total) { set_error("transformer_forward: workspace %zu < required %zu", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
   char* ws = (char*)workspace;
@@ -551,20 +576,22 @@ extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t 
   float* T1 = (float*)(ws + L.t1);
   const Drop dl = make_drop(opts->layer_dropout_p, opts->seed), dhd = make_drop(opts->head_dropout_p, opts->seed);
   const float att_scale = 1.0f / sqrtf((float)dh);
-  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream};
+  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream, seq_off_host};
 
   if (pos_table) SUMK_TRY(launch_add_pos(x, pos_table, pos_rows, R, D, stream));
-  SUMK_TRY(tf_tables(G, D, F, n_heads, n_seq, seq_off_dev, ws, stream));
+  SUMK_TRY(tf_tables(G, D, F, n_heads, n_seq, seq_off_dev, ws, stream, !stream_attn));
 
   const float* hin = x;
   for (int l = 0; l < n_layers; ++l) {
     const sumk_tf_layer_weights& W = layers[l];
     SUMK_ARG(W.in_proj_w && W.in_proj_b && W.out_proj_w && W.out_proj_b && W.lin1_w && W.lin1_b && W.lin2_w && W.lin2_b &&
              W.norm1_w && W.norm1_b && W.norm2_w && W.norm2_b, "transformer_forward: null weight in layer %d", l);
-    float *QKV, *E, *E2 = nullptr, *CTX, *T1a, *hmid, *FF, *T1b, *hout, *stats = nullptr;
+    float *QKV, *E = nullptr, *E2 = nullptr, *CTX, *T1a, *hmid, *FF, *T1b, *hout, *stats = nullptr, *astats = nullptr;
     if (training) {
       char* lb = ws + L.lay0 + (size_t)l * L.lay_stride;
-      QKV = (float*)(lb + L.l_qkv); E = (float*)(lb + L.l_p); E2 = dl.thr ? (float*)(lb + L.l_pd) : nullptr;
+      QKV = (float*)(lb + L.l_qkv);
+      if (stream_attn) astats = (float*)(lb + L.l_astats);
+      else { E = (float*)(lb + L.l_p); E2 = dl.thr ? (float*)(lb + L.l_pd) : nullptr; }
       CTX = (float*)(lb + L.l_ctx); T1a = (float*)(lb + L.l_t1a); hmid = (float*)(lb + L.l_hmid); FF = (float*)(lb + L.l_ff);
       T1b = (float*)(lb + L.l_t1b); hout = (float*)(lb + L.l_hout); stats = (float*)(lb + L.l_stats);
     } else {
@@ -591,7 +618,8 @@ extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t 
       } else {  // packed in-projection  [Q|K|V] = h Win^T + bin
         SUMK_TRY(tf_in_proj(run, hin, W.in_proj_w, W.in_proj_b, QKV));
       }
-      SUMK_TRY(tf_attn_core_fwd(run, tabs, QKV, QKV, E, E2, CTX, dl, site + 0));   // logits, softmax, context per (video, head)
+      if (stream_attn) SUMK_TRY(tf_attn_stream_fwd(run, QKV, CTX, astats, dl, site + 0));   // one launch, no logits
+      else SUMK_TRY(tf_attn_core_fwd(run, tabs, QKV, QKV, E, E2, CTX, dl, site + 0));        // logits, softmax, context per (video, head)
       if (pw) {
         SUMK_TRY(split_planes(CTX, R, D, D, npl, PA, stream));
         SUMK_TRY(pw_linear(PA, wl + WL.wo, D, D, W.out_proj_b, hin, 0, T1a, nullptr));
@@ -620,6 +648,35 @@ extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t 
   if (training) SUMK_HIP(hipMemcpyAsync(ws + L.scores, scores, (size_t)R * 4, hipMemcpyDeviceToDevice, stream));
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
+}
+
+extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                        const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                        const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                        const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
+                                        float* scores, void* workspace, size_t workspace_bytes, int32_t training,
+                                        void* stream_) {
+  return tf_forward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores, workspace,
+                        workspace_bytes, training, false, stream_);
+}
+
+// ---- training on the stream path: the training forward and the backward with every layer's attention on attn_stream.hip /
+// attn_stream_bwd.hip; the carve has no `e`, `l_p`, `l_pd` and no per-(video, head) tables
+extern "C" size_t sumk_transformer_stream_train_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                                const int32_t* seq_off_host) {
+  TfWs w;
+  if (n_layers < 1 || tf_carve_any(D, F, n_heads, n_layers, n_seq, seq_off_host, 1, false, &w) != SUMK_OK) return 0;
+  if (attn_stream_bwd_check(D, n_heads, n_seq, seq_off_host) != SUMK_OK) return 0;
+  return w.total;
+}
+
+extern "C" int sumk_transformer_forward_stream_train(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                     const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                                     const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                                     const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
+                                                     float* scores, void* workspace, size_t workspace_bytes, void* stream_) {
+  return tf_forward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores, workspace,
+                        workspace_bytes, 1, true, stream_);
 }
 
 // ---- the stream path: the inference of sumk_transformer_forward with tf_attn_core_fwd replaced by attn_stream.hip's launch; no `e` in the carve
@@ -682,16 +739,22 @@ extern "C" int sumk_transformer_forward_stream(float* x, int32_t D, int32_t F, i
   return SUMK_OK;
 }
 
-extern "C" int sumk_transformer_backward(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
-                                         int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
-                                         const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
-                                         const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* lgr,
-                                         const sumk_tf_head_grads* hgr, float* dx, void* workspace, size_t workspace_bytes,
-                                         void* stream_) {
+// The backward of sumk_transformer_backward and, stream_attn = true, of sumk_transformer_backward_stream (after
+// sumk_transformer_forward_stream_train on the same workspace)
+static int tf_backward_any(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                           const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_tf_layer_weights* layers,
+                           const sumk_tf_head_weights* head, const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* lgr,
+                           const sumk_tf_head_grads* hgr, float* dx, void* workspace, size_t workspace_bytes, bool stream_attn,
+                           void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SUMK_ARG(x && seq_off_dev && layers && head && opts && dscores && lgr && hgr && workspace, "transformer_backward: null pointer");
+  if (stream_attn) {
+    SUMK_ARG(opts->precision == SUMK_PRECISION_FP32 && !opts->wplanes, "transformer_backward_stream: exact fp32 only (precision=%d, wplanes %s)",
+             opts->precision, opts->wplanes ? "given" : "null");
+    SUMK_TRY(attn_stream_bwd_check(D, n_heads, n_seq, seq_off_host));
+  }
   TfGeom G;
-  SUMK_TRY(tf_geometry(D, F, n_heads, n_layers, n_seq, seq_off_host, 1, &G));
+  SUMK_TRY(tf_geometry_any(D, F, n_heads, n_layers, n_seq, seq_off_host, 1, !stream_attn, &G));
   const TfWs& L = G.L;
   if (workspace_bytes < L.total) { set_error("transformer_backward: workspace %zu < required %zu (needs the training-mode forward's workspace)", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
   char* ws = (char*)workspace;
@@ -707,7 +770,7 @@ extern "C" int sumk_transformer_backward(const float* x, int32_t D, int32_t F, i
   const Drop dl = make_drop(opts->layer_dropout_p, opts->seed), dhd = make_drop(opts->head_dropout_p, opts->seed);
   const Drop none = make_drop(0.f, 0);
   int nw = 0;
-  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream};
+  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream, seq_off_host};
   auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
   auto nn = [&](const float* A, const float* B, float* C, int prob, GemmEpi epi, int N) -> int {   // C (op)= A . B, B stored (K, N)
     GemmLaunch g; g.precision = opts->precision;
@@ -739,8 +802,10 @@ extern "C" int sumk_transformer_backward(const float* x, int32_t D, int32_t F, i
     const sumk_tf_layer_weights& W = layers[l];
     const sumk_tf_layer_grads& Gd = lgr[l];
     char* lb = ws + L.lay0 + (size_t)l * L.lay_stride;
-    const float* QKV = (const float*)(lb + L.l_qkv); const float* P = (const float*)(lb + L.l_p);
-    float* E2 = (float*)(lb + L.l_pd);
+    const float* QKV = (const float*)(lb + L.l_qkv);
+    const float* P = stream_attn ? nullptr : (const float*)(lb + L.l_p);
+    float* E2 = stream_attn ? nullptr : (float*)(lb + L.l_pd);
+    const float* astats = stream_attn ? (const float*)(lb + L.l_astats) : nullptr;
     const float* CTX = (const float*)(lb + L.l_ctx); const float* T1a = (const float*)(lb + L.l_t1a);
     const float* hmid = (const float*)(lb + L.l_hmid); const float* FFa = (const float*)(lb + L.l_ff);
     const float* T1b = (const float*)(lb + L.l_t1b); const float* stats = (const float*)(lb + L.l_stats);
@@ -757,7 +822,7 @@ extern "C" int sumk_transformer_backward(const float* x, int32_t D, int32_t F, i
     SUMK_TRY(ln_bwd_reduce(lnpart, nw, D, Gd.norm1_w, Gd.norm1_b, nullptr, nullptr, nullptr, stream));
     // dT1a (in dH) -> dHin: out-projection (dropout1 mask), per-(video, head) attention, in-projection backward; fa, fb scratch
     SUMK_TRY(tf_sa_bwd(run, TfAttnW{W.in_proj_w, W.in_proj_b, W.out_proj_w, W.out_proj_b},
-                       TfAttnG{Gd.in_proj_w, Gd.in_proj_b, Gd.out_proj_w, Gd.out_proj_b}, hin, QKV, P, E2, CTX, dH, fa, fb, dQKV, dl, site));
+                       TfAttnG{Gd.in_proj_w, Gd.in_proj_b, Gd.out_proj_w, Gd.out_proj_b}, hin, QKV, P, E2, CTX, dH, fa, fb, dQKV, dl, site, astats));
     // dH (= dT1a buffer) now holds the gradient w.r.t. this layer's input = the previous layer's output
   }
   if (dx) {
@@ -770,4 +835,24 @@ extern "C" int sumk_transformer_backward(const float* x, int32_t D, int32_t F, i
   }
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
+}
+
+extern "C" int sumk_transformer_backward(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
+                                         int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                         const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                         const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* lgr,
+                                         const sumk_tf_head_grads* hgr, float* dx, void* workspace, size_t workspace_bytes,
+                                         void* stream_) {
+  return tf_backward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, dscores, lgr, hgr, dx, workspace,
+                         workspace_bytes, false, stream_);
+}
+
+extern "C" int sumk_transformer_backward_stream(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
+                                                int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                                const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                                const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* lgr,
+                                                const sumk_tf_head_grads* hgr, float* dx, void* workspace, size_t workspace_bytes,
+                                                void* stream_) {
+  return tf_backward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, dscores, lgr, hgr, dx, workspace,
+                         workspace_bytes, true, stream_);
 }

@@ -1121,22 +1121,87 @@ def attn_stream(q, k, v, sb, n_heads, scale=None, want_lse=False):
     return (ctx, lse) if want_lse else ctx
 
 
-def transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, attention="dense"):
-    """Bytes of scratch one no-grad scoring call takes in exact fp32: "dense" holds heads x T x T logits per video
-    (sumk_transformer_workspace_bytes), "stream" none (sumk_transformer_stream_workspace_bytes)."""
+def _attn_stream_args(fn, tensors, sb):
+    for t, what in tensors:
+        _require_gpu(t, f"{fn} {what}")
+        if t.dim() != 2 or t.shape != tensors[0][0].shape or t.shape[0] != sb.n_rows or t.stride(1) != 1:
+            raise SumkError(f"{fn}: {what} must be (n_rows={sb.n_rows}, D) with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
+
+
+def attn_stream_train(q, k, v, sb, n_heads, scale=None, dropout_p=0.0, seed=0, site=0):
+    """attn_stream in its training form (sumk_attn_stream_train): the weights dropped with probability dropout_p by the library's hash masks
+    of (seed, site) -- the masks the dense Transformer path draws at that site -- and, for attn_stream_backward, stats (n_rows, n_heads, 2):
+    the row maximum of the scaled logits and the sum of exp(s - max).  With dropout_p == 0 ctx has attn_stream's bits.
+    Returns (ctx, stats).  Only enqueues work."""
+    lib = _lib.load()
+    _attn_stream_args("attn_stream_train", ((q, "q"), (k, "k"), (v, "v")), sb)
+    D = q.shape[1]
+    nb = attn_stream_workspace_bytes(D, n_heads, sb)
+    ws = workspace(nb, q.device)
+    ctx = torch.empty(sb.n_rows, D, dtype=torch.float32, device=q.device)
+    stats = torch.empty(sb.n_rows, int(n_heads), 2, dtype=torch.float32, device=q.device)
+    sc = 1.0 / math.sqrt(D // int(n_heads)) if scale is None else float(scale)
+    rc = lib.sumk_attn_stream_train(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq, sb.off_host_p,
+                                    sb.off_dev_p, sc, float(dropout_p), int(seed), int(site), _p(ctx), D, _p(stats), _p(ws), ws.numel(),
+                                    _stream())
+    _lib.check(rc, "sumk_attn_stream_train")
+    return ctx, stats
+
+
+def attn_stream_backward_workspace_bytes(D, n_heads, sb):
+    """Bytes of scratch one attn_stream_backward call takes: 16 per video + 4 per (row, head)."""
+    return _nonzero(_lib.load().sumk_attn_stream_backward_workspace_bytes(int(D), int(n_heads), sb.n_seq, sb.off_host_p),
+                    "sumk_attn_stream_backward_workspace_bytes")
+
+
+def attn_stream_backward(q, k, v, ctx, dctx, stats, sb, n_heads, scale=None, dropout_p=0.0, seed=0, site=0, out=None):
+    """Backward of attn_stream_train without anything of size T x T (csrc/attn_stream_bwd.hip; head widths up to 128): ctx and stats are that
+    call's results, scale / dropout_p / seed / site its arguments.  Returns (dq, dk, dv), each (n_rows, D) -- the column blocks of one
+    (n_rows, 3 D) buffer, `out` when given.  Deterministic; only enqueues work."""
+    lib = _lib.load()
+    _attn_stream_args("attn_stream_backward", ((q, "q"), (k, "k"), (v, "v"), (ctx, "ctx"), (dctx, "dctx")), sb)
+    D = q.shape[1]
+    _require_gpu(stats, "attn_stream_backward stats")
+    if tuple(stats.shape) != (sb.n_rows, int(n_heads), 2) or not stats.is_contiguous():
+        raise SumkError(f"attn_stream_backward: stats must be contiguous (n_rows={sb.n_rows}, n_heads={int(n_heads)}, 2), got {tuple(stats.shape)}")
+    nb = attn_stream_backward_workspace_bytes(D, n_heads, sb)
+    ws = workspace(nb, q.device)
+    if out is None:
+        out = torch.empty(sb.n_rows, 3 * D, dtype=torch.float32, device=q.device)
+    elif tuple(out.shape) != (sb.n_rows, 3 * D) or not out.is_contiguous():
+        raise SumkError(f"attn_stream_backward: out must be contiguous (n_rows={sb.n_rows}, {3 * D}), got {tuple(out.shape)}")
+    dq, dk, dv = out[:, :D], out[:, D:2 * D], out[:, 2 * D:]
+    sc = 1.0 / math.sqrt(D // int(n_heads)) if scale is None else float(scale)
+    rc = lib.sumk_attn_stream_backward(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(ctx), ctx.stride(0), _p(dctx),
+                                       dctx.stride(0), _p(stats), D, int(n_heads), sb.n_seq, sb.off_host_p, sb.off_dev_p, sc,
+                                       float(dropout_p), int(seed), int(site), _p(dq), 3 * D, _p(dk), 3 * D, _p(dv), 3 * D, _p(ws),
+                                       ws.numel(), _stream())
+    _lib.check(rc, "sumk_attn_stream_backward")
+    return dq, dk, dv
+
+
+def transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, attention="dense", training=False):
+    """Bytes of scratch one call takes in exact fp32.  Scoring: "dense" holds heads x T x T logits per video
+    (sumk_transformer_workspace_bytes), "stream" none (sumk_transformer_stream_workspace_bytes).  training=True, the forward that keeps
+    what the backward needs: "dense" keeps two heads x T x T blocks per video and layer, "stream" 8 bytes per (row, head) and layer
+    (sumk_transformer_stream_train_workspace_bytes)."""
     lib = _lib.load()
     if _tf_attention(attention) == "stream":
+        if training:
+            return _nonzero(lib.sumk_transformer_stream_train_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq,
+                                                                              sb.off_host_p), "sumk_transformer_stream_train_workspace_bytes")
         return _nonzero(lib.sumk_transformer_stream_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq, sb.off_host_p),
                         "sumk_transformer_stream_workspace_bytes")
-    return _nonzero(lib.sumk_transformer_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq, sb.off_host_p, 0),
+    return _nonzero(lib.sumk_transformer_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq, sb.off_host_p, int(training)),
                     "sumk_transformer_workspace_bytes")
 
 
 def transformer_forward_packed(x, sb, params, n_layers, n_heads, dff, opts, pos_table=None, pos_rows=None, training=False,
                                attention="dense"):
     """x: (n_rows, D) packed -> (scores (n_rows,), workspace or None).  params: state_dict-keyed tensors.
-    attention="stream" (inference in exact fp32 only): every layer's attention on csrc/attn_stream.hip, no (T x T) logits in the
-    workspace (sumk_transformer_forward_stream)."""
+    attention="stream" (exact fp32 only): every layer's attention on csrc/attn_stream.hip, no (T x T) logits in the workspace
+    (sumk_transformer_forward_stream; training=True: sumk_transformer_forward_stream_train, whose workspace goes to
+    transformer_backward_packed(..., attention="stream"))."""
     lib = _lib.load()
     _check_rows(x, sb, "transformer input")
     D = x.shape[1]
@@ -1144,7 +1209,15 @@ def transformer_forward_packed(x, sb, params, n_layers, n_heads, dff, opts, pos_
     o = _tf_opts(opts)
     if _tf_attention(attention) == "stream":
         if training:
-            raise SumkError("transformer_forward_packed: attention='stream' is the inference path (training=False)")
+            nbytes = transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, "stream", training=True)
+            ws = workspace(nbytes, x.device, persistent=True)
+            scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
+            rc = lib.sumk_transformer_forward_stream_train(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
+                                                           C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
+                                                           C.cast(C.pointer(o), C.c_void_p), _p(pos_table), _p(pos_rows), _p(scores),
+                                                           _p(ws), ws.numel(), _stream())
+            _lib.check(rc, "sumk_transformer_forward_stream_train")
+            return scores, ws
         nbytes = transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, "stream")
         ws = workspace(nbytes, x.device)
         scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
@@ -1166,7 +1239,8 @@ def transformer_forward_packed(x, sb, params, n_layers, n_heads, dff, opts, pos_
     return scores, (ws if training else None)
 
 
-def transformer_backward_packed(x, sb, params, grads, n_layers, n_heads, dff, opts, dscores, ws, want_dx=False):
+def transformer_backward_packed(x, sb, params, grads, n_layers, n_heads, dff, opts, dscores, ws, want_dx=False, attention="dense"):
+    """attention: the one of the training forward that filled `ws`."""
     lib = _lib.load()
     D = x.shape[1]
     layers, head = _tf_structs(params, n_layers, "weight", _lib.TfLayerWeights, _lib.TfHeadWeights)
@@ -1175,11 +1249,12 @@ def transformer_backward_packed(x, sb, params, grads, n_layers, n_heads, dff, op
     dx = torch.empty_like(x) if want_dx else None
     if not dscores.is_contiguous():
         dscores = dscores.contiguous()
-    rc = lib.sumk_transformer_backward(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
-                                       C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
-                                       C.cast(C.pointer(o), C.c_void_p), _p(dscores), C.cast(glayers, C.c_void_p),
-                                       C.cast(C.pointer(ghead), C.c_void_p), _p(dx), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "sumk_transformer_backward")
+    entry = "sumk_transformer_backward_stream" if _tf_attention(attention) == "stream" else "sumk_transformer_backward"
+    rc = getattr(lib, entry)(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
+                             C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
+                             C.cast(C.pointer(o), C.c_void_p), _p(dscores), C.cast(glayers, C.c_void_p),
+                             C.cast(C.pointer(ghead), C.c_void_p), _p(dx), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, entry)
     return dx
 
 

@@ -22,16 +22,21 @@ from ..training import FlatAdam, dist_info, plan_shards, step_video_total
 
 class Transformer(PositionalInput, nn.Module):
     def __init__(self, input_size=1024, encoder_layers=6, attention_heads=8, more_residuals=False, max_length=None,
-                 pos_embed="simple", epsilon=1e-5, weight_init=None, attention="dense"):
+                 pos_embed="simple", epsilon=1e-5, weight_init=None, attention="dense", attention_train="dense"):
         super().__init__()
         # attention (not in the reference, opt-in): how a no-grad call computes the multi-head attention of every layer.
         #   "dense"   heads x T x T logits per video in the workspace (csrc/transformer.hip): the default, every precision;
         #   "stream"  no logits anywhere: one fused launch per layer (csrc/attn_stream.hip), exact fp32 only -- the workspace is
         #             O(T (D + F)), so a video of 65 536 steps scores in under 8 GiB where "dense" would ask for over 100 GB.
-        #             A call that records a graph (training) keeps the dense path: the backward of the stream form is not built.
+        # attention_train (opt-in too, independent of `attention`): the same choice for a call that records a graph (training).
+        #   "dense"   keeps alpha and dropout(alpha), two heads x T x T blocks per video and LAYER: the default, its bits unchanged;
+        #   "stream"  keeps 8 bytes per (row, head) and layer and recomputes the weights in the backward (csrc/attn_stream_bwd.hip):
+        #             exact fp32 only, head widths up to 128, the same dropout masks as "dense" for the same seed.
         if attention not in kernels.TF_ATTENTION:
             raise ValueError(f"Transformer: attention must be one of {kernels.TF_ATTENTION}, got {attention!r}")
-        self.attention = attention
+        if attention_train not in kernels.TF_ATTENTION:
+            raise ValueError(f"Transformer: attention_train must be one of {kernels.TF_ATTENTION}, got {attention_train!r}")
+        self.attention, self.attention_train = attention, attention_train
         self.input_size = input_size
         self.encoder_layers, self.attention_heads, self.epsilon = encoder_layers, attention_heads, epsilon
         self._init_pos_embed(max_length, pos_embed)
@@ -69,7 +74,8 @@ class Transformer(PositionalInput, nn.Module):
 
     def _score(self, xp, sb, table, rows):
         """attention="stream": the no-grad branch scores through sumk_transformer_forward_stream (exact fp32; any other `precision`
-        raises ValueError); the autograd branch stays on the dense path, whose gradients are those of attention="dense" bit for bit."""
+        raises ValueError).  The autograd branch follows attention_train alone: "dense" (default) gives the gradients it always gave, bit
+        for bit; "stream" runs sumk_transformer_forward_stream_train / _backward_stream (exact fp32; any other `precision` raises)."""
         p = dict(self.named_parameters())
         opts = dict(layer_eps=1e-5, final_eps=self.epsilon, more_residuals=self.more_residuals,
                     precision=getattr(self, "precision", "fp32"))
@@ -82,6 +88,11 @@ class Transformer(PositionalInput, nn.Module):
                             seed=(torch.initial_seed() * 1000003 + self._seed_counter) & (2**63 - 1))
             names = kernels.transformer_param_names(self.encoder_layers)
             cfg = dict(n_layers=self.encoder_layers, n_heads=self.attention_heads, dff=self.input_size)
+            if self.attention_train == "stream":
+                if opts["precision"] not in (None, "fp32"):
+                    raise ValueError(f"Transformer(attention_train='stream') trains in exact fp32: precision={opts['precision']!r} needs "
+                                     "attention_train='dense' (or precision='fp32' with attention_train='stream')")
+                cfg["attention"] = "stream"
             return TransformerFunction.apply(xp, sb, cfg, opts, table, rows, names, *[p[n] for n in names])
         if self.attention == "stream":
             if opts["precision"] not in (None, "fp32"):
@@ -108,7 +119,8 @@ class TransformerTrainer(Trainer):
     """Mirror of the reference trainer (transformer.py:106-192): per-video MSE regression with Adam, periodic test, best-
     correlation weights; same `extra_params`.  Extensions as for VASNetTrainer: `batch_videos`, video sharding + one
     flat-bucket gradient all-reduce per step under torch.distributed.  extra_params["attention"] = "stream" scores (test, summaries)
-    without the (T x T) logits (Transformer's argument of that name); training stays on the dense path."""
+    without the (T x T) logits (Transformer's argument of that name); extra_params["attention_train"] = "stream" trains without the
+    (T x T) blocks (Transformer's attention_train); each defaults to "dense" and neither implies the other."""
     def _init_model(self):
         ep = self.hps.extra_params
         model = Transformer(
@@ -120,6 +132,7 @@ class TransformerTrainer(Trainer):
             epsilon=float(ep.get("epsilon", 1e-5)),
             weight_init=ep.get("weight_init", None),
             attention=ep.get("attention", "dense"),
+            attention_train=ep.get("attention_train", "dense"),
             **({"input_size": int(ep["input_size"])} if "input_size" in ep else {}))
         model.precision = ep.get("precision", "fp32")      # "fp32" | "bf16x3" (kernels.precision_code)
         if self.hps.use_cuda:
