@@ -662,6 +662,22 @@ int sumk_gemm_planes(const void* A_planes, int64_t a_rows, const void* B_planes,
 size_t sumk_attn_planes_alpha_bytes(int64_t rows, int32_t t_max, int32_t n_planes);
 int sumk_attn_planes(const void* qkv_planes, int64_t rows, int32_t D, int32_t n_planes, int32_t n_seq, const int32_t* seq_off_host,
                      float scale, int32_t ignore_self, int32_t aperture, float* E, void* alpha_planes, void* ctx_planes, void* stream);
+/* Fused attention strips of the bf16-source training step (csrc/attn_b16.hip) on their own: FOR TESTS AND PROBES ONLY -- the product
+ * reaches the same launch through sumk_vasnet_forward / sumk_vasnet_backward with precision bf16, this entry allocates, synchronises
+ * the stream and frees on every call.  All 16-bit arrays are bf16; per video s of T = seq_off[s + 1] - seq_off[s] <= 320 frames
+ * (D a multiple of 256, every ld >= D and a multiple of 8, every pointer 16-byte aligned):
+ *   backward == 0: A = Q, B = K, C = V (rows x D inside rows of ld elements).  E (written) = alpha = softmax(mask(Q K^T * scale)), fp32
+ *     (T x roundup4(T)) blocks back to back, pad columns 0; P16 (written) = bf16(dropout(alpha)), (T x roundup64(T)) blocks back to
+ *     back, pad columns 0; O16 (written, rows x D inside rows of ldo) = bf16(P16 V).  vasnet.py:118-131.
+ *   backward != 0: A = dCTX, B = V, C = K; E (read) = alpha of the forward; P16 (written) = bf16(dS),
+ *     dS = scale * alpha * (dropout'(dCTX V^T) - sum_j dropout'(dCTX V^T)_j alpha_j); O16 (written) = bf16(P16 K) = dQ.
+ * Dropout keeps element (packed row r, key j) when dropout_keep(seed, site 0, (r << 20) | j) says so, scaled by 1 / (1 - dropout_p).
+ * sumk_attn_strips_b16_sizes: the element counts of E and P16 for a batch (host arithmetic).  Bad arguments: SUMK_ERR_ARG, a message
+ * naming the argument in sumk_last_error, nothing launched. */
+int sumk_attn_strips_b16_sizes(int32_t n_seq, const int32_t* seq_off_host, int64_t* e_elems, int64_t* p16_elems);
+int sumk_attn_strips_b16(int32_t backward, const void* A16, int32_t lda, const void* B16, int32_t ldb, const void* C16, int32_t ldc,
+                         void* O16, int32_t ldo, float* E, void* P16, int32_t D, int32_t n_seq, const int32_t* seq_off_host,
+                         float scale, int32_t ignore_self, int32_t aperture, float dropout_p, uint64_t seed, void* stream);
 /* C(M,N) = A(M,K) * B(K,N) */
 int sumk_gemm_nn(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K, void* stream);
 /* C(M,N) = A^T * B with A given as (K,M), B as (K,N) */

@@ -33,7 +33,9 @@
 #include "pw_common.h"
 #include <math.h>
 #include <cstdlib>
+#include <algorithm>
 #include <atomic>
+#include <vector>
 
 namespace sumk {
 
@@ -401,3 +403,76 @@ int launch_attn_strip(bool backward, const AttnStripArgs& a_in, hipStream_t stre
 }
 
 }  // namespace sumk
+
+// ------------------------------------------------------------------------------------------------ C ABI (tests / probes)
+// The per-video tables exactly as vasnet_setup_kernel (csrc/vasnet.hip) lays them out, on the host.
+static int strips_table(const char* who, int32_t n_seq, const int32_t* seq_off_host, std::vector<sumk::SeqInfo>* h, int64_t* e_elems, int64_t* p16_elems,
+                        int* t_max) {
+  SUMK_ARG(seq_off_host, "%s: seq_off_host is null", who);
+  SUMK_ARG(n_seq >= 1, "%s: n_seq=%d must be at least 1", who, n_seq);
+  int64_t eoff = 0, e16off = 0;
+  int tm = 0;
+  if (h) h->resize(n_seq);
+  for (int s = 0; s < n_seq; ++s) {
+    const int T = seq_off_host[s + 1] - seq_off_host[s];
+    SUMK_ARG(T >= 1 && seq_off_host[s] >= 0, "%s: video %d has %d frames (seq_off_host)", who, s, T);
+    if (h) {
+      sumk::SeqInfo& q = (*h)[s];
+      q.eoff = eoff; q.row0 = seq_off_host[s]; q.T = T; q.ldE = (T + 3) & ~3; q.pad_ = 0; q.e16off = e16off;
+    }
+    eoff += (int64_t)T * ((T + 3) & ~3); e16off += (int64_t)T * ((T + 63) & ~63); tm = std::max(tm, T);
+  }
+  if (e_elems) *e_elems = eoff;
+  if (p16_elems) *p16_elems = e16off;
+  if (t_max) *t_max = tm;
+  return SUMK_OK;
+}
+
+extern "C" int sumk_attn_strips_b16_sizes(int32_t n_seq, const int32_t* seq_off_host, int64_t* e_elems, int64_t* p16_elems) {
+  SUMK_ARG(e_elems && p16_elems, "attn_strips_b16_sizes: e_elems / p16_elems is null");
+  *e_elems = 0; *p16_elems = 0;
+  return strips_table("attn_strips_b16_sizes", n_seq, seq_off_host, nullptr, e_elems, p16_elems, nullptr);
+}
+
+extern "C" int sumk_attn_strips_b16(int32_t backward, const void* A16, int32_t lda, const void* B16, int32_t ldb, const void* C16, int32_t ldc,
+                                    void* O16, int32_t ldo, float* E, void* P16, int32_t D, int32_t n_seq, const int32_t* seq_off_host,
+                                    float scale, int32_t ignore_self, int32_t aperture, float dropout_p, uint64_t seed, void* stream_) {
+  using namespace sumk;
+  hipStream_t stream = (hipStream_t)stream_;
+  SUMK_ARG(A16, "attn_strips_b16: A16 is null");
+  SUMK_ARG(B16, "attn_strips_b16: B16 is null");
+  SUMK_ARG(C16, "attn_strips_b16: C16 is null");
+  SUMK_ARG(O16, "attn_strips_b16: O16 is null");
+  SUMK_ARG(E, "attn_strips_b16: E is null");
+  SUMK_ARG(P16, "attn_strips_b16: P16 is null");
+  std::vector<SeqInfo> h;
+  int t_max = 0;
+  SUMK_TRY(strips_table("attn_strips_b16", n_seq, seq_off_host, &h, nullptr, nullptr, &t_max));
+  const struct { const char* name; int32_t ld; const void* p; } ops[] = {{"lda", lda, A16}, {"ldb", ldb, B16}, {"ldc", ldc, C16}, {"ldo", ldo, O16}};
+  for (const auto& o : ops) {
+    SUMK_ARG(o.ld >= D && o.ld % 8 == 0, "attn_strips_b16: %s=%d must be at least D=%d and a multiple of 8", o.name, o.ld, D);
+    SUMK_ARG(((uintptr_t)o.p & 15) == 0, "attn_strips_b16: the operand of %s is not 16-byte aligned", o.name);
+  }
+  SUMK_ARG(((uintptr_t)E & 15) == 0, "attn_strips_b16: E is not 16-byte aligned");
+  SUMK_ARG(((uintptr_t)P16 & 15) == 0, "attn_strips_b16: P16 is not 16-byte aligned");
+  SUMK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "attn_strips_b16: dropout_p=%g must lie in [0, 1)", (double)dropout_p);
+  const int ld_max = std::max(std::max(lda, ldb), std::max(ldc, ldo));
+  SUMK_ARG(attn_strip_ok(t_max, D, seq_off_host[n_seq], ld_max), "attn_strips_b16: not eligible (t_max=%d <= 320, D=%d %% 256 == 0, offsets inside 31 bits)",
+           t_max, D);
+  AttnStripArgs at;
+  at.A16 = (const unsigned short*)A16; at.lda = lda; at.B16 = (const unsigned short*)B16; at.ldb = ldb; at.C16 = (const unsigned short*)C16; at.ldc = ldc;
+  at.O16 = (unsigned short*)O16; at.ldo = ldo; at.E = E; at.P16 = (unsigned short*)P16;
+  at.n_seq = n_seq; at.strips = (t_max + 63) / 64; at.D = D;
+  at.scale = scale; at.ignore_self = ignore_self; at.aperture = aperture; at.drop = make_drop(dropout_p, seed);
+  SeqInfo* d = nullptr;
+  SUMK_HIP(hipMalloc(&d, sizeof(SeqInfo) * n_seq));
+  int rc = SUMK_OK;
+  const hipError_t e = hipMemcpyAsync(d, h.data(), sizeof(SeqInfo) * n_seq, hipMemcpyHostToDevice, stream);
+  if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync(SeqInfo table)");
+  at.seq = d;
+  if (rc == SUMK_OK) rc = launch_attn_strip(backward != 0, at, stream);
+  const hipError_t es = hipStreamSynchronize(stream);    // (test entry: the table is freed here)
+  if (rc == SUMK_OK && es != hipSuccess) rc = hip_fail(es, "hipStreamSynchronize");
+  (void)hipFree(d);
+  return rc;
+}

@@ -1093,6 +1093,35 @@ def _tf_attention(attention):
     return attention
 
 
+def attn_strips_b16_sizes(sb):
+    """(elements of E, elements of P16) the bf16 attention strips address for a batch (sumk_attn_strips_b16_sizes; host arithmetic)."""
+    e, p = C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.load().sumk_attn_strips_b16_sizes(sb.n_seq, sb.off_host_p, C.byref(e), C.byref(p)), "sumk_attn_strips_b16_sizes")
+    return e.value, p.value
+
+
+def attn_strips_b16(backward, a, b, c, out, E, P16, sb, scale, ignore_self=False, aperture=-1, dropout_p=0.0, seed=0):
+    """The fused attention strips of the bf16 training step on their own (csrc/attn_b16.hip through sumk_attn_strips_b16: TESTS AND PROBES,
+    the call synchronises).  a, b, c, out: bfloat16 (n_rows, D) with unit column stride, any row stride (slices of one buffer are fine);
+    E: float32, P16: bfloat16, both flat and caller-owned, at least attn_strips_b16_sizes(sb) elements.
+    Forward: a, b, c = Q, K, V; writes E (alpha), P16 (bf16 dropout(alpha)), out (CTX).  Backward: a, b, c = dCTX, V, K; reads E, writes
+    P16 (bf16 dS) and out (dQ)."""
+    lib = _lib.load()
+    for t, what in ((a, "a"), (b, "b"), (c, "c"), (out, "out")):
+        if not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape != a.shape or t.shape[0] != sb.n_rows or t.stride(1) != 1:
+            raise SumkError(f"attn_strips_b16: {what} must be a GPU bfloat16 (n_rows={sb.n_rows}, D) tensor with unit column stride, got "
+                            f"{t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    ne, np16 = attn_strips_b16_sizes(sb)
+    if not E.is_cuda or E.dtype != torch.float32 or not E.is_contiguous() or E.numel() < ne:
+        raise SumkError(f"attn_strips_b16: E must be a contiguous GPU float32 tensor of at least {ne} elements")
+    if not P16.is_cuda or P16.dtype != torch.bfloat16 or not P16.is_contiguous() or P16.numel() < np16:
+        raise SumkError(f"attn_strips_b16: P16 must be a contiguous GPU bfloat16 tensor of at least {np16} elements")
+    rc = lib.sumk_attn_strips_b16(int(bool(backward)), a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), c.data_ptr(), c.stride(0),
+                                  out.data_ptr(), out.stride(0), E.data_ptr(), P16.data_ptr(), a.shape[1], sb.n_seq, sb.off_host_p,
+                                  float(scale), int(bool(ignore_self)), int(aperture), float(dropout_p), int(seed), _stream())
+    _lib.check(rc, "sumk_attn_strips_b16")
+
+
 def attn_stream_workspace_bytes(D, n_heads, sb):
     """Bytes of scratch one attn_stream call takes: 16 per video (sumk_attn_stream_workspace_bytes)."""
     return _nonzero(_lib.load().sumk_attn_stream_workspace_bytes(int(D), int(n_heads), sb.n_seq, sb.off_host_p), "sumk_attn_stream_workspace_bytes")
