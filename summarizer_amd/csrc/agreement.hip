@@ -444,7 +444,7 @@ extern "C" int sumk_rank_rows(const sumk_agreement_video* videos_dev, const sumk
   SUMK_TRY(ag_check("rank_rows", videos_host, n_videos, true, t, &max_sc));
   if (max_sc == 0) return SUMK_OK;
   RankArgs a{videos_dev, avg_ranks_dev, dense_ranks_dev, ties_dev, mean_dev, ssq_dev, t};
-  SUMK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)AG_LDS_BYTES));
+  SUMK_TRY(lds_opt_in<rank_rows_kernel>((int)AG_LDS_BYTES));
   hipLaunchKernelGGL(rank_rows_kernel, dim3(max_sc, n_videos), dim3(KD_THREADS), AG_LDS_BYTES, (hipStream_t)stream, a);
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
@@ -489,7 +489,7 @@ extern "C" int sumk_agreement_corr(const sumk_agreement_video* videos_dev, const
   if (metric == SUMK_AGREEMENT_SPEARMAN) {
     if (max_sc > 0) hipLaunchKernelGGL(agreement_gram_kernel, dim3(max_sc, n_videos), dim3(AG_GRAM_THREADS), 0, (hipStream_t)stream, a);
   } else if (max_sc > 1) {
-    SUMK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(agreement_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)AG_LDS_BYTES));
+    SUMK_TRY(lds_opt_in<agreement_pair_kernel>((int)AG_LDS_BYTES));
     hipLaunchKernelGGL(agreement_pair_kernel, dim3(max_sc * (max_sc - 1) / 2, n_videos), dim3(KD_THREADS), AG_LDS_BYTES, (hipStream_t)stream, a);
   }
   SUMK_HIP(hipGetLastError());

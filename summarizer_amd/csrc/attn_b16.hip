@@ -34,7 +34,6 @@
 #include <math.h>
 #include <cstdlib>
 #include <algorithm>
-#include <atomic>
 #include <vector>
 
 namespace sumk {
@@ -385,16 +384,7 @@ bool attn_strip_ok(int t_max, int D, int64_t rows, int ld_max) {
 
 int launch_attn_strip(bool backward, const AttnStripArgs& a_in, hipStream_t stream) {
   const AttnStripArgs& a = a_in;
-  const void* fn = backward ? (const void*)attn_strip_kernel<true> : (const void*)attn_strip_kernel<false>;
-  // (the opt-in is per DEVICE: one bit per device, set atomically -- a process that drives a second GPU must not skip it there)
-  static std::atomic<uint64_t> attr_done[2];
-  int dev = 0;
-  SUMK_HIP(hipGetDevice(&dev));
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(attr_done[backward ? 1 : 0].load(std::memory_order_acquire) & bit)) {
-    SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, AT_LDS));
-    attr_done[backward ? 1 : 0].fetch_or(bit, std::memory_order_release);
-  }
+  SUMK_TRY(backward ? lds_opt_in<attn_strip_kernel<true>>(AT_LDS) : lds_opt_in<attn_strip_kernel<false>>(AT_LDS));
   const unsigned grid = (unsigned)(8 * ((a.n_seq + 7) / 8) * a.strips);
   if (backward) hipLaunchKernelGGL(attn_strip_kernel<true>, dim3(grid), dim3(512), AT_LDS, stream, a);
   else hipLaunchKernelGGL(attn_strip_kernel<false>, dim3(grid), dim3(512), AT_LDS, stream, a);

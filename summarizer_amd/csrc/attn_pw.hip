@@ -13,7 +13,6 @@
 // 0.2 of the split-bf16 ceiling (69 + 13 + 65 us at bf16x6 on S-TVSum) and CTX needed a separate fp32 -> planes pass (30 us).
 #include "pw_common.h"
 #include <math.h>
-#include <atomic>
 #include <vector>
 #include <algorithm>
 #include <cstdlib>
@@ -461,20 +460,6 @@ __global__ __launch_bounds__(512) void attn_pw_context_kernel(AttnPwArgs a) {
   attn_context_body<NP, HP2, RM, QT>(a, lds);
 }
 
-std::atomic<uint64_t> g_attr[28];
-
-template <typename K>
-int set_lds_once(K kernel, int inst, int bytes) {
-  int dev = 0;
-  SUMK_HIP(hipGetDevice(&dev));
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(g_attr[inst].load(std::memory_order_acquire) & bit)) {
-    SUMK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    g_attr[inst].fetch_or(bit, std::memory_order_release);
-  }
-  return SUMK_OK;
-}
-
 }  // namespace
 
 // T <= 320 keys per video, D a multiple of 256, every plane offset inside 31 bits
@@ -507,14 +492,14 @@ int launch_attn_pw_logits(int np, const void* qkv_planes, int64_t rows, int D, f
   const bool nt = nt_env >= 0 ? nt_env != 0 : (heads == 1 && pw_planes_bytes(rows, 3 * D, np) > ((size_t)192 << 20));
   if (heads > 1) {
     constexpr int LDSH3 = 2 * (6 * 384 * 16) + 4096, LDSH2 = 3 * (4 * 384 * 16) + 4096;      // 76 KB each: two blocks per CU
-#define SUMK_MH_CASE(NP_, NT_, LDS_, I_) { SUMK_TRY(set_lds_once(attn_pw_logits_mh_kernel<NP_, NT_>, I_, LDS_)); hipLaunchKernelGGL((attn_pw_logits_mh_kernel<NP_, NT_>), dim3(grid), dim3(512), LDS_, stream, a); }
-    if (np == 3) { if (nt) SUMK_MH_CASE(3, true, LDSH3, 24) else SUMK_MH_CASE(3, false, LDSH3, 8) }
-    else { if (nt) SUMK_MH_CASE(2, true, LDSH2, 25) else SUMK_MH_CASE(2, false, LDSH2, 14) }
+#define SUMK_MH_CASE(NP_, NT_, LDS_) { SUMK_TRY((lds_opt_in<attn_pw_logits_mh_kernel<NP_, NT_>>(LDS_))); hipLaunchKernelGGL((attn_pw_logits_mh_kernel<NP_, NT_>), dim3(grid), dim3(512), LDS_, stream, a); }
+    if (np == 3) { if (nt) SUMK_MH_CASE(3, true, LDSH3) else SUMK_MH_CASE(3, false, LDSH3) }
+    else { if (nt) SUMK_MH_CASE(2, true, LDSH2) else SUMK_MH_CASE(2, false, LDSH2) }
 #undef SUMK_MH_CASE
   } else {
-#define SUMK_A_CASE(NP_, NT_, LDS_, I_) { SUMK_TRY(set_lds_once(attn_pw_logits_kernel<NP_, NT_>, I_, LDS_)); hipLaunchKernelGGL((attn_pw_logits_kernel<NP_, NT_>), dim3(grid), dim3(512), LDS_, stream, a); }
-    if (np == 3) { if (nt) SUMK_A_CASE(3, true, LDS3, 26) else SUMK_A_CASE(3, false, LDS3, 2) }
-    else { if (nt) SUMK_A_CASE(2, true, LDS2, 27) else SUMK_A_CASE(2, false, LDS2, 5) }
+#define SUMK_A_CASE(NP_, NT_, LDS_) { SUMK_TRY((lds_opt_in<attn_pw_logits_kernel<NP_, NT_>>(LDS_))); hipLaunchKernelGGL((attn_pw_logits_kernel<NP_, NT_>), dim3(grid), dim3(512), LDS_, stream, a); }
+    if (np == 3) { if (nt) SUMK_A_CASE(3, true, LDS3) else SUMK_A_CASE(3, false, LDS3) }
+    else { if (nt) SUMK_A_CASE(2, true, LDS2) else SUMK_A_CASE(2, false, LDS2) }
 #undef SUMK_A_CASE
   }
   SUMK_HIP(hipGetLastError());
@@ -538,23 +523,23 @@ int launch_attn_pw_context(int np, const void* qkv_planes, int64_t rows, int D, 
     a.strips = (t_max + 127) / 128; a.csplit = 2;
     const unsigned gridw = (unsigned)(8 * ((n_seq + 7) / 8) * a.strips * a.csplit);
     constexpr int LDS3W = 4 * (12 + 24) * 1024, LDS2W = 6 * (8 + 16) * 1024, LDS3WH = 3 * (24 + 24) * 1024, LDS2WH = 4 * (16 + 16) * 1024;
-#define SUMK_B_WIDE(NP_, HP_, RM_, LDS_, I_) { SUMK_TRY(set_lds_once(attn_pw_context_kernel<NP_, HP_, RM_, 4>, I_, LDS_)); hipLaunchKernelGGL((attn_pw_context_kernel<NP_, HP_, RM_, 4>), dim3(gridw), dim3(512), LDS_, stream, a); }
-    if (heads > 1) { if (np == 3) SUMK_B_WIDE(3, true, false, LDS3WH, 22) else SUMK_B_WIDE(2, true, false, LDS2WH, 23) }
-    else if (R) { if (np == 3) SUMK_B_WIDE(3, false, true, LDS3W, 18) else SUMK_B_WIDE(2, false, true, LDS2W, 19) }
-    else { if (np == 3) SUMK_B_WIDE(3, false, false, LDS3W, 20) else SUMK_B_WIDE(2, false, false, LDS2W, 21) }
+#define SUMK_B_WIDE(NP_, HP_, RM_, LDS_) { SUMK_TRY((lds_opt_in<attn_pw_context_kernel<NP_, HP_, RM_, 4>>(LDS_))); hipLaunchKernelGGL((attn_pw_context_kernel<NP_, HP_, RM_, 4>), dim3(gridw), dim3(512), LDS_, stream, a); }
+    if (heads > 1) { if (np == 3) SUMK_B_WIDE(3, true, false, LDS3WH) else SUMK_B_WIDE(2, true, false, LDS2WH) }
+    else if (R) { if (np == 3) SUMK_B_WIDE(3, false, true, LDS3W) else SUMK_B_WIDE(2, false, true, LDS2W) }
+    else { if (np == 3) SUMK_B_WIDE(3, false, false, LDS3W) else SUMK_B_WIDE(2, false, false, LDS2W) }
 #undef SUMK_B_WIDE
     SUMK_HIP(hipGetLastError());
     return SUMK_OK;
   }
   const unsigned grid = (unsigned)(8 * ((n_seq + 7) / 8) * a.strips);
   if (heads > 1) {
-    if (np == 3) { SUMK_TRY(set_lds_once(attn_pw_context_kernel<3, true>, 12, LDS3H)); hipLaunchKernelGGL((attn_pw_context_kernel<3, true>), dim3(grid), dim3(512), LDS3H, stream, a); }
-    else { SUMK_TRY(set_lds_once(attn_pw_context_kernel<2, true>, 13, LDS2H)); hipLaunchKernelGGL((attn_pw_context_kernel<2, true>), dim3(grid), dim3(512), LDS2H, stream, a); }
+    if (np == 3) { SUMK_TRY((lds_opt_in<attn_pw_context_kernel<3, true>>(LDS3H))); hipLaunchKernelGGL((attn_pw_context_kernel<3, true>), dim3(grid), dim3(512), LDS3H, stream, a); }
+    else { SUMK_TRY((lds_opt_in<attn_pw_context_kernel<2, true>>(LDS2H))); hipLaunchKernelGGL((attn_pw_context_kernel<2, true>), dim3(grid), dim3(512), LDS2H, stream, a); }
   } else if (R) {
-    if (np == 3) { SUMK_TRY(set_lds_once(attn_pw_context_kernel<3, false, true>, 16, LDS3)); hipLaunchKernelGGL((attn_pw_context_kernel<3, false, true>), dim3(grid), dim3(512), LDS3, stream, a); }
-    else { SUMK_TRY(set_lds_once(attn_pw_context_kernel<2, false, true>, 17, LDS2)); hipLaunchKernelGGL((attn_pw_context_kernel<2, false, true>), dim3(grid), dim3(512), LDS2, stream, a); }
-  } else if (np == 3) { SUMK_TRY(set_lds_once(attn_pw_context_kernel<3, false>, 6, LDS3)); hipLaunchKernelGGL((attn_pw_context_kernel<3, false>), dim3(grid), dim3(512), LDS3, stream, a); }
-  else { SUMK_TRY(set_lds_once(attn_pw_context_kernel<2, false>, 7, LDS2)); hipLaunchKernelGGL((attn_pw_context_kernel<2, false>), dim3(grid), dim3(512), LDS2, stream, a); }
+    if (np == 3) { SUMK_TRY((lds_opt_in<attn_pw_context_kernel<3, false, true>>(LDS3))); hipLaunchKernelGGL((attn_pw_context_kernel<3, false, true>), dim3(grid), dim3(512), LDS3, stream, a); }
+    else { SUMK_TRY((lds_opt_in<attn_pw_context_kernel<2, false, true>>(LDS2))); hipLaunchKernelGGL((attn_pw_context_kernel<2, false, true>), dim3(grid), dim3(512), LDS2, stream, a); }
+  } else if (np == 3) { SUMK_TRY((lds_opt_in<attn_pw_context_kernel<3, false>>(LDS3))); hipLaunchKernelGGL((attn_pw_context_kernel<3, false>), dim3(grid), dim3(512), LDS3, stream, a); }
+  else { SUMK_TRY((lds_opt_in<attn_pw_context_kernel<2, false>>(LDS2))); hipLaunchKernelGGL((attn_pw_context_kernel<2, false>), dim3(grid), dim3(512), LDS2, stream, a); }
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
 }

@@ -13,18 +13,11 @@
 //                      32 WHOLE query rows; the workgroup walks the video's 64-key tiles in ascending order.  No column split.
 // No cooperative launch, no flag polled across workgroups, no atomics: bit-deterministic.
 //
-// Lane layout (v_mfma_f32_32x32x2_f32 for both products; lane = (li = lane & 31, lh = lane >> 5)):
-//   S^T = K_tile (A) x Q_strip^T (B), the swapped product of rs_stream_kernel: A[row li][k lh] = K[key 32 s + li][d], B[k lh][col li] =
-//     Q[query li][d]; one ds_read_b128 of a K row feeds four MFMAs, so MFMA j of group g contracts d = 8 g + j (lh 0) then 8 g + 4 + j
-//     (lh 1), groups ascending.  Accumulator register r of sub-tile s then holds, for QUERY li, key 32 s + crow(r, lh),
-//     crow(r, lh) = (r & 3) + 8 (r >> 2) + 4 lh: a lane owns one query row and 32 of the tile's 64 keys, its partner lane ^ 32 the others.
-//   O^T[d][q] += V^T[d][key] P^T[key][q]: with f32 operands that accumulator register IS the B operand of MFMA step (s, r) -- B[k lh][col li]
-//     = P[query li][key 32 s + crow(r, lh)] -- so P is never converted, never goes through LDS and never changes lane.  The matching A
-//     value is V[key 32 s + crow(r, lh)][d] with d chosen by the lane: d = (b % W) + W li + 32 W (b / W) for accumulator block b,
-//     W = min(NB, 4), so that ONE ds_read_b128 (W = 4) of a V row feeds the MFMAs of four blocks.  O block b register r of lane
-//     (li, lh) is O[query li][d = (b % W) + W crow(r, lh) + 32 W (b / W)]: the running rescale of O is a per-lane multiply.
+// Lane layout, the two products (S^T = K_tile x Q_strip^T, the swapped product of rs_stream_kernel, then O^T += V^T P^T with the
+// accumulator registers of the first as B operand of the second) and the strip prologue: attn_stream_common.h, shared with the backward.
+// Owner rows are queries, walked rows keys.  What is the forward's own:
 //   Row maximum: 31 fmax in the lane + one exchange with lane ^ 32.  Row sum: each lane half keeps its own partial (same rescale factor
-//     in both), joined once after the walk.
+//     in both), joined once after the walk.  The running rescale of O is a per-lane multiply (a lane owns one query row).
 //
 // Online softmax per tile, UNCONDITIONALLY (no deferred-max threshold, hence no rare data-dependent branch): m' = max(m, scale max_j s_j),
 // f = exp(m - m'), p_j = exp(fma(s_j, scale, -m')) (the dense kernel's expression), l = l f + sum p, O = O f + P V; at the end O / l and
@@ -42,8 +35,7 @@
 // K and V are single-buffered in LDS: two 64 x 256 tiles are 64 KiB each, so dh = 256 could not double-buffer both at 64 keys.  The
 // next tile travels in the staging registers instead, HALF a tile at a time (a whole one would not fit the budget at dh = 128): V(c)
 // is loaded under the first product of tile c, K(c + 1) under the softmax and the second product.  Two barriers per tile; at dh <= 128
-// the second workgroup of the CU fills them.  The fragment reads are software-pipelined by one step with a scheduling barrier per step:
-// left alone, the compiler hoists every ds_read of a phase and spills.
+// the second workgroup of the CU fills them.
 //
 // Vector-ALU work per tile and lane beside the 64 NB MFMAs (fp32 MFMA issues on the vector ALU here, so it adds to them): 32 fmax,
 // 1 multiply + 1 fmax + 1 exchange, 32 fma + 32 exp + 32 adds, 16 NB multiplies of O.  exp is the accurate expf (about 15
@@ -59,9 +51,7 @@
 // 256 VGPRs of its two-waves-per-SIMD budget and spills 85 (27 scratch instructions in the tile loop beside its 256 MFMAs); measured
 // 95 TFLOP/s at T = 8192 against 122 without dropout.
 #include "attn_stream_common.h"
-#include <math.h>
 #include <algorithm>
-#include <atomic>
 
 namespace sumk {
 
@@ -89,28 +79,19 @@ __global__ void as_setup_kernel(const int32_t* off, int n_seq, AsSeq* seq) {
 template <int NB, bool DROP>
 __global__ __launch_bounds__(256, NB <= 4 ? 2 : 1) void as_stream_kernel(AsArgs a) {
   extern __shared__ __attribute__((aligned(16))) float as_lds[];
-  constexpr int DP = 32 * NB, P = DP + 4;        // staged columns; LDS pitch (conflict-free ds_read_b128 of both images)
-  constexpr int C4 = DP / 4, NST = NB;           // float4 columns of a tile row; float4 per thread and half tile (32 C4 / 256)
-  constexpr int W = NB < 4 ? NB : 4, NQ = NB / W;
-  const int blk = blockIdx.x;
-  const int h = blk % a.heads, sg = blk / a.heads;
-  int lo = 0, hi = a.n_seq - 1;
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (a.seq[mid].strip0 <= sg) lo = mid; else hi = mid - 1; }
-  const AsSeq d = a.seq[lo];
-  const int T = d.T, dh = a.dh;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 31, lh = lane >> 5;
-  const int q0 = (sg - d.strip0) * AS_QS + wave * 32;          // this wave's first query row inside the video
-  const bool live = q0 < T;                                    // wave-uniform: a wave past the video only stages
-  const int64_t hcol = (int64_t)h * dh;
-  const float* Qh = a.Q + d.row0 * (int64_t)a.ldq + hcol;
-  const float* Kh = a.K + d.row0 * (int64_t)a.ldk + hcol;
-  const float* Vh = a.V + d.row0 * (int64_t)a.ldv + hcol;
+  using G = AsGeom<NB>;
+  constexpr int P = G::P, C4 = G::C4, NST = NB;  // NST: float4 per thread and half tile (32 C4 / 256)
+  const AsStrip w = as_strip(a.seq, a.n_seq, a.heads, a.dh);
+  const AsSeq d = w.d;
+  const int T = d.T, dh = a.dh, h = w.h, li = w.li, lh = w.lh, tid = threadIdx.x;
+  const bool live = w.live;
+  const float* Kh = a.K + d.row0 * (int64_t)a.ldk + w.hcol;
+  const float* Vh = a.V + d.row0 * (int64_t)a.ldv + w.hcol;
 
   // Q fragments: group g, MFMA j -> Q[query][8 g + 4 lh + j]
   float qf[4 * NB][4];
   {
-    const float* qp = Qh + (int64_t)min(q0 + li, T - 1) * a.ldq;
+    const float* qp = a.Q + d.row0 * (int64_t)a.ldq + w.hcol + (int64_t)w.orow * a.ldq;
 #pragma unroll
     for (int g = 0; g < 4 * NB; ++g) {
       const int dc = 8 * g + 4 * lh;
@@ -143,61 +124,18 @@ __global__ __launch_bounds__(256, NB <= 4 ? 2 : 1) void as_stream_kernel(AsArgs 
   };
 
   float* Kimg = as_lds;
-  float* Vimg = as_lds + AS_KT * P;
+  float* Vimg = as_lds + G::IMG;
   const int nt = (T + AS_KT - 1) / AS_KT;
-  f32x16 o[NB], s[2];
+  // s0, s1: the tile's two sub-tiles of logits, then weights.  Two objects, not s[2]: beside the shared products the compiler keeps
+  // such an array as ONE 32-wide vector (a 32-register tuple) and as_stream_kernel<4, false> spills (attn_stream_common.h)
+  f32x16 o[NB], s0, s1;
+  auto S = [&](int sb) -> f32x16& { return sb ? s1 : s0; };
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[b][r] = 0.f;
   float m = -INFINITY, l = 0.f;                   // running maximum of the row; this lane half's share of the running sum
-  const int64_t prow = d.row0 + min(q0 + li, T - 1);      // the packed row whose masks this lane draws (DROP)
-
-  // S^T += K Q^T over the groups [g0, g0 + 2 NB); the K fragments of group g + 1 are read under the MFMAs of group g
-  auto s_groups = [&](int g0) {
-    float4 kf[2], kn[2];
-    auto kread = [&](int g, float4 (&dst)[2]) {
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) dst[sb] = *reinterpret_cast<const float4*>(Kimg + (32 * sb + li) * P + 8 * g + 4 * lh);
-    };
-    kread(g0, kf);
-#pragma unroll
-    for (int gi = 0; gi < 2 * NB; ++gi) {         // every group: the columns past dh are zeros in both operands
-      const int g = g0 + gi;
-      if (gi + 1 < 2 * NB) kread(g + 1, kn);
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) {
-        s[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].x, qf[g][0], s[sb], 0, 0, 0);
-        s[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].y, qf[g][1], s[sb], 0, 0, 0);
-        s[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].z, qf[g][2], s[sb], 0, 0, 0);
-        s[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].w, qf[g][3], s[sb], 0, 0, 0);
-      }
-      kf[0] = kn[0]; kf[1] = kn[1];
-      __builtin_amdgcn_sched_barrier(0);          // keep the compiler from hoisting every group's reads (register budget)
-    }
-  };
-  // O^T += V^T P^T over the 16 steps of sub-tile sb; the V fragments of step r + 1 are read under the MFMAs of step r
-  auto pv_steps = [&](int sb) {
-    AsVec<W> vc[NQ], vn[NQ];
-    auto vread = [&](int r, AsVec<W> (&dst)[NQ]) {
-      const float* vp = Vimg + (32 * sb + as_crow(r, lh)) * P + W * li;
-#pragma unroll
-      for (int bq = 0; bq < NQ; ++bq) dst[bq].load(vp + 32 * W * bq);
-    };
-    vread(0, vc);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      if (r + 1 < 16) vread(r + 1, vn);
-#pragma unroll
-      for (int bq = 0; bq < NQ; ++bq)
-#pragma unroll
-        for (int bb = 0; bb < W; ++bb)
-          o[bq * W + bb] = __builtin_amdgcn_mfma_f32_32x32x2f32(vc[bq].v[bb], s[sb][r], o[bq * W + bb], 0, 0, 0);
-#pragma unroll
-      for (int bq = 0; bq < NQ; ++bq) vc[bq] = vn[bq];
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
+  const int64_t prow = d.row0 + w.orow;           // the packed row whose masks this lane draws (DROP)
 
   gload(Kh, a.ldk, 0, 0, false); swrite(Kimg, 0);
   gload(Kh, a.ldk, 0, 1, false); swrite(Kimg, 1);
@@ -207,12 +145,12 @@ __global__ __launch_bounds__(256, NB <= 4 ? 2 : 1) void as_stream_kernel(AsArgs 
 #pragma unroll
     for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) s[sb][r] = 0.f;
+      for (int r = 0; r < 16; ++r) S(sb)[r] = 0.f;
     gload(Vh, a.ldv, c, 0, true);                 // V(c) travels under the first product, half a tile at a time
-    if (live) s_groups(0);
+    if (live) as_first<NB, 0, 2 * NB>(Kimg, li, lh, qf, s0, s1);
     swrite(Vimg, 0);
     gload(Vh, a.ldv, c, 1, true);
-    if (live) s_groups(2 * NB);
+    if (live) as_first<NB, 2 * NB, 2 * NB>(Kimg, li, lh, qf, s0, s1);
     swrite(Vimg, 1);
     __syncthreads();                              // V(c) is visible; every wave is done with K(c)
     if (more) gload(Kh, a.ldk, c + 1, 0, false);  // K(c + 1) travels under the softmax and the second product
@@ -221,13 +159,13 @@ __global__ __launch_bounds__(256, NB <= 4 ? 2 : 1) void as_stream_kernel(AsArgs 
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) s[sb][r] = (c * AS_KT + 32 * sb + as_crow(r, lh) < T) ? s[sb][r] : -INFINITY;
+          for (int r = 0; r < 16; ++r) S(sb)[r] = (c * AS_KT + 32 * sb + as_crow(r, lh) < T) ? S(sb)[r] : -INFINITY;
       }
       float tm = -INFINITY;
 #pragma unroll
       for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) tm = fmaxf(tm, s[sb][r]);
+        for (int r = 0; r < 16; ++r) tm = fmaxf(tm, S(sb)[r]);
       tm = fmaxf(tm, __shfl_xor(tm, 32));
       const float mn = fmaxf(m, tm * a.scale);    // scale > 0: max_j (s_j scale) = (max_j s_j) scale, rounding is monotone
       const float f = expf(m - mn);
@@ -236,10 +174,10 @@ __global__ __launch_bounds__(256, NB <= 4 ? 2 : 1) void as_stream_kernel(AsArgs 
       for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float p = expf(__builtin_fmaf(s[sb][r], a.scale, -mn));
+          const float p = expf(__builtin_fmaf(S(sb)[r], a.scale, -mn));
           ps += p;
-          if (DROP) s[sb][r] = dropout_keep(a.seed, a.site, as_drop_idx(prow, a.heads, h, c * AS_KT + 32 * sb + as_crow(r, lh)), a.thr) ? p * a.keep_scale : 0.f;
-          else s[sb][r] = p;
+          if (DROP) S(sb)[r] = dropout_keep(a.seed, a.site, as_drop_idx(prow, a.heads, h, c * AS_KT + 32 * sb + as_crow(r, lh)), a.thr) ? p * a.keep_scale : 0.f;
+          else S(sb)[r] = p;
           if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
         }
       l = l * f + ps;
@@ -248,49 +186,28 @@ __global__ __launch_bounds__(256, NB <= 4 ? 2 : 1) void as_stream_kernel(AsArgs 
       for (int b = 0; b < NB; ++b)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[b][r] *= f;
-      pv_steps(0);
+      as_accum<NB>(Vimg, 0, li, lh, s0, o);
     }
     if (more) { swrite(Kimg, 0); gload(Kh, a.ldk, c + 1, 1, false); }
-    if (live) pv_steps(1);
+    if (live) as_accum<NB>(Vimg, 1, li, lh, s1, o);
     if (more) swrite(Kimg, 1);
   }
 
   if (!live) return;
   const float lt = l + __shfl_xor(l, 32);
-  const int q = q0 + li;
+  const int q = w.r0 + w.li;
   if (q >= T) return;
-  float* cp = a.ctx + (d.row0 + q) * (int64_t)a.ldc + hcol;
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int dd = (b % W) + W * as_crow(r, lh) + 32 * W * (b / W);
-      if (dd < dh) cp[dd] = o[b][r] / lt;
-    }
+  as_store_row<NB, true>(w, dh, a.ctx, a.ldc, o, lt);
   if (a.lse && lh == 0) a.lse[(d.row0 + q) * (int64_t)a.heads + h] = m + logf(lt);
   if (a.ml && lh == 0) a.ml[(d.row0 + q) * (int64_t)a.heads + h] = make_float2(m, lt);
 }
 
-std::atomic<uint64_t> g_as_attr[8];
+template <int NB> constexpr int AS_LDS = 2 * AsGeom<NB>::IMG * 4;
+}  // namespace
 
-template <int NB, bool DROP>
-int as_launch(const AsArgs& a, unsigned blocks, int inst, hipStream_t stream) {
-  constexpr int LDS = 2 * AS_KT * (32 * NB + 4) * 4;
-  if (LDS > 64 * 1024) {                          // once per device: more dynamic LDS than the default limit
-    int dev = 0;
-    SUMK_HIP(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(g_as_attr[inst].load(std::memory_order_acquire) & bit)) {
-      SUMK_HIP(hipFuncSetAttribute((const void*)as_stream_kernel<NB, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-      g_as_attr[inst].fetch_or(bit, std::memory_order_release);
-    }
-  }
-  hipLaunchKernelGGL((as_stream_kernel<NB, DROP>), dim3(blocks), dim3(256), LDS, stream, a);
-  return SUMK_OK;
-}
+size_t attn_stream_ws_bytes(int n_seq) { return align_up((size_t)n_seq * sizeof(AsSeq), 256); }
 
-// the batch's limits; *strips = query strips of all videos
-int as_check(int D, int heads, int n_seq, const int32_t* off, int64_t* strips) {
+int attn_stream_check(int D, int heads, int n_seq, const int32_t* off, int64_t* strips) {
   SUMK_ARG(D > 0 && heads > 0 && D % heads == 0, "attn_stream: D=%d is not a positive multiple of n_heads=%d", D, heads);
   const int dh = D / heads;
   SUMK_ARG(dh % 4 == 0 && dh <= AS_MAX_DH, "attn_stream: head width %d (D=%d, n_heads=%d) must be a multiple of 4, at most %d", dh, D, heads, AS_MAX_DH);
@@ -303,16 +220,8 @@ int as_check(int D, int heads, int n_seq, const int32_t* off, int64_t* strips) {
     n += (T + AS_QS - 1) / AS_QS;
   }
   SUMK_ARG(n * heads < ((int64_t)1 << 31), "attn_stream: %lld workgroups", (long long)(n * heads));
-  *strips = n;
+  if (strips) *strips = n;
   return SUMK_OK;
-}
-}  // namespace
-
-size_t attn_stream_ws_bytes(int n_seq) { return align_up((size_t)n_seq * sizeof(AsSeq), 256); }
-
-int attn_stream_check(int D, int heads, int n_seq, const int32_t* off) {
-  int64_t strips;
-  return as_check(D, heads, n_seq, off, &strips);
 }
 
 void attn_stream_setup(const int32_t* off_dev, int n_seq, void* ws, hipStream_t stream) {
@@ -325,11 +234,10 @@ static int as_run(const char* who, const float* Q, int ldq, const float* K, int 
                   uint32_t site, void* ws, int tag, hipStream_t stream) {
   SUMK_ARG(Q && K && V && ctx && off_dev && ws, "%s: null pointer", who);
   int64_t strips;
-  SUMK_TRY(as_check(D, heads, n_seq, off_host, &strips));
+  SUMK_TRY(attn_stream_check(D, heads, n_seq, off_host, &strips));
   SUMK_ARG(ldq >= D && ldk >= D && ldv >= D && ldc >= D, "%s: leading dimensions (%d, %d, %d, %d) must be at least D=%d", who, ldq, ldk, ldv, ldc, D);
   SUMK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldc % 4 == 0, "%s: leading dimensions (%d, %d, %d, %d) must be multiples of 4", who, ldq, ldk, ldv, ldc);
-  SUMK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)ctx) & 15) == 0, "%s: Q, K, V and ctx must be 16-byte aligned", who);
-  SUMK_ARG(scale > 0.f && scale < INFINITY, "%s: scale=%g must be positive and finite", who, (double)scale);
+  SUMK_TRY(as_check_operands(who, (uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)ctx, "Q, K, V and ctx", scale));
   AsArgs a;
   a.Q = Q; a.K = K; a.V = V; a.ctx = ctx; a.lse = lse; a.seq = (const AsSeq*)ws;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldc = ldc; a.dh = D / heads; a.heads = heads; a.n_seq = n_seq; a.scale = scale;
@@ -337,17 +245,9 @@ static int as_run(const char* who, const float* Q, int ldq, const float* K, int 
   attn_stream_setup(off_dev, n_seq, ws, stream);
   const unsigned blocks = (unsigned)(strips * heads);
   prof_begin(tag, stream);
-  if (dl.thr) {
-    if (a.dh <= 32) SUMK_TRY((as_launch<1, true>(a, blocks, 4, stream)));
-    else if (a.dh <= 64) SUMK_TRY((as_launch<2, true>(a, blocks, 5, stream)));
-    else if (a.dh <= 128) SUMK_TRY((as_launch<4, true>(a, blocks, 6, stream)));
-    else SUMK_TRY((as_launch<8, true>(a, blocks, 7, stream)));
-  } else {
-    if (a.dh <= 32) SUMK_TRY((as_launch<1, false>(a, blocks, 0, stream)));
-    else if (a.dh <= 64) SUMK_TRY((as_launch<2, false>(a, blocks, 1, stream)));
-    else if (a.dh <= 128) SUMK_TRY((as_launch<4, false>(a, blocks, 2, stream)));
-    else SUMK_TRY((as_launch<8, false>(a, blocks, 3, stream)));
-  }
+  SUMK_TRY(as_dispatch<8>(a.dh, dl.thr != 0, [&](auto nb, auto drop) {
+    return as_launch<as_stream_kernel<nb(), drop()>>(a, blocks, AS_LDS<nb()>, stream);
+  }));
   prof_end(tag, stream);
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;

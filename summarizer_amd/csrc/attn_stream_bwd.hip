@@ -32,9 +32,8 @@
 //   pass   owner X1, X2    walked Y1, Y2    accumulators
 //   dQ     Q, dctx         K, V             dQ^T += Y1^T dS^T
 //   dK/dV  K, V            Q, dctx          dK^T += Y1^T dS,  dV^T += Y2^T a~
-// Lane layout: attn_stream.hip's, for every product (v_mfma_f32_32x32x2_f32; lane = (li = lane & 31, lh = lane >> 5)).  Accumulator
-// register r of sub-tile sb holds, for OWNER row li, walked row 32 sb + as_crow(r, lh); accumulator block b register r is column
-// (b % W) + W as_crow(r, lh) + 32 W (b / W) of the owner row's output, W = min(NB, 4).
+// Lane layout, the products (as_first, as_accum), the strip prologue and the owner-row store: attn_stream_common.h, shared with the
+// forward.  This unit keeps its whole-tile double-image staging, the statistics in LDS and the formation of dS and a~.
 //
 // Walked rows past T are staged as zeros and their dS and a~ are set to 0 by a select in the video's last tile, so they contribute
 // exactly 0; owner rows past T are the video's last row (clamped) and never stored.  NaN: a select, never a multiply, applies the masks,
@@ -46,18 +45,16 @@
 // One wave per SIMD (__launch_bounds__(256, 1): 512 registers with the AGPRs).  By count at dh = 128: dQ pass 128 fragments + 64
 // accumulators + 64 S / dA + 64 staging = 320; dK / dV pass 128 + 128 + 64 + 64 = 384.
 // Compiler (hipcc -O3, gfx950) at dh = 128, VGPRs + AGPRs, spilled VGPRs (scratch bytes per lane), without / with dropout:
-//   asb_dq_kernel<4>   256 + 164, none                 / 256 + 179, none
-//   asb_dkv_kernel<4>  256 + 256, 59 (192 B)           / 256 + 256, 139 (512 B)
-// The dK / dV pass fills the register file and spills: scripts/asm_loop_audit.py counts 38 .. 48 scratch instructions in its tile loop
-// beside the loop's 512 MFMAs without dropout and 110 .. 161 with it (the hash's 64-bit temporaries); the dQ pass has none.  The smaller
+//   asb_dq_kernel<4>   256 + 163, none                 / 256 + 175, none
+//   asb_dkv_kernel<4>  256 + 256, 48 (148 B)           / 256 + 256, 134 (492 B)
+// The dK / dV pass fills the register file and spills: scripts/asm_loop_audit.py counts 18 .. 28 scratch instructions in its tile loop
+// beside the loop's 512 MFMAs without dropout and 105 .. 156 with it (the hash's 64-bit temporaries); the dQ pass has none.  The smaller
 // instances (NB = 1, 2) do not spill.  scripts/check_waterfalls.sh: 0.  Measured (scripts/attn_stream_train_timing.py, D = 1024, 8 heads,
 // dropout 0.1): at T = 8192 the dQ pass takes 3.97 ms (6 T^2 D FLOP: 101 TFLOP/s) and the dK / dV pass 6.00 ms (8 T^2 D: 89 TFLOP/s).
 // Tried at the compiler only, not run: both images double-buffered in the LDS that one workgroup per CU leaves free (134 KiB), staged
 // half a tile at a time, one barrier per tile.  By count it frees 32 registers; the compiler then moves more fragment reads across the
 // missing barrier and spills 117 (303 with dropout) in the dK / dV pass, so the single-buffered form above stayed.
 #include "attn_stream_common.h"
-#include <math.h>
-#include <atomic>
 
 namespace sumk {
 
@@ -89,29 +86,20 @@ __global__ __launch_bounds__(256) void asb_delta_kernel(const float* __restrict_
 
 template <int NB, bool DKV, bool DROP>
 __device__ __forceinline__ void asb_pass(const AsbArgs& a, float* lds) {
-  constexpr int DP = 32 * NB, P = DP + 4;        // staged columns; LDS pitch (conflict-free ds_read_b128 of both uses of an image)
-  constexpr int C4 = DP / 4, NST = 2 * NB;       // float4 columns of a tile row; float4 per thread and image (64 C4 / 256)
-  constexpr int W = NB < 4 ? NB : 4, NQ = NB / W;
-  const int blk = blockIdx.x;
-  const int h = blk % a.heads, sg = blk / a.heads;
-  int lo = 0, hi = a.n_seq - 1;
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (a.seq[mid].strip0 <= sg) lo = mid; else hi = mid - 1; }
-  const AsSeq d = a.seq[lo];
-  const int T = d.T, dh = a.dh;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 31, lh = lane >> 5;
-  const int r0 = (sg - d.strip0) * AS_QS + wave * 32;           // this wave's first owner row inside the video
-  const bool live = r0 < T;                                     // wave-uniform: a wave past the video only stages
-  const int orow = min(r0 + li, T - 1);                         // this lane's owner row (clamped: such rows are never stored)
-  const int64_t hcol = (int64_t)h * dh;
-  const float* Y1h = a.Y1 + d.row0 * (int64_t)a.ldy1 + hcol;
-  const float* Y2h = a.Y2 + d.row0 * (int64_t)a.ldy2 + hcol;
+  using G = AsGeom<NB>;
+  constexpr int P = G::P, C4 = G::C4, NST = 2 * NB;   // NST: float4 per thread and image (64 C4 / 256)
+  const AsStrip w = as_strip(a.seq, a.n_seq, a.heads, a.dh);
+  const AsSeq d = w.d;
+  const int T = d.T, dh = a.dh, h = w.h, li = w.li, lh = w.lh, r0 = w.r0, orow = w.orow, tid = threadIdx.x;
+  const bool live = w.live;
+  const float* Y1h = a.Y1 + d.row0 * (int64_t)a.ldy1 + w.hcol;
+  const float* Y2h = a.Y2 + d.row0 * (int64_t)a.ldy2 + w.hcol;
 
   // owner fragments: group g, MFMA j -> X[owner row][8 g + 4 lh + j]
   float xf1[4 * NB][4], xf2[4 * NB][4];
   {
-    const float* p1 = a.X1 + (d.row0 + orow) * (int64_t)a.ldx1 + hcol;
-    const float* p2 = a.X2 + (d.row0 + orow) * (int64_t)a.ldx2 + hcol;
+    const float* p1 = a.X1 + (d.row0 + orow) * (int64_t)a.ldx1 + w.hcol;
+    const float* p2 = a.X2 + (d.row0 + orow) * (int64_t)a.ldx2 + w.hcol;
 #pragma unroll
     for (int g = 0; g < 4 * NB; ++g) {
       const int dc = 8 * g + 4 * lh;
@@ -130,8 +118,8 @@ __device__ __forceinline__ void asb_pass(const AsbArgs& a, float* lds) {
   }
 
   float* img1 = lds;
-  float* img2 = lds + AS_KT * P;
-  float* sst = lds + 2 * AS_KT * P;               // dK / dV pass: m, 1 / l, delta of the tile's 64 queries
+  float* img2 = lds + G::IMG;
+  float* sst = lds + 2 * G::IMG;                  // dK / dV pass: m, 1 / l, delta of the tile's 64 queries
   // staging of one 64-row tile of both walked matrices: thread -> NST float4 per image (row = idx / C4, float4 column = idx % C4,
   // idx = tid + 256 i); rows past T and columns past dh are zeros
   float4 st1[NST], st2[NST];
@@ -179,54 +167,6 @@ __device__ __forceinline__ void asb_pass(const AsbArgs& a, float* lds) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) o2[b][r] = 0.f;
 
-  // acc^T += img (A) x frag^T (B) over all 4 NB groups; the image fragments of group g + 1 are read under the MFMAs of group g
-  auto first = [&](const float* img, const float (&xf)[4 * NB][4], f32x16 (&acc)[2]) {
-    float4 kf[2], kn[2];
-    auto kread = [&](int g, float4 (&dst)[2]) {
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) dst[sb] = *reinterpret_cast<const float4*>(img + (32 * sb + li) * P + 8 * g + 4 * lh);
-    };
-    kread(0, kf);
-#pragma unroll
-    for (int g = 0; g < 4 * NB; ++g) {            // every group: the columns past dh are zeros in both operands
-      if (g + 1 < 4 * NB) kread(g + 1, kn);
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) {
-        acc[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].x, xf[g][0], acc[sb], 0, 0, 0);
-        acc[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].y, xf[g][1], acc[sb], 0, 0, 0);
-        acc[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].z, xf[g][2], acc[sb], 0, 0, 0);
-        acc[sb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sb].w, xf[g][3], acc[sb], 0, 0, 0);
-      }
-      kf[0] = kn[0]; kf[1] = kn[1];
-      __builtin_amdgcn_sched_barrier(0);          // keep the compiler from hoisting every group's reads (register budget)
-    }
-  };
-  // out^T += img^T w^T over the 16 steps of both sub-tiles; the image fragments of step r + 1 are read under the MFMAs of step r
-  auto accum = [&](const float* img, const f32x16 (&w)[2], f32x16* out) {
-#pragma unroll
-    for (int sb = 0; sb < 2; ++sb) {
-      AsVec<W> vc[NQ], vn[NQ];
-      auto vread = [&](int r, AsVec<W> (&dst)[NQ]) {
-        const float* vp = img + (32 * sb + as_crow(r, lh)) * P + W * li;
-#pragma unroll
-        for (int bq = 0; bq < NQ; ++bq) dst[bq].load(vp + 32 * W * bq);
-      };
-      vread(0, vc);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (r + 1 < 16) vread(r + 1, vn);
-#pragma unroll
-        for (int bq = 0; bq < NQ; ++bq)
-#pragma unroll
-          for (int bb = 0; bb < W; ++bb)
-            out[bq * W + bb] = __builtin_amdgcn_mfma_f32_32x32x2f32(vc[bq].v[bb], w[sb][r], out[bq * W + bb], 0, 0, 0);
-#pragma unroll
-        for (int bq = 0; bq < NQ; ++bq) vc[bq] = vn[bq];
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  };
-
   gload(0);
   for (int c = 0; c < nt; ++c) {
     __syncthreads();                              // every wave is done with tile c - 1
@@ -238,8 +178,8 @@ __device__ __forceinline__ void asb_pass(const AsbArgs& a, float* lds) {
     for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) { s[sb][r] = 0.f; da[sb][r] = 0.f; }
-    first(img1, xf1, s);
-    first(img2, xf2, da);
+    as_first<NB, 0, 4 * NB>(img1, li, lh, xf1, s[0], s[1]);
+    as_first<NB, 0, 4 * NB>(img2, li, lh, xf2, da[0], da[1]);
     const bool partial = (c + 1) * AS_KT > T;     // the video's last tile: walked rows past T contribute exactly 0
 #pragma unroll
     for (int sb = 0; sb < 2; ++sb)
@@ -261,31 +201,17 @@ __device__ __forceinline__ void asb_pass(const AsbArgs& a, float* lds) {
         da[sb][r] = ds; s[sb][r] = at;
         if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
       }
-    accum(img1, da, o1);
-    if (DKV) accum(img2, s, o2);
+    as_accum<NB>(img1, 0, li, lh, da[0], o1);
+    as_accum<NB>(img1, 1, li, lh, da[1], o1);
+    if (DKV) {
+      as_accum<NB>(img2, 0, li, lh, s[0], o2);
+      as_accum<NB>(img2, 1, li, lh, s[1], o2);
+    }
   }
 
-  if (!live) return;
-  const int q = r0 + li;
-  if (q >= T) return;
-  float* p1 = a.O1 + (d.row0 + q) * (int64_t)a.ldo1 + hcol;
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int dd = (b % W) + W * as_crow(r, lh) + 32 * W * (b / W);
-      if (dd < dh) p1[dd] = o1[b][r];
-    }
-  if (DKV) {
-    float* p2 = a.O2 + (d.row0 + q) * (int64_t)a.ldo2 + hcol;
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int dd = (b % W) + W * as_crow(r, lh) + 32 * W * (b / W);
-        if (dd < dh) p2[dd] = o2[b][r];
-      }
-  }
+  if (!live || r0 + li >= T) return;
+  as_store_row<NB>(w, dh, a.O1, a.ldo1, o1);
+  if constexpr (DKV) as_store_row<NB>(w, dh, a.O2, a.ldo2, o2);
 }
 
 template <int NB, bool DROP>
@@ -299,44 +225,13 @@ __global__ __launch_bounds__(256, 1) void asb_dkv_kernel(AsbArgs a) {
   asb_pass<NB, true, DROP>(a, asb_lds);
 }
 
-std::atomic<uint64_t> g_asb_attr[12];
-
-template <int NB, bool DKV, bool DROP>
-int asb_launch(const AsbArgs& a, unsigned blocks, hipStream_t stream) {
-  constexpr int LDS = (2 * AS_KT * (32 * NB + 4) + 3 * AS_KT) * 4;
-  const void* fn = DKV ? (const void*)asb_dkv_kernel<NB, DROP> : (const void*)asb_dq_kernel<NB, DROP>;
-  if (LDS > 64 * 1024) {                          // once per device: more dynamic LDS than the default limit
-    constexpr int inst = (NB == 1 ? 0 : NB == 2 ? 1 : 2) * 4 + (DKV ? 2 : 0) + (DROP ? 1 : 0);
-    int dev = 0;
-    SUMK_HIP(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(g_asb_attr[inst].load(std::memory_order_acquire) & bit)) {
-      SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-      g_asb_attr[inst].fetch_or(bit, std::memory_order_release);
-    }
-  }
-  if (DKV) hipLaunchKernelGGL((asb_dkv_kernel<NB, DROP>), dim3(blocks), dim3(256), LDS, stream, a);
-  else hipLaunchKernelGGL((asb_dq_kernel<NB, DROP>), dim3(blocks), dim3(256), LDS, stream, a);
-  return SUMK_OK;
-}
-
-template <bool DKV>
-int asb_dispatch(const AsbArgs& a, unsigned blocks, hipStream_t stream) {
-  if (a.thr) {
-    if (a.dh <= 32) return asb_launch<1, DKV, true>(a, blocks, stream);
-    if (a.dh <= 64) return asb_launch<2, DKV, true>(a, blocks, stream);
-    return asb_launch<4, DKV, true>(a, blocks, stream);
-  }
-  if (a.dh <= 32) return asb_launch<1, DKV, false>(a, blocks, stream);
-  if (a.dh <= 64) return asb_launch<2, DKV, false>(a, blocks, stream);
-  return asb_launch<4, DKV, false>(a, blocks, stream);
-}
+template <int NB> constexpr int ASB_LDS = (2 * AsGeom<NB>::IMG + 3 * AS_KT) * 4;
 
 constexpr int ASB_MAX_DH = 128;
 }  // namespace
 
-int attn_stream_bwd_check(int D, int heads, int n_seq, const int32_t* off) {
-  SUMK_TRY(attn_stream_check(D, heads, n_seq, off));
+int attn_stream_bwd_check(int D, int heads, int n_seq, const int32_t* off, int64_t* strips) {
+  SUMK_TRY(attn_stream_check(D, heads, n_seq, off, strips));
   const int dh = D / heads;
   SUMK_ARG(dh <= ASB_MAX_DH, "attn_stream_backward: head width %d (D=%d, n_heads=%d) must be at most %d", dh, D, heads, ASB_MAX_DH);
   return SUMK_OK;
@@ -351,19 +246,17 @@ int launch_attn_stream_bwd(const float* Q, int ldq, const float* K, int ldk, con
                            const int32_t* off_dev, float scale, Drop dl, uint32_t site, float* dQ, int lddq, float* dK, int lddk, float* dV,
                            int lddv, void* ws, hipStream_t stream) {
   SUMK_ARG(Q && K && V && ctx && dctx && stats && dQ && dK && dV && off_dev && ws, "attn_stream_backward: null pointer");
-  SUMK_TRY(attn_stream_bwd_check(D, heads, n_seq, off_host));
+  int64_t strips;
+  SUMK_TRY(attn_stream_bwd_check(D, heads, n_seq, off_host, &strips));
   const int lds[8] = {ldq, ldk, ldv, ldc, ldd, lddq, lddk, lddv};
   for (int i = 0; i < 8; ++i) {
     SUMK_ARG(lds[i] >= D, "attn_stream_backward: leading dimension %d (argument %d of 8) must be at least D=%d", lds[i], i, D);
     SUMK_ARG(lds[i] % 4 == 0, "attn_stream_backward: leading dimension %d (argument %d of 8) must be a multiple of 4", lds[i], i);
   }
-  SUMK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)ctx | (uintptr_t)dctx | (uintptr_t)dQ | (uintptr_t)dK | (uintptr_t)dV) & 15) == 0,
-           "attn_stream_backward: Q, K, V, ctx, dctx, dQ, dK and dV must be 16-byte aligned");
   SUMK_ARG(((uintptr_t)stats & 7) == 0, "attn_stream_backward: stats must be 8-byte aligned");
-  SUMK_ARG(scale > 0.f && scale < INFINITY, "attn_stream_backward: scale=%g must be positive and finite", (double)scale);
+  SUMK_TRY(as_check_operands("attn_stream_backward", (uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)ctx | (uintptr_t)dctx | (uintptr_t)dQ | (uintptr_t)dK | (uintptr_t)dV,
+                             "Q, K, V, ctx, dctx, dQ, dK and dV", scale));
   SUMK_ARG(!dl.seed_dev, "attn_stream_backward: no device seed word");
-  int64_t strips = 0;
-  for (int s = 0; s < n_seq; ++s) strips += (off_host[s + 1] - off_host[s] + AS_QS - 1) / AS_QS;
   const int64_t n_rows = off_host[n_seq], nrh = n_rows * heads;
   float* delta = (float*)((char*)ws + attn_stream_ws_bytes(n_seq));
   attn_stream_setup(off_dev, n_seq, ws, stream);
@@ -378,12 +271,16 @@ int launch_attn_stream_bwd(const float* Q, int ldq, const float* K, int ldk, con
   a.X1 = Q; a.ldx1 = ldq; a.X2 = dctx; a.ldx2 = ldd; a.Y1 = K; a.ldy1 = ldk; a.Y2 = V; a.ldy2 = ldv;
   a.O1 = dQ; a.ldo1 = lddq; a.O2 = nullptr; a.ldo2 = 0;
   prof_begin(SUMK_PROF_ATTN_STREAM_BWD_DQ, stream);
-  SUMK_TRY(asb_dispatch<false>(a, blocks, stream));
+  SUMK_TRY(as_dispatch<4>(a.dh, a.thr != 0, [&](auto nb, auto drop) {
+    return as_launch<asb_dq_kernel<nb(), drop()>>(a, blocks, ASB_LDS<nb()>, stream);
+  }));
   prof_end(SUMK_PROF_ATTN_STREAM_BWD_DQ, stream);
   a.X1 = K; a.ldx1 = ldk; a.X2 = V; a.ldx2 = ldv; a.Y1 = Q; a.ldy1 = ldq; a.Y2 = dctx; a.ldy2 = ldd;
   a.O1 = dK; a.ldo1 = lddk; a.O2 = dV; a.ldo2 = lddv;
   prof_begin(SUMK_PROF_ATTN_STREAM_BWD_DKV, stream);
-  SUMK_TRY(asb_dispatch<true>(a, blocks, stream));
+  SUMK_TRY(as_dispatch<4>(a.dh, a.thr != 0, [&](auto nb, auto drop) {
+    return as_launch<asb_dkv_kernel<nb(), drop()>>(a, blocks, ASB_LDS<nb()>, stream);
+  }));
   prof_end(SUMK_PROF_ATTN_STREAM_BWD_DKV, stream);
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;

@@ -137,7 +137,7 @@ extern "C" int sumk_eval_device_kendall(const float* scores_dev, const sumk_eval
   if (n_videos == 0) return SUMK_OK;
   SUMK_ARG(scores_dev && videos_dev && kendall_dev && scratch_dev && corr_dev, "eval_device_kendall: null pointer");
   SUMK_ARG(n_videos <= 65535, "eval_device_kendall: n_videos=%d (at most 65535 per call)", n_videos);
-  SUMK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_kendall_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KD_LDS_BYTES));
+  SUMK_TRY(lds_opt_in<eval_kendall_kernel>((int)KD_LDS_BYTES));
   hipLaunchKernelGGL(eval_kendall_kernel, dim3(ED_MAX_USERS, n_videos), dim3(KD_THREADS), KD_LDS_BYTES, (hipStream_t)stream, scores_dev, videos_dev,
                      kendall_dev, (double*)scratch_dev, counts_dev);
   hipLaunchKernelGGL(eval_kendall_final_kernel, dim3((n_videos + 63) / 64), dim3(64), 0, (hipStream_t)stream, videos_dev, (const double*)scratch_dev,

@@ -22,7 +22,6 @@
 // MFMA TRANSPOSED (B rows on the M axis): a lane then owns ONE output row and 4 consecutive columns per register quad, which is
 // exactly an 8-byte piece of a KB-plane chunk -- the result is split into planes in registers and leaves as 512-byte contiguous runs.
 #include "pw_common.h"
-#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -332,19 +331,10 @@ __global__ __launch_bounds__(512) void gemm_pw_kernel(PwArgs a) {
   }
 }
 
-std::atomic<uint64_t> g_attr_done[64];      // per kernel instance (index below): bit d = device d has the dynamic-LDS opt-in
-
 template <int NP, int BM, int EPI, int NS, int VAR>
-int launch_one(const PwArgs& a, int inst, hipStream_t s) {
+int launch_one(const PwArgs& a, hipStream_t s) {
   constexpr int LDS = NS * (2 * NP * (BM + 256) * 16) + PW_CONST_BYTES;
-  const void* fn = (const void*)gemm_pw_kernel<NP, BM, EPI, NS, VAR>;
-  int dev = 0;
-  SUMK_HIP(hipGetDevice(&dev));
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(g_attr_done[inst].load(std::memory_order_acquire) & bit)) {
-    SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    g_attr_done[inst].fetch_or(bit, std::memory_order_release);
-  }
+  SUMK_TRY((lds_opt_in<gemm_pw_kernel<NP, BM, EPI, NS, VAR>>(LDS)));
   const int grid = a.xcd_map ? 256 : std::min(a.total_tiles, 256);
   hipLaunchKernelGGL((gemm_pw_kernel<NP, BM, EPI, NS, VAR>), dim3(grid), dim3(512), LDS, s, a);
   SUMK_HIP(hipGetLastError());
@@ -353,18 +343,17 @@ int launch_one(const PwArgs& a, int inst, hipStream_t s) {
 
 template <int NP, int NS>
 int launch_np(PwEpi epi, const PwArgs& a, int variant, hipStream_t s) {
-  constexpr int base = NP == 3 ? 0 : 16;
   switch (epi) {
     case PW_F32:
       switch (variant) {
-        case 10: return launch_one<NP, 192, PW_F32, NS, 0>(a, base + 4, s);      // (probe: waves 0-3 issue their DMA early)
-        case 1: return launch_one<NP, 192, PW_F32, NS, 1>(a, base + 5, s);
-        default: return launch_one<NP, 192, PW_F32, NS, 2>(a, base + 0, s);
+        case 10: return launch_one<NP, 192, PW_F32, NS, 0>(a, s);      // (probe: waves 0-3 issue their DMA early)
+        case 1: return launch_one<NP, 192, PW_F32, NS, 1>(a, s);
+        default: return launch_one<NP, 192, PW_F32, NS, 2>(a, s);
       }
-    case PW_PLANES: return launch_one<NP, 192, PW_PLANES, NS, 2>(a, base + 1, s);
-    case PW_RES_MOM_PLANES: return launch_one<NP, 192, PW_RES_MOM_PLANES, NS, 2>(a, base + 2, s);
-    case PW_HEAD: return launch_one<NP, 192, PW_HEAD, NS, 2>(a, base + 3, s);
-    case PW_RES_F32: return launch_one<NP, 192, PW_RES_F32, NS, 2>(a, base + 7, s);
+    case PW_PLANES: return launch_one<NP, 192, PW_PLANES, NS, 2>(a, s);
+    case PW_RES_MOM_PLANES: return launch_one<NP, 192, PW_RES_MOM_PLANES, NS, 2>(a, s);
+    case PW_HEAD: return launch_one<NP, 192, PW_HEAD, NS, 2>(a, s);
+    case PW_RES_F32: return launch_one<NP, 192, PW_RES_F32, NS, 2>(a, s);
   }
   set_error("gemm_pw: bad epilogue %d", (int)epi);
   return SUMK_ERR_ARG;

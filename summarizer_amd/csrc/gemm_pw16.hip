@@ -10,7 +10,6 @@
 // Accumulation order: a term is summed over 32 k before the next term starts -- results agree with the 32x32x16 / in-loop kernels to rounding (tested
 // against float64 and against them), not bit for bit.  Epilogues as gemm_pw.hip (PwEpi); C/D map of the shape: col = lane & 15, row = 4 (lane >> 4) + reg.
 #include "pw_common.h"
-#include <atomic>
 
 namespace sumk {
 
@@ -284,18 +283,10 @@ __global__ __launch_bounds__(512) void gemm_pw16_kernel(PwArgs a) {
   }
 }
 
-std::atomic<uint64_t> g_attr16[5];
-
 template <int EPI>
 int launch16(const PwArgs& a, hipStream_t stream) {
   constexpr int LDS = 5 * (4 * (192 + 256) * 16) + PW_CONST_BYTES;
-  int dev = 0;
-  SUMK_HIP(hipGetDevice(&dev));
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(g_attr16[EPI].load(std::memory_order_acquire) & bit)) {
-    SUMK_HIP(hipFuncSetAttribute((const void*)gemm_pw16_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    g_attr16[EPI].fetch_or(bit, std::memory_order_release);
-  }
+  SUMK_TRY(lds_opt_in<gemm_pw16_kernel<EPI>>(LDS));
   hipLaunchKernelGGL(gemm_pw16_kernel<EPI>, dim3(a.xcd_map ? 256 : std::min(a.total_tiles, 256)), dim3(512), LDS, stream, a);
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;

@@ -540,9 +540,9 @@ extern "C" int sumk_bigru_layer_forward(const float* x, int32_t In, int32_t H, i
   pa.upm = std::min(8, (H + 31) / 32); pa.n_active = (H + pa.upm - 1) / pa.upm;
   pa.ll = (unsigned long long*)(ws + L.ll); pa.ll_bytes = (int32_t)L.ll_bytes;
   const bool m16 = L.gsize <= 16;
-  const void* fn = m16 ? (const void*)gru_persist_kernel<true> : (const void*)gru_persist_kernel<false>;
   prof_begin(SUMK_PROF_LSTM_REC, stream);
-  SUMK_TRY(persist_launch(fn, &pa, 96 * 1024, stream));   // 33 KB used; > 80 KB keeps one block per CU
+  // 33 KB used; > 80 KB keeps one block per CU
+  SUMK_TRY(m16 ? persist_launch<gru_persist_kernel<true>>(&pa, 96 * 1024, stream) : persist_launch<gru_persist_kernel<false>>(&pa, 96 * 1024, stream));
   prof_end(SUMK_PROF_LSTM_REC, stream);
   return SUMK_OK;
 }
@@ -582,8 +582,8 @@ extern "C" int sumk_bigru_layer_backward(const float* x, const float* h_out, con
     const bool shard = pk_items_shard(pa.n_items);
     pa.item_words = shard ? PSTATE_ITEM_WORDS : 1; pa.n_shards = shard ? 4 : 1;
     const bool m16 = L.gsize <= 16;
-    const void* fn = m16 ? (const void*)gru_persist_bwd_kernel<true> : (const void*)gru_persist_bwd_kernel<false>;
-    SUMK_TRY(persist_launch(fn, &pa, 96 * 1024, stream));   // 24 x 260 + 32 x 36 floats + tables = 30 KB used; > 80 KB keeps one block per CU
+    // 24 x 260 + 32 x 36 floats + tables = 30 KB used; > 80 KB keeps one block per CU
+    SUMK_TRY(m16 ? persist_launch<gru_persist_bwd_kernel<true>>(&pa, 96 * 1024, stream) : persist_launch<gru_persist_bwd_kernel<false>>(&pa, 96 * 1024, stream));
   }
   // weight gradients: dW_ih[d] += dGx_d^T X (both directions in one split-K launch); dW_hh[d] += dGh_d^T h_prev_d with
   // dGh_d = [dr | dz] of dGx_d (rows 0 .. 2H of W_hh) and the stored n block (rows 2H .. 3H)

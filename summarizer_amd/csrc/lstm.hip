@@ -1853,10 +1853,9 @@ static int fwd_persist(const LstmWs& L, char* ws, const LstmFwdIo& io, hipStream
   const size_t shmem = std::max<size_t>(((size_t)L.gsize * (H + 4) + 8 * 32 * 32 + 96) * sizeof(float), 96 * 1024);  // >80 KB: one block per CU
   const bool ll = sw.ll && L.ll_ok;
   const bool m16 = ll && sw.m16 && L.gsize <= 16;
-  const void* fn = m16 ? (const void*)lstm_persist_kernel<true, true>
-                 : ll  ? (const void*)lstm_persist_kernel<true>
-                       : (const void*)lstm_persist_kernel<>;
-  return persist_launch(fn, &pa, shmem, stream);
+  return m16 ? persist_launch<lstm_persist_kernel<true, true>>(&pa, shmem, stream)
+       : ll  ? persist_launch<lstm_persist_kernel<true>>(&pa, shmem, stream)
+             : persist_launch<lstm_persist_kernel<>>(&pa, shmem, stream);
 }
 
 // LSTM_WIDE.  The recurrent product follows the layer's arithmetic: exact fp32 MFMA, bf16x3 (hi / lo) or the fp32-grade bf16x6 (three
@@ -1873,9 +1872,10 @@ static int fwd_wide(const LstmWs& L, char* ws, const LstmFwdIo& io, int precisio
   w2.upm = (H + 127) / 128; w2.n_active = (H + w2.upm - 1) / w2.upm;     // <= 8 units per member, <= 128 members per team
   w2.pack16 = (w2.upm == 8 && w2.n_active * 8 == H) ? 1 : 0;
   const int mode = precision == SUMK_PRECISION_BF16X3 ? 1 : (precision == SUMK_PRECISION_BF16X6 && !L.training) ? 2 : 0;
-  const void* fn = mode == 2 ? (const void*)lstm_wide2_kernel<2> : mode == 1 ? (const void*)lstm_wide2_kernel<1> : (const void*)lstm_wide2_kernel<0>;
   const size_t shmem = mode == 2 ? (size_t)(64 + 1 + 64) * 1024 : (size_t)96 * 1024;   // 65 KB (+ 64 KB of W_hh plane 3); > 80 KB keeps one block per CU
-  return persist_launch(fn, &w2, shmem, stream);
+  return mode == 2 ? persist_launch<lstm_wide2_kernel<2>>(&w2, shmem, stream)
+       : mode == 1 ? persist_launch<lstm_wide2_kernel<1>>(&w2, shmem, stream)
+                   : persist_launch<lstm_wide2_kernel<0>>(&w2, shmem, stream);
 }
 
 // LSTM_STEPS, one or two directions: one lstm_step_kernel per time step over every (sequence, direction) still running
@@ -2002,7 +2002,7 @@ static int bwd_persist(const LstmWs& L, char* ws, const LstmBwdIo& io, hipStream
   pa.coal = (sw.bwd_r6 && pa.upm == 8 && pa.n_active * 8 == H) ? 1 : 0;
   const size_t shmem = std::max<size_t>(((size_t)32 * (H + 4) + 32 * 36 + 96) * sizeof(float), 96 * 1024);  // >80 KB: one block per CU
   const bool m16 = sw.m16 && L.gsize <= 16;
-  return persist_launch(m16 ? (const void*)lstm_persist_bwd_kernel<true> : (const void*)lstm_persist_bwd_kernel<false>, &pa, shmem, stream);
+  return m16 ? persist_launch<lstm_persist_bwd_kernel<true>>(&pa, shmem, stream) : persist_launch<lstm_persist_bwd_kernel<false>>(&pa, shmem, stream);
 }
 
 // LSTM_WIDE
@@ -2018,7 +2018,7 @@ static int bwd_wide(const LstmWs& L, char* ws, const LstmBwdIo& io, hipStream_t 
   // round 6: sharded step counter while the items fit the state block (SUMK_LSTM_BWD_R6=0: one word per item, as round 5)
   const bool shard = lstm_switches().bwd_r6 && pk_items_shard(2 * wa.n_groups);
   wa.item_words = shard ? PSTATE_ITEM_WORDS : 1; wa.n_shards = shard ? 4 : 1;
-  return persist_launch((const void*)lstm_wide_bwd_kernel, &wa, 96 * 1024, stream);   // 35 KB used; > 80 KB keeps one block per CU
+  return persist_launch<lstm_wide_bwd_kernel>(&wa, 96 * 1024, stream);   // 35 KB used; > 80 KB keeps one block per CU
 }
 
 // the extra pass t = -1 writes dh0 / dc0

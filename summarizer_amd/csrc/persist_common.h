@@ -81,18 +81,12 @@ inline int workspace_fits(const char* who, size_t have, size_t need, const char*
 }
 
 // Cooperative launch of one persistent kernel instance over the chip: 256 blocks of PK_THREADS, `shmem` bytes of dynamic LDS (callers ask
-// for > 80 KB to keep one block per CU).  The instance's dynamic-LDS ceiling is raised the first time it is launched.
-inline int persist_launch(const void* fn, void* args, size_t shmem, hipStream_t stream) {
-  static const void* raised[16];
-  static int n_raised = 0;
-  bool seen = false;
-  for (int i = 0; i < n_raised; ++i) seen |= raised[i] == fn;
-  if (!seen) {
-    SUMK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (n_raised < 16) raised[n_raised++] = fn;
-  }
+// for > 80 KB to keep one block per CU).  The instance's dynamic-LDS ceiling is raised the first time it is launched on a device.
+template <auto Kernel>
+int persist_launch(void* args, size_t shmem, hipStream_t stream) {
+  SUMK_TRY(lds_opt_in<Kernel>(160 * 1024));
   void* kargs[] = {args};
-  SUMK_HIP(hipLaunchCooperativeKernel(fn, dim3(PK_TEAMS * 32), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
+  SUMK_HIP(hipLaunchCooperativeKernel((const void*)Kernel, dim3(PK_TEAMS * 32), dim3(PK_THREADS), kargs, (unsigned)shmem, stream));
   return SUMK_OK;
 }
 

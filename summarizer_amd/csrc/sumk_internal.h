@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <atomic>
 #include "../../include/sumk.h"
 
 namespace sumk {
@@ -23,6 +24,22 @@ int hip_fail(hipError_t e, const char* what);
   do { int _r = (call); if (_r != SUMK_OK) return _r; } while (0)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Raises Kernel's dynamic-LDS ceiling to `bytes` (the one size that instance is launched with) the first time it is about to be launched
+// on the current device.  The opt-in is a per-DEVICE attribute -- a process that drives a second GPU must not skip it there -- so the
+// record is one bit per device, set atomically, in a static of this instantiation: keyed by the kernel itself, no table to index.
+template <auto Kernel>
+int lds_opt_in(int bytes) {
+  static std::atomic<uint64_t> done{0};
+  int dev = 0;
+  SUMK_HIP(hipGetDevice(&dev));
+  const uint64_t bit = 1ull << (dev & 63);
+  if (!(done.load(std::memory_order_acquire) & bit)) {
+    SUMK_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done.fetch_or(bit, std::memory_order_release);
+  }
+  return SUMK_OK;
+}
 
 // Environment switches the library reads: the A/B switches that have a test comparing both settings (SUMK_SK, SUMK_LEAN,
 // SUMK_FUSED_HEAD, SUMK_FUSED_LN, SUMK_BF16_SRC, SUMK_B16_WIDE, SUMK_ATTN_FUSED, SUMK_ATTN_WIDE, SUMK_ATTN_NT, SUMK_PW_LONG,
@@ -333,9 +350,10 @@ int launch_attn_pw_context(int np, const void* qkv_planes, int64_t rows, int D, 
 
 // Multi-head attention without the logits (attn_stream.hip): ctx[rows of v, h dh ..] = softmax(scale Q_h K_h^T) V_h per (video, head) in exact
 // fp32, head h at column h * (D / heads) of Q, K, V and ctx; lse (may be null): (rows, heads).  ws: attn_stream_ws_bytes(n_seq) bytes.
-// attn_stream_check: the batch's limits (dh % 4 == 0, dh <= 256, 1 <= T < 2^20, at most 65 535 videos), SUMK_ERR_ARG past them.
+// attn_stream_check: the batch's limits (dh % 4 == 0, dh <= 256, 1 <= T < 2^20, at most 65 535 videos), SUMK_ERR_ARG past them; *strips
+// (may be null): the strips of 128 rows of all videos -- workgroups per head of the forward's launch and of each pass of the backward.
 size_t attn_stream_ws_bytes(int n_seq);
-int attn_stream_check(int D, int heads, int n_seq, const int32_t* off_host);
+int attn_stream_check(int D, int heads, int n_seq, const int32_t* off_host, int64_t* strips = nullptr);
 int launch_attn_stream(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
                        const int32_t* off_host, const int32_t* off_dev, float scale, float* ctx, int ldc, float* lse, void* ws,
                        hipStream_t stream);
@@ -348,7 +366,7 @@ int launch_attn_stream_train(const float* Q, int ldq, const float* K, int ldk, c
 // Its backward (attn_stream_bwd.hip), head widths up to 128 (attn_stream_bwd_check): dQ, dK, dV from Q, K, V, ctx, dctx and stats, the
 // weights recomputed per tile and the masks regenerated in registers.  ws: attn_stream_bwd_ws_bytes(heads, n_seq, n_rows) bytes.
 size_t attn_stream_bwd_ws_bytes(int heads, int n_seq, int64_t n_rows);
-int attn_stream_bwd_check(int D, int heads, int n_seq, const int32_t* off_host);
+int attn_stream_bwd_check(int D, int heads, int n_seq, const int32_t* off_host, int64_t* strips = nullptr);
 int launch_attn_stream_bwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* ctx, int ldc,
                            const float* dctx, int ldd, const float* stats, int D, int heads, int n_seq, const int32_t* off_host,
                            const int32_t* off_dev, float scale, Drop dl, uint32_t site, float* dQ, int lddq, float* dK, int lddk, float* dV,

@@ -163,6 +163,22 @@ def test_training_forward(dev):
         assert np.abs(ctx[:, :T][keep] - want).max() <= 4 * np.spacing(np.float32(want)) and not ctx[:, T:].any()
 
 
+def test_training_forward_head_width_256_with_dropout(dev):
+    """The one training-forward instance no other test launches: head width 256 (as_stream_kernel<8, true>, 130 KiB of dynamic LDS, which the
+    backward refuses).  ctx against the float64 specification by the family's rule: yardstick |float32 spec - float64 spec|, limit 4.  T = 129 and
+    65: two strips, a partial last tile, waves past the video, a second video behind the first."""
+    from summarizer_amd import kernels
+    c = cases.with_grad(cases.fwd.case("fwd256", (129, 65), 256, 1, 23), 0.1)
+    s64, s32 = cases.spec(c)
+    yard = float(np.abs(s32["ctx"] - s64["ctx"]).max())
+    sb = kernels.SeqBatch.get(c["lens"], dev)
+    q, k, v = (torch.from_numpy(c[n]).to(dev) for n in "qkv")
+    ctx, stats = kernels.attn_stream_train(q, k, v, sb, 1, dropout_p=c["p"], seed=cases.SEED, site=cases.SITE)
+    r = worst(ctx, s64["ctx"], yard, (c["name"], "ctx"))
+    print(f"attn_stream_train dh 256, p 0.1: ctx {r:.3f} yardsticks ({yard:.3e})")
+    assert bool(torch.isfinite(stats).all())
+
+
 def test_determinism_and_capture(dev):
     from summarizer_amd import kernels
     c = cases.with_grad(cases.fwd.case("det", (1, 64, 65, 200, 3, 129), 256, 2, 21), 0.1)
