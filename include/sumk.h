@@ -451,6 +451,26 @@ int sumk_transformer_forward_stream(float* x, int32_t D, int32_t F, int32_t n_he
                                     const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
                                     const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows, float* scores,
                                     void* workspace, size_t workspace_bytes, void* stream);
+/* sumk_attn_stream in the bf16x3 arithmetic (csrc/attn_stream_split.hip), scoring only: Q, K and V are split once per call into two
+ * bf16 planes (hi = bf16(x) to nearest even, lo = bf16(x - hi)) in the workspace -- 4 bytes per staged element, videos padded to whole
+ * 64-key tiles, head widths to 32 / 64 / 128 columns -- and both products run as hi.hi + hi.lo + lo.hi on the bf16 MFMA with fp32
+ * accumulation; the softmax is sumk_attn_stream's in fp32, the weights are split in registers.  Three launches (descriptors, split,
+ * attention), no cooperative launch, no atomics: same bits every call, capturable.  `precision` / `attention_precision` accept
+ * SUMK_PRECISION_BF16X3 only (any other value: SUMK_ERR_ARG with the value in the message).  Limits: dh % 8 == 0 and dh <= 128, the
+ * workspace 16-byte aligned, otherwise sumk_attn_stream's; errors as there.  The NaN rules are sumk_attn_stream's.
+ * sumk_transformer_forward_stream_split: sumk_transformer_forward_stream with every layer's attention on that call; the projections stay
+ * exact fp32 (opts->precision must be SUMK_PRECISION_FP32).  Workspace: the stream carve + the planes of one layer's [Q | K | V]. */
+size_t sumk_attn_stream_split_workspace_bytes(int32_t D, int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host, int32_t precision);
+int sumk_attn_stream_split(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, int32_t D,
+                           int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale,
+                           int32_t precision, float* ctx, int32_t ldc, float* lse, void* workspace, size_t workspace_bytes, void* stream);
+size_t sumk_transformer_stream_split_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                     const int32_t* seq_off_host, int32_t attention_precision);
+int sumk_transformer_forward_stream_split(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                          const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                          const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                          const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows, float* scores,
+                                          int32_t attention_precision, void* workspace, size_t workspace_bytes, void* stream);
 /* Gradient targets, same shapes as the weights; ACCUMULATED into (caller zeroes them). */
 typedef struct sumk_tf_layer_grads {
   float* in_proj_w; float* in_proj_b; float* out_proj_w; float* out_proj_b; float* lin1_w; float* lin1_b;
@@ -1079,7 +1099,10 @@ int sumk_pack_rows_bf16(uint16_t* dst_bf16, const float* const* srcs, const int3
 #define SUMK_PROF_ATTN_STREAM_BWD_DELTA 23
 #define SUMK_PROF_ATTN_STREAM_BWD_DQ 24
 #define SUMK_PROF_ATTN_STREAM_BWD_DKV 25
-#define SUMK_PROF_NTAGS 26
+/* the stream form in bf16x3 (csrc/attn_stream_split.hip): the pass that splits Q, K, V into bf16 planes, and the attention launch */
+#define SUMK_PROF_ATTN_STREAM_SPLIT_PLANES 26
+#define SUMK_PROF_ATTN_STREAM_SPLIT 27
+#define SUMK_PROF_NTAGS 28
 /* The small-batch GEMM form by itself (tests, probes): C = epilogue(A . B) for ONE exact-fp32 problem on 64x64 tiles whose K is cut
  * into `slices` (1 .. 8) slices INSIDE the launch -- every (tile, slice) block stores a partial tile, the last one to arrive adds
  * them in slice order and runs the epilogue (csrc/gemm_lean.hip, SK instances; what sumk_vasnet_forward / _backward launch for batches

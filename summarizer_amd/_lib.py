@@ -29,7 +29,9 @@ PROF_ATTN_STREAM_TRAIN = 22  # the streaming attention launch in its training fo
 PROF_ATTN_STREAM_BWD_DELTA = 23     # its backward's three launches (csrc/attn_stream_bwd.hip), one by one
 PROF_ATTN_STREAM_BWD_DQ = 24
 PROF_ATTN_STREAM_BWD_DKV = 25
-PROF_NTAGS = 26
+PROF_ATTN_STREAM_SPLIT_PLANES = 26  # the bf16x3 stream form (csrc/attn_stream_split.hip): the pass that splits Q, K, V into bf16 planes
+PROF_ATTN_STREAM_SPLIT = 27         # ... and its attention launch
+PROF_NTAGS = 28
 
 
 class VasnetWeights(C.Structure):
@@ -224,6 +226,14 @@ _SIGS = {
     "sumk_transformer_forward_stream": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, c_i32p, c_f32p, C.c_void_p, C.c_size_t,
                                                   C.c_void_p]),
+    "sumk_attn_stream_split_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, HOST_I32P, C.c_int32]),
+    "sumk_attn_stream_split": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P,
+                                         c_i32p, C.c_float, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_transformer_stream_split_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P,
+                                                                   C.c_int32]),
+    "sumk_transformer_forward_stream_split": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, c_i32p, c_f32p, C.c_int32, C.c_void_p,
+                                                        C.c_size_t, C.c_void_p]),
     "sumk_transformer_backward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p, c_f32p,
                                             C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -357,6 +357,12 @@ int attn_stream_check(int D, int heads, int n_seq, const int32_t* off_host, int6
 int launch_attn_stream(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
                        const int32_t* off_host, const int32_t* off_dev, float scale, float* ctx, int ldc, float* lse, void* ws,
                        hipStream_t stream);
+// The same call in the bf16x3 arithmetic (attn_stream_split.hip; precision: SUMK_PRECISION_BF16X3 only; dh % 8 == 0, dh <= 128).  ws:
+// attn_stream_split_ws_bytes(...) bytes (0 = arguments the call refuses), 16-byte aligned: descriptors + the bf16 planes of Q, K, V.
+size_t attn_stream_split_ws_bytes(int D, int heads, int n_seq, const int32_t* off_host, int precision);
+int launch_attn_stream_split(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
+                             const int32_t* off_host, const int32_t* off_dev, float scale, int precision, float* ctx, int ldc, float* lse,
+                             void* ws, hipStream_t stream);
 // The training form (attn_stream.hip): the weights dropped at `site` (dl.thr == 0: none, and then ctx has launch_attn_stream's bits; mask index
 // ((packed row * heads + h) << 20) | key as tf_softmax_kernel), and stats (rows, heads, 2) = the row maximum m and the sum l of exp(s - m) per
 // (row, head) for the backward.  Same workspace.

@@ -688,11 +688,12 @@ extern "C" size_t sumk_transformer_stream_workspace_bytes(int32_t D, int32_t F, 
   return w.total;
 }
 
-extern "C" int sumk_transformer_forward_stream(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
-                                               const int32_t* seq_off_host, const int32_t* seq_off_dev,
-                                               const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
-                                               const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
-                                               float* scores, void* workspace, size_t workspace_bytes, void* stream_) {
+// split = false: sumk_transformer_forward_stream.  split = true: sumk_transformer_forward_stream_split -- the same layer loop with the
+// attention core on attn_stream_split.hip in `attn_prec`; its descriptors and planes lie behind the stream carve.
+static int tf_forward_stream_any(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                 const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_tf_layer_weights* layers,
+                                 const sumk_tf_head_weights* head, const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
+                                 float* scores, bool split, int attn_prec, void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SUMK_ARG(x && seq_off_dev && layers && head && opts && scores && workspace, "transformer_forward_stream: null pointer");
   SUMK_ARG(n_layers > 0, "transformer_forward_stream: n_layers=%d", n_layers);
@@ -710,7 +711,13 @@ extern "C" int sumk_transformer_forward_stream(float* x, int32_t D, int32_t F, i
   SUMK_TRY(tf_geometry_any(D, F, n_heads, n_layers, n_seq, seq_off_host, 0, false, &G));
   SUMK_TRY(attn_stream_check(D, n_heads, n_seq, seq_off_host));
   const TfWs& L = G.L;
-  if (workspace_bytes < L.total) { set_error("transformer_forward_stream: workspace %zu < required %zu", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
+  size_t need = L.total;
+  if (split) {
+    const size_t planes = attn_stream_split_ws_bytes(D, n_heads, n_seq, seq_off_host, attn_prec);
+    if (!planes) return SUMK_ERR_ARG;           // the message is attn_stream_split's
+    need += planes;
+  }
+  if (workspace_bytes < need) { set_error("transformer_forward_stream: workspace %zu < required %zu", workspace_bytes, need); return SUMK_ERR_WORKSPACE; }
   char* ws = (char*)workspace;
   const int R = G.R;
   float* T1 = (float*)(ws + L.t1); float* QKV = (float*)(ws + L.qkv); float* CTX = (float*)(ws + L.ctx); float* FF = (float*)(ws + L.ff);
@@ -726,8 +733,12 @@ extern "C" int sumk_transformer_forward_stream(float* x, int32_t D, int32_t F, i
     const sumk_tf_layer_weights& W = layers[l];
     float* hmid = Hb[0]; float* hout = Hb[1 + (l & 1)];      // never aliases this layer's input (x or the previous hout)
     SUMK_TRY(tf_in_proj(run, hin, W.in_proj_w, W.in_proj_b, QKV));
-    SUMK_TRY(launch_attn_stream(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, n_heads, n_seq, seq_off_host, seq_off_dev, att_scale, CTX, D,
-                                nullptr, ws + L.as_seq, stream));
+    if (split)
+      SUMK_TRY(launch_attn_stream_split(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, n_heads, n_seq, seq_off_host, seq_off_dev, att_scale,
+                                        attn_prec, CTX, D, nullptr, ws + L.total, stream));
+    else
+      SUMK_TRY(launch_attn_stream(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, n_heads, n_seq, seq_off_host, seq_off_dev, att_scale, CTX, D,
+                                  nullptr, ws + L.as_seq, stream));
     SUMK_TRY(tf_out_proj(run, CTX, W.out_proj_w, W.out_proj_b, hin, T1, none, 0u));
     SUMK_TRY(launch_layernorm(T1, hmid, W.norm1_w, W.norm1_b, R, D, opts->layer_eps, nullptr, stream));
     SUMK_TRY(tf_ff_fwd(run, TfFfW{W.lin1_w, W.lin1_b, W.lin2_w, W.lin2_b}, hmid, FF, T1, none, 0u, 0u));
@@ -737,6 +748,35 @@ extern "C" int sumk_transformer_forward_stream(float* x, int32_t D, int32_t F, i
   SUMK_TRY(tf_tail(run, x, hin, Hb[0], T1, nullptr, head, opts, none, scores, false, [] { return (int)SUMK_OK; }));
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
+}
+
+extern "C" int sumk_transformer_forward_stream(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                               const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                               const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                               const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
+                                               float* scores, void* workspace, size_t workspace_bytes, void* stream_) {
+  return tf_forward_stream_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores,
+                               false, SUMK_PRECISION_FP32, workspace, workspace_bytes, stream_);
+}
+
+// ---- the stream path with the attention in bf16x3 (attn_stream_split.hip): the stream carve + the planes of one layer's [Q | K | V]
+extern "C" size_t sumk_transformer_stream_split_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                                const int32_t* seq_off_host, int32_t attention_precision) {
+  const size_t base = sumk_transformer_stream_workspace_bytes(D, F, n_heads, n_layers, n_seq, seq_off_host);
+  const size_t planes = base ? attn_stream_split_ws_bytes(D, n_heads, n_seq, seq_off_host, attention_precision) : 0;
+  return planes ? base + planes : 0;
+}
+
+extern "C" int sumk_transformer_forward_stream_split(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                     const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                                     const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                                     const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
+                                                     float* scores, int32_t attention_precision, void* workspace, size_t workspace_bytes,
+                                                     void* stream_) {
+  SUMK_ARG(attention_precision == SUMK_PRECISION_BF16X3, "transformer_forward_stream_split: attention_precision=%d (only SUMK_PRECISION_BF16X3 = %d)",
+           attention_precision, SUMK_PRECISION_BF16X3);
+  return tf_forward_stream_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores,
+                               true, attention_precision, workspace, workspace_bytes, stream_);
 }
 
 // The backward of sumk_transformer_backward and, stream_attn = true, of sumk_transformer_backward_stream (after

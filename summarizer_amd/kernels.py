@@ -1085,12 +1085,21 @@ def transformer_wplanes(params, D, dff, n_layers, n_planes, out=None):
 
 
 TF_ATTENTION = ("dense", "stream")
+TF_ATTENTION_PRECISION = ("fp32", "bf16x3")     # arithmetic of the attention products on "stream" (scoring)
 
 
 def _tf_attention(attention):
     if attention not in TF_ATTENTION:
         raise SumkError(f"transformer: attention must be one of {TF_ATTENTION}, got {attention!r}")
     return attention
+
+
+def _tf_attention_precision(attention, attention_precision, training):
+    """None for "fp32", else the code of the bf16x3 stream entries: scoring on attention="stream" only."""
+    code = _stream_precision(attention_precision, "transformer attention")
+    if code is not None and (_tf_attention(attention) != "stream" or training):
+        raise SumkError(f"transformer: attention_precision={attention_precision!r} needs attention=\"stream\" and training=False")
+    return code
 
 
 def attn_strips_b16_sizes(sb):
@@ -1122,28 +1131,51 @@ def attn_strips_b16(backward, a, b, c, out, E, P16, sb, scale, ignore_self=False
     _lib.check(rc, "sumk_attn_strips_b16")
 
 
-def attn_stream_workspace_bytes(D, n_heads, sb):
-    """Bytes of scratch one attn_stream call takes: 16 per video (sumk_attn_stream_workspace_bytes)."""
+def _stream_precision(precision, what):
+    """None for "fp32" (the exact stream entries), else the code the bf16x3 stream entries take (they refuse all but "bf16x3")."""
+    code = precision_code(precision)
+    if code == PRECISIONS["fp32"]:
+        return None
+    if precision != "bf16x3":
+        raise SumkError(f"{what}: precision must be \"fp32\" or \"bf16x3\", got {precision!r}")
+    return code
+
+
+def attn_stream_workspace_bytes(D, n_heads, sb, precision="fp32"):
+    """Bytes of scratch one attn_stream call takes: 16 per video (sumk_attn_stream_workspace_bytes); precision="bf16x3": 24 per video + the
+    bf16 planes of Q, K and V, 12 bytes per (padded row, staged column) (sumk_attn_stream_split_workspace_bytes)."""
+    code = _stream_precision(precision, "attn_stream")
+    if code is not None:
+        return _nonzero(_lib.load().sumk_attn_stream_split_workspace_bytes(int(D), int(n_heads), sb.n_seq, sb.off_host_p, code),
+                        "sumk_attn_stream_split_workspace_bytes")
     return _nonzero(_lib.load().sumk_attn_stream_workspace_bytes(int(D), int(n_heads), sb.n_seq, sb.off_host_p), "sumk_attn_stream_workspace_bytes")
 
 
-def attn_stream(q, k, v, sb, n_heads, scale=None, want_lse=False):
+def attn_stream(q, k, v, sb, n_heads, scale=None, want_lse=False, precision="fp32"):
     """Multi-head attention of a packed batch without the (T x T) logits (csrc/attn_stream.hip; exact fp32, no mask): q, k, v are (n_rows, D)
     float32, each with unit column stride and any row stride >= D that is a multiple of 4 -- three buffers, or the column slices of one
     (n_rows, 3 D) [Q | K | V] buffer; head h is columns [h D / n_heads, (h + 1) D / n_heads).  scale: None = 1 / sqrt(D / n_heads); it must
     be positive and finite (the kernel takes a row's maximum before scaling), anything else is refused.
+    precision="bf16x3": both products in the split-bf16 arithmetic on the bf16 MFMA (csrc/attn_stream_split.hip; head widths % 8 == 0, up
+    to 128); the default keeps the exact call and its bits.
     Returns ctx (n_rows, D), or (ctx, lse (n_rows, n_heads)) with want_lse.  Only enqueues work."""
     lib = _lib.load()
+    code = _stream_precision(precision, "attn_stream")
     for t, what in ((q, "q"), (k, "k"), (v, "v")):
         _require_gpu(t, "attn_stream " + what)
         if t.dim() != 2 or t.shape != q.shape or t.shape[0] != sb.n_rows or t.stride(1) != 1:
             raise SumkError(f"attn_stream: {what} must be (n_rows={sb.n_rows}, D) with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
     D = q.shape[1]
-    nb = attn_stream_workspace_bytes(D, n_heads, sb)
+    nb = attn_stream_workspace_bytes(D, n_heads, sb, precision)
     ws = workspace(nb, q.device)
     ctx = torch.empty(sb.n_rows, D, dtype=torch.float32, device=q.device)
     lse = torch.empty(sb.n_rows, int(n_heads), dtype=torch.float32, device=q.device) if want_lse else None
     sc = 1.0 / math.sqrt(D // int(n_heads)) if scale is None else float(scale)
+    if code is not None:
+        rc = lib.sumk_attn_stream_split(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq, sb.off_host_p,
+                                        sb.off_dev_p, sc, code, _p(ctx), D, _p(lse), _p(ws), ws.numel(), _stream())
+        _lib.check(rc, "sumk_attn_stream_split")
+        return (ctx, lse) if want_lse else ctx
     rc = lib.sumk_attn_stream(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq, sb.off_host_p,
                               sb.off_dev_p, sc, _p(ctx), D, _p(lse), _p(ws), ws.numel(), _stream())
     _lib.check(rc, "sumk_attn_stream")
@@ -1209,12 +1241,17 @@ def attn_stream_backward(q, k, v, ctx, dctx, stats, sb, n_heads, scale=None, dro
     return dq, dk, dv
 
 
-def transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, attention="dense", training=False):
-    """Bytes of scratch one call takes in exact fp32.  Scoring: "dense" holds heads x T x T logits per video
+def transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, attention="dense", training=False, attention_precision="fp32"):
+    """Bytes of scratch one call takes in exact fp32 (attention_precision="bf16x3", scoring on "stream" only: + the bf16 planes of one
+    layer's [Q | K | V], sumk_transformer_stream_split_workspace_bytes).  Scoring: "dense" holds heads x T x T logits per video
     (sumk_transformer_workspace_bytes), "stream" none (sumk_transformer_stream_workspace_bytes).  training=True, the forward that keeps
     what the backward needs: "dense" keeps two heads x T x T blocks per video and layer, "stream" 8 bytes per (row, head) and layer
     (sumk_transformer_stream_train_workspace_bytes)."""
     lib = _lib.load()
+    code = _tf_attention_precision(attention, attention_precision, training)
+    if code is not None:
+        return _nonzero(lib.sumk_transformer_stream_split_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq,
+                                                                          sb.off_host_p, code), "sumk_transformer_stream_split_workspace_bytes")
     if _tf_attention(attention) == "stream":
         if training:
             return _nonzero(lib.sumk_transformer_stream_train_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq,
@@ -1226,16 +1263,28 @@ def transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, attention="dense"
 
 
 def transformer_forward_packed(x, sb, params, n_layers, n_heads, dff, opts, pos_table=None, pos_rows=None, training=False,
-                               attention="dense"):
+                               attention="dense", attention_precision="fp32"):
     """x: (n_rows, D) packed -> (scores (n_rows,), workspace or None).  params: state_dict-keyed tensors.
     attention="stream" (exact fp32 only): every layer's attention on csrc/attn_stream.hip, no (T x T) logits in the workspace
     (sumk_transformer_forward_stream; training=True: sumk_transformer_forward_stream_train, whose workspace goes to
-    transformer_backward_packed(..., attention="stream"))."""
+    transformer_backward_packed(..., attention="stream")).  attention_precision="bf16x3" (scoring on "stream" only): every layer's
+    attention on csrc/attn_stream_split.hip, the projections still exact fp32 (sumk_transformer_forward_stream_split)."""
     lib = _lib.load()
     _check_rows(x, sb, "transformer input")
     D = x.shape[1]
     layers, head = _tf_structs(params, n_layers, "weight", _lib.TfLayerWeights, _lib.TfHeadWeights)
     o = _tf_opts(opts)
+    code = _tf_attention_precision(attention, attention_precision, training)
+    if code is not None:
+        nbytes = transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, "stream", attention_precision=attention_precision)
+        ws = workspace(nbytes, x.device)
+        scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
+        rc = lib.sumk_transformer_forward_stream_split(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
+                                                       C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
+                                                       C.cast(C.pointer(o), C.c_void_p), _p(pos_table), _p(pos_rows), _p(scores), code,
+                                                       _p(ws), ws.numel(), _stream())
+        _lib.check(rc, "sumk_transformer_forward_stream_split")
+        return scores, None
     if _tf_attention(attention) == "stream":
         if training:
             nbytes = transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, "stream", training=True)

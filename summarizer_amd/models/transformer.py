@@ -22,7 +22,8 @@ from ..training import FlatAdam, dist_info, plan_shards, step_video_total
 
 class Transformer(PositionalInput, nn.Module):
     def __init__(self, input_size=1024, encoder_layers=6, attention_heads=8, more_residuals=False, max_length=None,
-                 pos_embed="simple", epsilon=1e-5, weight_init=None, attention="dense", attention_train="dense"):
+                 pos_embed="simple", epsilon=1e-5, weight_init=None, attention="dense", attention_train="dense",
+                 attention_precision="fp32"):
         super().__init__()
         # attention (not in the reference, opt-in): how a no-grad call computes the multi-head attention of every layer.
         #   "dense"   heads x T x T logits per video in the workspace (csrc/transformer.hip): the default, every precision;
@@ -32,11 +33,19 @@ class Transformer(PositionalInput, nn.Module):
         #   "dense"   keeps alpha and dropout(alpha), two heads x T x T blocks per video and LAYER: the default, its bits unchanged;
         #   "stream"  keeps 8 bytes per (row, head) and layer and recomputes the weights in the backward (csrc/attn_stream_bwd.hip):
         #             exact fp32 only, head widths up to 128, the same dropout masks as "dense" for the same seed.
+        # attention_precision (opt-in, attention="stream" only; governs the no-grad branch alone): the arithmetic of the attention products.
+        #   "fp32"    exact (csrc/attn_stream.hip): the default, its bits unchanged;
+        #   "bf16x3"  hi + lo bf16 planes, three bf16 MFMAs per product (csrc/attn_stream_split.hip): head widths % 8 == 0 up to 128;
+        #             the projections stay exact fp32.  A separate argument because `precision` other than "fp32" is refused with "stream".
         if attention not in kernels.TF_ATTENTION:
             raise ValueError(f"Transformer: attention must be one of {kernels.TF_ATTENTION}, got {attention!r}")
         if attention_train not in kernels.TF_ATTENTION:
             raise ValueError(f"Transformer: attention_train must be one of {kernels.TF_ATTENTION}, got {attention_train!r}")
-        self.attention, self.attention_train = attention, attention_train
+        if attention_precision not in kernels.TF_ATTENTION_PRECISION:
+            raise ValueError(f"Transformer: attention_precision must be one of {kernels.TF_ATTENTION_PRECISION}, got {attention_precision!r}")
+        if attention_precision != "fp32" and attention != "stream":
+            raise ValueError(f"Transformer: attention_precision={attention_precision!r} needs attention='stream', got attention={attention!r}")
+        self.attention, self.attention_train, self.attention_precision = attention, attention_train, attention_precision
         self.input_size = input_size
         self.encoder_layers, self.attention_heads, self.epsilon = encoder_layers, attention_heads, epsilon
         self._init_pos_embed(max_length, pos_embed)
@@ -74,8 +83,8 @@ class Transformer(PositionalInput, nn.Module):
 
     def _score(self, xp, sb, table, rows):
         """attention="stream": the no-grad branch scores through sumk_transformer_forward_stream (exact fp32; any other `precision`
-        raises ValueError).  The autograd branch follows attention_train alone: "dense" (default) gives the gradients it always gave, bit
-        for bit; "stream" runs sumk_transformer_forward_stream_train / _backward_stream (exact fp32; any other `precision` raises)."""
+        raises ValueError), its attention products in attention_precision.  The autograd branch follows attention_train alone: "dense"
+        (default) gives the gradients it always gave, bit for bit; "stream" runs sumk_transformer_forward_stream_train / _backward_stream (exact fp32; any other `precision` raises)."""
         p = dict(self.named_parameters())
         opts = dict(layer_eps=1e-5, final_eps=self.epsilon, more_residuals=self.more_residuals,
                     precision=getattr(self, "precision", "fp32"))
@@ -99,7 +108,8 @@ class Transformer(PositionalInput, nn.Module):
                 raise ValueError(f"Transformer(attention='stream') scores in exact fp32: precision={opts['precision']!r} needs "
                                  "attention='dense' (or precision='fp32' with attention='stream')")
             scores, _ = kernels.transformer_forward_packed(xp, sb, p, self.encoder_layers, self.attention_heads, self.input_size,
-                                                           opts, table, rows, attention="stream")
+                                                           opts, table, rows, attention="stream",
+                                                           attention_precision=self.attention_precision)
             return scores
         if opts["precision"] in kernels.PLANES_OF:          # inference in a split-bf16 arithmetic: every projection on the plane GEMM
             opts["wplanes"] = self._wplanes(p, opts["precision"])
@@ -120,7 +130,8 @@ class TransformerTrainer(Trainer):
     correlation weights; same `extra_params`.  Extensions as for VASNetTrainer: `batch_videos`, video sharding + one
     flat-bucket gradient all-reduce per step under torch.distributed.  extra_params["attention"] = "stream" scores (test, summaries)
     without the (T x T) logits (Transformer's argument of that name); extra_params["attention_train"] = "stream" trains without the
-    (T x T) blocks (Transformer's attention_train); each defaults to "dense" and neither implies the other."""
+    (T x T) blocks (Transformer's attention_train); each defaults to "dense" and neither implies the other.
+    extra_params["attention_precision"] = "bf16x3" (with attention "stream") scores with the attention products in the split-bf16 arithmetic."""
     def _init_model(self):
         ep = self.hps.extra_params
         model = Transformer(
@@ -133,6 +144,7 @@ class TransformerTrainer(Trainer):
             weight_init=ep.get("weight_init", None),
             attention=ep.get("attention", "dense"),
             attention_train=ep.get("attention_train", "dense"),
+            attention_precision=ep.get("attention_precision", "fp32"),
             **({"input_size": int(ep["input_size"])} if "input_size" in ep else {}))
         model.precision = ep.get("precision", "fp32")      # "fp32" | "bf16x3" (kernels.precision_code)
         if self.hps.use_cuda:
