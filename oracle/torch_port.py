@@ -2,7 +2,8 @@
 The SumGAN recurrences (lstm_stack_ref, dlstm_ref) and make_gru also run in float64: the high-precision oracles of
 tests/test_gpu_sumgan_full.py; transformer_ref likewise for tests/test_gpu_transformer_f64.py, tf_encoder_stack_ref / tf_decoder_stack_ref for
 tests/test_gpu_sumgan_att_f64.py, bilstm_stack_ref for
-tests/test_gpu_lstm_f64.py (float64 reference and, in fp32 with the kernels' gate formulas, its yardstick).
+tests/test_gpu_lstm_f64.py (float64 reference and, in fp32 with the kernels' gate formulas, its yardstick), bigru_stack_ref the same
+for tests/test_gpu_gru_f64.py.
 
 This is (1) a second, autograd-capable checker for the HIP path (forward AND gradients), and
 (2) the `cpu_baseline` ("kind": "port") that bench.py times on the GPU node's host cores: it issues the
@@ -431,6 +432,73 @@ def bilstm_stack_ref(x_list, params, gate_math="exact", matmul=None):
                 i, f, g, o = (gx[t, :nb] + mm(h[:nb], w_hh, "hh")).chunk(4, dim=-1)
                 c = sig(f) * c[:nb] + sig(i) * tanh(g)
                 h = sig(o) * tanh(c)
+                outs.append(torch.cat([h, h.new_zeros(len(lens) - nb, H)]) if nb < len(lens) else h)
+            out = torch.stack(outs)                                                  # (T_max, B, H), rows in `order`
+            per = [None] * len(lens)
+            for r, i in enumerate(order):
+                per[i] = torch.flip(out[:lens[i], r], (0,)) if suf else out[:lens[i], r]
+            halves.append(per)
+        cur = [torch.cat([a, b], dim=1) for a, b in zip(*halves)]
+        layers.append(cur)
+    return layers
+
+
+class LinearDw3(torch.autograd.Function):
+    """y = x W^T (2-D x) taken exactly, forward and dx = dy W, whose WEIGHT gradient alone is dW = dy^T x in bf16x3: the recurrent
+    product of the persistent GRU layer in that precision (csrc/gru_persist.hip: the recurrence and the BPTT's dGh . W_hh multiply in
+    fp32 inside the kernels; the split-K launches of dW_hh take the layer's precision)."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        ctx.save_for_backward(x, w)
+        return x @ w.t()
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        return dy @ w, mm3(dy.t(), x)
+
+
+def _gru_cell(gx, hw, b_hh, h, sig, tanh):
+    """One nn.GRU step: gx = x W_ih^T + b_ih (precomputed), hw = h W_hh^T; gate order r, z, n as in torch, b_hn inside r * (...).
+    The sums in the kernels' order: gx + (hw + b_hh)."""
+    xr, xz, xn = gx.chunk(3, dim=-1)
+    hr, hz, hn = (hw + b_hh).chunk(3, dim=-1)
+    r, z = sig(xr + hr), sig(xz + hz)
+    n = tanh(xn + r * hn)
+    return (1.0 - z) * n + z * h
+
+
+def bigru_stack_ref(x_list, params, gate_math="exact", matmul=None):
+    """Stacked nn.GRU(num_layers=L, bidirectional=True) over a ragged list of videos, written out step by step with plain torch ops
+    in the dtype of the inputs (float64: the reference of tests/test_gpu_gru_f64.py; float32: its yardstick) -- bilstm_stack_ref's
+    twin.  x_list: [(T_i, In)]; params: nn.GRU state_dict names (weight_ih_l0, weight_ih_l0_reverse, ...).
+    gate_math: a key of GATE_MATH.  matmul: optional hook (a (n, K), w (N, K), site) -> a @ w.T with site "ih" (input projection) or
+    "hh" (recurrent product); None: a @ w.T in the dtype.
+    The videos run side by side in descending order of length, each direction over its own frames only (the reverse direction
+    starts at a video's LAST frame).  As in the kernels, the input projection of all frames comes first and carries b_ih; b_hh joins
+    the recurrent product in every step (r multiplies b_hn).
+    Returns [[h_i (T_i, 2H) = [h_fwd || h_rev] per video] per layer]; differentiable in inputs and parameters."""
+    sig, tanh = GATE_MATH[gate_math]
+    mm = matmul if matmul is not None else (lambda a, w, site: a @ w.t())
+    L = sum(1 for k in params if k.startswith("weight_ih_l") and not k.endswith("_reverse"))
+    H = params["weight_hh_l0"].shape[1]
+    lens = [int(x.shape[0]) for x in x_list]
+    order = sorted(range(len(lens)), key=lambda i: -lens[i])
+    n_act = [sum(1 for n in lens if n > t) for t in range(max(lens))]                # videos still running at step t: a prefix of `order`
+    layers, cur = [], list(x_list)
+    for l in range(L):
+        halves = []
+        for suf in ("", "_reverse"):
+            w_ih, w_hh = params[f"weight_ih_l{l}{suf}"], params[f"weight_hh_l{l}{suf}"]
+            b_ih, b_hh = params[f"bias_ih_l{l}{suf}"], params[f"bias_hh_l{l}{suf}"]
+            own = [torch.flip(cur[i], (0,)) if suf else cur[i] for i in order]       # each video in this direction's step order
+            seq = torch.nn.utils.rnn.pad_sequence(own)                               # (T_max, B, In)
+            gx = (mm(seq.reshape(-1, seq.shape[-1]), w_ih, "ih") + b_ih).reshape(seq.shape[0], seq.shape[1], 3 * H)
+            h = seq.new_zeros(len(lens), H)
+            outs = []
+            for t, nb in enumerate(n_act):
+                h = _gru_cell(gx[t, :nb], mm(h[:nb], w_hh, "hh"), b_hh, h[:nb], sig, tanh)
                 outs.append(torch.cat([h, h.new_zeros(len(lens) - nb, H)]) if nb < len(lens) else h)
             out = torch.stack(outs)                                                  # (T_max, B, H), rows in `order`
             per = [None] * len(lens)

@@ -336,6 +336,63 @@ def test_bilstm_stack_ref_vs_nn_lstm_float64():
         close(a, b)
 
 
+def test_bigru_stack_ref_vs_nn_gru_float64():
+    """bigru_stack_ref (the float64 reference of tests/test_gpu_gru_f64.py) against make_gru(dtype=float64) -- stock
+    nn.GRU(bidirectional=True) in float64 -- through pack_sequence: a ragged batch with a one-frame video and a tie in length, two
+    layers; hidden states of the top layer (and of layer 0 against a one-layer module carrying the same weights), scores of a
+    Linear(2H, 1) + sigmoid head, and the gradient of a random-weighted sum of the scores w.r.t. every parameter and the inputs, all to
+    1e-12.  gate_math="rcp_form" is the same function.  The bf16x3 hooks differ from the plain product by 2^-16 relative, not more:
+    Linear3 everywhere (the step path), and LinearDw3 on the recurrent product (the persistent path: only dW_hh moves, every forward
+    value and every other gradient's recurrent part stays exact).  The one-accumulator dX product is the plain product in another order."""
+    from torch.nn.utils.rnn import pack_sequence, pad_packed_sequence
+    torch.manual_seed(19)
+    D, H, L, lens = 12, 10, 2, [5, 1, 9, 5, 2]
+    sd = {f"rnn.{k}": v.detach() for k, v in torch.nn.GRU(D, H, num_layers=L, bidirectional=True).state_dict().items()}
+    gru = torch_port.make_gru(sd, "rnn.", D, H, L, dtype=torch.float64)
+    head = torch.nn.Linear(2 * H, 1).double()
+    p = dict(gru.named_parameters())
+    assert all(v.dtype == torch.float64 for v in p.values())
+    xs = [torch.randn(T, D, dtype=torch.float64, requires_grad=True) for T in lens]
+    cw = [torch.randn(T, dtype=torch.float64) for T in lens]
+    leaves = xs + list(p.values()) + [head.weight, head.bias]
+    close = lambda a, b: torch.testing.assert_close(a, b, rtol=0, atol=1e-12)
+    grads = lambda layers: torch.autograd.grad(sum((torch.sigmoid(head(h))[:, 0] * w).sum() for h, w in zip(layers[-1], cw)), leaves)
+
+    out, _ = pad_packed_sequence(gru(pack_sequence(xs, enforce_sorted=False))[0])             # (T_max, B, 2H)
+    want_h = [out[:T, i] for i, T in enumerate(lens)]
+    want_s = [torch.sigmoid(head(h))[:, 0] for h in want_h]
+    want_g = torch.autograd.grad(sum((s * w).sum() for s, w in zip(want_s, cw)), leaves)
+    l0 = torch_port.make_gru({k: v for k, v in sd.items() if k.split("_reverse")[0].endswith("_l0")}, "rnn.", D, H, 1, dtype=torch.float64)
+    out0, _ = pad_packed_sequence(l0(pack_sequence(xs, enforce_sorted=False))[0])
+
+    for gate_math in ("exact", "rcp_form"):
+        layers = torch_port.bigru_stack_ref(xs, p, gate_math=gate_math)
+        assert len(layers) == L and all(len(v) == len(lens) for v in layers)
+        for i, T in enumerate(lens):
+            assert tuple(layers[0][i].shape) == tuple(layers[1][i].shape) == (T, 2 * H)
+            close(layers[1][i], want_h[i]); close(layers[0][i], out0[:T, i]); close(torch.sigmoid(head(layers[1][i]))[:, 0], want_s[i])
+        for a, b in zip(grads(layers), want_g):
+            close(a, b)
+
+    rel = lambda got: {k: float((a - b).abs().max() / b.abs().max()) for k, a, b in zip([f"x{i}" for i in range(len(xs))] + list(p) + ["hw", "hb"], got, want_g)}
+    layers3 = torch_port.bigru_stack_ref(xs, p, matmul=lambda a, w, site: torch_port.Linear3.apply(a, w, False))
+    dh = max(float((a - b).detach().abs().max()) for a, b in zip(layers3[-1], want_h))
+    dg = max(rel(grads(layers3)).values())
+    assert 0 < dh < 1e-4 and 0 < dg < 1e-3, (dh, dg)                                          # the roundings happen, and stay at 2^-16
+
+    dw3 = lambda a, w, site: torch_port.LinearDw3.apply(a, w) if site == "hh" else a @ w.t()
+    layers_w = torch_port.bigru_stack_ref(xs, p, matmul=dw3)
+    for a, b in zip(layers_w[-1], want_h):
+        close(a, b)                                                                           # the forward is untouched
+    rw = rel(grads(layers_w))
+    # the weight_hh gradients of both layers carry the bf16x3 rounding and nothing else does (a weight gradient feeds no other gradient)
+    assert all((0 < v < 1e-3) if "weight_hh" in k else v < 1e-12 for k, v in rw.items()), rw
+
+    chain = lambda x_, w_, site: torch_port.LinearChainDx.apply(x_, w_) if site == "ih" else x_ @ w_.t()
+    for a, b in zip(grads(torch_port.bigru_stack_ref(xs, p, matmul=chain)), want_g):
+        close(a, b)
+
+
 def test_make_gru_float64():
     torch.manual_seed(2)
     m = torch.nn.GRU(6, 5, num_layers=2, bidirectional=True)
