@@ -17,18 +17,21 @@ import torch.nn.functional as F
 
 
 def _r16(t):
-    """fp32 -> bf16 (round to nearest even, what v_cvt_pk_bf16_f32 does) -> fp32"""
-    return t.to(torch.bfloat16).to(torch.float32)
+    """fp32 -> bf16 (round to nearest even, what v_cvt_pk_bf16_f32 does) -> back to the dtype of t.  A float64 t goes through fp32 first:
+    the kernels round an fp32 value, so the float64 emulation (tests/vasnet_bf16_common.py) rounds at the same two steps."""
+    return t.to(torch.float32).to(torch.bfloat16).to(t.dtype)
 
 
 class _Linear16(torch.autograd.Function):
-    """y = x W^T with BOTH operands rounded to bf16 and fp32 accumulation -- and the same in the backward: dx = bf16(dy) bf16(W),
-    dW = bf16(dy)^T bf16(x).  This is the arithmetic of the mixed-precision training step (csrc/gemm_b16.hip: every GEMM reads bf16
-    shadows of its operands, gradients included), restated with stock fp32 matmuls (a product of two bf16 values is exact in fp32)."""
+    """y = x W^T with BOTH operands rounded to bf16 and accumulation in the dtype of x (fp32: what the kernels do; float64: the
+    high-precision form of the same arithmetic) -- and the same in the backward: dx = bf16(dy) bf16(W), dW = bf16(dy)^T bf16(x).  This
+    is the arithmetic of the mixed-precision training step (csrc/gemm_b16.hip: every GEMM reads bf16 shadows of its operands, gradients
+    included), restated with stock matmuls (a product of two bf16 values is exact in fp32).  round_x / round_w = False: that operand is
+    taken as it is (a caller that knows it to be bf16-representable)."""
 
     @staticmethod
-    def forward(ctx, x, w):
-        xr, wr = _r16(x), _r16(w)
+    def forward(ctx, x, w, round_x=True, round_w=True):
+        xr, wr = _r16(x) if round_x else x, _r16(w) if round_w else w
         ctx.save_for_backward(xr, wr)
         return xr @ wr.t()
 
@@ -36,7 +39,7 @@ class _Linear16(torch.autograd.Function):
     def backward(ctx, dy):
         xr, wr = ctx.saved_tensors
         dyr = _r16(dy)
-        return dyr @ wr, dyr.reshape(-1, dyr.shape[-1]).t() @ xr.reshape(-1, xr.shape[-1])
+        return dyr @ wr, dyr.reshape(-1, dyr.shape[-1]).t() @ xr.reshape(-1, xr.shape[-1]), None, None
 
 
 class _Bmm16(torch.autograd.Function):
@@ -56,13 +59,17 @@ class _Bmm16(torch.autograd.Function):
 
 
 def vasnet_scores(x, p, ignore_self=False, aperture=None, scale=None, eps=1e-6, pos_table=None,
-                  pos_kind="simple", drop_masks=None, return_logits=False, bf16_products=False):
+                  pos_kind="simple", drop_masks=None, return_logits=False, bf16_products=False, round_leaves=True, key_mask=None):
     """x: (T,B,D) -> (T,B,1).  Op order of vasnet.py:99-147.
 
     drop_masks: optional (m_alpha (B,T,T), m_y (B,T,D), m_z (B,T,D)) of already-scaled keep masks
     (0 or 1/(1-p)) so training-mode dropout can be checked deterministically.
     return_logits: also return the pre-sigmoid outputs of k2 (vasnet.py:144).
-    bf16_products: emulate the mixed-precision training arithmetic (see _Linear16) instead of fp32 products.
+    bf16_products: emulate the mixed-precision training arithmetic (see _Linear16) instead of fp32 products; everything but the
+    roundings of the product operands runs in the dtype of x and p (float64: the reference of tests/vasnet_bf16_common.py).
+    round_leaves=False (with bf16_products): x and the weight matrices are NOT rounded -- for inputs that are bf16 values already.
+    key_mask: optional (B,T,T) bool, True = this (query, key) pair is masked as well (the seeded faults of
+    tests/test_vasnet_bf16_host.py).
     """
     T, B, D = x.shape
     xb = x.permute(1, 0, 2)
@@ -73,10 +80,14 @@ def vasnet_scores(x, p, ignore_self=False, aperture=None, scale=None, eps=1e-6, 
     sc = scale if scale is not None else 1.0 / math.sqrt(D)
     # bf16_products: the emulated mixed-precision arithmetic (precision="bf16"): every matrix product on bf16-rounded operands with
     # fp32 accumulation, forward and backward; softmax / LayerNorm / residual / head stay fp32 as in csrc/vasnet.hip
-    lin = (lambda a, w_, b_=None: _Linear16.apply(a, w_) + (b_ if b_ is not None else 0.0)) if bf16_products else F.linear
+    rl = bool(round_leaves)
+    lin = (lambda a, w_, b_=None, ra=True: _Linear16.apply(a, w_, ra, rl) + (b_ if b_ is not None else 0.0)) if bf16_products else \
+        (lambda a, w_, b_=None, ra=True: F.linear(a, w_, b_))
     bmm = _Bmm16.apply if bf16_products else torch.bmm
-    K = lin(xb, p["K.weight"]); Q = lin(xb, p["Q.weight"]); V = lin(xb, p["V.weight"])
+    K = lin(xb, p["K.weight"], None, rl); Q = lin(xb, p["Q.weight"], None, rl); V = lin(xb, p["V.weight"], None, rl)
     e = bmm(Q, K.transpose(1, 2)) * sc
+    if key_mask is not None:
+        e = e.masked_fill(key_mask, float("-inf"))
     if ignore_self:
         e = e.masked_fill(torch.eye(T, dtype=torch.bool, device=e.device).unsqueeze(0), float("-inf"))
     if aperture is not None:
