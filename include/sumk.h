@@ -511,6 +511,46 @@ int sumk_attn_stream_backward(const float* Q, int32_t ldq, const float* K, int32
                               int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale, float dropout_p,
                               uint64_t seed, uint32_t site, float* dQ, int32_t lddq, float* dK, int32_t lddk, float* dV, int32_t lddv,
                               void* workspace, size_t workspace_bytes, void* stream);
+/* The two calls above in the bf16x3 arithmetic of sumk_attn_stream_split (csrc/attn_stream_split.hip: training forward;
+ * csrc/attn_stream_split_bwd.hip: backward), opt-in.  Every operand is two bf16 planes, every one of the seven products hi.hi + hi.lo +
+ * lo.hi with fp32 accumulation on the bf16 MFMA; softmax, masks and the dS arithmetic stay in fp32, and a~ and dS are split in registers.
+ * sumk_attn_stream_split_train: sumk_attn_stream_train's arguments + `precision`; masks, mask index and stats as there; with
+ * dropout_p == 0 ctx has the bits of sumk_attn_stream_split.  Workspace: sumk_attn_stream_split_workspace_bytes.
+ * sumk_attn_stream_split_backward: sumk_attn_stream_backward's arguments + `precision`.  delta is the fp32 launch; one pass splits Q, K,
+ * V and dctx into planes (row-major for all four, transposed per 64-row tile for Q, K and dctx: 28 bytes per (padded row, staged column));
+ * the dQ and dK / dV passes have the structure of the fp32 backward and are deterministic.  Workspace
+ * (sumk_attn_stream_split_backward_workspace_bytes): descriptors + delta + those planes, 16-byte aligned.
+ * `precision` accepts SUMK_PRECISION_BF16X3 only (any other value: SUMK_ERR_ARG with the value in the message).  Limits: dh % 8 == 0 and
+ * dh <= 128 (refused with the head width in the message), otherwise those of the fp32 calls. */
+int sumk_attn_stream_split_train(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, int32_t D,
+                                 int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale,
+                                 float dropout_p, uint64_t seed, uint32_t site, float* ctx, int32_t ldc, float* stats, void* workspace,
+                                 size_t workspace_bytes, void* stream, int32_t precision);
+size_t sumk_attn_stream_split_backward_workspace_bytes(int32_t D, int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host,
+                                                       int32_t precision);
+int sumk_attn_stream_split_backward(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv,
+                                    const float* ctx, int32_t ldc, const float* dctx, int32_t ldd, const float* stats, int32_t D,
+                                    int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, float scale,
+                                    float dropout_p, uint64_t seed, uint32_t site, float* dQ, int32_t lddq, float* dK, int32_t lddk,
+                                    float* dV, int32_t lddv, void* workspace, size_t workspace_bytes, void* stream, int32_t precision);
+/* sumk_transformer_forward_stream_split_train / sumk_transformer_backward_stream_split: the stream training entries below with every
+ * layer's attention on the two calls above (`attention_precision`: SUMK_PRECISION_BF16X3 only); projections and everything else stay
+ * exact fp32 (opts->precision must be SUMK_PRECISION_FP32, opts->wplanes NULL); same dropout sites and masks.  Workspace
+ * (sumk_transformer_stream_split_train_workspace_bytes): the stream training carve + sumk_attn_stream_split_backward_workspace_bytes --
+ * the planes are those of one layer, re-split in the backward from the saved [Q | K | V]; the state kept per layer is unchanged. */
+size_t sumk_transformer_stream_split_train_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                           const int32_t* seq_off_host, int32_t attention_precision);
+int sumk_transformer_forward_stream_split_train(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                                const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                                const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows, float* scores,
+                                                int32_t attention_precision, void* workspace, size_t workspace_bytes, void* stream);
+int sumk_transformer_backward_stream_split(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                           const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                           const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                           const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* layer_grads,
+                                           const sumk_tf_head_grads* head_grads, float* dx, int32_t attention_precision, void* workspace,
+                                           size_t workspace_bytes, void* stream);
 size_t sumk_transformer_stream_train_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
                                                      const int32_t* seq_off_host);
 int sumk_transformer_forward_stream_train(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
@@ -1102,7 +1142,14 @@ int sumk_pack_rows_bf16(uint16_t* dst_bf16, const float* const* srcs, const int3
 /* the stream form in bf16x3 (csrc/attn_stream_split.hip): the pass that splits Q, K, V into bf16 planes, and the attention launch */
 #define SUMK_PROF_ATTN_STREAM_SPLIT_PLANES 26
 #define SUMK_PROF_ATTN_STREAM_SPLIT 27
-#define SUMK_PROF_NTAGS 28
+/* the bf16x3 stream form under training: the backward's split pass (Q, K, V, dctx -> planes), the training-forward launch
+ * (csrc/attn_stream_split.hip with the statistic and the dropout; its own split pass keeps tag 26), and the two passes of the backward
+ * (csrc/attn_stream_split_bwd.hip); its delta launch keeps tag 23 */
+#define SUMK_PROF_ATTN_STREAM_SPLIT_BWD_PLANES 28
+#define SUMK_PROF_ATTN_STREAM_SPLIT_TRAIN 29
+#define SUMK_PROF_ATTN_STREAM_SPLIT_BWD_DQ 30
+#define SUMK_PROF_ATTN_STREAM_SPLIT_BWD_DKV 31
+#define SUMK_PROF_NTAGS 32
 /* The small-batch GEMM form by itself (tests, probes): C = epilogue(A . B) for ONE exact-fp32 problem on 64x64 tiles whose K is cut
  * into `slices` (1 .. 8) slices INSIDE the launch -- every (tile, slice) block stores a partial tile, the last one to arrive adds
  * them in slice order and runs the epilogue (csrc/gemm_lean.hip, SK instances; what sumk_vasnet_forward / _backward launch for batches

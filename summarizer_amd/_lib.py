@@ -31,7 +31,11 @@ PROF_ATTN_STREAM_BWD_DQ = 24
 PROF_ATTN_STREAM_BWD_DKV = 25
 PROF_ATTN_STREAM_SPLIT_PLANES = 26  # the bf16x3 stream form (csrc/attn_stream_split.hip): the pass that splits Q, K, V into bf16 planes
 PROF_ATTN_STREAM_SPLIT = 27         # ... and its attention launch
-PROF_NTAGS = 28
+PROF_ATTN_STREAM_SPLIT_BWD_PLANES = 28  # the bf16x3 stream form under training (csrc/attn_stream_split_bwd.hip): the backward's split pass,
+PROF_ATTN_STREAM_SPLIT_TRAIN = 29       # the training-forward launch (csrc/attn_stream_split.hip; its split pass keeps tag 26),
+PROF_ATTN_STREAM_SPLIT_BWD_DQ = 30      # and the backward's two passes (its delta launch keeps tag 23)
+PROF_ATTN_STREAM_SPLIT_BWD_DKV = 31
+PROF_NTAGS = 32
 
 
 class VasnetWeights(C.Structure):
@@ -245,6 +249,22 @@ _SIGS = {
                                             c_f32p, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p, C.c_float, C.c_float, C.c_uint64,
                                             C.c_uint32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_void_p, C.c_size_t,
                                             C.c_void_p]),
+    "sumk_attn_stream_split_train": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               HOST_I32P, c_i32p, C.c_float, C.c_float, C.c_uint64, C.c_uint32, c_f32p, C.c_int32, c_f32p,
+                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32]),
+    "sumk_attn_stream_split_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, HOST_I32P, C.c_int32]),
+    "sumk_attn_stream_split_backward": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p,
+                                                  C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p, C.c_float,
+                                                  C.c_float, C.c_uint64, C.c_uint32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p,
+                                                  C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32]),
+    "sumk_transformer_stream_split_train_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P,
+                                                                         C.c_int32]),
+    "sumk_transformer_forward_stream_split_train": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P,
+                                                              c_i32p, C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, c_i32p, c_f32p, C.c_int32,
+                                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sumk_transformer_backward_stream_split": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p, c_f32p,
+                                                         C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sumk_transformer_stream_train_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P]),
     "sumk_transformer_forward_stream_train": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, HOST_I32P, c_i32p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, c_i32p, c_f32p, C.c_void_p,

@@ -181,13 +181,15 @@ class BiGruLayerFunction(torch.autograd.Function):
 
 class TransformerFunction(torch.autograd.Function):
     """scores = Transformer-encoder scorer(x) for a packed batch (transformer.py:74-103).  cfg: n_layers, n_heads, dff and, optionally,
-    attention ("dense" | "stream": which attention the training forward and the backward run, kernels.transformer_forward_packed)."""
+    attention ("dense" | "stream": which attention the training forward and the backward run, kernels.transformer_forward_packed) and
+    attention_train_precision ("fp32" | "bf16x3": the arithmetic of the attention products on "stream")."""
 
     @staticmethod
     def forward(ctx, xp, sb, cfg, opts, table, rows, names, *params):
         p = dict(zip(names, params))
         scores, ws = kernels.transformer_forward_packed(xp, sb, p, cfg["n_layers"], cfg["n_heads"], cfg["dff"], opts, table,
-                                                        rows, training=True, attention=cfg.get("attention", "dense"))
+                                                        rows, training=True, attention=cfg.get("attention", "dense"),
+                                                        attention_train_precision=cfg.get("attention_train_precision", "fp32"))
         ctx.meta = (sb, cfg, opts, names, rows)
         ctx.ws, ctx.params, ctx.table = ws, params, table
         ctx.table_is_param = isinstance(table, torch.nn.Parameter) and table.requires_grad
@@ -202,7 +204,8 @@ class TransformerFunction(torch.autograd.Function):
         grads, ret = _grad_targets(names, ctx.params)
         want_dx = ctx.needs_input_grad[0] or ctx.table_is_param
         dx = kernels.transformer_backward_packed(xp, sb, p, grads, cfg["n_layers"], cfg["n_heads"], cfg["dff"], opts, dscores,
-                                                 ctx.ws, want_dx=want_dx, attention=cfg.get("attention", "dense"))
+                                                 ctx.ws, want_dx=want_dx, attention=cfg.get("attention", "dense"),
+                                                 attention_train_precision=cfg.get("attention_train_precision", "fp32"))
         if ctx.table_is_param:
             _table_grad(ctx.table, rows, dx)
         ctx.ws = ctx.params = None

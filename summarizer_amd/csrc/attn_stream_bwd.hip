@@ -237,6 +237,14 @@ int attn_stream_bwd_check(int D, int heads, int n_seq, const int32_t* off, int64
   return SUMK_OK;
 }
 
+void launch_attn_stream_bwd_delta(const float* ctx, int ldc, const float* dctx, int ldd, float* delta, int64_t n_rows, int heads, int dh,
+                                  hipStream_t stream) {
+  const int64_t nrh = n_rows * heads;
+  prof_begin(SUMK_PROF_ATTN_STREAM_BWD_DELTA, stream);
+  hipLaunchKernelGGL(asb_delta_kernel, dim3((unsigned)((nrh + 255) / 256)), dim3(256), 0, stream, ctx, ldc, dctx, ldd, delta, nrh, heads, dh);
+  prof_end(SUMK_PROF_ATTN_STREAM_BWD_DELTA, stream);
+}
+
 size_t attn_stream_bwd_ws_bytes(int heads, int n_seq, int64_t n_rows) {
   return attn_stream_ws_bytes(n_seq) + align_up((size_t)n_rows * (size_t)heads * sizeof(float), 256);
 }
@@ -257,12 +265,10 @@ int launch_attn_stream_bwd(const float* Q, int ldq, const float* K, int ldk, con
   SUMK_TRY(as_check_operands("attn_stream_backward", (uintptr_t)Q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)ctx | (uintptr_t)dctx | (uintptr_t)dQ | (uintptr_t)dK | (uintptr_t)dV,
                              "Q, K, V, ctx, dctx, dQ, dK and dV", scale));
   SUMK_ARG(!dl.seed_dev, "attn_stream_backward: no device seed word");
-  const int64_t n_rows = off_host[n_seq], nrh = n_rows * heads;
+  const int64_t n_rows = off_host[n_seq];
   float* delta = (float*)((char*)ws + attn_stream_ws_bytes(n_seq));
   attn_stream_setup(off_dev, n_seq, ws, stream);
-  prof_begin(SUMK_PROF_ATTN_STREAM_BWD_DELTA, stream);
-  hipLaunchKernelGGL(asb_delta_kernel, dim3((unsigned)((nrh + 255) / 256)), dim3(256), 0, stream, ctx, ldc, dctx, ldd, delta, nrh, heads, D / heads);
-  prof_end(SUMK_PROF_ATTN_STREAM_BWD_DELTA, stream);
+  launch_attn_stream_bwd_delta(ctx, ldc, dctx, ldd, delta, n_rows, heads, D / heads, stream);
   AsbArgs a;
   a.ml = (const float2*)stats; a.delta = delta; a.seq = (const AsSeq*)ws;
   a.dh = D / heads; a.heads = heads; a.n_seq = n_seq; a.scale = scale;

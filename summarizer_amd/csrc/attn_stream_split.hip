@@ -1,5 +1,5 @@
 // Streaming multi-head attention in the library's bf16x3 arithmetic: attn_stream.hip's call on v_mfma_f32_32x32x16_bf16, for the long
-// videos whose attention is nearly the whole cost of a scoring call.  Scoring only, opt-in; the fp32 kernel is untouched.
+// videos whose attention is nearly the whole cost of a scoring call.  Scoring and the training forward, opt-in; the fp32 kernel is untouched.
 //
 //   ctx[rows of v, h dh : (h + 1) dh] = softmax_j(scale Q_h K_h^T) V_h          per video v and head h of a packed batch, no mask
 //
@@ -55,53 +55,29 @@
 // Measured (scripts/attn_stream_split_timing.py, D = 1024, 8 heads, split pass + attention per layer): 0.750 ms at T = 8192 against
 // 2.239 ms of the fp32 launch (2.99x), 44.3 ms against 136.2 ms at T = 65 536 (3.08x); the attention launch alone runs its 12 T^2 D FLOP at
 // 1.17 / 1.20 PFLOP/s, the split pass takes 0.044 / 0.339 ms.
-#include "attn_stream_common.h"
-#include "pw_common.h"
+//
+// The training form (sumk_attn_stream_split_train; its backward: attn_stream_split_bwd.hip) is the same kernel with the two additions of
+// as_stream_kernel<NB, DROP>.  The statistic (m, l) per (row, head) is written whenever a.ml is given.  DROP instances drop the weights:
+// the running sum l takes the undropped p, the second product keep ? p / (1 - p) : 0 with the dense path's mask index at the TRUE key of
+// each accumulator register (32 sb + as_crow(r, lh); only the planes are permuted).  With dropout_p == 0 the non-DROP instances run: no hash
+// in the instruction stream, ctx has the bits of sumk_attn_stream_split.  The hash costs registers: ass_kernel<4, true> takes all 256 VGPRs
+// of its two-waves-per-SIMD budget and spills 83 (336 B of scratch), as the fp32 twin does (85); NB = 1, 2 take 218 / 255, no spill.
+// Measured (scripts/attn_stream_split_train_timing.py, D = 1024, 8 heads, dropout 0.1): 1.486 ms at T = 8192 against 2.800 ms of the fp32
+// training forward in the same run.
+#include "attn_stream_split_common.h"
 #include <algorithm>
 
 namespace sumk {
 
 namespace {
-constexpr int ASS_MAX_DH = 128;
-constexpr int ASS_VP = 272;                     // bytes of a V image row: 64 keys x 2 planes x 2 bytes + 16
-
-struct AssSeq { int64_t row0; int64_t prow0; int32_t T; int32_t strip0; };   // first packed row, first padded row, frames, first strip
-
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 struct AssArgs {
   const float* Q; const float* K; const float* V; float* ctx; float* lse; const AssSeq* seq;
   char* qp; char* kp; char* vp;                 // the planes
   int64_t RP;                                   // padded rows of the batch (a multiple of 64)
   int32_t ldq, ldk, ldv, ldc, dh, heads, n_seq; float scale;
+  // the training form: the statistic (m, l) per (row, head) for the backward, and the dropout of the weights (DROP instances only)
+  float2* ml; uint64_t seed; uint32_t site, thr; float keep_scale;
 };
-
-// position p of a tile's 64 keys in the V planes <-> key: bits 2 and 3 swapped (an involution)
-__device__ __forceinline__ int ass_perm(int p) { return (p & ~12) | ((p & 8) >> 1) | ((p & 4) << 1); }
-
-__device__ __forceinline__ AssSeq ass_find(const AssSeq* seq, int n_seq, int64_t key, bool by_strip) {
-  int lo = 0, hi = n_seq - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    const int64_t v = by_strip ? (int64_t)seq[mid].strip0 : seq[mid].prow0;
-    if (v <= key) lo = mid; else hi = mid - 1;
-  }
-  return seq[lo];
-}
-
-__global__ void ass_setup_kernel(const int32_t* off, int n_seq, AssSeq* seq) {
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n_seq) return;
-  int strip0 = 0; int64_t prow0 = 0;
-  for (int q = 0; q < s; ++q) {
-    const int T = off[q + 1] - off[q];
-    strip0 += (T + AS_QS - 1) / AS_QS;
-    prow0 += (int64_t)((T + AS_KT - 1) / AS_KT) * AS_KT;
-  }
-  AssSeq d; d.row0 = off[s]; d.prow0 = prow0; d.T = off[s + 1] - off[s]; d.strip0 = strip0;
-  seq[s] = d;
-}
 
 // One workgroup per (64-row tile of a video, head): the tile's rows of Q and K as [hi DP | lo DP], of V transposed through LDS.
 template <int NB>
@@ -159,9 +135,10 @@ template <int NB> struct AssGeom {
   static constexpr int LDS = KIMG + VIMG;
 };
 
-__device__ __forceinline__ bf16x8 ass_ld(const char* p) { return *reinterpret_cast<const bf16x8*>(p); }
-
-template <int NB>
+// DROP: the training form with dropout of the weights -- the running sum takes the undropped p, the second product keep ? p / (1 - p) : 0,
+// the mask drawn at the TRUE key of each accumulator register (the second product walks a tile's keys in the planes' permuted order, the
+// registers do not).  Without it the instruction stream holds no hash and ctx has the bits of the scoring call.
+template <int NB, bool DROP>
 __global__ __launch_bounds__(256, 2) void ass_kernel(AssArgs a) {
   extern __shared__ __attribute__((aligned(16))) char ass_lds[];
   using G = AssGeom<NB>;
@@ -220,6 +197,7 @@ __global__ __launch_bounds__(256, 2) void ass_kernel(AssArgs a) {
     for (int r = 0; r < 16; ++r) o[b][r] = 0.f;
   float m = -INFINITY, l = 0.f;                   // running maximum of the row; this lane half's share of the running sum
   constexpr float LOG2E = 1.4426950408889634f;
+  const int64_t prow = d.row0 + orow;             // the packed row whose masks this lane draws (DROP)
 
   // first product over the k-steps [g0, g1)
   auto first = [&](int g0, int g1) {
@@ -294,7 +272,10 @@ __global__ __launch_bounds__(256, 2) void ass_kernel(AssArgs a) {
         for (int r = 0; r < 16; ++r) {
           const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(S(sb)[r], a.scale, -mn) * LOG2E);
           ps += p;
-          S(sb)[r] = p;
+          if (DROP) {
+            S(sb)[r] = dropout_keep(a.seed, a.site, as_drop_idx(prow, a.heads, h, c * AS_KT + 32 * sb + as_crow(r, lh)), a.thr) ? p * a.keep_scale : 0.f;
+            if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+          } else S(sb)[r] = p;
         }
       l = l * f + ps;
       m = mn;
@@ -322,27 +303,15 @@ __global__ __launch_bounds__(256, 2) void ass_kernel(AssArgs a) {
       if (dd < dh) *reinterpret_cast<float4*>(cp + dd) = make_float4(o[b][4 * r4] / lt, o[b][4 * r4 + 1] / lt, o[b][4 * r4 + 2] / lt, o[b][4 * r4 + 3] / lt);
     }
   if (a.lse && lh == 0) a.lse[(d.row0 + q) * (int64_t)a.heads + h] = m + logf(lt);
+  if (a.ml && lh == 0) a.ml[(d.row0 + q) * (int64_t)a.heads + h] = make_float2(m, lt);
 }
 
 struct AssLayout { size_t desc, qp, kp, vp, total; int64_t RP, strips; int nb; };
 
-int ass_layout(int D, int heads, int n_seq, const int32_t* off, int precision, AssLayout* L) {
-  SUMK_ARG(precision == SUMK_PRECISION_BF16X3, "attn_stream_split: precision=%d (only SUMK_PRECISION_BF16X3 = %d)", precision, SUMK_PRECISION_BF16X3);
-  SUMK_ARG(D > 0 && heads > 0 && D % heads == 0, "attn_stream_split: D=%d is not a positive multiple of n_heads=%d", D, heads);
-  const int dh = D / heads;
-  SUMK_ARG(dh % 8 == 0 && dh <= ASS_MAX_DH, "attn_stream_split: head width %d (D=%d, n_heads=%d) must be a multiple of 8, at most %d", dh, D, heads, ASS_MAX_DH);
-  SUMK_ARG(n_seq > 0 && n_seq <= AS_MAX_SEQ && off && off[0] == 0, "attn_stream_split: n_seq=%d (1 .. %d videos, seq_off[0] == 0)", n_seq, AS_MAX_SEQ);
-  int64_t n = 0, rp = 0;
-  for (int s = 0; s < n_seq; ++s) {
-    const int T = off[s + 1] - off[s];
-    SUMK_ARG(T > 0, "attn_stream_split: video %d has %d frames", s, T);
-    SUMK_ARG(T < AS_MAX_T, "attn_stream_split: video %d has %d frames (limit 2^20)", s, T);
-    n += (T + AS_QS - 1) / AS_QS;
-    rp += (int64_t)((T + AS_KT - 1) / AS_KT) * AS_KT;
-  }
-  SUMK_ARG(n * heads < ((int64_t)1 << 31) && rp / AS_KT < ((int64_t)1 << 31), "attn_stream_split: %lld workgroups", (long long)(n * heads));
-  L->nb = dh <= 32 ? 1 : dh <= 64 ? 2 : 4;
-  L->RP = rp; L->strips = n;
+int ass_layout(const char* who, int D, int heads, int n_seq, const int32_t* off, int precision, AssLayout* L) {
+  int64_t rp;
+  SUMK_TRY(ass_check(who, D, heads, n_seq, off, precision, &rp, &L->strips, &L->nb));
+  L->RP = rp;
   const size_t plane = (size_t)heads * (size_t)rp * (size_t)(32 * L->nb) * 4;   // hi + lo, 2 bytes each
   size_t p = 0;
   auto take = [&](size_t bytes) { size_t at = p; p += align_up(bytes, 256); return at; };
@@ -352,30 +321,25 @@ int ass_layout(int D, int heads, int n_seq, const int32_t* off, int precision, A
   return SUMK_OK;
 }
 
+// tag: the profiler tag of the attention launch; ml / dl / site: the training form (ml null and dl.thr == 0: the scoring call)
 template <int NB>
-int ass_launch(const AssArgs& a, const AssLayout& L, hipStream_t stream) {
+int ass_launch(const AssArgs& a, const AssLayout& L, int tag, hipStream_t stream) {
   prof_begin(SUMK_PROF_ATTN_STREAM_SPLIT_PLANES, stream);
   hipLaunchKernelGGL(ass_split_kernel<NB>, dim3((unsigned)(L.RP / AS_KT), (unsigned)a.heads), dim3(256), 0, stream, a);
   prof_end(SUMK_PROF_ATTN_STREAM_SPLIT_PLANES, stream);
-  prof_begin(SUMK_PROF_ATTN_STREAM_SPLIT, stream);
-  const int rc = as_launch<ass_kernel<NB>>(a, (unsigned)(L.strips * a.heads), AssGeom<NB>::LDS, stream);
-  prof_end(SUMK_PROF_ATTN_STREAM_SPLIT, stream);
+  prof_begin(tag, stream);
+  const int rc = a.thr ? as_launch<ass_kernel<NB, true>>(a, (unsigned)(L.strips * a.heads), AssGeom<NB>::LDS, stream)
+                       : as_launch<ass_kernel<NB, false>>(a, (unsigned)(L.strips * a.heads), AssGeom<NB>::LDS, stream);
+  prof_end(tag, stream);
   return rc;
 }
-}  // namespace
 
-size_t attn_stream_split_ws_bytes(int D, int heads, int n_seq, const int32_t* off, int precision) {
-  AssLayout L;
-  return ass_layout(D, heads, n_seq, off, precision, &L) == SUMK_OK ? L.total : 0;
-}
-
-int launch_attn_stream_split(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
-                             const int32_t* off_host, const int32_t* off_dev, float scale, int precision, float* ctx, int ldc, float* lse,
-                             void* ws, hipStream_t stream) {
-  const char* who = "attn_stream_split";
+int ass_run(const char* who, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
+            const int32_t* off_host, const int32_t* off_dev, float scale, int precision, float* ctx, int ldc, float* lse, float2* ml, Drop dl,
+            uint32_t site, void* ws, int tag, hipStream_t stream) {
   SUMK_ARG(Q && K && V && ctx && off_dev && ws, "%s: null pointer", who);
   AssLayout L;
-  SUMK_TRY(ass_layout(D, heads, n_seq, off_host, precision, &L));
+  SUMK_TRY(ass_layout(who, D, heads, n_seq, off_host, precision, &L));
   SUMK_ARG(heads <= 65535, "%s: n_heads=%d", who, heads);
   SUMK_ARG(ldq >= D && ldk >= D && ldv >= D && ldc >= D, "%s: leading dimensions (%d, %d, %d, %d) must be at least D=%d", who, ldq, ldk, ldv, ldc, D);
   SUMK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldc % 4 == 0, "%s: leading dimensions (%d, %d, %d, %d) must be multiples of 4", who, ldq, ldk, ldv, ldc);
@@ -384,10 +348,33 @@ int launch_attn_stream_split(const float* Q, int ldq, const float* K, int ldk, c
   a.Q = Q; a.K = K; a.V = V; a.ctx = ctx; a.lse = lse; a.seq = (const AssSeq*)((char*)ws + L.desc);
   a.qp = (char*)ws + L.qp; a.kp = (char*)ws + L.kp; a.vp = (char*)ws + L.vp; a.RP = L.RP;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldc = ldc; a.dh = D / heads; a.heads = heads; a.n_seq = n_seq; a.scale = scale;
+  a.ml = ml; a.seed = dl.seed; a.site = site; a.thr = dl.thr; a.keep_scale = dl.scale;
   hipLaunchKernelGGL(ass_setup_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, stream, off_dev, n_seq, (AssSeq*)((char*)ws + L.desc));
-  SUMK_TRY(L.nb == 1 ? ass_launch<1>(a, L, stream) : L.nb == 2 ? ass_launch<2>(a, L, stream) : ass_launch<4>(a, L, stream));
+  SUMK_TRY(L.nb == 1 ? ass_launch<1>(a, L, tag, stream) : L.nb == 2 ? ass_launch<2>(a, L, tag, stream) : ass_launch<4>(a, L, tag, stream));
   SUMK_HIP(hipGetLastError());
   return SUMK_OK;
+}
+}  // namespace
+
+size_t attn_stream_split_ws_bytes(int D, int heads, int n_seq, const int32_t* off, int precision) {
+  AssLayout L;
+  return ass_layout("attn_stream_split", D, heads, n_seq, off, precision, &L) == SUMK_OK ? L.total : 0;
+}
+
+int launch_attn_stream_split(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
+                             const int32_t* off_host, const int32_t* off_dev, float scale, int precision, float* ctx, int ldc, float* lse,
+                             void* ws, hipStream_t stream) {
+  return ass_run("attn_stream_split", Q, ldq, K, ldk, V, ldv, D, heads, n_seq, off_host, off_dev, scale, precision, ctx, ldc, lse, nullptr,
+                 make_drop(0.f, 0), 0u, ws, SUMK_PROF_ATTN_STREAM_SPLIT, stream);
+}
+
+int launch_attn_stream_split_train(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
+                                   const int32_t* off_host, const int32_t* off_dev, float scale, int precision, Drop dl, uint32_t site,
+                                   float* ctx, int ldc, float* stats, void* ws, hipStream_t stream) {
+  SUMK_ARG(stats && ((uintptr_t)stats & 7) == 0, "attn_stream_split_train: stats must be a non-null, 8-byte aligned (n_rows, n_heads, 2) array");
+  SUMK_ARG(!dl.seed_dev, "attn_stream_split_train: no device seed word");
+  return ass_run("attn_stream_split_train", Q, ldq, K, ldk, V, ldv, D, heads, n_seq, off_host, off_dev, scale, precision, ctx, ldc, nullptr,
+                 (float2*)stats, dl, site, ws, SUMK_PROF_ATTN_STREAM_SPLIT_TRAIN, stream);
 }
 
 }  // namespace sumk
@@ -405,8 +392,22 @@ extern "C" int sumk_attn_stream_split(const float* Q, int32_t ldq, const float* 
                                       void* stream) {
   SUMK_ARG(workspace, "attn_stream_split: null pointer");
   AssLayout L;
-  SUMK_TRY(ass_layout(D, n_heads, n_seq, seq_off_host, precision, &L));
+  SUMK_TRY(ass_layout("attn_stream_split", D, n_heads, n_seq, seq_off_host, precision, &L));
   if (workspace_bytes < L.total) { set_error("attn_stream_split: workspace %zu < required %zu", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
   return launch_attn_stream_split(Q, ldq, K, ldk, V, ldv, D, n_heads, n_seq, seq_off_host, seq_off_dev, scale, precision, ctx, ldc, lse,
                                   workspace, (hipStream_t)stream);
+}
+
+extern "C" int sumk_attn_stream_split_train(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, int32_t D,
+                                            int32_t n_heads, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                            float scale, float dropout_p, uint64_t seed, uint32_t site, float* ctx, int32_t ldc, float* stats,
+                                            void* workspace, size_t workspace_bytes, void* stream, int32_t precision) {
+  const char* who = "attn_stream_split_train";
+  SUMK_ARG(workspace, "%s: null pointer", who);
+  SUMK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "%s: dropout_p=%g must lie in [0, 1)", who, (double)dropout_p);
+  AssLayout L;
+  SUMK_TRY(ass_layout(who, D, n_heads, n_seq, seq_off_host, precision, &L));
+  if (workspace_bytes < L.total) { set_error("%s: workspace %zu < required %zu", who, workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
+  return launch_attn_stream_split_train(Q, ldq, K, ldk, V, ldv, D, n_heads, n_seq, seq_off_host, seq_off_dev, scale, precision,
+                                        make_drop(dropout_p, seed), site, ctx, ldc, stats, workspace, (hipStream_t)stream);
 }

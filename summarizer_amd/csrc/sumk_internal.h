@@ -377,6 +377,20 @@ int launch_attn_stream_bwd(const float* Q, int ldq, const float* K, int ldk, con
                            const float* dctx, int ldd, const float* stats, int D, int heads, int n_seq, const int32_t* off_host,
                            const int32_t* off_dev, float scale, Drop dl, uint32_t site, float* dQ, int lddq, float* dK, int lddk, float* dV,
                            int lddv, void* ws, hipStream_t stream);
+// its first launch by itself: delta[row, head] = dctx . ctx in fp32 (the bf16x3 backward takes it as it is)
+void launch_attn_stream_bwd_delta(const float* ctx, int ldc, const float* dctx, int ldd, float* delta, int64_t n_rows, int heads, int dh,
+                                  hipStream_t stream);
+// The training form and the backward in the bf16x3 arithmetic (attn_stream_split.hip; attn_stream_split_bwd.hip): precision, head widths and
+// workspace alignment as launch_attn_stream_split, everything else as the two fp32 calls above.  Forward ws: attn_stream_split_ws_bytes;
+// backward ws: attn_stream_split_bwd_ws_bytes (descriptors + delta + the planes of Q, K, V, dctx; 0 = arguments the call refuses).
+int launch_attn_stream_split_train(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int D, int heads, int n_seq,
+                                   const int32_t* off_host, const int32_t* off_dev, float scale, int precision, Drop dl, uint32_t site,
+                                   float* ctx, int ldc, float* stats, void* ws, hipStream_t stream);
+size_t attn_stream_split_bwd_ws_bytes(int D, int heads, int n_seq, const int32_t* off_host, int precision);
+int launch_attn_stream_split_bwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* ctx, int ldc,
+                                 const float* dctx, int ldd, const float* stats, int D, int heads, int n_seq, const int32_t* off_host,
+                                 const int32_t* off_dev, float scale, int precision, Drop dl, uint32_t site, float* dQ, int lddq, float* dK,
+                                 int lddk, float* dV, int lddv, void* ws, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------- shared row kernels (vasnet.hip)
 // Y = LayerNorm(X) * g + b over D (one wave per row); optional (mean, rstd) per row into stats.

@@ -43,6 +43,9 @@ __global__ void mask_scale_kernel(float* __restrict__ dst, const float* __restri
 struct TfRun {
   const TfGeom* G; char* ws; int D, F, heads, n_seq; const int32_t* off_dev; int precision; hipStream_t stream;
   const int32_t* off_host;   // the stream form of the attention blocks needs the host offsets too (null elsewhere)
+  // the stream form in bf16x3 (sumk_transformer_forward_stream_split_train / _backward_stream_split): the attention's precision (0: exact
+  // fp32, the launches of attn_stream.hip / attn_stream_bwd.hip) and where its descriptors, delta and planes lie in ws (behind the carve)
+  int attn_prec; size_t as_split;
 };
 struct TfAttnW { const float* in_w; const float* in_b; const float* out_w; const float* out_b; };
 struct TfAttnG { float* in_w; float* in_b; float* out_w; float* out_b; };
@@ -63,7 +66,8 @@ int tf_attn_core_fwd(const TfRun& r, const GemmProb* tabs, const float* qbase, c
 int tf_attn_core_bwd(const TfRun& r, const GemmProb* tabs, const float* qbase, const float* kvbase, const float* P, float* E2,
                      const float* dCTX, float* dq_base, float* dkv_base, Drop dl, uint32_t site);
 // the stream form of the two cores above for self-attention on the in-place [Q | K | V] (R,3D) buffer (attn_stream.hip,
-// attn_stream_bwd.hip; the stream training carve): no E, E2; astats (R, heads, 2) is the statistic the forward saves for the backward
+// attn_stream_bwd.hip; the stream training carve): no E, E2; astats (R, heads, 2) is the statistic the forward saves for the backward.
+// r.attn_prec picks the core: 0 those two units, SUMK_PRECISION_BF16X3 attn_stream_split.hip / attn_stream_split_bwd.hip
 int tf_attn_stream_fwd(const TfRun& r, const float* QKV, float* CTX, float* astats, Drop dl, uint32_t site);
 int tf_attn_stream_bwd(const TfRun& r, const float* QKV, const float* CTX, const float* dCTX, const float* astats, float* dQKV, Drop dl,
                        uint32_t site);

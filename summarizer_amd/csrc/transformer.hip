@@ -361,6 +361,9 @@ int tf_attn_core_bwd(const TfRun& r, const GemmProb* tabs, const float* qbase, c
 
 int tf_attn_stream_fwd(const TfRun& r, const float* QKV, float* CTX, float* astats, Drop dl, uint32_t site) {
   const int D = r.D;
+  if (r.attn_prec)
+    return launch_attn_stream_split_train(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, r.heads, r.n_seq, r.off_host, r.off_dev,
+                                          1.0f / sqrtf((float)r.G->dh), r.attn_prec, dl, site, CTX, D, astats, r.ws + r.as_split, r.stream);
   return launch_attn_stream_train(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, r.heads, r.n_seq, r.off_host, r.off_dev,
                                   1.0f / sqrtf((float)r.G->dh), dl, site, CTX, D, astats, r.ws + r.G->L.as_seq, r.stream);
 }
@@ -368,6 +371,10 @@ int tf_attn_stream_fwd(const TfRun& r, const float* QKV, float* CTX, float* asta
 int tf_attn_stream_bwd(const TfRun& r, const float* QKV, const float* CTX, const float* dCTX, const float* astats, float* dQKV, Drop dl,
                        uint32_t site) {
   const int D = r.D;
+  if (r.attn_prec)
+    return launch_attn_stream_split_bwd(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, CTX, D, dCTX, D, astats, D, r.heads, r.n_seq, r.off_host,
+                                        r.off_dev, 1.0f / sqrtf((float)r.G->dh), r.attn_prec, dl, site, dQKV, 3 * D, dQKV + D, 3 * D,
+                                        dQKV + 2 * D, 3 * D, r.ws + r.as_split, r.stream);
   return launch_attn_stream_bwd(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, CTX, D, dCTX, D, astats, D, r.heads, r.n_seq, r.off_host,
                                 r.off_dev, 1.0f / sqrtf((float)r.G->dh), dl, site, dQKV, 3 * D, dQKV + D, 3 * D, dQKV + 2 * D, 3 * D,
                                 r.ws + r.G->L.as_seq, r.stream);
@@ -529,7 +536,8 @@ extern "C" int sumk_transformer_wplanes_build(int32_t D, int32_t F, int32_t n_la
 static int tf_forward_any(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
                           const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_tf_layer_weights* layers,
                           const sumk_tf_head_weights* head, const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
-                          float* scores, void* workspace, size_t workspace_bytes, int32_t training, bool stream_attn, void* stream_) {
+                          float* scores, void* workspace, size_t workspace_bytes, int32_t training, bool stream_attn, int attn_prec,
+                          void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SUMK_ARG(x && seq_off_dev && layers && head && opts && scores && workspace, "transformer_forward: null pointer");
   if (stream_attn) {
@@ -544,7 +552,12 @@ static int tf_forward_any(float* x, int32_t D, int32_t F, int32_t n_heads, int32
   TfGeom G;
   SUMK_TRY(tf_geometry_any(D, F, n_heads, n_layers, n_seq, seq_off_host, training, !stream_attn, &G));
   const TfWs& L = G.L;
-  if (workspace_bytes < L.total) { set_error("transformer_forward: workspace %zu < required %zu", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
+  size_t split_ws = 0;                            // attn_prec: the bf16x3 attention's descriptors, delta and planes lie behind the carve
+  if (attn_prec) {
+    split_ws = attn_stream_split_bwd_ws_bytes(D, n_heads, n_seq, seq_off_host, attn_prec);
+    if (!split_ws) return SUMK_ERR_ARG;           // the message is attn_stream_split_backward's
+  }
+  if (workspace_bytes < L.total + split_ws) { set_error("transformer_forward: workspace %zu < required %zu", workspace_bytes, L.total + split_ws); return SUMK_ERR_WORKSPACE; }
   char* ws = (char*)workspace;
   const int R = G.R, dh = G.dh;
   // the plane path: inference in a split-bf16 arithmetic with the weights' planes at hand
@@ -576,7 +589,7 @@ static int tf_forward_any(float* x, int32_t D, int32_t F, int32_t n_heads, int32
   float* T1 = (float*)(ws + L.t1);
   const Drop dl = make_drop(opts->layer_dropout_p, opts->seed), dhd = make_drop(opts->head_dropout_p, opts->seed);
   const float att_scale = 1.0f / sqrtf((float)dh);
-  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream, seq_off_host};
+  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream, seq_off_host, attn_prec, L.total};
 
   if (pos_table) SUMK_TRY(launch_add_pos(x, pos_table, pos_rows, R, D, stream));
   SUMK_TRY(tf_tables(G, D, F, n_heads, n_seq, seq_off_dev, ws, stream, !stream_attn));
@@ -657,7 +670,7 @@ extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t 
                                         float* scores, void* workspace, size_t workspace_bytes, int32_t training,
                                         void* stream_) {
   return tf_forward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores, workspace,
-                        workspace_bytes, training, false, stream_);
+                        workspace_bytes, training, false, 0, stream_);
 }
 
 // ---- training on the stream path: the training forward and the backward with every layer's attention on attn_stream.hip /
@@ -676,7 +689,29 @@ extern "C" int sumk_transformer_forward_stream_train(float* x, int32_t D, int32_
                                                      const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
                                                      float* scores, void* workspace, size_t workspace_bytes, void* stream_) {
   return tf_forward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores, workspace,
-                        workspace_bytes, 1, true, stream_);
+                        workspace_bytes, 1, true, 0, stream_);
+}
+
+// ---- the same two entries with every layer's attention in bf16x3 (attn_stream_split.hip's training form, attn_stream_split_bwd.hip):
+// the stream training carve + the descriptors, delta and planes of ONE layer (re-split in the backward from the saved [Q | K | V]);
+// projections and everything else stay exact fp32
+extern "C" size_t sumk_transformer_stream_split_train_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                                      const int32_t* seq_off_host, int32_t attention_precision) {
+  const size_t planes = attn_stream_split_bwd_ws_bytes(D, n_heads, n_seq, seq_off_host, attention_precision);
+  const size_t base = planes ? sumk_transformer_stream_train_workspace_bytes(D, F, n_heads, n_layers, n_seq, seq_off_host) : 0;
+  return base ? base + planes : 0;
+}
+
+extern "C" int sumk_transformer_forward_stream_split_train(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                           const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                                           const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                                           const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
+                                                           float* scores, int32_t attention_precision, void* workspace,
+                                                           size_t workspace_bytes, void* stream_) {
+  SUMK_ARG(attention_precision == SUMK_PRECISION_BF16X3, "transformer_forward_stream_split_train: attention_precision=%d (only SUMK_PRECISION_BF16X3 = %d)",
+           attention_precision, SUMK_PRECISION_BF16X3);
+  return tf_forward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores, workspace,
+                        workspace_bytes, 1, true, attention_precision, stream_);
 }
 
 // ---- the stream path: the inference of sumk_transformer_forward with tf_attn_core_fwd replaced by attn_stream.hip's launch; no `e` in the carve
@@ -785,7 +820,7 @@ static int tf_backward_any(const float* x, int32_t D, int32_t F, int32_t n_heads
                            const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_tf_layer_weights* layers,
                            const sumk_tf_head_weights* head, const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* lgr,
                            const sumk_tf_head_grads* hgr, float* dx, void* workspace, size_t workspace_bytes, bool stream_attn,
-                           void* stream_) {
+                           int attn_prec, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SUMK_ARG(x && seq_off_dev && layers && head && opts && dscores && lgr && hgr && workspace, "transformer_backward: null pointer");
   if (stream_attn) {
@@ -796,7 +831,12 @@ static int tf_backward_any(const float* x, int32_t D, int32_t F, int32_t n_heads
   TfGeom G;
   SUMK_TRY(tf_geometry_any(D, F, n_heads, n_layers, n_seq, seq_off_host, 1, !stream_attn, &G));
   const TfWs& L = G.L;
-  if (workspace_bytes < L.total) { set_error("transformer_backward: workspace %zu < required %zu (needs the training-mode forward's workspace)", workspace_bytes, L.total); return SUMK_ERR_WORKSPACE; }
+  size_t split_ws = 0;
+  if (attn_prec) {
+    split_ws = attn_stream_split_bwd_ws_bytes(D, n_heads, n_seq, seq_off_host, attn_prec);
+    if (!split_ws) return SUMK_ERR_ARG;           // the message is attn_stream_split_backward's
+  }
+  if (workspace_bytes < L.total + split_ws) { set_error("transformer_backward: workspace %zu < required %zu (needs the training-mode forward's workspace)", workspace_bytes, L.total + split_ws); return SUMK_ERR_WORKSPACE; }
   char* ws = (char*)workspace;
   const int R = G.R;
   const int64_t nRD = (int64_t)R * D;
@@ -810,7 +850,7 @@ static int tf_backward_any(const float* x, int32_t D, int32_t F, int32_t n_heads
   const Drop dl = make_drop(opts->layer_dropout_p, opts->seed), dhd = make_drop(opts->head_dropout_p, opts->seed);
   const Drop none = make_drop(0.f, 0);
   int nw = 0;
-  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream, seq_off_host};
+  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream, seq_off_host, attn_prec, L.total};
   auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
   auto nn = [&](const float* A, const float* B, float* C, int prob, GemmEpi epi, int N) -> int {   // C (op)= A . B, B stored (K, N)
     GemmLaunch g; g.precision = opts->precision;
@@ -884,7 +924,7 @@ extern "C" int sumk_transformer_backward(const float* x, int32_t D, int32_t F, i
                                          const sumk_tf_head_grads* hgr, float* dx, void* workspace, size_t workspace_bytes,
                                          void* stream_) {
   return tf_backward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, dscores, lgr, hgr, dx, workspace,
-                         workspace_bytes, false, stream_);
+                         workspace_bytes, false, 0, stream_);
 }
 
 extern "C" int sumk_transformer_backward_stream(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
@@ -894,5 +934,17 @@ extern "C" int sumk_transformer_backward_stream(const float* x, int32_t D, int32
                                                 const sumk_tf_head_grads* hgr, float* dx, void* workspace, size_t workspace_bytes,
                                                 void* stream_) {
   return tf_backward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, dscores, lgr, hgr, dx, workspace,
-                         workspace_bytes, true, stream_);
+                         workspace_bytes, true, 0, stream_);
+}
+
+extern "C" int sumk_transformer_backward_stream_split(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
+                                                      int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                                      const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                                      const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* lgr,
+                                                      const sumk_tf_head_grads* hgr, float* dx, int32_t attention_precision, void* workspace,
+                                                      size_t workspace_bytes, void* stream_) {
+  SUMK_ARG(attention_precision == SUMK_PRECISION_BF16X3, "transformer_backward_stream_split: attention_precision=%d (only SUMK_PRECISION_BF16X3 = %d)",
+           attention_precision, SUMK_PRECISION_BF16X3);
+  return tf_backward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, dscores, lgr, hgr, dx, workspace,
+                         workspace_bytes, true, attention_precision, stream_);
 }

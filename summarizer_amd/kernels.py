@@ -1102,6 +1102,14 @@ def _tf_attention_precision(attention, attention_precision, training):
     return code
 
 
+def _tf_attention_train_precision(attention, attention_train_precision, training):
+    """None for "fp32", else the code of the bf16x3 stream TRAINING entries: training=True on attention="stream" only."""
+    code = _stream_precision(attention_train_precision, "transformer attention (training)")
+    if code is not None and (_tf_attention(attention) != "stream" or not training):
+        raise SumkError(f"transformer: attention_train_precision={attention_train_precision!r} needs attention=\"stream\" and training=True")
+    return code
+
+
 def attn_strips_b16_sizes(sb):
     """(elements of E, elements of P16) the bf16 attention strips address for a batch (sumk_attn_strips_b16_sizes; host arithmetic)."""
     e, p = C.c_int64(0), C.c_int64(0)
@@ -1189,19 +1197,28 @@ def _attn_stream_args(fn, tensors, sb):
             raise SumkError(f"{fn}: {what} must be (n_rows={sb.n_rows}, D) with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
 
 
-def attn_stream_train(q, k, v, sb, n_heads, scale=None, dropout_p=0.0, seed=0, site=0):
+def attn_stream_train(q, k, v, sb, n_heads, scale=None, dropout_p=0.0, seed=0, site=0, precision="fp32"):
     """attn_stream in its training form (sumk_attn_stream_train): the weights dropped with probability dropout_p by the library's hash masks
     of (seed, site) -- the masks the dense Transformer path draws at that site -- and, for attn_stream_backward, stats (n_rows, n_heads, 2):
     the row maximum of the scaled logits and the sum of exp(s - max).  With dropout_p == 0 ctx has attn_stream's bits.
+    precision="bf16x3": both products in the split-bf16 arithmetic (sumk_attn_stream_split_train; head widths % 8 == 0, up to 128; same
+    masks); the default keeps the exact call and its bits.
     Returns (ctx, stats).  Only enqueues work."""
     lib = _lib.load()
+    code = _stream_precision(precision, "attn_stream_train")
     _attn_stream_args("attn_stream_train", ((q, "q"), (k, "k"), (v, "v")), sb)
     D = q.shape[1]
-    nb = attn_stream_workspace_bytes(D, n_heads, sb)
+    nb = attn_stream_workspace_bytes(D, n_heads, sb, precision)
     ws = workspace(nb, q.device)
     ctx = torch.empty(sb.n_rows, D, dtype=torch.float32, device=q.device)
     stats = torch.empty(sb.n_rows, int(n_heads), 2, dtype=torch.float32, device=q.device)
     sc = 1.0 / math.sqrt(D // int(n_heads)) if scale is None else float(scale)
+    if code is not None:
+        rc = lib.sumk_attn_stream_split_train(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq,
+                                              sb.off_host_p, sb.off_dev_p, sc, float(dropout_p), int(seed), int(site), _p(ctx), D, _p(stats),
+                                              _p(ws), ws.numel(), _stream(), code)
+        _lib.check(rc, "sumk_attn_stream_split_train")
+        return ctx, stats
     rc = lib.sumk_attn_stream_train(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq, sb.off_host_p,
                                     sb.off_dev_p, sc, float(dropout_p), int(seed), int(site), _p(ctx), D, _p(stats), _p(ws), ws.numel(),
                                     _stream())
@@ -1209,46 +1226,67 @@ def attn_stream_train(q, k, v, sb, n_heads, scale=None, dropout_p=0.0, seed=0, s
     return ctx, stats
 
 
-def attn_stream_backward_workspace_bytes(D, n_heads, sb):
-    """Bytes of scratch one attn_stream_backward call takes: 16 per video + 4 per (row, head)."""
+def attn_stream_backward_workspace_bytes(D, n_heads, sb, precision="fp32"):
+    """Bytes of scratch one attn_stream_backward call takes: 16 per video + 4 per (row, head); precision="bf16x3": 24 per video + 4 per (row,
+    head) + the bf16 planes of Q, K, V and dctx, 28 bytes per (padded row, staged column)."""
+    code = _stream_precision(precision, "attn_stream_backward")
+    if code is not None:
+        return _nonzero(_lib.load().sumk_attn_stream_split_backward_workspace_bytes(int(D), int(n_heads), sb.n_seq, sb.off_host_p, code),
+                        "sumk_attn_stream_split_backward_workspace_bytes")
     return _nonzero(_lib.load().sumk_attn_stream_backward_workspace_bytes(int(D), int(n_heads), sb.n_seq, sb.off_host_p),
                     "sumk_attn_stream_backward_workspace_bytes")
 
 
-def attn_stream_backward(q, k, v, ctx, dctx, stats, sb, n_heads, scale=None, dropout_p=0.0, seed=0, site=0, out=None):
+def attn_stream_backward(q, k, v, ctx, dctx, stats, sb, n_heads, scale=None, dropout_p=0.0, seed=0, site=0, out=None, precision="fp32", ws=None):
     """Backward of attn_stream_train without anything of size T x T (csrc/attn_stream_bwd.hip; head widths up to 128): ctx and stats are that
     call's results, scale / dropout_p / seed / site its arguments.  Returns (dq, dk, dv), each (n_rows, D) -- the column blocks of one
-    (n_rows, 3 D) buffer, `out` when given.  Deterministic; only enqueues work."""
+    (n_rows, 3 D) buffer, `out` when given.  precision="bf16x3": the seven products in the split-bf16 arithmetic
+    (csrc/attn_stream_split_bwd.hip).  ws: a uint8 scratch tensor of at least attn_stream_backward_workspace_bytes, else the shared one.
+    Deterministic; only enqueues work."""
     lib = _lib.load()
+    code = _stream_precision(precision, "attn_stream_backward")
     _attn_stream_args("attn_stream_backward", ((q, "q"), (k, "k"), (v, "v"), (ctx, "ctx"), (dctx, "dctx")), sb)
     D = q.shape[1]
     _require_gpu(stats, "attn_stream_backward stats")
     if tuple(stats.shape) != (sb.n_rows, int(n_heads), 2) or not stats.is_contiguous():
         raise SumkError(f"attn_stream_backward: stats must be contiguous (n_rows={sb.n_rows}, n_heads={int(n_heads)}, 2), got {tuple(stats.shape)}")
-    nb = attn_stream_backward_workspace_bytes(D, n_heads, sb)
-    ws = workspace(nb, q.device)
+    nb = attn_stream_backward_workspace_bytes(D, n_heads, sb, precision)
+    if ws is None:
+        ws = workspace(nb, q.device)
+    else:
+        if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nb:
+            raise SumkError(f"attn_stream_backward: ws must be a contiguous uint8 GPU tensor of at least {nb} bytes")
     if out is None:
         out = torch.empty(sb.n_rows, 3 * D, dtype=torch.float32, device=q.device)
     elif tuple(out.shape) != (sb.n_rows, 3 * D) or not out.is_contiguous():
         raise SumkError(f"attn_stream_backward: out must be contiguous (n_rows={sb.n_rows}, {3 * D}), got {tuple(out.shape)}")
     dq, dk, dv = out[:, :D], out[:, D:2 * D], out[:, 2 * D:]
     sc = 1.0 / math.sqrt(D // int(n_heads)) if scale is None else float(scale)
-    rc = lib.sumk_attn_stream_backward(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(ctx), ctx.stride(0), _p(dctx),
-                                       dctx.stride(0), _p(stats), D, int(n_heads), sb.n_seq, sb.off_host_p, sb.off_dev_p, sc,
-                                       float(dropout_p), int(seed), int(site), _p(dq), 3 * D, _p(dk), 3 * D, _p(dv), 3 * D, _p(ws),
-                                       ws.numel(), _stream())
-    _lib.check(rc, "sumk_attn_stream_backward")
+    args = (_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(ctx), ctx.stride(0), _p(dctx), dctx.stride(0), _p(stats), D,
+            int(n_heads), sb.n_seq, sb.off_host_p, sb.off_dev_p, sc, float(dropout_p), int(seed), int(site), _p(dq), 3 * D, _p(dk), 3 * D,
+            _p(dv), 3 * D, _p(ws), ws.numel(), _stream())
+    if code is not None:
+        _lib.check(lib.sumk_attn_stream_split_backward(*args, code), "sumk_attn_stream_split_backward")
+    else:
+        _lib.check(lib.sumk_attn_stream_backward(*args), "sumk_attn_stream_backward")
     return dq, dk, dv
 
 
-def transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, attention="dense", training=False, attention_precision="fp32"):
+def transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, attention="dense", training=False, attention_precision="fp32",
+                                attention_train_precision="fp32"):
     """Bytes of scratch one call takes in exact fp32 (attention_precision="bf16x3", scoring on "stream" only: + the bf16 planes of one
     layer's [Q | K | V], sumk_transformer_stream_split_workspace_bytes).  Scoring: "dense" holds heads x T x T logits per video
     (sumk_transformer_workspace_bytes), "stream" none (sumk_transformer_stream_workspace_bytes).  training=True, the forward that keeps
     what the backward needs: "dense" keeps two heads x T x T blocks per video and layer, "stream" 8 bytes per (row, head) and layer
-    (sumk_transformer_stream_train_workspace_bytes)."""
+    (sumk_transformer_stream_train_workspace_bytes); attention_train_precision="bf16x3" (training on "stream" only): + the descriptors,
+    delta and planes of one layer's attention backward (sumk_transformer_stream_split_train_workspace_bytes)."""
     lib = _lib.load()
     code = _tf_attention_precision(attention, attention_precision, training)
+    tcode = _tf_attention_train_precision(attention, attention_train_precision, training)
+    if tcode is not None:
+        return _nonzero(lib.sumk_transformer_stream_split_train_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq,
+                                                                                sb.off_host_p, tcode),
+                        "sumk_transformer_stream_split_train_workspace_bytes")
     if code is not None:
         return _nonzero(lib.sumk_transformer_stream_split_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq,
                                                                           sb.off_host_p, code), "sumk_transformer_stream_split_workspace_bytes")
@@ -1263,18 +1301,32 @@ def transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, attention="dense"
 
 
 def transformer_forward_packed(x, sb, params, n_layers, n_heads, dff, opts, pos_table=None, pos_rows=None, training=False,
-                               attention="dense", attention_precision="fp32"):
+                               attention="dense", attention_precision="fp32", attention_train_precision="fp32"):
     """x: (n_rows, D) packed -> (scores (n_rows,), workspace or None).  params: state_dict-keyed tensors.
     attention="stream" (exact fp32 only): every layer's attention on csrc/attn_stream.hip, no (T x T) logits in the workspace
     (sumk_transformer_forward_stream; training=True: sumk_transformer_forward_stream_train, whose workspace goes to
     transformer_backward_packed(..., attention="stream")).  attention_precision="bf16x3" (scoring on "stream" only): every layer's
-    attention on csrc/attn_stream_split.hip, the projections still exact fp32 (sumk_transformer_forward_stream_split)."""
+    attention on csrc/attn_stream_split.hip, the projections still exact fp32 (sumk_transformer_forward_stream_split).
+    attention_train_precision="bf16x3" (training=True on "stream" only): every layer's attention on the bf16x3 training form
+    (sumk_transformer_forward_stream_split_train; the backward takes the same argument)."""
     lib = _lib.load()
     _check_rows(x, sb, "transformer input")
     D = x.shape[1]
     layers, head = _tf_structs(params, n_layers, "weight", _lib.TfLayerWeights, _lib.TfHeadWeights)
     o = _tf_opts(opts)
     code = _tf_attention_precision(attention, attention_precision, training)
+    tcode = _tf_attention_train_precision(attention, attention_train_precision, training)
+    if tcode is not None:
+        nbytes = transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, "stream", training=True,
+                                             attention_train_precision=attention_train_precision)
+        ws = workspace(nbytes, x.device, persistent=True)
+        scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
+        rc = lib.sumk_transformer_forward_stream_split_train(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
+                                                             C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
+                                                             C.cast(C.pointer(o), C.c_void_p), _p(pos_table), _p(pos_rows), _p(scores),
+                                                             tcode, _p(ws), ws.numel(), _stream())
+        _lib.check(rc, "sumk_transformer_forward_stream_split_train")
+        return scores, ws
     if code is not None:
         nbytes = transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, "stream", attention_precision=attention_precision)
         ws = workspace(nbytes, x.device)
@@ -1317,8 +1369,9 @@ def transformer_forward_packed(x, sb, params, n_layers, n_heads, dff, opts, pos_
     return scores, (ws if training else None)
 
 
-def transformer_backward_packed(x, sb, params, grads, n_layers, n_heads, dff, opts, dscores, ws, want_dx=False, attention="dense"):
-    """attention: the one of the training forward that filled `ws`."""
+def transformer_backward_packed(x, sb, params, grads, n_layers, n_heads, dff, opts, dscores, ws, want_dx=False, attention="dense",
+                                attention_train_precision="fp32"):
+    """attention, attention_train_precision: those of the training forward that filled `ws`."""
     lib = _lib.load()
     D = x.shape[1]
     layers, head = _tf_structs(params, n_layers, "weight", _lib.TfLayerWeights, _lib.TfHeadWeights)
@@ -1327,6 +1380,14 @@ def transformer_backward_packed(x, sb, params, grads, n_layers, n_heads, dff, op
     dx = torch.empty_like(x) if want_dx else None
     if not dscores.is_contiguous():
         dscores = dscores.contiguous()
+    tcode = _tf_attention_train_precision(attention, attention_train_precision, True)
+    if tcode is not None:
+        rc = lib.sumk_transformer_backward_stream_split(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
+                                                        C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
+                                                        C.cast(C.pointer(o), C.c_void_p), _p(dscores), C.cast(glayers, C.c_void_p),
+                                                        C.cast(C.pointer(ghead), C.c_void_p), _p(dx), tcode, _p(ws), ws.numel(), _stream())
+        _lib.check(rc, "sumk_transformer_backward_stream_split")
+        return dx
     entry = "sumk_transformer_backward_stream" if _tf_attention(attention) == "stream" else "sumk_transformer_backward"
     rc = getattr(lib, entry)(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
                              C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),

@@ -23,7 +23,7 @@ from ..training import FlatAdam, dist_info, plan_shards, step_video_total
 class Transformer(PositionalInput, nn.Module):
     def __init__(self, input_size=1024, encoder_layers=6, attention_heads=8, more_residuals=False, max_length=None,
                  pos_embed="simple", epsilon=1e-5, weight_init=None, attention="dense", attention_train="dense",
-                 attention_precision="fp32"):
+                 attention_precision="fp32", attention_train_precision="fp32"):
         super().__init__()
         # attention (not in the reference, opt-in): how a no-grad call computes the multi-head attention of every layer.
         #   "dense"   heads x T x T logits per video in the workspace (csrc/transformer.hip): the default, every precision;
@@ -37,6 +37,10 @@ class Transformer(PositionalInput, nn.Module):
         #   "fp32"    exact (csrc/attn_stream.hip): the default, its bits unchanged;
         #   "bf16x3"  hi + lo bf16 planes, three bf16 MFMAs per product (csrc/attn_stream_split.hip): head widths % 8 == 0 up to 128;
         #             the projections stay exact fp32.  A separate argument because `precision` other than "fp32" is refused with "stream".
+        # attention_train_precision (opt-in, attention_train="stream" only; governs the autograd branch alone): the same choice for training.
+        #   "fp32"    exact (csrc/attn_stream.hip, csrc/attn_stream_bwd.hip): the default, its bits unchanged;
+        #   "bf16x3"  the seven attention products of a training step on the bf16 MFMA (csrc/attn_stream_split.hip's training form,
+        #             csrc/attn_stream_split_bwd.hip): head widths % 8 == 0 up to 128, the same masks; everything else stays exact fp32.
         if attention not in kernels.TF_ATTENTION:
             raise ValueError(f"Transformer: attention must be one of {kernels.TF_ATTENTION}, got {attention!r}")
         if attention_train not in kernels.TF_ATTENTION:
@@ -45,7 +49,13 @@ class Transformer(PositionalInput, nn.Module):
             raise ValueError(f"Transformer: attention_precision must be one of {kernels.TF_ATTENTION_PRECISION}, got {attention_precision!r}")
         if attention_precision != "fp32" and attention != "stream":
             raise ValueError(f"Transformer: attention_precision={attention_precision!r} needs attention='stream', got attention={attention!r}")
+        if attention_train_precision not in kernels.TF_ATTENTION_PRECISION:
+            raise ValueError(f"Transformer: attention_train_precision must be one of {kernels.TF_ATTENTION_PRECISION}, got {attention_train_precision!r}")
+        if attention_train_precision != "fp32" and attention_train != "stream":
+            raise ValueError(f"Transformer: attention_train_precision={attention_train_precision!r} needs attention_train='stream', "
+                             f"got attention_train={attention_train!r}")
         self.attention, self.attention_train, self.attention_precision = attention, attention_train, attention_precision
+        self.attention_train_precision = attention_train_precision
         self.input_size = input_size
         self.encoder_layers, self.attention_heads, self.epsilon = encoder_layers, attention_heads, epsilon
         self._init_pos_embed(max_length, pos_embed)
@@ -84,7 +94,8 @@ class Transformer(PositionalInput, nn.Module):
     def _score(self, xp, sb, table, rows):
         """attention="stream": the no-grad branch scores through sumk_transformer_forward_stream (exact fp32; any other `precision`
         raises ValueError), its attention products in attention_precision.  The autograd branch follows attention_train alone: "dense"
-        (default) gives the gradients it always gave, bit for bit; "stream" runs sumk_transformer_forward_stream_train / _backward_stream (exact fp32; any other `precision` raises)."""
+        (default) gives the gradients it always gave, bit for bit; "stream" runs sumk_transformer_forward_stream_train / _backward_stream (exact fp32; any other `precision` raises), or with
+        attention_train_precision="bf16x3" their _split forms: the attention products in bf16x3, everything else exact fp32."""
         p = dict(self.named_parameters())
         opts = dict(layer_eps=1e-5, final_eps=self.epsilon, more_residuals=self.more_residuals,
                     precision=getattr(self, "precision", "fp32"))
@@ -102,6 +113,7 @@ class Transformer(PositionalInput, nn.Module):
                     raise ValueError(f"Transformer(attention_train='stream') trains in exact fp32: precision={opts['precision']!r} needs "
                                      "attention_train='dense' (or precision='fp32' with attention_train='stream')")
                 cfg["attention"] = "stream"
+                cfg["attention_train_precision"] = self.attention_train_precision
             return TransformerFunction.apply(xp, sb, cfg, opts, table, rows, names, *[p[n] for n in names])
         if self.attention == "stream":
             if opts["precision"] not in (None, "fp32"):
@@ -131,7 +143,8 @@ class TransformerTrainer(Trainer):
     flat-bucket gradient all-reduce per step under torch.distributed.  extra_params["attention"] = "stream" scores (test, summaries)
     without the (T x T) logits (Transformer's argument of that name); extra_params["attention_train"] = "stream" trains without the
     (T x T) blocks (Transformer's attention_train); each defaults to "dense" and neither implies the other.
-    extra_params["attention_precision"] = "bf16x3" (with attention "stream") scores with the attention products in the split-bf16 arithmetic."""
+    extra_params["attention_precision"] = "bf16x3" (with attention "stream") scores with the attention products in the split-bf16 arithmetic;
+    extra_params["attention_train_precision"] = "bf16x3" (with attention_train "stream") trains with them."""
     def _init_model(self):
         ep = self.hps.extra_params
         model = Transformer(
@@ -145,6 +158,7 @@ class TransformerTrainer(Trainer):
             attention=ep.get("attention", "dense"),
             attention_train=ep.get("attention_train", "dense"),
             attention_precision=ep.get("attention_precision", "fp32"),
+            attention_train_precision=ep.get("attention_train_precision", "fp32"),
             **({"input_size": int(ep["input_size"])} if "input_size" in ep else {}))
         model.precision = ep.get("precision", "fp32")      # "fp32" | "bf16x3" (kernels.precision_code)
         if self.hps.use_cuda:
