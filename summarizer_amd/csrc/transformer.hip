@@ -33,11 +33,9 @@ static TfWPlanes tf_wplanes_layout(int D, int F, int n_layers, int np) {
   l.total = l.k1 + align_up(pw_planes_bytes(D, D, np), 256);
   return l;
 }
-// ... and, when the batch is eligible (T <= 320, heads of 128 columns: attn_pw.hip's multi-head form), the attention on planes too: [Q | K | V] planes
-// written by the in-projection's epilogue, one set of alpha planes per head, the SeqInfo table those kernels read.
-struct TfPwExtra { size_t pa, pb, qp, ap, seqinfo, total; bool attn; };
+// ... and, when the batch is eligible, the attention on planes too (TfPwExtra, tf_internal.h)
 static TfPwExtra tf_pw_extra(int D, int F, int64_t R, int np, size_t base, int heads, int n_seq, int t_max) {
-  TfPwExtra e; size_t p = align_up(base, 256);
+  TfPwExtra e; size_t p = align_up(base, 256); e.t_max = t_max;
   auto take = [&](size_t bytes) { size_t at = p; p += align_up(bytes, 256); return at; };
   e.pa = take(pw_planes_bytes(R, std::max(D, F), np)); e.pb = take(pw_planes_bytes(R, std::max(D, F), np));
   e.attn = attn_pw_heads_ok(t_max, D, heads, R, np);
@@ -272,6 +270,36 @@ int tf_geometry(int D, int F, int heads, int n_layers, int n_seq, const int32_t*
   return tf_geometry_any(D, F, heads, n_layers, n_seq, off, training, true, G);
 }
 
+int tf_plan(const char* what, int attn, int training, int attn_prec, int D, int F, int heads, int n_layers, int n_seq, const int32_t* off_host,
+            const sumk_tf_opts* opts, TfPlan* P) {
+  P->stream = attn != TF_DENSE; P->training = training != 0; P->attn_prec = attn == TF_STREAM_SPLIT ? attn_prec : 0; P->planes = 0; P->px = TfPwExtra{};
+  SUMK_ARG(n_layers >= 1, "%s: n_layers=%d", what, n_layers);
+  SUMK_ARG(attn != TF_STREAM_SPLIT || attn_prec == SUMK_PRECISION_BF16X3, "%s: attention_precision=%d (only SUMK_PRECISION_BF16X3 = %d)", what,
+           attn_prec, SUMK_PRECISION_BF16X3);
+  SUMK_TRY(tf_geometry_any(D, F, heads, n_layers, n_seq, off_host, P->training, !P->stream, &P->G));
+  P->tail = P->G.L.total; P->tail_bytes = 0;
+  if (P->stream) {
+    SUMK_ARG(!opts || (opts->precision == SUMK_PRECISION_FP32 && !opts->wplanes), "%s: exact fp32 only (precision=%d, wplanes %s)", what,
+             opts->precision, opts->wplanes ? "given" : "null");
+    SUMK_TRY(P->training ? attn_stream_bwd_check(D, heads, n_seq, off_host) : attn_stream_check(D, heads, n_seq, off_host));
+    if (P->attn_prec) {   // one layer's descriptors, (training: delta) and planes; a refusal's message is the attention unit's
+      P->tail_bytes = P->training ? attn_stream_split_bwd_ws_bytes(D, heads, n_seq, off_host, P->attn_prec)
+                                  : attn_stream_split_ws_bytes(D, heads, n_seq, off_host, P->attn_prec);
+      if (!P->tail_bytes) return SUMK_ERR_ARG;
+    }
+  }
+  if (opts && (opts->layer_dropout_p != 0.f || opts->head_dropout_p != 0.f))
+    SUMK_ARG(P->training, P->stream ? "%s: inference only (dropout must be 0)" : "%s: dropout needs training mode", what);
+  const int np = opts && opts->wplanes ? tf_np(opts->precision) : 0;
+  if (!P->stream && !P->training && np && tf_wplanes_ok(D, F, np) && tf_pw_rows_ok(D, F, P->G.R, np)) {
+    P->planes = np;
+    P->px = tf_pw_extra(D, F, P->G.R, np, P->tail, heads, n_seq, tf_t_max(n_seq, off_host));
+    P->tail_bytes = P->px.total - P->tail;
+  }
+  P->total = P->tail + P->tail_bytes;
+  return SUMK_OK;
+}
+
 int tf_tables(const TfGeom& G, int D, int F, int heads, int n_seq, const int32_t* off_dev, char* ws, hipStream_t stream, bool head_tables) {
   const int R = G.R;
   GemmProb* prow = (GemmProb*)(ws + G.L.prob_row);
@@ -360,21 +388,26 @@ int tf_attn_core_bwd(const TfRun& r, const GemmProb* tabs, const float* qbase, c
 }
 
 int tf_attn_stream_fwd(const TfRun& r, const float* QKV, float* CTX, float* astats, Drop dl, uint32_t site) {
-  const int D = r.D;
-  if (r.attn_prec)
-    return launch_attn_stream_split_train(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, r.heads, r.n_seq, r.off_host, r.off_dev,
-                                          1.0f / sqrtf((float)r.G->dh), r.attn_prec, dl, site, CTX, D, astats, r.ws + r.as_split, r.stream);
-  return launch_attn_stream_train(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, r.heads, r.n_seq, r.off_host, r.off_dev,
-                                  1.0f / sqrtf((float)r.G->dh), dl, site, CTX, D, astats, r.ws + r.G->L.as_seq, r.stream);
+  const int D = r.D, prec = r.plan->attn_prec; const float scale = 1.0f / sqrtf((float)r.G->dh);
+  char* const split_ws = r.ws + r.plan->tail; char* const as_seq = r.ws + r.G->L.as_seq;
+  if (!astats)   // scoring: no statistic, no masks
+    return prec ? launch_attn_stream_split(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, r.heads, r.n_seq, r.off_host, r.off_dev, scale, prec,
+                                           CTX, D, nullptr, split_ws, r.stream)
+                : launch_attn_stream(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, r.heads, r.n_seq, r.off_host, r.off_dev, scale, CTX, D,
+                                     nullptr, as_seq, r.stream);
+  return prec ? launch_attn_stream_split_train(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, r.heads, r.n_seq, r.off_host, r.off_dev, scale,
+                                               prec, dl, site, CTX, D, astats, split_ws, r.stream)
+              : launch_attn_stream_train(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, r.heads, r.n_seq, r.off_host, r.off_dev, scale, dl, site,
+                                         CTX, D, astats, as_seq, r.stream);
 }
 
 int tf_attn_stream_bwd(const TfRun& r, const float* QKV, const float* CTX, const float* dCTX, const float* astats, float* dQKV, Drop dl,
                        uint32_t site) {
   const int D = r.D;
-  if (r.attn_prec)
+  if (r.plan->attn_prec)
     return launch_attn_stream_split_bwd(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, CTX, D, dCTX, D, astats, D, r.heads, r.n_seq, r.off_host,
-                                        r.off_dev, 1.0f / sqrtf((float)r.G->dh), r.attn_prec, dl, site, dQKV, 3 * D, dQKV + D, 3 * D,
-                                        dQKV + 2 * D, 3 * D, r.ws + r.as_split, r.stream);
+                                        r.off_dev, 1.0f / sqrtf((float)r.G->dh), r.plan->attn_prec, dl, site, dQKV, 3 * D, dQKV + D, 3 * D,
+                                        dQKV + 2 * D, 3 * D, r.ws + r.plan->tail, r.stream);
   return launch_attn_stream_bwd(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, CTX, D, dCTX, D, astats, D, r.heads, r.n_seq, r.off_host,
                                 r.off_dev, 1.0f / sqrtf((float)r.G->dh), dl, site, dQKV, 3 * D, dQKV + D, 3 * D, dQKV + 2 * D, 3 * D,
                                 r.ws + r.G->L.as_seq, r.stream);
@@ -383,7 +416,7 @@ int tf_attn_stream_bwd(const TfRun& r, const float* QKV, const float* CTX, const
 int tf_sa_fwd(const TfRun& r, const TfAttnW& W, const float* hin, float* QKV, float* E, float* E2, float* CTX, float* T1a, Drop dl,
               uint32_t site, float* astats) {
   SUMK_TRY(tf_in_proj(r, hin, W.in_w, W.in_b, QKV));
-  if (astats) SUMK_TRY(tf_attn_stream_fwd(r, QKV, CTX, astats, dl, site + 0));
+  if (r.plan && r.plan->stream) SUMK_TRY(tf_attn_stream_fwd(r, QKV, CTX, astats, dl, site + 0));
   else SUMK_TRY(tf_attn_core_fwd(r, (const GemmProb*)(r.ws + r.G->L.prob_tabs), QKV, QKV, E, E2, CTX, dl, site + 0));
   return tf_out_proj(r, CTX, W.out_w, W.out_b, hin, T1a, dl, site + 1);
 }
@@ -486,21 +519,43 @@ static int tf_tail(const TfRun& r, const float* x, const float* hin, float* hfin
 
 using namespace sumk;
 
+// ---- the size queries: each names its path to the plan (0 = arguments the path refuses, the reason in sumk_last_error())
+static size_t tf_query(const char* what, int attn, int training, int attn_prec, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
+                       int32_t n_seq, const int32_t* seq_off_host, const sumk_tf_opts* opts = nullptr) {
+  TfPlan P;
+  return tf_plan(what, attn, training, attn_prec, D, F, n_heads, n_layers, n_seq, seq_off_host, opts, &P) == SUMK_OK ? P.total : 0;
+}
+
 extern "C" size_t sumk_transformer_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
                                                    const int32_t* seq_off_host, int32_t training) {
-  TfWs w;
-  if (tf_carve(D, F, n_heads, n_layers, n_seq, seq_off_host, training, &w) != SUMK_OK) return 0;
-  return w.total;
+  return tf_query("transformer_workspace_bytes", TF_DENSE, training, 0, D, F, n_heads, n_layers, n_seq, seq_off_host);
 }
 
 extern "C" size_t sumk_transformer_workspace_bytes_for(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
                                                        const int32_t* seq_off_host, int32_t training, int32_t precision) {
-  TfWs w;
-  if (tf_carve(D, F, n_heads, n_layers, n_seq, seq_off_host, training, &w) != SUMK_OK) return 0;
-  const int np = tf_np(precision);
-  if (!training && np && tf_wplanes_ok(D, F, np) && tf_pw_rows_ok(D, F, w.n_rows, np))
-    return tf_pw_extra(D, F, w.n_rows, np, w.total, n_heads, n_seq, tf_t_max(n_seq, seq_off_host)).total;
-  return w.total;
+  sumk_tf_opts o{}; o.precision = precision; o.wplanes = &o;   // a call in `precision` with the weights' planes given
+  return tf_query("transformer_workspace_bytes_for", TF_DENSE, training, 0, D, F, n_heads, n_layers, n_seq, seq_off_host, &o);
+}
+
+extern "C" size_t sumk_transformer_stream_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                          const int32_t* seq_off_host) {
+  return tf_query("transformer_stream_workspace_bytes", TF_STREAM, 0, 0, D, F, n_heads, n_layers, n_seq, seq_off_host);
+}
+
+extern "C" size_t sumk_transformer_stream_split_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                                const int32_t* seq_off_host, int32_t attention_precision) {
+  return tf_query("transformer_stream_split_workspace_bytes", TF_STREAM_SPLIT, 0, attention_precision, D, F, n_heads, n_layers, n_seq, seq_off_host);
+}
+
+extern "C" size_t sumk_transformer_stream_train_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                                const int32_t* seq_off_host) {
+  return tf_query("transformer_stream_train_workspace_bytes", TF_STREAM, 1, 0, D, F, n_heads, n_layers, n_seq, seq_off_host);
+}
+
+extern "C" size_t sumk_transformer_stream_split_train_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                                      const int32_t* seq_off_host, int32_t attention_precision) {
+  return tf_query("transformer_stream_split_train_workspace_bytes", TF_STREAM_SPLIT, 1, attention_precision, D, F, n_heads, n_layers, n_seq,
+                  seq_off_host);
 }
 
 extern "C" size_t sumk_transformer_wplanes_bytes(int32_t D, int32_t F, int32_t n_layers, int32_t n_planes) {
@@ -531,47 +586,39 @@ extern "C" int sumk_transformer_wplanes_build(int32_t D, int32_t F, int32_t n_la
   return SUMK_OK;
 }
 
-// The forward of sumk_transformer_forward and, stream_attn = true (training only, exact fp32), of sumk_transformer_forward_stream_train:
-// the same layer loop with every layer's attention core on attn_stream.hip's training form, on the stream training carve.
-static int tf_forward_any(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
-                          const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_tf_layer_weights* layers,
-                          const sumk_tf_head_weights* head, const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
-                          float* scores, void* workspace, size_t workspace_bytes, int32_t training, bool stream_attn, int attn_prec,
-                          void* stream_) {
+// The one forward: the layer loop of every scoring and training entry.  The plan says which attention core a layer runs (dense; stream in
+// exact fp32 or bf16x3, in its scoring or its training form) and whether the projections run on the plane path.
+static int tf_forward_any(const char* what, int attn, int32_t training, int attn_prec, float* x, int32_t D, int32_t F, int32_t n_heads,
+                          int32_t n_layers, int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                          const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head, const sumk_tf_opts* opts,
+                          const float* pos_table, const int32_t* pos_rows, float* scores, void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  SUMK_ARG(x && seq_off_dev && layers && head && opts && scores && workspace, "transformer_forward: null pointer");
-  if (stream_attn) {
-    SUMK_ARG(opts->precision == SUMK_PRECISION_FP32 && !opts->wplanes, "transformer_forward_stream_train: exact fp32 only (precision=%d, wplanes %s)",
-             opts->precision, opts->wplanes ? "given" : "null");
-    SUMK_TRY(attn_stream_bwd_check(D, n_heads, n_seq, seq_off_host));
+  SUMK_ARG(x && seq_off_dev && layers && head && opts && scores && workspace, "%s: null pointer", what);
+  SUMK_ARG((pos_table == nullptr) == (pos_rows == nullptr), "%s: pos_table and pos_rows go together", what);
+  SUMK_ARG(head->ln_w && head->ln_b && head->k1_w && head->k1_b && head->k2_w && head->k2_b, "%s: null head weight", what);
+  for (int l = 0; l < n_layers; ++l) {
+    const sumk_tf_layer_weights& W = layers[l];
+    SUMK_ARG(W.in_proj_w && W.in_proj_b && W.out_proj_w && W.out_proj_b && W.lin1_w && W.lin1_b && W.lin2_w && W.lin2_b &&
+             W.norm1_w && W.norm1_b && W.norm2_w && W.norm2_b, "%s: null weight in layer %d", what, l);
   }
-  SUMK_ARG(n_layers > 0, "transformer_forward: n_layers=%d", n_layers);
-  SUMK_ARG((pos_table == nullptr) == (pos_rows == nullptr), "transformer_forward: pos_table and pos_rows go together");
-  SUMK_ARG(head->ln_w && head->ln_b && head->k1_w && head->k1_b && head->k2_w && head->k2_b, "transformer_forward: null head weight");
-  SUMK_ARG((opts->layer_dropout_p == 0.f && opts->head_dropout_p == 0.f) || training, "transformer_forward: dropout needs training mode");
-  TfGeom G;
-  SUMK_TRY(tf_geometry_any(D, F, n_heads, n_layers, n_seq, seq_off_host, training, !stream_attn, &G));
-  const TfWs& L = G.L;
-  size_t split_ws = 0;                            // attn_prec: the bf16x3 attention's descriptors, delta and planes lie behind the carve
-  if (attn_prec) {
-    split_ws = attn_stream_split_bwd_ws_bytes(D, n_heads, n_seq, seq_off_host, attn_prec);
-    if (!split_ws) return SUMK_ERR_ARG;           // the message is attn_stream_split_backward's
+  TfPlan P;
+  SUMK_TRY(tf_plan(what, attn, training, attn_prec, D, F, n_heads, n_layers, n_seq, seq_off_host, opts, &P));
+  if (workspace_bytes < P.total) {
+    set_error(P.planes ? "%s: workspace %zu < %zu the plane path needs (sumk_transformer_workspace_bytes_for)" : "%s: workspace %zu < required %zu",
+              what, workspace_bytes, P.total);
+    return SUMK_ERR_WORKSPACE;
   }
-  if (workspace_bytes < L.total + split_ws) { set_error("transformer_forward: workspace %zu < required %zu", workspace_bytes, L.total + split_ws); return SUMK_ERR_WORKSPACE; }
+  const TfGeom& G = P.G; const TfWs& L = G.L; const TfPwExtra& PX = P.px;
   char* ws = (char*)workspace;
   const int R = G.R, dh = G.dh;
   // the plane path: inference in a split-bf16 arithmetic with the weights' planes at hand
-  const int npl = tf_np(opts->precision);
-  const bool pw = !training && npl && opts->wplanes && tf_wplanes_ok(D, F, npl) && tf_pw_rows_ok(D, F, R, npl);
-  TfPwExtra PX{}; TfWPlanes WL{};
-  const int t_max = tf_t_max(n_seq, seq_off_host);
+  const int npl = P.planes; const bool pw = npl != 0, pw_attn = pw && PX.attn;
+  TfWPlanes WL{};
   if (pw) {
-    PX = tf_pw_extra(D, F, R, npl, L.total, n_heads, n_seq, t_max); WL = tf_wplanes_layout(D, F, n_layers, npl);
-    SUMK_ARG(((uintptr_t)opts->wplanes & 255) == 0, "transformer_forward: wplanes must be 256-byte aligned");
-    if (workspace_bytes < PX.total) { set_error("transformer_forward: workspace %zu < %zu the plane path needs (sumk_transformer_workspace_bytes_for)", workspace_bytes, PX.total); return SUMK_ERR_WORKSPACE; }
+    WL = tf_wplanes_layout(D, F, n_layers, npl);
+    SUMK_ARG(((uintptr_t)opts->wplanes & 255) == 0, "%s: wplanes must be 256-byte aligned", what);
   }
   char* const PA = ws + PX.pa; char* const PB = ws + PX.pb;
-  const bool pw_attn = pw && PX.attn;
   SeqInfo* const seqinfo = (SeqInfo*)(ws + PX.seqinfo);
   if (pw_attn) {
     hipLaunchKernelGGL(tf_seqinfo_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, stream, seq_off_dev, n_seq, seqinfo);
@@ -589,21 +636,19 @@ static int tf_forward_any(float* x, int32_t D, int32_t F, int32_t n_heads, int32
   float* T1 = (float*)(ws + L.t1);
   const Drop dl = make_drop(opts->layer_dropout_p, opts->seed), dhd = make_drop(opts->head_dropout_p, opts->seed);
   const float att_scale = 1.0f / sqrtf((float)dh);
-  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream, seq_off_host, attn_prec, L.total};
+  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream, seq_off_host, &P};
 
   if (pos_table) SUMK_TRY(launch_add_pos(x, pos_table, pos_rows, R, D, stream));
-  SUMK_TRY(tf_tables(G, D, F, n_heads, n_seq, seq_off_dev, ws, stream, !stream_attn));
+  SUMK_TRY(tf_tables(G, D, F, n_heads, n_seq, seq_off_dev, ws, stream, !P.stream));
 
   const float* hin = x;
   for (int l = 0; l < n_layers; ++l) {
     const sumk_tf_layer_weights& W = layers[l];
-    SUMK_ARG(W.in_proj_w && W.in_proj_b && W.out_proj_w && W.out_proj_b && W.lin1_w && W.lin1_b && W.lin2_w && W.lin2_b &&
-             W.norm1_w && W.norm1_b && W.norm2_w && W.norm2_b, "transformer_forward: null weight in layer %d", l);
     float *QKV, *E = nullptr, *E2 = nullptr, *CTX, *T1a, *hmid, *FF, *T1b, *hout, *stats = nullptr, *astats = nullptr;
     if (training) {
       char* lb = ws + L.lay0 + (size_t)l * L.lay_stride;
       QKV = (float*)(lb + L.l_qkv);
-      if (stream_attn) astats = (float*)(lb + L.l_astats);
+      if (P.stream) astats = (float*)(lb + L.l_astats);
       else { E = (float*)(lb + L.l_p); E2 = dl.thr ? (float*)(lb + L.l_pd) : nullptr; }
       CTX = (float*)(lb + L.l_ctx); T1a = (float*)(lb + L.l_t1a); hmid = (float*)(lb + L.l_hmid); FF = (float*)(lb + L.l_ff);
       T1b = (float*)(lb + L.l_t1b); hout = (float*)(lb + L.l_hout); stats = (float*)(lb + L.l_stats);
@@ -621,24 +666,17 @@ static int tf_forward_any(float* x, int32_t D, int32_t F, int32_t n_heads, int32
         g.bias = W.in_proj_b; g.O = ws + PX.qp; g.o_rows = R; g.o_store_rows = pw_rows_pitch(R);      // (pad rows = the bias: finite -- the context kernel multiplies V rows up to 31 past the last video by alpha = 0)
         SUMK_TRY(launch_gemm_pw(PW_PLANES, g, stream));
       }
-      SUMK_TRY(launch_attn_pw_logits(npl, ws + PX.qp, R, D, nullptr, ws + PX.ap, seqinfo, n_seq, t_max, att_scale, 0, -1, stream, n_heads));
-      SUMK_TRY(launch_attn_pw_context(npl, ws + PX.qp, R, D, ws + PX.ap, PA, seqinfo, n_seq, t_max, stream, n_heads));      // PA: the planes of hin are spent
+      SUMK_TRY(launch_attn_pw_logits(npl, ws + PX.qp, R, D, nullptr, ws + PX.ap, seqinfo, n_seq, PX.t_max, att_scale, 0, -1, stream, n_heads));
+      SUMK_TRY(launch_attn_pw_context(npl, ws + PX.qp, R, D, ws + PX.ap, PA, seqinfo, n_seq, PX.t_max, stream, n_heads));      // PA: the planes of hin are spent
       SUMK_TRY(pw_linear(PA, wl + WL.wo, D, D, W.out_proj_b, hin, 0, T1a, nullptr));
-    } else {   // the per-(video, head) products stay on the in-loop kernels (fp32 Q / K / V, logits, context), between plane GEMMs when the weights' planes are given
-      if (pw) {
-        SUMK_TRY(split_planes(hin, R, D, D, npl, PA, stream));
-        SUMK_TRY(pw_linear(PA, wl + WL.win, 3 * D, D, W.in_proj_b, nullptr, 0, QKV, nullptr));
-      } else {  // packed in-projection  [Q|K|V] = h Win^T + bin
-        SUMK_TRY(tf_in_proj(run, hin, W.in_proj_w, W.in_proj_b, QKV));
-      }
-      if (stream_attn) SUMK_TRY(tf_attn_stream_fwd(run, QKV, CTX, astats, dl, site + 0));   // one launch, no logits
-      else SUMK_TRY(tf_attn_core_fwd(run, tabs, QKV, QKV, E, E2, CTX, dl, site + 0));        // logits, softmax, context per (video, head)
-      if (pw) {
-        SUMK_TRY(split_planes(CTX, R, D, D, npl, PA, stream));
-        SUMK_TRY(pw_linear(PA, wl + WL.wo, D, D, W.out_proj_b, hin, 0, T1a, nullptr));
-      } else {  // out-projection + bias (+dropout1) + residual
-        SUMK_TRY(tf_out_proj(run, CTX, W.out_proj_w, W.out_proj_b, hin, T1a, dl, site + 1));
-      }
+    } else if (pw) {   // the per-(video, head) products stay on the in-loop kernels (fp32 Q / K / V, logits, context), between plane GEMMs
+      SUMK_TRY(split_planes(hin, R, D, D, npl, PA, stream));
+      SUMK_TRY(pw_linear(PA, wl + WL.win, 3 * D, D, W.in_proj_b, nullptr, 0, QKV, nullptr));
+      SUMK_TRY(tf_attn_core_fwd(run, tabs, QKV, QKV, E, E2, CTX, dl, site + 0));
+      SUMK_TRY(split_planes(CTX, R, D, D, npl, PA, stream));
+      SUMK_TRY(pw_linear(PA, wl + WL.wo, D, D, W.out_proj_b, hin, 0, T1a, nullptr));
+    } else {   // in-projection, the plan's attention core (dense: logits, softmax, context; stream: one launch, no logits), out-projection
+      SUMK_TRY(tf_sa_fwd(run, TfAttnW{W.in_proj_w, W.in_proj_b, W.out_proj_w, W.out_proj_b}, hin, QKV, E, E2, CTX, T1a, dl, site, astats));
     }
     SUMK_TRY(launch_layernorm(T1a, hmid, W.norm1_w, W.norm1_b, R, D, opts->layer_eps, stats, stream));
     if (pw) {  // both feed-forward layers; ReLU(lin1) exists as planes only
@@ -663,126 +701,15 @@ static int tf_forward_any(float* x, int32_t D, int32_t F, int32_t n_heads, int32
   return SUMK_OK;
 }
 
+// ---- the forward entries: each names its path to the plan
+#define TF_FWD_ARGS x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores, workspace, workspace_bytes, stream_
 extern "C" int sumk_transformer_forward(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
                                         const int32_t* seq_off_host, const int32_t* seq_off_dev,
                                         const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
                                         const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
                                         float* scores, void* workspace, size_t workspace_bytes, int32_t training,
                                         void* stream_) {
-  return tf_forward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores, workspace,
-                        workspace_bytes, training, false, 0, stream_);
-}
-
-// ---- training on the stream path: the training forward and the backward with every layer's attention on attn_stream.hip /
-// attn_stream_bwd.hip; the carve has no `e`, `l_p`, `l_pd` and no per-(video, head) tables
-extern "C" size_t sumk_transformer_stream_train_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
-                                                                const int32_t* seq_off_host) {
-  TfWs w;
-  if (n_layers < 1 || tf_carve_any(D, F, n_heads, n_layers, n_seq, seq_off_host, 1, false, &w) != SUMK_OK) return 0;
-  if (attn_stream_bwd_check(D, n_heads, n_seq, seq_off_host) != SUMK_OK) return 0;
-  return w.total;
-}
-
-extern "C" int sumk_transformer_forward_stream_train(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
-                                                     const int32_t* seq_off_host, const int32_t* seq_off_dev,
-                                                     const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
-                                                     const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
-                                                     float* scores, void* workspace, size_t workspace_bytes, void* stream_) {
-  return tf_forward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores, workspace,
-                        workspace_bytes, 1, true, 0, stream_);
-}
-
-// ---- the same two entries with every layer's attention in bf16x3 (attn_stream_split.hip's training form, attn_stream_split_bwd.hip):
-// the stream training carve + the descriptors, delta and planes of ONE layer (re-split in the backward from the saved [Q | K | V]);
-// projections and everything else stay exact fp32
-extern "C" size_t sumk_transformer_stream_split_train_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
-                                                                      const int32_t* seq_off_host, int32_t attention_precision) {
-  const size_t planes = attn_stream_split_bwd_ws_bytes(D, n_heads, n_seq, seq_off_host, attention_precision);
-  const size_t base = planes ? sumk_transformer_stream_train_workspace_bytes(D, F, n_heads, n_layers, n_seq, seq_off_host) : 0;
-  return base ? base + planes : 0;
-}
-
-extern "C" int sumk_transformer_forward_stream_split_train(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
-                                                           const int32_t* seq_off_host, const int32_t* seq_off_dev,
-                                                           const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
-                                                           const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
-                                                           float* scores, int32_t attention_precision, void* workspace,
-                                                           size_t workspace_bytes, void* stream_) {
-  SUMK_ARG(attention_precision == SUMK_PRECISION_BF16X3, "transformer_forward_stream_split_train: attention_precision=%d (only SUMK_PRECISION_BF16X3 = %d)",
-           attention_precision, SUMK_PRECISION_BF16X3);
-  return tf_forward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores, workspace,
-                        workspace_bytes, 1, true, attention_precision, stream_);
-}
-
-// ---- the stream path: the inference of sumk_transformer_forward with tf_attn_core_fwd replaced by attn_stream.hip's launch; no `e` in the carve
-extern "C" size_t sumk_transformer_stream_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
-                                                          const int32_t* seq_off_host) {
-  TfWs w;
-  if (n_layers < 1 || tf_carve_any(D, F, n_heads, n_layers, n_seq, seq_off_host, 0, false, &w) != SUMK_OK) return 0;
-  if (attn_stream_check(D, n_heads, n_seq, seq_off_host) != SUMK_OK) return 0;
-  return w.total;
-}
-
-// split = false: sumk_transformer_forward_stream.  split = true: sumk_transformer_forward_stream_split -- the same layer loop with the
-// attention core on attn_stream_split.hip in `attn_prec`; its descriptors and planes lie behind the stream carve.
-static int tf_forward_stream_any(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
-                                 const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_tf_layer_weights* layers,
-                                 const sumk_tf_head_weights* head, const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
-                                 float* scores, bool split, int attn_prec, void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SUMK_ARG(x && seq_off_dev && layers && head && opts && scores && workspace, "transformer_forward_stream: null pointer");
-  SUMK_ARG(n_layers > 0, "transformer_forward_stream: n_layers=%d", n_layers);
-  SUMK_ARG((pos_table == nullptr) == (pos_rows == nullptr), "transformer_forward_stream: pos_table and pos_rows go together");
-  SUMK_ARG(head->ln_w && head->ln_b && head->k1_w && head->k1_b && head->k2_w && head->k2_b, "transformer_forward_stream: null head weight");
-  SUMK_ARG(opts->precision == SUMK_PRECISION_FP32 && !opts->wplanes, "transformer_forward_stream: exact fp32 only (precision=%d, wplanes %s)",
-           opts->precision, opts->wplanes ? "given" : "null");
-  SUMK_ARG(opts->layer_dropout_p == 0.f && opts->head_dropout_p == 0.f, "transformer_forward_stream: inference only (dropout must be 0)");
-  for (int l = 0; l < n_layers; ++l) {
-    const sumk_tf_layer_weights& W = layers[l];
-    SUMK_ARG(W.in_proj_w && W.in_proj_b && W.out_proj_w && W.out_proj_b && W.lin1_w && W.lin1_b && W.lin2_w && W.lin2_b &&
-             W.norm1_w && W.norm1_b && W.norm2_w && W.norm2_b, "transformer_forward_stream: null weight in layer %d", l);
-  }
-  TfGeom G;
-  SUMK_TRY(tf_geometry_any(D, F, n_heads, n_layers, n_seq, seq_off_host, 0, false, &G));
-  SUMK_TRY(attn_stream_check(D, n_heads, n_seq, seq_off_host));
-  const TfWs& L = G.L;
-  size_t need = L.total;
-  if (split) {
-    const size_t planes = attn_stream_split_ws_bytes(D, n_heads, n_seq, seq_off_host, attn_prec);
-    if (!planes) return SUMK_ERR_ARG;           // the message is attn_stream_split's
-    need += planes;
-  }
-  if (workspace_bytes < need) { set_error("transformer_forward_stream: workspace %zu < required %zu", workspace_bytes, need); return SUMK_ERR_WORKSPACE; }
-  char* ws = (char*)workspace;
-  const int R = G.R;
-  float* T1 = (float*)(ws + L.t1); float* QKV = (float*)(ws + L.qkv); float* CTX = (float*)(ws + L.ctx); float* FF = (float*)(ws + L.ff);
-  float* Hb[3] = {(float*)(ws + L.h0), (float*)(ws + L.h1), (float*)(ws + L.h2)};
-  const Drop none = make_drop(0.f, 0);
-  const float att_scale = 1.0f / sqrtf((float)G.dh);
-  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, SUMK_PRECISION_FP32, stream};
-
-  if (pos_table) SUMK_TRY(launch_add_pos(x, pos_table, pos_rows, R, D, stream));
-  SUMK_TRY(tf_tables(G, D, F, n_heads, n_seq, seq_off_dev, ws, stream, false));
-  const float* hin = x;
-  for (int l = 0; l < n_layers; ++l) {
-    const sumk_tf_layer_weights& W = layers[l];
-    float* hmid = Hb[0]; float* hout = Hb[1 + (l & 1)];      // never aliases this layer's input (x or the previous hout)
-    SUMK_TRY(tf_in_proj(run, hin, W.in_proj_w, W.in_proj_b, QKV));
-    if (split)
-      SUMK_TRY(launch_attn_stream_split(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, n_heads, n_seq, seq_off_host, seq_off_dev, att_scale,
-                                        attn_prec, CTX, D, nullptr, ws + L.total, stream));
-    else
-      SUMK_TRY(launch_attn_stream(QKV, 3 * D, QKV + D, 3 * D, QKV + 2 * D, 3 * D, D, n_heads, n_seq, seq_off_host, seq_off_dev, att_scale, CTX, D,
-                                  nullptr, ws + L.as_seq, stream));
-    SUMK_TRY(tf_out_proj(run, CTX, W.out_proj_w, W.out_proj_b, hin, T1, none, 0u));
-    SUMK_TRY(launch_layernorm(T1, hmid, W.norm1_w, W.norm1_b, R, D, opts->layer_eps, nullptr, stream));
-    SUMK_TRY(tf_ff_fwd(run, TfFfW{W.lin1_w, W.lin1_b, W.lin2_w, W.lin2_b}, hmid, FF, T1, none, 0u, 0u));
-    SUMK_TRY(launch_layernorm(T1, hout, W.norm2_w, W.norm2_b, R, D, opts->layer_eps, nullptr, stream));
-    hin = hout;
-  }
-  SUMK_TRY(tf_tail(run, x, hin, Hb[0], T1, nullptr, head, opts, none, scores, false, [] { return (int)SUMK_OK; }));
-  SUMK_HIP(hipGetLastError());
-  return SUMK_OK;
+  return tf_forward_any("transformer_forward", TF_DENSE, training != 0, 0, TF_FWD_ARGS);
 }
 
 extern "C" int sumk_transformer_forward_stream(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
@@ -790,16 +717,7 @@ extern "C" int sumk_transformer_forward_stream(float* x, int32_t D, int32_t F, i
                                                const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
                                                const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
                                                float* scores, void* workspace, size_t workspace_bytes, void* stream_) {
-  return tf_forward_stream_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores,
-                               false, SUMK_PRECISION_FP32, workspace, workspace_bytes, stream_);
-}
-
-// ---- the stream path with the attention in bf16x3 (attn_stream_split.hip): the stream carve + the planes of one layer's [Q | K | V]
-extern "C" size_t sumk_transformer_stream_split_workspace_bytes(int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
-                                                                const int32_t* seq_off_host, int32_t attention_precision) {
-  const size_t base = sumk_transformer_stream_workspace_bytes(D, F, n_heads, n_layers, n_seq, seq_off_host);
-  const size_t planes = base ? attn_stream_split_ws_bytes(D, n_heads, n_seq, seq_off_host, attention_precision) : 0;
-  return planes ? base + planes : 0;
+  return tf_forward_any("transformer_forward_stream", TF_STREAM, 0, 0, TF_FWD_ARGS);
 }
 
 extern "C" int sumk_transformer_forward_stream_split(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
@@ -808,68 +726,59 @@ extern "C" int sumk_transformer_forward_stream_split(float* x, int32_t D, int32_
                                                      const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
                                                      float* scores, int32_t attention_precision, void* workspace, size_t workspace_bytes,
                                                      void* stream_) {
-  SUMK_ARG(attention_precision == SUMK_PRECISION_BF16X3, "transformer_forward_stream_split: attention_precision=%d (only SUMK_PRECISION_BF16X3 = %d)",
-           attention_precision, SUMK_PRECISION_BF16X3);
-  return tf_forward_stream_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, pos_table, pos_rows, scores,
-                               true, attention_precision, workspace, workspace_bytes, stream_);
+  return tf_forward_any("transformer_forward_stream_split", TF_STREAM_SPLIT, 0, attention_precision, TF_FWD_ARGS);
 }
 
-// The backward of sumk_transformer_backward and, stream_attn = true, of sumk_transformer_backward_stream (after
-// sumk_transformer_forward_stream_train on the same workspace)
-static int tf_backward_any(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
-                           const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_tf_layer_weights* layers,
+extern "C" int sumk_transformer_forward_stream_train(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                     const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                                     const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                                     const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
+                                                     float* scores, void* workspace, size_t workspace_bytes, void* stream_) {
+  return tf_forward_any("transformer_forward_stream_train", TF_STREAM, 1, 0, TF_FWD_ARGS);
+}
+
+extern "C" int sumk_transformer_forward_stream_split_train(float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers, int32_t n_seq,
+                                                           const int32_t* seq_off_host, const int32_t* seq_off_dev,
+                                                           const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
+                                                           const sumk_tf_opts* opts, const float* pos_table, const int32_t* pos_rows,
+                                                           float* scores, int32_t attention_precision, void* workspace,
+                                                           size_t workspace_bytes, void* stream_) {
+  return tf_forward_any("transformer_forward_stream_split_train", TF_STREAM_SPLIT, 1, attention_precision, TF_FWD_ARGS);
+}
+#undef TF_FWD_ARGS
+
+// The one backward, after a training forward of the same path on the same workspace
+static int tf_backward_any(const char* what, int attn, int attn_prec, const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
+                           int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev, const sumk_tf_layer_weights* layers,
                            const sumk_tf_head_weights* head, const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* lgr,
-                           const sumk_tf_head_grads* hgr, float* dx, void* workspace, size_t workspace_bytes, bool stream_attn,
-                           int attn_prec, void* stream_) {
+                           const sumk_tf_head_grads* hgr, float* dx, void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  SUMK_ARG(x && seq_off_dev && layers && head && opts && dscores && lgr && hgr && workspace, "transformer_backward: null pointer");
-  if (stream_attn) {
-    SUMK_ARG(opts->precision == SUMK_PRECISION_FP32 && !opts->wplanes, "transformer_backward_stream: exact fp32 only (precision=%d, wplanes %s)",
-             opts->precision, opts->wplanes ? "given" : "null");
-    SUMK_TRY(attn_stream_bwd_check(D, n_heads, n_seq, seq_off_host));
+  SUMK_ARG(x && seq_off_dev && layers && head && opts && dscores && lgr && hgr && workspace, "%s: null pointer", what);
+  TfPlan P;
+  SUMK_TRY(tf_plan(what, attn, 1, attn_prec, D, F, n_heads, n_layers, n_seq, seq_off_host, opts, &P));
+  if (workspace_bytes < P.total) {
+    set_error("%s: workspace %zu < required %zu (needs the training-mode forward's workspace)", what, workspace_bytes, P.total);
+    return SUMK_ERR_WORKSPACE;
   }
-  TfGeom G;
-  SUMK_TRY(tf_geometry_any(D, F, n_heads, n_layers, n_seq, seq_off_host, 1, !stream_attn, &G));
-  const TfWs& L = G.L;
-  size_t split_ws = 0;
-  if (attn_prec) {
-    split_ws = attn_stream_split_bwd_ws_bytes(D, n_heads, n_seq, seq_off_host, attn_prec);
-    if (!split_ws) return SUMK_ERR_ARG;           // the message is attn_stream_split_backward's
-  }
-  if (workspace_bytes < L.total + split_ws) { set_error("transformer_backward: workspace %zu < required %zu (needs the training-mode forward's workspace)", workspace_bytes, L.total + split_ws); return SUMK_ERR_WORKSPACE; }
+  const TfGeom& G = P.G; const TfWs& L = G.L;
   char* ws = (char*)workspace;
   const int R = G.R;
   const int64_t nRD = (int64_t)R * D;
-  GemmProb* prow = (GemmProb*)(ws + L.prob_row);
-  GemmProb* psk = (GemmProb*)(ws + L.prob_sk);
   float* g0 = (float*)(ws + L.g0); float* g1 = (float*)(ws + L.g1); float* g2 = (float*)(ws + L.g2);
-  float* dQKV = (float*)(ws + L.dqkv); float* dFF = (float*)(ws + L.dff);
-  float* lnpart = (float*)(ws + L.lnpart); float* slab = (float*)(ws + L.slab);
+  float* dQKV = (float*)(ws + L.dqkv); float* dFF = (float*)(ws + L.dff); float* lnpart = (float*)(ws + L.lnpart);
   const float* hfin = (const float*)(ws + L.hfin); const float* Z = (const float*)(ws + L.z);
   const float* sfin = (const float*)(ws + L.stats_fin); const float* scores = (const float*)(ws + L.scores);
   const Drop dl = make_drop(opts->layer_dropout_p, opts->seed), dhd = make_drop(opts->head_dropout_p, opts->seed);
   const Drop none = make_drop(0.f, 0);
   int nw = 0;
-  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream, seq_off_host, attn_prec, L.total};
-  auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-  auto nn = [&](const float* A, const float* B, float* C, int prob, GemmEpi epi, int N) -> int {   // C (op)= A . B, B stored (K, N)
-    GemmLaunch g; g.precision = opts->precision;
-    g.A = A; g.B[0] = B; g.C = C; g.probs = prow + prob; g.small_tile = (N == F ? G.c_df : G.c_dd);
-    g.total_tiles = gemm_tiles(R, N, g.small_tile);
-    return launch_gemm(GEMM_NN, epi, g, stream);
-  };
-  auto wgrad = [&](const float* dY, int ldy, int M, const float* Xin, int ldx, int N, float* out0, float* out1, float* out2,
-                   int rows_per_out) -> int {   // out[M,N] += dY^T Xin
-    float* out[4] = {out0, out1, out2, nullptr};
-    return gemm_tn_splitk_accum(dY, ldy, Xin, ldx, M, N, R, slab, L.slab_elems, psk, TF_SPLITK_PROBS, out, rows_per_out, N, 1.f, stream, opts->precision);
-  };
+  const TfRun run{&G, ws, D, F, n_heads, n_seq, seq_off_dev, opts->precision, stream, seq_off_host, &P};
 
   // ---- scoring head: dZ (ReLU + head dropout masks applied), dk2, db2, shared-LN grads
   SUMK_TRY(launch_ln_head_bwd(D, R, Z, sfin + 2 * (size_t)R, head->ln_w, head->ln_b, head->k2_w, scores, dscores, g0, lnpart, dhd,
                               1000u, &nw, stream));
   SUMK_TRY(ln_bwd_reduce(lnpart, nw, D, hgr->ln_w, hgr->ln_b, hgr->k2_w, hgr->k2_b, hgr->k1_b, stream));   // dk1_b = column sums of g0
-  SUMK_TRY(wgrad(g0, D, D, hfin, D, D, hgr->k1_w, nullptr, nullptr, D));
-  SUMK_TRY(nn(g0, head->k1_w, g1, P_DD, EPI_NONE, D));                       // dHfin' -> g1
+  SUMK_TRY(tf_wgrad(run, g0, D, D, hfin, D, D, hgr->k1_w));
+  SUMK_TRY(tf_nn(run, g0, head->k1_w, g1, P_DD, EPI_NONE, D));               // dHfin' -> g1
   if (opts->more_residuals && dx) SUMK_HIP(hipMemcpyAsync(dx, g1, (size_t)nRD * 4, hipMemcpyDeviceToDevice, stream));
   // encoder's final (shared) LayerNorm
   const float* hlast = (const float*)(ws + L.lay0 + (size_t)(n_layers - 1) * L.lay_stride + L.l_hout);
@@ -883,9 +792,9 @@ static int tf_backward_any(const float* x, int32_t D, int32_t F, int32_t n_heads
     const sumk_tf_layer_grads& Gd = lgr[l];
     char* lb = ws + L.lay0 + (size_t)l * L.lay_stride;
     const float* QKV = (const float*)(lb + L.l_qkv);
-    const float* P = stream_attn ? nullptr : (const float*)(lb + L.l_p);
-    float* E2 = stream_attn ? nullptr : (float*)(lb + L.l_pd);
-    const float* astats = stream_attn ? (const float*)(lb + L.l_astats) : nullptr;
+    const float* Pa = P.stream ? nullptr : (const float*)(lb + L.l_p);
+    float* E2 = P.stream ? nullptr : (float*)(lb + L.l_pd);
+    const float* astats = P.stream ? (const float*)(lb + L.l_astats) : nullptr;
     const float* CTX = (const float*)(lb + L.l_ctx); const float* T1a = (const float*)(lb + L.l_t1a);
     const float* hmid = (const float*)(lb + L.l_hmid); const float* FFa = (const float*)(lb + L.l_ff);
     const float* T1b = (const float*)(lb + L.l_t1b); const float* stats = (const float*)(lb + L.l_stats);
@@ -900,15 +809,15 @@ static int tf_backward_any(const float* x, int32_t D, int32_t F, int32_t n_heads
     // norm1
     SUMK_TRY(launch_ln_bwd_rows(D, R, T1a, stats, W.norm1_w, W.norm1_b, fa, dH, lnpart, none, 0u, &nw, stream));   // dH buffer reused: dT1a
     SUMK_TRY(ln_bwd_reduce(lnpart, nw, D, Gd.norm1_w, Gd.norm1_b, nullptr, nullptr, nullptr, stream));
-    // dT1a (in dH) -> dHin: out-projection (dropout1 mask), per-(video, head) attention, in-projection backward; fa, fb scratch
+    // dT1a (in dH) -> dHin: out-projection (dropout1 mask), the plan's attention core, in-projection backward; fa, fb scratch
     SUMK_TRY(tf_sa_bwd(run, TfAttnW{W.in_proj_w, W.in_proj_b, W.out_proj_w, W.out_proj_b},
-                       TfAttnG{Gd.in_proj_w, Gd.in_proj_b, Gd.out_proj_w, Gd.out_proj_b}, hin, QKV, P, E2, CTX, dH, fa, fb, dQKV, dl, site, astats));
+                       TfAttnG{Gd.in_proj_w, Gd.in_proj_b, Gd.out_proj_w, Gd.out_proj_b}, hin, QKV, Pa, E2, CTX, dH, fa, fb, dQKV, dl, site, astats));
     // dH (= dT1a buffer) now holds the gradient w.r.t. this layer's input = the previous layer's output
   }
   if (dx) {
     if (opts->more_residuals) {
       int64_t n4 = nRD >> 2;
-      hipLaunchKernelGGL(add_rows_kernel, blocks(n4), dim3(256), 0, stream, dx, dH, n4);
+      hipLaunchKernelGGL(add_rows_kernel, tf_blocks(n4), dim3(256), 0, stream, dx, dH, n4);
     } else {
       SUMK_HIP(hipMemcpyAsync(dx, dH, (size_t)nRD * 4, hipMemcpyDeviceToDevice, stream));
     }
@@ -917,14 +826,15 @@ static int tf_backward_any(const float* x, int32_t D, int32_t F, int32_t n_heads
   return SUMK_OK;
 }
 
+// ---- the backward entries
+#define TF_BWD_ARGS x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, dscores, lgr, hgr, dx, workspace, workspace_bytes, stream_
 extern "C" int sumk_transformer_backward(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
                                          int32_t n_seq, const int32_t* seq_off_host, const int32_t* seq_off_dev,
                                          const sumk_tf_layer_weights* layers, const sumk_tf_head_weights* head,
                                          const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* lgr,
                                          const sumk_tf_head_grads* hgr, float* dx, void* workspace, size_t workspace_bytes,
                                          void* stream_) {
-  return tf_backward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, dscores, lgr, hgr, dx, workspace,
-                         workspace_bytes, false, 0, stream_);
+  return tf_backward_any("transformer_backward", TF_DENSE, 0, TF_BWD_ARGS);
 }
 
 extern "C" int sumk_transformer_backward_stream(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
@@ -933,8 +843,7 @@ extern "C" int sumk_transformer_backward_stream(const float* x, int32_t D, int32
                                                 const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* lgr,
                                                 const sumk_tf_head_grads* hgr, float* dx, void* workspace, size_t workspace_bytes,
                                                 void* stream_) {
-  return tf_backward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, dscores, lgr, hgr, dx, workspace,
-                         workspace_bytes, true, 0, stream_);
+  return tf_backward_any("transformer_backward_stream", TF_STREAM, 0, TF_BWD_ARGS);
 }
 
 extern "C" int sumk_transformer_backward_stream_split(const float* x, int32_t D, int32_t F, int32_t n_heads, int32_t n_layers,
@@ -943,8 +852,6 @@ extern "C" int sumk_transformer_backward_stream_split(const float* x, int32_t D,
                                                       const sumk_tf_opts* opts, const float* dscores, const sumk_tf_layer_grads* lgr,
                                                       const sumk_tf_head_grads* hgr, float* dx, int32_t attention_precision, void* workspace,
                                                       size_t workspace_bytes, void* stream_) {
-  SUMK_ARG(attention_precision == SUMK_PRECISION_BF16X3, "transformer_backward_stream_split: attention_precision=%d (only SUMK_PRECISION_BF16X3 = %d)",
-           attention_precision, SUMK_PRECISION_BF16X3);
-  return tf_backward_any(x, D, F, n_heads, n_layers, n_seq, seq_off_host, seq_off_dev, layers, head, opts, dscores, lgr, hgr, dx, workspace,
-                         workspace_bytes, true, attention_precision, stream_);
+  return tf_backward_any("transformer_backward_stream_split", TF_STREAM_SPLIT, attention_precision, TF_BWD_ARGS);
 }
+#undef TF_BWD_ARGS

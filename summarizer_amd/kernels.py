@@ -1,6 +1,7 @@
 """Thin Python layer over the C ABI: packed-batch bookkeeping (sequence offsets, workspaces) and
 torch.autograd.Function wrappers.  Every arithmetic result comes from libsumk.so; nothing here computes on
 the CPU or through torch ops (torch only allocates the buffers and carries the stream)."""
+import collections
 import ctypes as C
 import math
 import os
@@ -1094,20 +1095,27 @@ def _tf_attention(attention):
     return attention
 
 
-def _tf_attention_precision(attention, attention_precision, training):
-    """None for "fp32", else the code of the bf16x3 stream entries: scoring on attention="stream" only."""
+_TfPath = collections.namedtuple("_TfPath", "query forward backward code persistent")
+
+
+def _tf_path(attention, attention_precision="fp32", attention_train_precision="fp32", training=False):
+    """The library path of one scorer call: the entries of its size query, forward and backward (None outside training), the precision
+    code the bf16x3 stream entries take (None: the path has no such argument) and whether the workspace outlives the call (the training
+    forward's goes to the backward).  attention_precision="bf16x3" is scoring on "stream" only, attention_train_precision="bf16x3"
+    training on "stream" only."""
     code = _stream_precision(attention_precision, "transformer attention")
     if code is not None and (_tf_attention(attention) != "stream" or training):
         raise SumkError(f"transformer: attention_precision={attention_precision!r} needs attention=\"stream\" and training=False")
-    return code
-
-
-def _tf_attention_train_precision(attention, attention_train_precision, training):
-    """None for "fp32", else the code of the bf16x3 stream TRAINING entries: training=True on attention="stream" only."""
-    code = _stream_precision(attention_train_precision, "transformer attention (training)")
-    if code is not None and (_tf_attention(attention) != "stream" or not training):
+    tcode = _stream_precision(attention_train_precision, "transformer attention (training)")
+    if tcode is not None and (_tf_attention(attention) != "stream" or not training):
         raise SumkError(f"transformer: attention_train_precision={attention_train_precision!r} needs attention=\"stream\" and training=True")
-    return code
+    if _tf_attention(attention) == "dense":
+        return _TfPath("sumk_transformer_workspace_bytes_for", "sumk_transformer_forward", "sumk_transformer_backward" if training else None,
+                       None, bool(training))
+    code = tcode if training else code
+    split, train = "_split" if code is not None else "", "_train" if training else ""
+    return _TfPath(f"sumk_transformer_stream{split}{train}_workspace_bytes", f"sumk_transformer_forward_stream{split}{train}",
+                   f"sumk_transformer_backward_stream{split}" if training else None, code, bool(training))
 
 
 def attn_strips_b16_sizes(sb):
@@ -1149,14 +1157,25 @@ def _stream_precision(precision, what):
     return code
 
 
+def _attn_stream_entry(suffix, precision, what):
+    """(entry, its precision argument as a tuple): sumk_attn_stream<suffix> with nothing for "fp32", sumk_attn_stream_split<suffix> with
+    the code for "bf16x3"."""
+    code = _stream_precision(precision, what)
+    return "sumk_attn_stream" + ("" if code is None else "_split") + suffix, () if code is None else (code,)
+
+
+def _attn_stream_args(fn, tensors, sb):
+    for t, what in tensors:
+        _require_gpu(t, f"{fn} {what}")
+        if t.dim() != 2 or t.shape != tensors[0][0].shape or t.shape[0] != sb.n_rows or t.stride(1) != 1:
+            raise SumkError(f"{fn}: {what} must be (n_rows={sb.n_rows}, D) with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
+
+
 def attn_stream_workspace_bytes(D, n_heads, sb, precision="fp32"):
     """Bytes of scratch one attn_stream call takes: 16 per video (sumk_attn_stream_workspace_bytes); precision="bf16x3": 24 per video + the
     bf16 planes of Q, K and V, 12 bytes per (padded row, staged column) (sumk_attn_stream_split_workspace_bytes)."""
-    code = _stream_precision(precision, "attn_stream")
-    if code is not None:
-        return _nonzero(_lib.load().sumk_attn_stream_split_workspace_bytes(int(D), int(n_heads), sb.n_seq, sb.off_host_p, code),
-                        "sumk_attn_stream_split_workspace_bytes")
-    return _nonzero(_lib.load().sumk_attn_stream_workspace_bytes(int(D), int(n_heads), sb.n_seq, sb.off_host_p), "sumk_attn_stream_workspace_bytes")
+    entry, code = _attn_stream_entry("_workspace_bytes", precision, "attn_stream")
+    return _nonzero(getattr(_lib.load(), entry)(int(D), int(n_heads), sb.n_seq, sb.off_host_p, *code), entry)
 
 
 def attn_stream(q, k, v, sb, n_heads, scale=None, want_lse=False, precision="fp32"):
@@ -1167,34 +1186,17 @@ def attn_stream(q, k, v, sb, n_heads, scale=None, want_lse=False, precision="fp3
     precision="bf16x3": both products in the split-bf16 arithmetic on the bf16 MFMA (csrc/attn_stream_split.hip; head widths % 8 == 0, up
     to 128); the default keeps the exact call and its bits.
     Returns ctx (n_rows, D), or (ctx, lse (n_rows, n_heads)) with want_lse.  Only enqueues work."""
-    lib = _lib.load()
-    code = _stream_precision(precision, "attn_stream")
-    for t, what in ((q, "q"), (k, "k"), (v, "v")):
-        _require_gpu(t, "attn_stream " + what)
-        if t.dim() != 2 or t.shape != q.shape or t.shape[0] != sb.n_rows or t.stride(1) != 1:
-            raise SumkError(f"attn_stream: {what} must be (n_rows={sb.n_rows}, D) with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
+    entry, code = _attn_stream_entry("", precision, "attn_stream")
+    _attn_stream_args("attn_stream", ((q, "q"), (k, "k"), (v, "v")), sb)
     D = q.shape[1]
-    nb = attn_stream_workspace_bytes(D, n_heads, sb, precision)
-    ws = workspace(nb, q.device)
+    ws = workspace(attn_stream_workspace_bytes(D, n_heads, sb, precision), q.device)
     ctx = torch.empty(sb.n_rows, D, dtype=torch.float32, device=q.device)
     lse = torch.empty(sb.n_rows, int(n_heads), dtype=torch.float32, device=q.device) if want_lse else None
     sc = 1.0 / math.sqrt(D // int(n_heads)) if scale is None else float(scale)
-    if code is not None:
-        rc = lib.sumk_attn_stream_split(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq, sb.off_host_p,
-                                        sb.off_dev_p, sc, code, _p(ctx), D, _p(lse), _p(ws), ws.numel(), _stream())
-        _lib.check(rc, "sumk_attn_stream_split")
-        return (ctx, lse) if want_lse else ctx
-    rc = lib.sumk_attn_stream(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq, sb.off_host_p,
-                              sb.off_dev_p, sc, _p(ctx), D, _p(lse), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "sumk_attn_stream")
+    rc = getattr(_lib.load(), entry)(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq, sb.off_host_p,
+                                     sb.off_dev_p, sc, *code, _p(ctx), D, _p(lse), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, entry)
     return (ctx, lse) if want_lse else ctx
-
-
-def _attn_stream_args(fn, tensors, sb):
-    for t, what in tensors:
-        _require_gpu(t, f"{fn} {what}")
-        if t.dim() != 2 or t.shape != tensors[0][0].shape or t.shape[0] != sb.n_rows or t.stride(1) != 1:
-            raise SumkError(f"{fn}: {what} must be (n_rows={sb.n_rows}, D) with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
 
 
 def attn_stream_train(q, k, v, sb, n_heads, scale=None, dropout_p=0.0, seed=0, site=0, precision="fp32"):
@@ -1204,37 +1206,25 @@ def attn_stream_train(q, k, v, sb, n_heads, scale=None, dropout_p=0.0, seed=0, s
     precision="bf16x3": both products in the split-bf16 arithmetic (sumk_attn_stream_split_train; head widths % 8 == 0, up to 128; same
     masks); the default keeps the exact call and its bits.
     Returns (ctx, stats).  Only enqueues work."""
-    lib = _lib.load()
-    code = _stream_precision(precision, "attn_stream_train")
+    entry, code = _attn_stream_entry("_train", precision, "attn_stream_train")
     _attn_stream_args("attn_stream_train", ((q, "q"), (k, "k"), (v, "v")), sb)
     D = q.shape[1]
-    nb = attn_stream_workspace_bytes(D, n_heads, sb, precision)
-    ws = workspace(nb, q.device)
+    ws = workspace(attn_stream_workspace_bytes(D, n_heads, sb, precision), q.device)
     ctx = torch.empty(sb.n_rows, D, dtype=torch.float32, device=q.device)
     stats = torch.empty(sb.n_rows, int(n_heads), 2, dtype=torch.float32, device=q.device)
     sc = 1.0 / math.sqrt(D // int(n_heads)) if scale is None else float(scale)
-    if code is not None:
-        rc = lib.sumk_attn_stream_split_train(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq,
-                                              sb.off_host_p, sb.off_dev_p, sc, float(dropout_p), int(seed), int(site), _p(ctx), D, _p(stats),
-                                              _p(ws), ws.numel(), _stream(), code)
-        _lib.check(rc, "sumk_attn_stream_split_train")
-        return ctx, stats
-    rc = lib.sumk_attn_stream_train(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq, sb.off_host_p,
-                                    sb.off_dev_p, sc, float(dropout_p), int(seed), int(site), _p(ctx), D, _p(stats), _p(ws), ws.numel(),
-                                    _stream())
-    _lib.check(rc, "sumk_attn_stream_train")
+    rc = getattr(_lib.load(), entry)(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), D, int(n_heads), sb.n_seq, sb.off_host_p,
+                                     sb.off_dev_p, sc, float(dropout_p), int(seed), int(site), _p(ctx), D, _p(stats), _p(ws), ws.numel(),
+                                     _stream(), *code)
+    _lib.check(rc, entry)
     return ctx, stats
 
 
 def attn_stream_backward_workspace_bytes(D, n_heads, sb, precision="fp32"):
     """Bytes of scratch one attn_stream_backward call takes: 16 per video + 4 per (row, head); precision="bf16x3": 24 per video + 4 per (row,
     head) + the bf16 planes of Q, K, V and dctx, 28 bytes per (padded row, staged column)."""
-    code = _stream_precision(precision, "attn_stream_backward")
-    if code is not None:
-        return _nonzero(_lib.load().sumk_attn_stream_split_backward_workspace_bytes(int(D), int(n_heads), sb.n_seq, sb.off_host_p, code),
-                        "sumk_attn_stream_split_backward_workspace_bytes")
-    return _nonzero(_lib.load().sumk_attn_stream_backward_workspace_bytes(int(D), int(n_heads), sb.n_seq, sb.off_host_p),
-                    "sumk_attn_stream_backward_workspace_bytes")
+    entry, code = _attn_stream_entry("_backward_workspace_bytes", precision, "attn_stream_backward")
+    return _nonzero(getattr(_lib.load(), entry)(int(D), int(n_heads), sb.n_seq, sb.off_host_p, *code), entry)
 
 
 def attn_stream_backward(q, k, v, ctx, dctx, stats, sb, n_heads, scale=None, dropout_p=0.0, seed=0, site=0, out=None, precision="fp32", ws=None):
@@ -1243,8 +1233,7 @@ def attn_stream_backward(q, k, v, ctx, dctx, stats, sb, n_heads, scale=None, dro
     (n_rows, 3 D) buffer, `out` when given.  precision="bf16x3": the seven products in the split-bf16 arithmetic
     (csrc/attn_stream_split_bwd.hip).  ws: a uint8 scratch tensor of at least attn_stream_backward_workspace_bytes, else the shared one.
     Deterministic; only enqueues work."""
-    lib = _lib.load()
-    code = _stream_precision(precision, "attn_stream_backward")
+    entry, code = _attn_stream_entry("_backward", precision, "attn_stream_backward")
     _attn_stream_args("attn_stream_backward", ((q, "q"), (k, "k"), (v, "v"), (ctx, "ctx"), (dctx, "dctx")), sb)
     D = q.shape[1]
     _require_gpu(stats, "attn_stream_backward stats")
@@ -1253,120 +1242,63 @@ def attn_stream_backward(q, k, v, ctx, dctx, stats, sb, n_heads, scale=None, dro
     nb = attn_stream_backward_workspace_bytes(D, n_heads, sb, precision)
     if ws is None:
         ws = workspace(nb, q.device)
-    else:
-        if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nb:
-            raise SumkError(f"attn_stream_backward: ws must be a contiguous uint8 GPU tensor of at least {nb} bytes")
+    elif not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nb:
+        raise SumkError(f"attn_stream_backward: ws must be a contiguous uint8 GPU tensor of at least {nb} bytes")
     if out is None:
         out = torch.empty(sb.n_rows, 3 * D, dtype=torch.float32, device=q.device)
     elif tuple(out.shape) != (sb.n_rows, 3 * D) or not out.is_contiguous():
         raise SumkError(f"attn_stream_backward: out must be contiguous (n_rows={sb.n_rows}, {3 * D}), got {tuple(out.shape)}")
     dq, dk, dv = out[:, :D], out[:, D:2 * D], out[:, 2 * D:]
     sc = 1.0 / math.sqrt(D // int(n_heads)) if scale is None else float(scale)
-    args = (_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(ctx), ctx.stride(0), _p(dctx), dctx.stride(0), _p(stats), D,
-            int(n_heads), sb.n_seq, sb.off_host_p, sb.off_dev_p, sc, float(dropout_p), int(seed), int(site), _p(dq), 3 * D, _p(dk), 3 * D,
-            _p(dv), 3 * D, _p(ws), ws.numel(), _stream())
-    if code is not None:
-        _lib.check(lib.sumk_attn_stream_split_backward(*args, code), "sumk_attn_stream_split_backward")
-    else:
-        _lib.check(lib.sumk_attn_stream_backward(*args), "sumk_attn_stream_backward")
+    rc = getattr(_lib.load(), entry)(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(ctx), ctx.stride(0), _p(dctx),
+                                     dctx.stride(0), _p(stats), D, int(n_heads), sb.n_seq, sb.off_host_p, sb.off_dev_p, sc, float(dropout_p),
+                                     int(seed), int(site), _p(dq), 3 * D, _p(dk), 3 * D, _p(dv), 3 * D, _p(ws), ws.numel(), _stream(), *code)
+    _lib.check(rc, entry)
     return dq, dk, dv
+
+
+def _tf_workspace_bytes(path, D, dff, n_heads, n_layers, sb, training, plane_precision=0):
+    """plane_precision: the dense entry's plane path (scoring in bf16x6 / bf16x3 with the weights' planes given) keeps plane buffers
+    behind the carve; 0 elsewhere."""
+    extra = (int(training), plane_precision) if path.forward == "sumk_transformer_forward" else () if path.code is None else (path.code,)
+    return _nonzero(getattr(_lib.load(), path.query)(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq, sb.off_host_p, *extra), path.query)
 
 
 def transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, attention="dense", training=False, attention_precision="fp32",
                                 attention_train_precision="fp32"):
-    """Bytes of scratch one call takes in exact fp32 (attention_precision="bf16x3", scoring on "stream" only: + the bf16 planes of one
-    layer's [Q | K | V], sumk_transformer_stream_split_workspace_bytes).  Scoring: "dense" holds heads x T x T logits per video
-    (sumk_transformer_workspace_bytes), "stream" none (sumk_transformer_stream_workspace_bytes).  training=True, the forward that keeps
-    what the backward needs: "dense" keeps two heads x T x T blocks per video and layer, "stream" 8 bytes per (row, head) and layer
-    (sumk_transformer_stream_train_workspace_bytes); attention_train_precision="bf16x3" (training on "stream" only): + the descriptors,
-    delta and planes of one layer's attention backward (sumk_transformer_stream_split_train_workspace_bytes)."""
-    lib = _lib.load()
-    code = _tf_attention_precision(attention, attention_precision, training)
-    tcode = _tf_attention_train_precision(attention, attention_train_precision, training)
-    if tcode is not None:
-        return _nonzero(lib.sumk_transformer_stream_split_train_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq,
-                                                                                sb.off_host_p, tcode),
-                        "sumk_transformer_stream_split_train_workspace_bytes")
-    if code is not None:
-        return _nonzero(lib.sumk_transformer_stream_split_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq,
-                                                                          sb.off_host_p, code), "sumk_transformer_stream_split_workspace_bytes")
-    if _tf_attention(attention) == "stream":
-        if training:
-            return _nonzero(lib.sumk_transformer_stream_train_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq,
-                                                                              sb.off_host_p), "sumk_transformer_stream_train_workspace_bytes")
-        return _nonzero(lib.sumk_transformer_stream_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq, sb.off_host_p),
-                        "sumk_transformer_stream_workspace_bytes")
-    return _nonzero(lib.sumk_transformer_workspace_bytes(int(D), int(dff), int(n_heads), int(n_layers), sb.n_seq, sb.off_host_p, int(training)),
-                    "sumk_transformer_workspace_bytes")
+    """Bytes of scratch one call takes in exact fp32, from the size query of the call's path (_tf_path).  Scoring: "dense" holds heads x
+    T x T logits per video, "stream" none; attention_precision="bf16x3" (scoring on "stream" only): + the bf16 planes of one layer's
+    [Q | K | V].  training=True, the forward that keeps what the backward needs: "dense" keeps two heads x T x T blocks per video and
+    layer, "stream" 8 bytes per (row, head) and layer; attention_train_precision="bf16x3" (training on "stream" only): + the
+    descriptors, delta and planes of one layer's attention backward."""
+    path = _tf_path(attention, attention_precision, attention_train_precision, training)
+    return _tf_workspace_bytes(path, D, dff, n_heads, n_layers, sb, training)
 
 
 def transformer_forward_packed(x, sb, params, n_layers, n_heads, dff, opts, pos_table=None, pos_rows=None, training=False,
                                attention="dense", attention_precision="fp32", attention_train_precision="fp32"):
-    """x: (n_rows, D) packed -> (scores (n_rows,), workspace or None).  params: state_dict-keyed tensors.
-    attention="stream" (exact fp32 only): every layer's attention on csrc/attn_stream.hip, no (T x T) logits in the workspace
-    (sumk_transformer_forward_stream; training=True: sumk_transformer_forward_stream_train, whose workspace goes to
-    transformer_backward_packed(..., attention="stream")).  attention_precision="bf16x3" (scoring on "stream" only): every layer's
-    attention on csrc/attn_stream_split.hip, the projections still exact fp32 (sumk_transformer_forward_stream_split).
-    attention_train_precision="bf16x3" (training=True on "stream" only): every layer's attention on the bf16x3 training form
-    (sumk_transformer_forward_stream_split_train; the backward takes the same argument)."""
+    """x: (n_rows, D) packed -> (scores (n_rows,), workspace or None).  params: state_dict-keyed tensors.  One call of the forward entry
+    of the path (_tf_path); with training=True its workspace goes to transformer_backward_packed with the same attention arguments.
+    attention="stream" (exact fp32 only): every layer's attention on csrc/attn_stream.hip, no (T x T) logits in the workspace.
+    attention_precision="bf16x3" (scoring on "stream" only) / attention_train_precision="bf16x3" (training=True on "stream" only):
+    every layer's attention on csrc/attn_stream_split.hip, the projections still exact fp32."""
     lib = _lib.load()
     _check_rows(x, sb, "transformer input")
     D = x.shape[1]
     layers, head = _tf_structs(params, n_layers, "weight", _lib.TfLayerWeights, _lib.TfHeadWeights)
     o = _tf_opts(opts)
-    code = _tf_attention_precision(attention, attention_precision, training)
-    tcode = _tf_attention_train_precision(attention, attention_train_precision, training)
-    if tcode is not None:
-        nbytes = transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, "stream", training=True,
-                                             attention_train_precision=attention_train_precision)
-        ws = workspace(nbytes, x.device, persistent=True)
-        scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
-        rc = lib.sumk_transformer_forward_stream_split_train(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
-                                                             C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
-                                                             C.cast(C.pointer(o), C.c_void_p), _p(pos_table), _p(pos_rows), _p(scores),
-                                                             tcode, _p(ws), ws.numel(), _stream())
-        _lib.check(rc, "sumk_transformer_forward_stream_split_train")
-        return scores, ws
-    if code is not None:
-        nbytes = transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, "stream", attention_precision=attention_precision)
-        ws = workspace(nbytes, x.device)
-        scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
-        rc = lib.sumk_transformer_forward_stream_split(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
-                                                       C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
-                                                       C.cast(C.pointer(o), C.c_void_p), _p(pos_table), _p(pos_rows), _p(scores), code,
-                                                       _p(ws), ws.numel(), _stream())
-        _lib.check(rc, "sumk_transformer_forward_stream_split")
-        return scores, None
-    if _tf_attention(attention) == "stream":
-        if training:
-            nbytes = transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, "stream", training=True)
-            ws = workspace(nbytes, x.device, persistent=True)
-            scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
-            rc = lib.sumk_transformer_forward_stream_train(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
-                                                           C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
-                                                           C.cast(C.pointer(o), C.c_void_p), _p(pos_table), _p(pos_rows), _p(scores),
-                                                           _p(ws), ws.numel(), _stream())
-            _lib.check(rc, "sumk_transformer_forward_stream_train")
-            return scores, ws
-        nbytes = transformer_workspace_bytes(D, dff, n_heads, n_layers, sb, "stream")
-        ws = workspace(nbytes, x.device)
-        scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
-        rc = lib.sumk_transformer_forward_stream(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
-                                                 C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
-                                                 C.cast(C.pointer(o), C.c_void_p), _p(pos_table), _p(pos_rows), _p(scores), _p(ws),
-                                                 ws.numel(), _stream())
-        _lib.check(rc, "sumk_transformer_forward_stream")
-        return scores, None
-    nbytes = _nonzero(lib.sumk_transformer_workspace_bytes_for(D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, int(training),
-                                                               o.precision if o.wplanes else 0), "sumk_transformer_workspace_bytes_for")
-    ws = workspace(nbytes, x.device, persistent=training)
+    path = _tf_path(attention, attention_precision, attention_train_precision, training)
+    dense = path.forward == "sumk_transformer_forward"
+    nbytes = _tf_workspace_bytes(path, D, dff, n_heads, n_layers, sb, training, o.precision if dense and o.wplanes else 0)
+    ws = workspace(nbytes, x.device, persistent=path.persistent)
     scores = torch.empty(sb.n_rows, dtype=torch.float32, device=x.device)
-    rc = lib.sumk_transformer_forward(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
-                                      C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
-                                      C.cast(C.pointer(o), C.c_void_p), _p(pos_table), _p(pos_rows), _p(scores), _p(ws),
-                                      ws.numel(), int(training), _stream())
-    _lib.check(rc, "sumk_transformer_forward")
-    return scores, (ws if training else None)
+    code = () if path.code is None else (path.code,)
+    mode = (int(training),) if dense else ()
+    rc = getattr(lib, path.forward)(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p, C.cast(layers, C.c_void_p),
+                                    C.cast(C.pointer(head), C.c_void_p), C.cast(C.pointer(o), C.c_void_p), _p(pos_table), _p(pos_rows),
+                                    _p(scores), *code, _p(ws), ws.numel(), *mode, _stream())
+    _lib.check(rc, path.forward)
+    return scores, (ws if path.persistent else None)
 
 
 def transformer_backward_packed(x, sb, params, grads, n_layers, n_heads, dff, opts, dscores, ws, want_dx=False, attention="dense",
@@ -1380,20 +1312,13 @@ def transformer_backward_packed(x, sb, params, grads, n_layers, n_heads, dff, op
     dx = torch.empty_like(x) if want_dx else None
     if not dscores.is_contiguous():
         dscores = dscores.contiguous()
-    tcode = _tf_attention_train_precision(attention, attention_train_precision, True)
-    if tcode is not None:
-        rc = lib.sumk_transformer_backward_stream_split(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
-                                                        C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
-                                                        C.cast(C.pointer(o), C.c_void_p), _p(dscores), C.cast(glayers, C.c_void_p),
-                                                        C.cast(C.pointer(ghead), C.c_void_p), _p(dx), tcode, _p(ws), ws.numel(), _stream())
-        _lib.check(rc, "sumk_transformer_backward_stream_split")
-        return dx
-    entry = "sumk_transformer_backward_stream" if _tf_attention(attention) == "stream" else "sumk_transformer_backward"
-    rc = getattr(lib, entry)(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p,
-                             C.cast(layers, C.c_void_p), C.cast(C.pointer(head), C.c_void_p),
-                             C.cast(C.pointer(o), C.c_void_p), _p(dscores), C.cast(glayers, C.c_void_p),
-                             C.cast(C.pointer(ghead), C.c_void_p), _p(dx), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, entry)
+    path = _tf_path(attention, attention_train_precision=attention_train_precision, training=True)
+    code = () if path.code is None else (path.code,)
+    rc = getattr(lib, path.backward)(_p(x), D, dff, n_heads, n_layers, sb.n_seq, sb.off_host_p, sb.off_dev_p, C.cast(layers, C.c_void_p),
+                                     C.cast(C.pointer(head), C.c_void_p), C.cast(C.pointer(o), C.c_void_p), _p(dscores),
+                                     C.cast(glayers, C.c_void_p), C.cast(C.pointer(ghead), C.c_void_p), _p(dx), *code, _p(ws), ws.numel(),
+                                     _stream())
+    _lib.check(rc, path.backward)
     return dx
 
 

@@ -92,10 +92,12 @@ class Transformer(PositionalInput, nn.Module):
         return self._score(xp, sb, None, None)
 
     def _score(self, xp, sb, table, rows):
-        """attention="stream": the no-grad branch scores through sumk_transformer_forward_stream (exact fp32; any other `precision`
-        raises ValueError), its attention products in attention_precision.  The autograd branch follows attention_train alone: "dense"
-        (default) gives the gradients it always gave, bit for bit; "stream" runs sumk_transformer_forward_stream_train / _backward_stream (exact fp32; any other `precision` raises), or with
-        attention_train_precision="bf16x3" their _split forms: the attention products in bf16x3, everything else exact fp32."""
+        """Every branch is one call of kernels.transformer_forward_packed: the library runs one layer loop under one plan, and the
+        arguments below only name the path.  The no-grad branch follows attention / attention_precision: "stream" scores without the
+        (T x T) logits (exact fp32; any other `precision` raises ValueError), its attention products in attention_precision.  The
+        autograd branch follows attention_train / attention_train_precision alone: "dense" (default) gives the gradients it always gave,
+        bit for bit; "stream" trains without the (T x T) blocks (exact fp32; any other `precision` raises), with "bf16x3" the attention
+        products in bf16x3 and everything else exact fp32."""
         p = dict(self.named_parameters())
         opts = dict(layer_eps=1e-5, final_eps=self.epsilon, more_residuals=self.more_residuals,
                     precision=getattr(self, "precision", "fp32"))
