@@ -3,7 +3,7 @@ The SumGAN recurrences (lstm_stack_ref, dlstm_ref) and make_gru also run in floa
 tests/test_gpu_sumgan_full.py; transformer_ref likewise for tests/test_gpu_transformer_f64.py, tf_encoder_stack_ref / tf_decoder_stack_ref for
 tests/test_gpu_sumgan_att_f64.py, bilstm_stack_ref for
 tests/test_gpu_lstm_f64.py (float64 reference and, in fp32 with the kernels' gate formulas, its yardstick), bigru_stack_ref the same
-for tests/test_gpu_gru_f64.py.
+for tests/test_gpu_gru_f64.py, lstm_stack_ref / dlstm_ref (gate_math, matmul) the same for tests/test_gpu_sumgan_lstm_f64.py.
 
 This is (1) a second, autograd-capable checker for the HIP path (forward AND gradients), and
 (2) the `cpu_baseline` ("kind": "port") that bench.py times on the GPU node's host cores: it issues the
@@ -304,23 +304,30 @@ def make_gru(p, prefix, input_size, hidden_size, num_layers, dtype=torch.float32
     return m
 
 
-def _lstm_cell(gx, h, c, w_hh, b_hh):
-    """One nn.LSTM step: gx = x W_ih^T + b_ih (precomputed); gate order i, f, g, o as in torch."""
-    i, f, g, o = (gx + F.linear(h, w_hh, b_hh)).chunk(4, dim=-1)
-    c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
-    return torch.sigmoid(o) * torch.tanh(c), c
+def _lstm_cell(gx, h, c, w_hh, b_hh, sig=torch.sigmoid, tanh=torch.tanh, mm=None):
+    """One nn.LSTM step: gx = x W_ih^T + b_ih (precomputed); gate order i, f, g, o as in torch.  mm: the matmul hook of
+    lstm_stack_ref / dlstm_ref -- gx then carries BOTH biases already (as the kernels' pre-activations do) and b_hh is not added."""
+    pre = gx + F.linear(h, w_hh, b_hh) if mm is None else gx + mm(h, w_hh, "hh")
+    i, f, g, o = pre.chunk(4, dim=-1)
+    c = sig(f) * c + sig(i) * tanh(g)
+    return sig(o) * tanh(c), c
 
 
 def _num_layers(params):
     return sum(1 for k in params if k.startswith("weight_ih_l"))
 
 
-def lstm_stack_ref(x_list, params, h0=None, c0=None):
+def lstm_stack_ref(x_list, params, h0=None, c0=None, gate_math="exact", matmul=None, layer_outs=None):
     """Forward-running nn.LSTM(num_layers=L, bidirectional=False) over a ragged list of videos, in the dtype of the inputs.
     x_list: [(T_i, In)]; params: nn.LSTM state_dict names (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, ...);
     h0 / c0: (L, B, H) or None (zeros).  Returns ([out_i (T_i, H)] of the top layer, (h_n, c_n) (L, B, H)): the state after
     each video's OWN last frame.  Videos run side by side, time-major; a video that has ended keeps its state.  Everything
-    is differentiable (inputs, parameters, initial state)."""
+    is differentiable (inputs, parameters, initial state).
+    gate_math: a key of GATE_MATH.  matmul: optional hook (a (n, K), w (N, K), site) -> a @ w.T with site "ih" (input projection) or
+    "hh" (recurrent product), as in bilstm_stack_ref (Linear3, LinearDw3, LinearChainDx); with a hook the sums run in the kernels' order
+    (csrc/lstm.hip: the projection's epilogue adds b_ih and b_hh, a step adds the recurrent product to that).  The defaults keep the
+    plain F.linear form bit for bit.  layer_outs: optional list that receives [h_i (T_i, H) per video] of every layer."""
+    sig, tanh = GATE_MATH[gate_math]
     L, B = _num_layers(params), len(x_list)
     H = params["weight_hh_l0"].shape[1]
     lens = [int(x.shape[0]) for x in x_list]
@@ -330,24 +337,32 @@ def lstm_stack_ref(x_list, params, h0=None, c0=None):
     seq = torch.nn.utils.rnn.pad_sequence(list(x_list))                              # (T, B, In), zero padded
     hn, cn = [], []
     for l in range(L):
-        gx = F.linear(seq, params[f"weight_ih_l{l}"], params[f"bias_ih_l{l}"])           # input projection, all frames at once
+        if matmul is None:
+            gx = F.linear(seq, params[f"weight_ih_l{l}"], params[f"bias_ih_l{l}"])       # input projection, all frames at once
+        else:
+            gx = (matmul(seq.reshape(T * B, -1), params[f"weight_ih_l{l}"], "ih") + params[f"bias_ih_l{l}"]
+                  + params[f"bias_hh_l{l}"]).reshape(T, B, 4 * H)
         h = h0[l] if h0 is not None else ref.new_zeros(B, H)
         c = c0[l] if c0 is not None else ref.new_zeros(B, H)
         outs = []
         for t in range(T):
-            hs, cs = _lstm_cell(gx[t], h, c, params[f"weight_hh_l{l}"], params[f"bias_hh_l{l}"])
+            hs, cs = _lstm_cell(gx[t], h, c, params[f"weight_hh_l{l}"], params[f"bias_hh_l{l}"], sig, tanh, matmul)
             h, c = torch.where(act[t], hs, h), torch.where(act[t], cs, c)
             outs.append(h)
         seq = torch.stack(outs)
         hn.append(h); cn.append(c)
+        if layer_outs is not None:
+            layer_outs.append([seq[:n, b] for b, n in enumerate(lens)])
     return [seq[:n, b] for b, n in enumerate(lens)], (torch.stack(hn), torch.stack(cn))
 
 
 GATE_MATH = {
     # "exact": torch's own sigmoid / tanh.  "rcp_form": the formulas of the recurrence kernels (csrc/persist_common.h: fast_sigmoid,
     # fast_tanh) in plain torch ops, so that autograd differentiates the same formula the kernels evaluate.
+    # "rcp_sigmoid": the launch-per-step kernels of csrc/lstm.hip (sigmoidf_ = 1 / (1 + expf(-v)) next to the library's tanhf).
     "exact": (torch.sigmoid, torch.tanh),
     "rcp_form": (lambda v: 1.0 / (1.0 + torch.exp(-v)), lambda v: 1.0 - 2.0 / (1.0 + torch.exp(2.0 * v))),
+    "rcp_sigmoid": (lambda v: 1.0 / (1.0 + torch.exp(-v)), torch.tanh),
 }
 
 
@@ -521,12 +536,15 @@ def bigru_stack_ref(x_list, params, gate_math="exact", matmul=None):
     return layers
 
 
-def dlstm_ref(params, recons, T, h0, c0):
+def dlstm_ref(params, recons, T, h0, c0, gate_math="exact", matmul=None):
     """SumGAN's step-wise decoder (dLSTM, sumgan.py:74-115) in the dtype of h0: an nn.LSTM stack run one step at a time
     whose input at step t is its own top-layer output of step t-1 (zeros at t = 0), then recons = (weight, bias) on every
     output, then time reversed.  T: one length for every video, or a list of per-video lengths (each video decodes its own
     steps; the others do not see them).  h0 / c0: (L, B, H).  Returns [x_hat_i (T_i, out)]; with recons=None, the top
-    layer's outputs [(T_i, H)] in time order (neither projected nor reversed: what the decoder kernels return)."""
+    layer's outputs [(T_i, H)] in time order (neither projected nor reversed: what the decoder kernels return).
+    gate_math / matmul: as lstm_stack_ref; with a hook both biases join the input product before the recurrent product is added
+    (the decoder kernels add b_ih + b_hh to one accumulator that holds both products)."""
+    sig, tanh = GATE_MATH[gate_math]
     L, B, H = h0.shape
     lens = [int(T)] * B if isinstance(T, int) else [int(n) for n in T]
     assert len(lens) == B and _num_layers(params) == L
@@ -535,8 +553,11 @@ def dlstm_ref(params, recons, T, h0, c0):
     outs = []
     for t in range(max(lens)):
         for l in range(L):
-            gx = F.linear(x, params[f"weight_ih_l{l}"], params[f"bias_ih_l{l}"])
-            h[l], c[l] = _lstm_cell(gx, h[l], c[l], params[f"weight_hh_l{l}"], params[f"bias_hh_l{l}"])
+            if matmul is None:
+                gx = F.linear(x, params[f"weight_ih_l{l}"], params[f"bias_ih_l{l}"])
+            else:
+                gx = (params[f"bias_ih_l{l}"] + params[f"bias_hh_l{l}"]) + matmul(x, params[f"weight_ih_l{l}"], "ih")
+            h[l], c[l] = _lstm_cell(gx, h[l], c[l], params[f"weight_hh_l{l}"], params[f"bias_hh_l{l}"], sig, tanh, matmul)
             x = h[l]
         outs.append(x)
     seq = torch.stack(outs)                                                          # (T_max, B, H)

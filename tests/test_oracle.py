@@ -279,6 +279,100 @@ def test_sumgan_lstm_refs_ragged_and_initial_state_vs_nn_lstm():
         torch.testing.assert_close(got[i], torch.flip(recons(steps), (0,)), rtol=1e-12, atol=1e-12)
 
 
+def _lstm_stack_before_hooks(x_list, params, h0, c0):
+    """lstm_stack_ref as it stood before it took gate_math / matmul, op for op (F.linear with the bias inside, torch.sigmoid / torch.tanh)."""
+    F = torch.nn.functional
+    L, lens = sum(1 for k in params if k.startswith("weight_ih_l")), [int(x.shape[0]) for x in x_list]
+    act = torch.tensor([[t < n for n in lens] for t in range(max(lens))]).unsqueeze(-1)
+    seq = torch.nn.utils.rnn.pad_sequence(list(x_list))
+    hn, cn = [], []
+    for l in range(L):
+        gx = F.linear(seq, params[f"weight_ih_l{l}"], params[f"bias_ih_l{l}"])
+        h, c, outs = h0[l], c0[l], []
+        for t in range(max(lens)):
+            i, f, g, o = (gx[t] + F.linear(h, params[f"weight_hh_l{l}"], params[f"bias_hh_l{l}"])).chunk(4, dim=-1)
+            cs = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+            hs = torch.sigmoid(o) * torch.tanh(cs)
+            h, c = torch.where(act[t], hs, h), torch.where(act[t], cs, c)
+            outs.append(h)
+        seq = torch.stack(outs)
+        hn.append(h); cn.append(c)
+    return [seq[:n, b] for b, n in enumerate(lens)], (torch.stack(hn), torch.stack(cn))
+
+
+def _dlstm_before_hooks(params, lens, h0, c0):
+    """dlstm_ref(recons=None) as it stood before it took gate_math / matmul, op for op."""
+    F = torch.nn.functional
+    L, B, H = h0.shape
+    x, h, c, outs = h0.new_zeros(B, H), list(h0.unbind(0)), list(c0.unbind(0)), []
+    for t in range(max(lens)):
+        for l in range(L):
+            gx = F.linear(x, params[f"weight_ih_l{l}"], params[f"bias_ih_l{l}"])
+            i, f, g, o = (gx + F.linear(h[l], params[f"weight_hh_l{l}"], params[f"bias_hh_l{l}"])).chunk(4, dim=-1)
+            c[l] = torch.sigmoid(f) * c[l] + torch.sigmoid(i) * torch.tanh(g)
+            h[l] = torch.sigmoid(o) * torch.tanh(c[l])
+            x = h[l]
+        outs.append(x)
+    seq = torch.stack(outs)
+    return [seq[:n, b] for b, n in enumerate(lens)]
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["float64", "float32"])
+def test_sumgan_lstm_refs_hooks_keep_the_defaults_bit_for_bit(dtype):
+    """lstm_stack_ref / dlstm_ref with gate_math / matmul (the hooks of tests/test_gpu_sumgan_lstm_f64.py): with the defaults, outputs,
+    final states and every gradient of a ragged batch with h0 / c0 are BIT-identical to the functions as they stood before the hooks
+    (restated above), in float64 and in float32, and in float64 still equal nn.LSTM to 1e-12.  Each gate_math is the same function (1e-12
+    in float64); a plain-product hook and the one-accumulator dX product (LinearChainDx) change the summation order only; Linear3 on the
+    input projection with LinearDw3 on the recurrent product make the bf16x3 roundings (2^-16 relative, not more) and nothing else."""
+    torch.manual_seed(18)
+    D, H, L, lens = 12, 10, 2, [5, 1, 9, 5, 2]
+    lstm = torch.nn.LSTM(D, H, num_layers=L).to(dtype)
+    dl = torch.nn.LSTM(H, H, num_layers=L).to(dtype)
+    p, pd = dict(lstm.named_parameters()), dict(dl.named_parameters())
+    xs = [torch.randn(T, D, dtype=dtype, requires_grad=True) for T in lens]
+    h0 = torch.randn(L, len(lens), H, dtype=dtype, requires_grad=True)
+    c0 = torch.randn(L, len(lens), H, dtype=dtype, requires_grad=True)
+    cw = [torch.randn(T, H, dtype=dtype) for T in lens]
+    cwh, cwc = torch.randn(L, len(lens), H, dtype=dtype), torch.randn(L, len(lens), H, dtype=dtype)
+
+    def stack(fn, **kw):
+        outs, (hn, cn) = fn(xs, p, h0, c0, **kw)
+        leaves = xs + [h0, c0] + list(p.values())
+        g = torch.autograd.grad(sum((o * w).sum() for o, w in zip(outs, cw)) + (hn * cwh).sum() + (cn * cwc).sum(), leaves)
+        return [o.detach() for o in outs] + [hn.detach(), cn.detach()] + list(g)
+
+    def dec(fn, **kw):
+        outs = fn(pd, lens, h0, c0, **kw)
+        g = torch.autograd.grad(sum((o * w).sum() for o, w in zip(outs, cw)), [h0, c0] + list(pd.values()))
+        return [o.detach() for o in outs] + list(g)
+
+    s_old, s_new = stack(_lstm_stack_before_hooks), stack(torch_port.lstm_stack_ref)
+    d_old, d_new = dec(_dlstm_before_hooks), dec(lambda q, n, h, c, **kw: torch_port.dlstm_ref(q, None, n, h, c, **kw))
+    assert len(s_old) == len(s_new) and all(torch.equal(a, b) for a, b in zip(s_old, s_new))
+    assert len(d_old) == len(d_new) and all(torch.equal(a, b) for a, b in zip(d_old, d_new))
+    if dtype != torch.float64:
+        return
+    close = lambda a, b: torch.testing.assert_close(a, b, rtol=0, atol=1e-12)
+    for i, x in enumerate(xs):
+        o, (h, c) = lstm(x.unsqueeze(1), (h0[:, i:i + 1].contiguous(), c0[:, i:i + 1].contiguous()))
+        close(s_new[i], o[:, 0].detach()); close(s_new[len(lens)][:, i], h[:, 0].detach()); close(s_new[len(lens) + 1][:, i], c[:, 0].detach())
+    lo = []
+    torch_port.lstm_stack_ref(xs, p, h0, c0, layer_outs=lo)
+    assert len(lo) == L and all(torch.equal(a.detach(), b) for a, b in zip(lo[-1], s_new))
+    plain = lambda a, w, site: a @ w.t()
+    chain = lambda a, w, site: torch_port.LinearChainDx.apply(a, w) if site == "ih" else a @ w.t()
+    for kw in (dict(gate_math="rcp_form"), dict(gate_math="rcp_sigmoid"), dict(matmul=plain), dict(gate_math="rcp_sigmoid", matmul=chain)):
+        for a, b in zip(stack(torch_port.lstm_stack_ref, **kw), s_new):
+            close(a, b)
+        for a, b in zip(dec(lambda q, n, h, c, **k2: torch_port.dlstm_ref(q, None, n, h, c, **k2), **kw), d_new):
+            close(a, b)
+    x3 = lambda a, w, site: torch_port.Linear3.apply(a, w, False) if site == "ih" else torch_port.LinearDw3.apply(a, w)
+    for got, want in ((stack(torch_port.lstm_stack_ref, matmul=x3), s_new),
+                      (dec(lambda q, n, h, c, **k2: torch_port.dlstm_ref(q, None, n, h, c, **k2), matmul=x3), d_new)):
+        rel = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(got, want))
+        assert 0 < rel < 1e-3, rel                                                            # the roundings happen, and stay at 2^-16
+
+
 def test_bilstm_stack_ref_vs_nn_lstm_float64():
     """bilstm_stack_ref (the float64 reference of tests/test_gpu_lstm_f64.py) against stock nn.LSTM(bidirectional=True).double()
     through pack_sequence: a ragged batch with a one-frame video and a tie in length, two layers; hidden states of the top layer
